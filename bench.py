@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- tracked frames/s of the per-frame tracking hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json metric: "tracked frames/sec (ORB+ImageAlign+PnP) at 640x480, 1000 kp"):
 one *step* tracks a batch of B independent 640x480 frames, all resident in HBM:
@@ -23,7 +23,13 @@ Tracking::TrackWithMotionModel as one device-side call; track adds Tracking::Tra
 --orb-only times extraction alone, --hamming extraction + brute-force SearchByPoints (BASELINE configs[1]: "ORB extract +
 Hamming match"), --res WxH other frame sizes, --batch 1 the single-frame latency.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step,
+higher_is_better, dtype, config).  --dump-outputs DIR writes what the last timed step computed -- the pose records and the
+per-frame read-outs of every stage, per-keypoint arrays for a fixed, seeded sample of frames -- as DIR/<name>.npy (float32 /
+float64); the inputs are seeded, so two builds can be compared output for output.
+
+--full adds everything beyond the headline: per-stage HIP-event timers inside the timed region (stages_ms_per_step), the
+tracking summary, the check of the device-packed / gathered records, the run-to-run spread, and these objects:
   roofline     -- dominant kernel stage: algorithmic bytes per launch / its mean duration (HIP events on the
                   launch stream inside the timed region) against HBM peak; `valu` = the same stage against the measured
                   vector-ALU issue rate, `traffic` = HBM bytes from the committed rocprofv3 PMC passes
@@ -535,6 +541,129 @@ def h2d_leg(wl, steps=4):
             "note": "synchronous upload from page-locked memory, not overlapped with the previous step"}
 
 
+DUMP_SAMPLE_FRAMES = 64          # frames whose per-keypoint arrays are written (fixed seed); per-frame arrays cover the batch
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(wl, out_dir, records=None, gathered=None):
+    """`--dump-outputs DIR`: what the timed path computed in its last step, as a caller of it receives it -- the packed pose
+    records and the stages' read-outs (keypoints, descriptors, alignment, matches, pose solve) -- one DIR/<name>.npy each.
+    Floating-point arrays keep their width; integer / boolean ones are stored as float32 when exact there, float64 otherwise.
+    Per-keypoint arrays ([frames, cap, ...]) are limited to a fixed, seeded sample of DUMP_SAMPLE_FRAMES frames."""
+    B, trk = wl.B, wl.trk
+    S = np.sort(np.random.default_rng(0).choice(B, min(B, DUMP_SAMPLE_FRAMES), replace=False))
+    k, d, n = wl.cur.download(0, B)
+    out = {"sample_frames": S, "n_keypoints": n, "keypoints": np.stack([k[f][S].astype(np.float32) for f in k.dtype.names], -1),   # x y size angle response octave class_id
+           "descriptors": d[S]}
+    if records is not None:
+        out["records"] = records
+    if gathered is not None:
+        out["records_gathered"] = gathered
+    if wl.hamming:
+        m, nm = trk.get_point_matches(0, B)
+        out.update(point_matches=m[S], n_point_matches=nm)
+    elif not wl.orb_only:
+        al = trk.get_align(0, B)
+        cm, nm = trk.get_matches(0, B)
+        out.update(align_T=np.stack(al["T"]), align_ok=al["ok"], align_error=al["error"], align_iterations=al["iters"],
+                   align_chi2=al["chi2"], matches=cm[S], n_matches=nm)
+        if wl.pose_solver == "pnp":
+            g = trk.get_pnp(0, B)
+            out.update(pnp_T=g["T"], pnp_ok=g["ok"], pnp_n_inliers=g["n_inliers"], pnp_iterations=g["iterations"],
+                       pnp_refined=g["refined"], pnp_inliers=g["inliers"][S])
+        else:
+            po = trk.get_pose_opt(0, B)
+            out.update(pose_opt_T=np.stack(po["T"]), pose_opt_n_inliers=po["n_inliers"], pose_opt_iterations=po["iterations"],
+                       pose_opt_outliers=po["outlier"][S])
+            if wl.pose_solver in ("motion_model", "track"):
+                tw = trk.get_tracked(0, B)
+                out.update(tracked_status=tw["status"], tracked_nmatches=tw["nmatches"], tracked_nmatches_map=tw["nmatches_map"])
+            if wl.pose_solver == "track":
+                tl = trk.get_local_map(0, B)
+                out.update(local_map_matches=tl["match"][S], local_map_status=tl["status"], local_map_n_inliers=tl["n_inliers"])
+    arrays = {}
+    for name, a in out.items():
+        a = np.asarray(a)
+        if a.dtype.kind != "f":
+            a = a.astype(np.float32 if a.size == 0 or np.abs(a.astype(np.int64)).max() < (1 << 24) else np.float64)
+        arrays[name] = a
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def full_figures(line, args, wl, scenes, rec_host, orb_ms, trk_ms, full_step):
+    """`--full` (rank 0): per-stage times and the roofline of the dominant stage, the tracking summary, then the legs that run
+    after the timed region -- run-to-run spread, stress, h2d, drop-in, CPU baseline -- added to `line`."""
+    import sdslam_amd
+    B, cur, trk, nu, world = wl.B, wl.cur, wl.trk, wl.nu, line["n_gpus"]
+    al, cm, nm, pn = wl.results()
+    if not args.orb_only and not args.hamming:      # the device-packed records equal the per-stage read-outs
+        assert np.array_equal(rec_host[:, 17], nm.astype(np.float64)) and np.array_equal(rec_host[:, 18], pn["n_inliers"].astype(np.float64))
+    solver_name = "pnp_ransac" if args.pose_solver == "pnp" else "pose_optimization"
+    names = cur.stage_names() + ["image_align", "search_by_points" if args.hamming else "search_by_projection", solver_name]
+    stage_ms = np.concatenate([orb_ms, trk_ms])
+    sbytes = list(cur.stage_bytes())
+    # algorithmic bytes of the tracking stages (SURVEY §8d), from what this run actually did
+    P = float(np.mean([min(300, int(l["valid"].sum())) for l in wl.lasts_u]))
+    its = float(al["iters"][:, :8].sum(axis=1).mean())
+    lv = sdslam_amd.plan_info(*CFG, W, H)["levels"]
+    px_l = float(sum(lv[l, 0] * lv[l, 1] for l in (2, 3, 4)))
+    sbytes += [its * P * (25 + 64) + 2 * px_l,                       # ImageAlign
+               2 * 1000 * 32 if args.hamming else P * (32 + 10 * 32),   # brute force: compulsory descriptor reads; windowed: c ~ 10
+               float(pn["iterations"].mean()) * (4 * 20 + float(pn["N"].mean()) * 24)]   # PnP
+    dom = int(np.argmax(stage_ms))
+    achieved = sbytes[dom] * B / (stage_ms[dom] * 1e-3) / 1e9
+    traffic, valu = pmc_for_stage(names[dom], B)
+    terr = float(np.mean([np.abs(al["T"][b][:3, 3] - scenes[wl.idx[b]]["T_cur"][:3, 3]).max() for b in range(min(B, nu))]))
+    line.update({
+        "stages_ms_per_step": {nm_: float(ms) for nm_, ms in zip(names, stage_ms)},
+        "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                     "algorithmic_bytes_per_frame": float(sbytes[dom]), "ms_per_step": float(stage_ms[dom]),
+                     "note": "integer/byte kernel limited by vector-ALU issue, not HBM (DESIGN.md section 6); traffic = HBM bytes per "
+                             "step from the committed rocprofv3 FETCH_SIZE/WRITE_SIZE passes (profiles/), scaled to this batch",
+                     "valu": valu,
+                     "valu_frac": (valu["min_ms_if_all_vop2"] / float(stage_ms[dom])) if valu else None,
+                     "valu_frac_at_vop3_rate": (valu["min_ms_if_all_vop3"] / float(stage_ms[dom])) if valu else None},
+        "tracking": {"align_ok": int(al["ok"].sum()), "mean_gn_iterations": its, "mean_matches": float(nm.mean()),
+                     "pnp_ok": int(np.asarray(pn["ok"]).sum()), "mean_pnp_inliers": float(pn["n_inliers"].mean()),
+                     "mean_pnp_iterations": float(pn["iterations"].mean()), "align_translation_err_m": terr},
+    })
+    if args.hamming:
+        m12, n12 = trk.get_point_matches(0, B)
+        line["tracking"]["mean_point_matches"] = float(n12.mean())
+    if world == 1 and not args.no_extras:
+        # run-to-run spread (VERDICT r2 weak #11: the headline is one timed region): three more blocks of the same step, each
+        # bracketed like the timed region, AFTER it; `value` stays the K-step figure above
+        blocks = []
+        nb = max(10, min(50, args.steps // 3))
+        for _ in range(3):
+            cur.sync()
+            trk.get_tracked(0, 1)
+            tb = time.perf_counter()
+            for k in range(nb):
+                full_step(k)
+            cur.sync()
+            trk.get_tracked(0, 1)
+            blocks.append(B * nb / (time.perf_counter() - tb))
+        line["repeatability"] = {"blocks": 3, "steps_per_block": nb, "frames_per_s": blocks,
+                                 "spread": (max(blocks) - min(blocks)) / float(np.median(blocks))}
+    if world == 1 and not args.orb_only and not args.hamming and not args.no_extras:
+        line["stress"] = stress_legs(wl)
+        line["h2d_inclusive"] = h2d_leg(wl)
+        line["h2d_overlapped"] = h2d_overlapped_leg(wl)
+        if CFG[1:3] == (1.2, 8) and (W, H) == (640, 480):
+            line["drop_in"] = drop_in_leg(wl)
+    if not args.no_cpu_baseline and world == 1 and not args.orb_only and not args.hamming:
+        line["cpu_baseline"] = cpu_baseline(scenes[:min(nu, 8)], wl.lasts_u[:min(nu, 8)], wl.T0_u[:min(nu, 8)], wl.rs, pose_solver=args.pose_solver,
+                                            locals_=wl.locals_u)
+    else:
+        line["cpu_baseline"] = None
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start N child ranks (fresh processes, nothing GPU-related has run in
     this one), wait for all, fail if any fails."""
@@ -562,8 +691,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=1024, help="frames per GPU per step")
     ap.add_argument("--unique", type=int, default=64, help="distinct synthetic scenes (tiled to --batch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the stress / h2d legs (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="also everything beyond the headline: per-stage timers, roofline, tracking "
+                                                        "summary, record checks, run-to-run spread, stress / h2d / drop-in legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the spread / stress / h2d / drop-in legs (profiling runs)")
     ap.add_argument("--orb-only", action="store_true", help="time ORB extraction alone (configs[1] without matching)")
     ap.add_argument("--hamming", action="store_true", help="BASELINE configs[1]: ORB extract + brute-force Hamming match "
                                                             "(ORBmatcher::SearchByPoints, 1000 x 1000 per frame pair)")
@@ -658,8 +790,9 @@ def main():
     for k in range(args.warmup):
         full_step(k)
     cur.sync()
-    cur.set_profiling(True)
-    trk.set_profiling(True)
+    if args.full:                       # per-stage HIP events on the launch streams, inside the timed region
+        cur.set_profiling(True)
+        trk.set_profiling(True)
     wl.k = 0
     barrier()
     t0 = time.perf_counter()
@@ -669,42 +802,27 @@ def main():
     trk.get_tracked(0, 1)               # host-side wait for the tracking stream (its work is not on torch's streams)
     barrier()
     dt = time.perf_counter() - t0
-    orb_ms = cur.stage_ms()
-    trk_ms = trk.stage_ms() if not args.orb_only else np.zeros(3, np.float32)
-    if args.pose_solver == "track" and not args.orb_only and not args.hamming:
-        trk_ms[1:] *= 2      # the timers average per call; search and PoseOptimization run twice per step here
-    cur.set_profiling(False)
-    trk.set_profiling(False)
+    if args.full:
+        orb_ms = cur.stage_ms()
+        trk_ms = trk.stage_ms() if not args.orb_only else np.zeros(3, np.float32)
+        if args.pose_solver == "track" and not args.orb_only and not args.hamming:
+            trk_ms[1:] *= 2      # the timers average per call; search and PoseOptimization run twice per step here
+        cur.set_profiling(False)
+        trk.set_profiling(False)
     dt = dist_util.max_over_ranks(dt, dist, red_dev)                  # MAX over ranks
 
-    # ---- check what was gathered: every rank's block of the last step equals that rank's own records
     last = (args.steps - 1) % 2
-    if world > 1 and not args.orb_only:
+    # ---- check what was gathered: every rank's block of the last step equals that rank's own records
+    if args.full and world > 1 and not args.orb_only:
         mine = gathered[last][rank * B:(rank + 1) * B]
         assert torch.equal(mine, rec[last]), "gathered records differ from the local ones"
     rec_host = rec[last].cpu().numpy()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(wl, args.dump_outputs, None if args.orb_only else rec_host,
+                     gathered[last].cpu().numpy() if world > 1 and not args.orb_only else None)
 
     if rank == 0:
-        al, cm, nm, pn = wl.results()
-        if not args.orb_only and not args.hamming:      # the device-packed records equal the per-stage read-outs
-            assert np.array_equal(rec_host[:, 17], nm.astype(np.float64)) and np.array_equal(rec_host[:, 18], pn["n_inliers"].astype(np.float64))
         total_frames = B * args.steps * world
-        solver_name = "pnp_ransac" if args.pose_solver == "pnp" else "pose_optimization"
-        names = cur.stage_names() + ["image_align", "search_by_points" if args.hamming else "search_by_projection", solver_name]
-        stage_ms = np.concatenate([orb_ms, trk_ms])
-        sbytes = list(cur.stage_bytes())
-        # algorithmic bytes of the tracking stages, from what this run actually did
-        P = float(np.mean([min(300, int(l["valid"].sum())) for l in wl.lasts_u]))
-        its = float(al["iters"][:, :8].sum(axis=1).mean())
-        lv = sdslam_amd.plan_info(*CFG, W, H)["levels"]
-        px_l = float(sum(lv[l, 0] * lv[l, 1] for l in (2, 3, 4)))
-        sbytes += [its * P * (25 + 64) + 2 * px_l,                       # ImageAlign
-                   2 * 1000 * 32 if args.hamming else P * (32 + 10 * 32),   # brute force: compulsory descriptor reads; windowed: c ~ 10
-                   float(pn["iterations"].mean()) * (4 * 20 + float(pn["N"].mean()) * 24)]   # PnP
-        dom = int(np.argmax(stage_ms))
-        achieved = sbytes[dom] * B / (stage_ms[dom] * 1e-3) / 1e9
-        traffic, valu = pmc_for_stage(names[dom], B)
-        terr = float(np.mean([np.abs(al["T"][b][:3, 3] - scenes[wl.idx[b]]["T_cur"][:3, 3]).max() for b in range(min(B, nu))]))
         if args.orb_only:
             workload = f"ORB extract only (BASELINE configs[1] without matching), {W}x{H}, {pyr_txt}"
         elif args.hamming:
@@ -713,7 +831,7 @@ def main():
         else:
             which = "BASELINE configs[3] at the configs[1] pyramid" if CFG[2:0:-1] == (8, 1.2) else "BASELINE configs[3] at the reference's default pyramid (src/Config.cc:48-51)"
             workload = (f"{which}: {W}x{H}, {pyr_txt}, 1000 kp; ORB extract + ImageAlign (levels 4,3,2) + "
-                        "SearchByProjection + " + ("PnP RANSAC (maxIts 200; iterations actually run: tracking.mean_pnp_iterations)"
+                        "SearchByProjection + " + ("PnP RANSAC (maxIts 200; iterations actually run: tracking.mean_pnp_iterations with --full)"
                                                    if args.pose_solver == "pnp" else "Optimizer::PoseOptimization (g2o LM, 4x10 its)") +
                         (", as one Tracking::TrackWithMotionModel call" if args.pose_solver in ("motion_model", "track") else "") +
                         (" + Tracking::TrackLocalMap (th 1, <=1000 local points)" if args.pose_solver == "track" else ""))
@@ -727,49 +845,9 @@ def main():
                        "pose_records": ("REHEARSAL ONLY (SD_BENCH_REHEARSAL): all ranks on one GPU, gloo over host memory -- not a measurement" if rehearsal else
                                         "all-gathered over RCCL every step inside the timed region, straight from the device buffer the "
                                         "last tracking kernel wrote") if world > 1 else "packed on the device every step (single GPU: no collective)"},
-            "stages_ms_per_step": {nm_: float(ms) for nm_, ms in zip(names, stage_ms)},
-            "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "algorithmic_bytes_per_frame": float(sbytes[dom]), "ms_per_step": float(stage_ms[dom]),
-                         "note": "integer/byte kernel limited by vector-ALU issue, not HBM (DESIGN.md section 6); traffic = HBM bytes per "
-                                 "step from the committed rocprofv3 FETCH_SIZE/WRITE_SIZE passes (profiles/), scaled to this batch",
-                         "valu": valu,
-                         "valu_frac": (valu["min_ms_if_all_vop2"] / float(stage_ms[dom])) if valu else None,
-                         "valu_frac_at_vop3_rate": (valu["min_ms_if_all_vop3"] / float(stage_ms[dom])) if valu else None},
-            "tracking": {"align_ok": int(al["ok"].sum()), "mean_gn_iterations": its, "mean_matches": float(nm.mean()),
-                         "pnp_ok": int(np.asarray(pn["ok"]).sum()), "mean_pnp_inliers": float(pn["n_inliers"].mean()),
-                         "mean_pnp_iterations": float(pn["iterations"].mean()), "align_translation_err_m": terr},
         }
-        if args.hamming:
-            m12, n12 = trk.get_point_matches(0, B)
-            line["tracking"]["mean_point_matches"] = float(n12.mean())
-        if world == 1 and not args.no_extras:
-            # run-to-run spread (the headline is one timed region): three more blocks of the same step, each
-            # bracketed like the timed region, AFTER it; `value` stays the K-step figure above
-            blocks = []
-            nb = max(10, min(50, args.steps // 3))
-            for _ in range(3):
-                cur.sync()
-                trk.get_tracked(0, 1)
-                tb = time.perf_counter()
-                for k in range(nb):
-                    full_step(k)
-                cur.sync()
-                trk.get_tracked(0, 1)
-                blocks.append(B * nb / (time.perf_counter() - tb))
-            line["repeatability"] = {"blocks": 3, "steps_per_block": nb, "frames_per_s": blocks,
-                                     "spread": (max(blocks) - min(blocks)) / float(np.median(blocks))}
-        if world == 1 and not args.orb_only and not args.hamming and not args.no_extras:
-            line["stress"] = stress_legs(wl)
-            line["h2d_inclusive"] = h2d_leg(wl)
-            line["h2d_overlapped"] = h2d_overlapped_leg(wl)
-            if CFG[1:3] == (1.2, 8) and (W, H) == (640, 480):
-                line["drop_in"] = drop_in_leg(wl)
-        if not args.no_cpu_baseline and world == 1 and not args.orb_only and not args.hamming:
-            line["cpu_baseline"] = cpu_baseline(scenes[:min(nu, 8)], wl.lasts_u[:min(nu, 8)], wl.T0_u[:min(nu, 8)], wl.rs, pose_solver=args.pose_solver,
-                                                locals_=wl.locals_u)
-        else:
-            line["cpu_baseline"] = None
+        if args.full:
+            full_figures(line, args, wl, scenes, rec_host, orb_ms, trk_ms, full_step)
         print(json.dumps(line, default=float))
     if dist is not None:
         dist.barrier()

@@ -167,8 +167,45 @@ def test_bench_two_ranks_rehearsal(shape):
     # configs4_shard: the exact per-rank workload of BASELINE configs[4] on 8 GPUs (8192 x 1280x720 frames / 8 = 1024 per rank)
     B, extra = (64, []) if shape == "vga_b64" else (1024, ["--res", "1280x720"])
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", str(B),
-                        "--unique", "4", "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True, timeout=900)
+                        "--unique", "4", "--full", "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["frames_per_gpu_per_step"] == B and "REHEARSAL" in line["config"]["pose_records"]
     assert line["tracking"]["pnp_ok"] == B and line["value"] > 0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline line alone, and `--dump-outputs DIR` writes what its last timed step
+    computed: float32 / float64 arrays within 64 MB, the packed records agreeing with the stage read-outs, and the same
+    arrays from a run with another number of steps (seeded inputs, every step starts from the same resident state)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SD_BENCH_REHEARSAL"):
+        env.pop(k, None)
+    dumps = []
+    for steps in (3, 5):
+        d = tmp_path / f"steps{steps}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                            "--batch", "64", "--unique", "4", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+        assert line["value"] > 0 and abs(line["ms_per_step"] * steps - line["config"]["timed_region_s"] * 1e3) < 1e-6 * line["ms_per_step"] * steps
+        assert not {"stages_ms_per_step", "roofline", "stress", "cpu_baseline"} & set(line)
+        arrays = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        rec = arrays["records"]
+        assert rec.shape == (64, 20)
+        np.testing.assert_array_equal(rec[:, 17], arrays["n_matches"])
+        np.testing.assert_array_equal(rec[:, 18], arrays["pnp_n_inliers"])
+        assert arrays["keypoints"].shape[:2] == arrays["descriptors"].shape[:2] == (len(arrays["sample_frames"]), 1000)
+        assert (arrays["n_keypoints"] > 0).all() and (arrays["n_matches"] > 0).all()
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k], err_msg=k)

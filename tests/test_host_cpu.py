@@ -104,15 +104,15 @@ def test_known_level_tables(sd):
     assert (info["cells"][info["cells"][:, 0] == 4][:, 3] == 0).all()
 
 
-def _native(name, extra=()):
-    out = os.path.join("/tmp", f"sd_{name}.so")
+def _native(tmp_path, name, extra=()):
+    out = str(tmp_path / f"sd_{name}.so")
     src = os.path.join(ROOT, "tests", "native", f"{name}.cc")
     subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", *extra, src, "-o", out, "-lm"])
     return C.CDLL(out)
 
 
-def test_introselect_replays_libstdcxx_nth_element():
-    L = _native("introselect_check")
+def test_introselect_replays_libstdcxx_nth_element(tmp_path):
+    L = _native(tmp_path, "introselect_check")
     L.introselect_selftest.restype = C.c_long
     L.introselect_heap_cases.restype = C.c_long
     assert L.introselect_selftest(1, 4000, 3000, 40) == 0
@@ -126,9 +126,9 @@ def test_introselect_replays_libstdcxx_nth_element():
     assert heap_calls.value > 100      # the depth-limit / heap_select fallback really was exercised
 
 
-def test_sincosf_restatement_matches_host_libm_sampled():
+def test_sincosf_restatement_matches_host_libm_sampled(tmp_path):
     # exhaustive run (1.09e9 floats, 0 mismatches): tools/check_sincosf.cc; here every 257th float
-    exe = "/tmp/sd_check_sincosf"
+    exe = str(tmp_path / "sd_check_sincosf")
     subprocess.check_call(["g++", "-O2", "-mfma", "-ffp-contract=off", os.path.join(ROOT, "tools", "check_sincosf.cc"),
                            "-o", exe, "-lm"])
     out = subprocess.run([exe, "257"], capture_output=True, text=True)
@@ -136,15 +136,15 @@ def test_sincosf_restatement_matches_host_libm_sampled():
     assert "sin mismatches 0, cos mismatches 0" in out.stdout
 
 
-def test_hypot_restatement_matches_host_libm_sampled():
-    exe = "/tmp/sd_check_hypot"
+def test_hypot_restatement_matches_host_libm_sampled(tmp_path):
+    exe = str(tmp_path / "sd_check_hypot")
     subprocess.check_call(["g++", "-O2", "-ffp-contract=off", os.path.join(ROOT, "tools", "check_hypot.cc"), "-o", exe, "-lm"])
     out = subprocess.run([exe, "5000000"], capture_output=True, text=True)
     assert out.returncode == 0 and "hypot mismatches 0" in out.stdout, out.stdout
 
 
-def test_cpp_facade_compiles_and_links(sd):
-    exe = "/tmp/sd_facade_check"
+def test_cpp_facade_compiles_and_links(sd, tmp_path):
+    exe = str(tmp_path / "sd_facade_check")
     libdir = os.path.dirname(sd.lib_path())
     subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(ROOT, "include"),
                            os.path.join(ROOT, "tests", "native", "facade_compile.cc"), "-o", exe,
@@ -153,10 +153,10 @@ def test_cpp_facade_compiles_and_links(sd):
     assert out.returncode == 0 and "facade ok" in out.stdout, (out.returncode, out.stdout, out.stderr)
 
 
-def test_cpp_frame_overloads_compile_on_reference_shaped_types(sd):
+def test_cpp_frame_overloads_compile_on_reference_shaped_types(sd, tmp_path):
     """The Frame&-style overloads (FrameTracker in sdslam.hpp) instantiate on stand-ins for the reference's Frame /
     MapPoint / Eigen / cv::Mat types: the call sites of src/Tracking.cc:668-693 need a type alias, not a rewrite."""
-    exe = "/tmp/sd_facade_frame_check"
+    exe = str(tmp_path / "sd_facade_frame_check")
     libdir = os.path.dirname(sd.lib_path())
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"),
                            os.path.join(ROOT, "tests", "native", "facade_frame.cc"), "-o", exe,
