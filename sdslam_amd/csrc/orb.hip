@@ -509,33 +509,52 @@ __device__ __forceinline__ fu16 fmax16(fu16 a, fu16 b) { return a > b ? a : b; }
 // B = max over the arcs of min(p), a 9-arc darker than v - th exists iff v - A > th, a brighter one iff
 // B - v > th, and cornerScore = max(v - A, B - v) - 1 (the same quantity as fast_corner_score: min / max
 // of the differences d = v - p over an arc are v - max(p) / v - min(p)).  Sliding 9-windows on the ring
-// are built from 3-windows with v_max3 / v_min3: 2 x (16 + 16 + 8) instructions.  Returns the score;
-// the pixel is a corner iff score >= th.
-__device__ __forceinline__ int fast_ring_score(const uint8_t* __restrict__ c, int tp) {
-  int p[16];
-  const int v = c[0];
-  p[0] = c[3 * tp]; p[1] = c[3 * tp + 1]; p[2] = c[2 * tp + 2]; p[3] = c[tp + 3];
-  p[4] = c[3]; p[5] = c[-tp + 3]; p[6] = c[-2 * tp + 2]; p[7] = c[-3 * tp + 1];
-  p[8] = c[-3 * tp]; p[9] = c[-3 * tp - 1]; p[10] = c[-2 * tp - 2]; p[11] = c[-tp - 3];
-  p[12] = c[-3]; p[13] = c[tp - 3]; p[14] = c[2 * tp - 2]; p[15] = c[3 * tp - 1];
-  int x3[16], n3[16];
+// are built from 3-windows: 2 x (16 + 16 + 8) three-input min / max.  The pixel is a corner iff score >= th.
+// r4: TWO pixels at once (ca: low 16-bit half, cb: high half), every min / max a gfx950 v_pk_minimum3_f16 /
+// v_pk_maximum3_f16 (4.16 cycles at 8 waves per SIMD, the rate of v_max3_i32: profiles/r04_valu_microbench_pk3.json), so the
+// 80 min / max per pixel become 80 per pair.  The ring bytes go into the halves as they are, i.e. as f16 bit patterns 0..255:
+// zero and subnormals, exact and ordered like the integers only because the code object keeps f16 denormals
+// (.amdhsa_float_denorm_mode_16_64 3, the compiler default, loaded into MODE from the kernel descriptor at every launch; no
+// flag of the build turns on denormal flushing).  A and B come back out of the halves as the same integers.  The halves are
+// filled by ds_read_u8 + v_perm: the compiler does not use ds_read_u8_d16_hi for a code object that may run with SRAM ECC on.
+typedef _Float16 fh2 __attribute__((ext_vector_type(2)));
+typedef unsigned short fu2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ fh2 hmax3(fh2 a, fh2 b, fh2 c) { return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c); }
+__device__ __forceinline__ fh2 hmin3(fh2 a, fh2 b, fh2 c) { return __builtin_elementwise_minimum(__builtin_elementwise_minimum(a, b), c); }
+__device__ __forceinline__ fh2 ring_pair(const uint8_t* __restrict__ ca, const uint8_t* __restrict__ cb, int o) {
+  const fu2 r = {ca[o], cb[o]};
+  return __builtin_bit_cast(fh2, r);
+}
+__device__ __forceinline__ void fast_ring_score2(const uint8_t* __restrict__ ca, const uint8_t* __restrict__ cb, int tp, int& sa, int& sb) {
+  fh2 p[16];
+  const int va = ca[0], vb = cb[0];
+  p[0] = ring_pair(ca, cb, 3 * tp); p[1] = ring_pair(ca, cb, 3 * tp + 1); p[2] = ring_pair(ca, cb, 2 * tp + 2); p[3] = ring_pair(ca, cb, tp + 3);
+  p[4] = ring_pair(ca, cb, 3); p[5] = ring_pair(ca, cb, -tp + 3); p[6] = ring_pair(ca, cb, -2 * tp + 2); p[7] = ring_pair(ca, cb, -3 * tp + 1);
+  p[8] = ring_pair(ca, cb, -3 * tp); p[9] = ring_pair(ca, cb, -3 * tp - 1); p[10] = ring_pair(ca, cb, -2 * tp - 2); p[11] = ring_pair(ca, cb, -tp - 3);
+  p[12] = ring_pair(ca, cb, -3); p[13] = ring_pair(ca, cb, tp - 3); p[14] = ring_pair(ca, cb, 2 * tp - 2); p[15] = ring_pair(ca, cb, 3 * tp - 1);
+  fh2 x3[16], n3[16];
 #pragma unroll
   for (int k = 0; k < 16; k++) {
-    x3[k] = max(max(p[k], p[(k + 1) & 15]), p[(k + 2) & 15]);
-    n3[k] = min(min(p[k], p[(k + 1) & 15]), p[(k + 2) & 15]);
+    x3[k] = hmax3(p[k], p[(k + 1) & 15], p[(k + 2) & 15]);
+    n3[k] = hmin3(p[k], p[(k + 1) & 15], p[(k + 2) & 15]);
   }
-  // (16-bit min / max for the final reductions would issue at 2.2 instead of 4.1 cycles, but the compiler then loses the
-  // v_max3 / v_min3 merges across the two stages, or fuses pairs into v_min3_u16 / v_max3_u16 at 8.1 cycles: 365 cycles per
-  // 64 pixels either way -- measured, profiles/r03_valu_microbench*.json)
-  int A = 255, B = 0;
+  fh2 x9[16], n9[16];
 #pragma unroll
   for (int k = 0; k < 16; k++) {
-    const int x9 = max(max(x3[k], x3[(k + 3) & 15]), x3[(k + 6) & 15]);
-    const int n9 = min(min(n3[k], n3[(k + 3) & 15]), n3[(k + 6) & 15]);
-    A = min(A, x9);
-    B = max(B, n9);
+    x9[k] = hmax3(x3[k], x3[(k + 3) & 15], x3[(k + 6) & 15]);
+    n9[k] = hmin3(n3[k], n3[(k + 3) & 15], n3[(k + 6) & 15]);
   }
-  return max(v - A, B - v) - 1;
+  fh2 A = hmin3(x9[0], x9[1], x9[2]), B = hmax3(n9[0], n9[1], n9[2]);   // 8 three-input steps each over the 16 windows
+#pragma unroll
+  for (int k = 3; k < 15; k += 2) {
+    A = hmin3(A, x9[k], x9[k + 1]);
+    B = hmax3(B, n9[k], n9[k + 1]);
+  }
+  A = __builtin_elementwise_minimum(A, x9[15]);
+  B = __builtin_elementwise_maximum(B, n9[15]);
+  const fu2 Au = __builtin_bit_cast(fu2, A), Bu = __builtin_bit_cast(fu2, B);
+  sa = max(va - (int)Au.x, (int)Bu.x - va) - 1;
+  sb = max(vb - (int)Au.y, (int)Bu.y - vb) - 1;
 }
 
 #ifdef SD_PNP_PROF   // stage timers of k_fast_cells (tools/prof_select.py --fast): cycles of thread 0 per phase
@@ -572,7 +591,7 @@ __device__ unsigned long long g_fast_prof_wg[(size_t)FPROF_FRAMES * FPROF_CELLS 
 //      (a 9-arc always contains two ADJACENT compass points of the same polarity) rejects most
 //      pixels; survivors are appended, in raster order, to the wave's LDS queue (ballot prefix);
 //   B. the queue is processed densely (all lanes busy): one pass computes cornerScore from sliding
-//      min / max windows on the ring (fast_ring_score); score >= th is the corner test; corners are
+//      min / max windows on the ring (fast_ring_score2, two pixels per lane); score >= th is the corner test; corners are
 //      re-compacted in place (still raster order) and their scores go to the LDS score map;
 //   C. after a block barrier, NMS on the queued corners against the LDS score map, then ordered
 //      emission (wave bands are contiguous in raster order, so per-wave counts give offsets).
@@ -707,22 +726,35 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
 #ifdef FAST_SKIP_B   // instruction-budget experiments only (tools/fast_budget.sh): results are wrong by design
     qn = 0;
 #endif
-    // ---- B: ring test + score of the queued pixels in one pass (dense); corners re-compacted in place
+    // ---- B: ring test + score of the queued pixels in one pass (dense); corners re-compacted in place.  r4: 128 entries per
+    // chunk, a pair per lane (entry e0 + lane in the low halves, e0 + 64 + lane in the high halves: fast_ring_score2).  A lane
+    // whose high entry is past the queue's end scores its low pixel twice and drops the second result.  Corners of the low
+    // halves are compacted first, then those of the high halves: raster order.  All reads of a chunk precede its writes, which
+    // land below e0 + 128 (cn <= e0).
     int cn = 0;
-    for (int e0 = 0; e0 < qn; e0 += 64) {
-      const int e = e0 + lane;
-      bool corner = false;
-      unsigned q = 0;
-      if (e < qn) {
-        q = queue[e];
-        const int y = (int)__umulhi(q, magic), x = (int)q - __mul24(y, zw);
-        const int sc_v = fast_ring_score(tile + __mul24(y + 3, TP) + x + 3 + sh, TP);
-        corner = sc_v >= th;
-        if (corner && sc_v > 0) sc[__mul24(y + 1, SP) + x + 1] = (uint8_t)sc_v;
+    for (int e0 = 0; e0 < qn; e0 += 128) {
+      const int ea = e0 + lane, eb = ea + 64;
+      bool corner_a = false, corner_b = false;
+      unsigned qa = 0, qb = 0;
+      if (ea < qn) {
+        const bool has_b = eb < qn;
+        qa = queue[ea];
+        qb = has_b ? queue[eb] : qa;
+        const int y_a = (int)__umulhi(qa, magic), x_a = (int)qa - __mul24(y_a, zw);
+        const int y_b = (int)__umulhi(qb, magic), x_b = (int)qb - __mul24(y_b, zw);
+        int sa, sb;
+        fast_ring_score2(tile + __mul24(y_a + 3, TP) + x_a + 3 + sh, tile + __mul24(y_b + 3, TP) + x_b + 3 + sh, TP, sa, sb);
+        corner_a = sa >= th;
+        corner_b = has_b && sb >= th;
+        if (corner_a && sa > 0) sc[__mul24(y_a + 1, SP) + x_a + 1] = (uint8_t)sa;
+        if (corner_b && sb > 0) sc[__mul24(y_b + 1, SP) + x_b + 1] = (uint8_t)sb;
       }
-      const unsigned long long m = __builtin_amdgcn_ballot_w64(corner);   // all reads of this chunk precede the writes (cn <= e0)
-      if (corner) queue[cn + __popcll(m & lt)] = (uint16_t)q;
-      cn += __popcll(m);
+      const unsigned long long ma = __builtin_amdgcn_ballot_w64(corner_a);
+      if (corner_a) queue[cn + __popcll(ma & lt)] = (uint16_t)qa;
+      cn += __popcll(ma);
+      const unsigned long long mb = __builtin_amdgcn_ballot_w64(corner_b);
+      if (corner_b) queue[cn + __popcll(mb & lt)] = (uint16_t)qb;
+      cn += __popcll(mb);
     }
     qn = cn;
 #ifdef FAST_SKIP_C
