@@ -46,8 +46,8 @@ const char* sd_version(void);
  *   track.poseopt_waves        0     k_pose_opt waves per frame: 0 = by batch size (4 up to 256 frames, else 1), 1, 4
  *   track.match_split          1     SearchByProjection(Frame, Frame / KeyFrame) as candidate + one-wave assignment kernels
  *                                    (6 KB of LDS per frame through the serial part); 0: the single 39-KB kernel
- *   extract.fast0_early        1     device-input extractions: FAST of level 0 starts behind the PREVIOUS call's selection (beside its
- *                                    descriptor kernel) instead of behind the whole previous call; 0: as before
+ *   extract.fast0_early        1     device-input extractions on the handle's own stream: FAST of level 0 starts behind the PREVIOUS
+ *                                    call's selection (beside its descriptor kernel) instead of behind the whole previous call; 0: as before
  *   extract.pyr_early          0     1: ... and, on an extractor with two output sets (one a tracker is attached to), the resize chain as
  *                                    well, on the auxiliary stream in front of the blur (measured: loses 8 % with the PnP step)
  * Results never depend on an option (each setting is covered by a parity test); only speed does. */
@@ -101,7 +101,14 @@ int sd_orb_extract(sd_orb* h, const uint8_t* img, int w, int hgt, int stride,
 /* Batched-frames mode: n_frames independent frames of identical size.
  * Host variant copies in/out; device variant takes a device pointer, launches asynchronously
  * on the handle's stream and leaves the results resident (read them with sd_orb_download or
- * chain into sd_match_ / sd_align_ calls on the same handle). */
+ * chain into sd_match_ / sd_align_ calls on the same handle).
+ * When the device variant may read d_imgs: on the handle's own stream, only what was complete
+ * when the call was made (a producer the host has synchronised with) or what a stream fenced
+ * with sd_orb_stream_fence(h, stream, 1) before the call has queued -- the extraction may start
+ * on other streams of the handle ahead of the own stream (extract.fast0_early, extract.pyr_early).
+ * On a caller's stream (sd_orb_set_stream) everything queued on that stream before the call, in
+ * stream order.  The frames may be overwritten once the host has synchronised with the handle
+ * (sd_orb_sync, sd_orb_download) or behind sd_orb_stream_fence(h, stream, 0). */
 int sd_orb_extract_batch(sd_orb* h, const uint8_t* imgs, int n_frames, int w, int hgt, int stride,
                          size_t frame_stride, sd_keypoint* kps_out, uint8_t* desc_out,
                          int cap_per_frame, int32_t* n_out);
@@ -130,14 +137,17 @@ int sd_orb_debug_cell_counts(sd_orb* h, int frame, int level, int32_t* out, int 
 int sd_orb_debug_level_keys(sd_orb* h, int frame, int level, uint32_t* keys_out, int cap, int* n);
 
 /* Stream / timing plumbing (bench + rocprof).  sd_orb_set_stream: run on a caller-owned
- * hipStream_t (NULL restores the handle's own stream).  With profiling on, every extract call
+ * hipStream_t (NULL restores the handle's own stream); it first waits for the work queued on the
+ * previous stream.  On a caller's stream every extraction starts behind everything queued on that
+ * stream before the call (the early level-0 FAST launch is the own stream's alone).  With profiling on, every extract call
  * brackets each stage with HIP events on the launch stream; sd_orb_stage_ms returns the mean
  * elapsed ms per stage over the calls made since profiling was switched on (last 128 at most;
  * names from sd_orb_stage_name). */
 int sd_orb_set_stream(sd_orb* h, void* hip_stream);
 /* Ordering against a caller-owned hipStream_t (e.g. the stream that uploads the NEXT batch's frames while this batch is being
  * processed): direction 0 = that stream waits for the extractions queued so far (their input frames may then be overwritten),
- * 1 = the extractions queued from now on wait for everything queued on that stream so far (the upload of their frames). */
+ * 1 = the extractions queued from now on -- on all of the handle's streams -- wait for everything queued on that stream so far
+ * (the upload of their frames).  Every fence holds: fences on several streams order the extractions behind all of them. */
 int sd_orb_stream_fence(sd_orb* h, void* hip_stream, int direction);
 int sd_orb_sync(sd_orb* h);
 int sd_orb_set_profiling(sd_orb* h, int on);

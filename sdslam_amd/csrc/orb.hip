@@ -1511,12 +1511,12 @@ static int pipeline_body(sd_orb* h, const uint8_t* d_imgs, int n, int stride, si
   // r3: FAST of level 0 reads the caller's frames and needs nothing else of THIS call, so with frames that are already on the
   // device (frames_ready: the device-input entry point) it is ordered behind the previous SELECTION only (ev_select_done)
   // and runs beside the previous batch's descriptor kernel, a gather-latency-bound kernel that leaves the vector ALUs idle.
-  // Otherwise (host frames copied on this stream, a captured graph, option off, first call) behind everything queued so far.
-  const bool fast_early = frames_ready && !capturing && h->select_recorded && opt(OPT_FAST0_EARLY) != 0;
-  if (fast_early) {
-    SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_select_done, 0));
-    if (h->user_fence_live) SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_user_fence[1], 0));   // the upload of these frames
-  }
+  // The upload of these frames is then ordered by sd_orb_stream_fence, which makes the FAST and auxiliary streams wait as
+  // well.  Only on the handle's own stream: on a caller's stream the producer of the frames may be queued on that very
+  // stream, and stream order is the contract.  Otherwise (host frames copied on this stream, a caller's stream, a captured
+  // graph, option off, first call) behind everything queued so far.
+  const bool fast_early = frames_ready && !capturing && h->select_recorded && h->stream == h->own_stream && opt(OPT_FAST0_EARLY) != 0;
+  if (fast_early) SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_select_done, 0));
   SD_HIP_CHECK(hipEventRecord(h->ev_body_start, s));
   if (!fast_early) SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_body_start, 0));
   // r3: with two output sets (a tracker is attached) the pyramid of this call goes into the set the previous call does NOT read,
@@ -1532,7 +1532,6 @@ static int pipeline_body(sd_orb* h, const uint8_t* d_imgs, int n, int stride, si
   if (prof && !pyr_early) SD_HIP_CHECK(hipEventRecord(ev[0], s));
   if (pyr_early) {
     SD_HIP_CHECK(hipStreamWaitEvent(ps, h->ev_select_done, 0));
-    if (h->user_fence_live) SD_HIP_CHECK(hipStreamWaitEvent(ps, h->ev_user_fence[1], 0));
     if (prof) SD_HIP_CHECK(hipEventRecord(ev[0], ps));   // (the pyramid stage is timed on the stream it runs on)
   }
   const bool src_aligned = (((uintptr_t)d_imgs | (uintptr_t)stride | (uintptr_t)frame_stride) & 3) == 0;
@@ -1726,7 +1725,12 @@ static int launch_pipeline(sd_orb* h, const uint8_t* d_imgs, int n, int stride, 
       }
       if (graph) (void)hipGraphDestroy(graph);
     }
-    if (rc == SD_OK) SD_HIP_CHECK(hipGraphLaunch(ge->exec, s));
+    if (rc == SD_OK) {
+      SD_HIP_CHECK(hipGraphLaunch(ge->exec, s));
+      // a replayed selection records no event either: the next direct call's level-0 FAST must not wait for an older one
+      // (it would overwrite d_cand / d_cell_count under this graph's FAST and selection)
+      h->select_recorded = false;
+    }
   }
   if (rc != SD_OK) return rc;
   // inside a captured graph ev_pyr_done is a graph node, not an event record a later hipStreamWaitEvent could see
@@ -2135,8 +2139,10 @@ int sd_orb_set_stream(sd_orb* h, void* hip_stream) {
 
 // Ordering against a caller's HIP stream (an upload stream that fills the frames of the next batch while this one is being
 // processed).  direction 0: `hip_stream` waits for everything queued on the extraction stream so far (the frames of the
-// extractions queued so far have been consumed when it proceeds); 1: the extraction stream -- and with it the FAST stream,
-// which is ordered behind it at the start of every extraction -- waits for everything queued on `hip_stream` so far.
+// extractions queued so far have been consumed when it proceeds); 1: the extraction stream and the FAST and auxiliary
+// streams, on which an early level-0 FAST / resize chain of a later extraction reads the frames (pipeline_body), wait for
+// everything queued on `hip_stream` so far.  A wait takes the event's state at the time it is queued, so every fence
+// holds, not only the last one.
 int sd_orb_stream_fence(sd_orb* h, void* hip_stream, int direction) {
   SD_REQUIRE(h && (direction == 0 || direction == 1), SD_ERR_INVALID_ARG, "bad arguments");
   SD_HIP_CHECK(hipSetDevice(h->device));
@@ -2149,7 +2155,8 @@ int sd_orb_stream_fence(sd_orb* h, void* hip_stream, int direction) {
   } else {
     SD_HIP_CHECK(hipEventRecord(h->ev_user_fence[1], ext));
     SD_HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_user_fence[1], 0));
-    h->user_fence_live = true;   // an early level-0 FAST launch (pipeline_body) waits for it as well
+    SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_user_fence[1], 0));
+    SD_HIP_CHECK(hipStreamWaitEvent(h->aux_stream, h->ev_user_fence[1], 0));
   }
   return SD_OK;
 }

@@ -78,15 +78,19 @@ def test_image_align_matches_oracle(sd, oracle, rig, init):
     else:
         T0 = [synth.se3_exp((0.003, -0.002, 0.001), (0.05, 0.02, -0.04)) @ s["T_cur"] for s in rig["scenes"]]
     trk.set_poses(0, [s["T_ref"] for s in rig["scenes"]], T0)
-    trk.align(B, mode=0)
-    g = trk.get_align(0, B)
-    for i in range(B):
-        r = _oracle_align(oracle, rig["oras"][i], rig["scenes"][i], T0[i])
-        assert g["ok"][i] == r["ok"]
-        assert np.abs(g["T"][i] - r["T"]).max() <= POSE_TOL, (i, np.abs(g["T"][i] - r["T"]).max())
-        assert np.array_equal(g["iters"][i][:len(r["iters"])], r["iters"]), (i, g["iters"][i][:len(r["iters"])], r["iters"])
-        assert abs(g["error"][i] - r["error"]) <= 1e-7 * max(1.0, abs(r["error"]))
-        assert abs(g["chi2"][i] - r["chi2"]) <= 1e-9 * max(1.0, abs(r["chi2"]))
+    ora = [_oracle_align(oracle, rig["oras"][i], rig["scenes"][i], T0[i]) for i in range(B)]
+    # every register budget of k_align (separately compiled k_align<3> / <4> / <5>): the same bar
+    for waves in (5, 3, 4):
+        with sd.options({"track.align_min_waves": waves}):
+            trk.align(B, mode=0)
+            g = trk.get_align(0, B)
+        for i in range(B):
+            r = ora[i]
+            assert g["ok"][i] == r["ok"], waves
+            assert np.abs(g["T"][i] - r["T"]).max() <= POSE_TOL, (waves, i, np.abs(g["T"][i] - r["T"]).max())
+            assert np.array_equal(g["iters"][i][:len(r["iters"])], r["iters"]), (waves, i, g["iters"][i][:len(r["iters"])], r["iters"])
+            assert abs(g["error"][i] - r["error"]) <= 1e-7 * max(1.0, abs(r["error"])), waves
+            assert abs(g["chi2"][i] - r["chi2"]) <= 1e-9 * max(1.0, abs(r["chi2"])), waves
 
 
 def test_image_align_modes(sd, oracle, rig):
@@ -317,13 +321,17 @@ def test_epnp_device_vs_oracle(sd, oracle):
         assert np.abs(R - Rg).max() <= 1e-9 and np.abs(t - tg).max() <= 1e-9, (trial, n, np.abs(t - tg).max())
 
 
-@pytest.mark.parametrize("opts", [{}, {"extract.fast0_early": 0}, {"extract.pyr_early": 1}, {"track.align_start": 0}, {"track.align_start": 1}],
-                         ids=["default", "fast0_late", "pyr_early", "align_after_extraction", "align_after_pyramid"])
+@pytest.mark.parametrize("opts", [{}, {"extract.fast0_early": 0}, {"extract.pyr_early": 1}, {"track.align_start": 0}, {"track.align_start": 1},
+                                  {"track.stream_priority": 0}, {"track.stream_priority": 1}],
+                         ids=["default", "fast0_late", "pyr_early", "align_after_extraction", "align_after_pyramid", "track_prio_low",
+                              "track_prio_normal"])
 def test_pipelined_steps_match_isolated_steps(sd, oracle, opts):
     """Back-to-back steps without host synchronisation (extraction of batch n+1 overlaps tracking of batch n on
     the double-buffered extractor; level-0 FAST -- and optionally the resize chain -- of batch n+1 start behind the
     SELECTION of batch n, beside its descriptors) give exactly the results of the same steps run one at a time, under
-    every setting of the scheduling options."""
+    every setting of the scheduling options (track.stream_priority is read when the Tracker is created, inside the
+    option scope).  Every step's records are packed on the device into a slice of their own and compared, not only the
+    last step's read-outs."""
     with sd.options(opts):
         _pipelined_vs_isolated(sd)
 
@@ -338,18 +346,22 @@ def _pipelined_vs_isolated(sd):
     trk.set_camera(*K, 0.0, BOUNDS)
     rs = synth.glibc_rand_stream(800)
     trk.set_rand(0, np.tile(rs, (B, 1)))
-    from sdslam_amd.capi import DeviceBuffer
+    from sdslam_amd.capi import DeviceBuffer, _check, _p, lib
 
     def prepare(scenes):
         rk, rd, rn = ref.extract_batch(np.stack([s["ref"] for s in scenes]))
         trk.set_last(0, [synth.tracking_case(i, rk[i, :rn[i]], rd[i, :rn[i]]) for i in range(B)])
         trk.set_poses(0, [s["T_ref"] for s in scenes], [s["T_cur"] for s in scenes])
 
-    def run(d_frames):
+    rec = DeviceBuffer(6 * B * 160)       # records, B x 20 doubles per step: 0, 1 = isolated A, B; 2..5 = the pipelined steps
+    rec.upload(np.full((6 * B, 20), -7.0))
+
+    def run(d_frames, slot):
         cur.extract_batch_device(d_frames.ptr, B, 640, 480)
         trk.align(B, 0)
         trk.match(B, 8.0, True, True)
         trk.pnp(B, 0.99, 10, 200, 4, 0.28, 5.991, 200)
+        trk.pack_records(B, 0, rec.ptr.value + slot * B * 160)
 
     def results():
         al, (cm, nm), pn = trk.get_align(0, B), trk.get_matches(0, B), trk.get_pnp(0, B)
@@ -362,17 +374,26 @@ def _pipelined_vs_isolated(sd):
         db = DeviceBuffer(fr.nbytes)
         db.upload(fr)
         bufs.append(db)
-    # isolated: B alone (same last-frame state as in the pipelined run below)
+    # isolated: A alone, then B alone (same last-frame state as in the pipelined run below)
     prepare(scenes_b)
-    run(bufs[1])
+    run(bufs[0], 0)
+    results()
+    run(bufs[1], 1)
     iso = results()
-    # pipelined: A, then B, then A, then B without any host sync in between; last results must equal `iso`
-    for j in (0, 1, 0, 1):
-        run(bufs[j])
+    # pipelined: A, then B, then A, then B without any host sync in between; last results must equal `iso`, every step's
+    # records those of the isolated step on the same frames
+    for k, j in enumerate((0, 1, 0, 1)):
+        run(bufs[j], 2 + k)
     pip = results()
     for x, y in zip(iso, pip):
         assert np.array_equal(x, y)
     assert pip[2].min() > 50
+    got = np.zeros((6, B, 20))
+    _check(lib().sd_dev_download(_p(got), rec.ptr, got.nbytes))
+    assert not np.array_equal(got[0], got[1])
+    for k, j in enumerate((0, 1, 0, 1)):
+        assert np.array_equal(got[2 + k], got[j]), ("step", k)
+    rec.free()
 
 
 def test_local_map_search_bit_exact(sd, oracle, rig):
