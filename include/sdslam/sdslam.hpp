@@ -123,7 +123,7 @@ struct LastFrameView {
 class TrackBatch {
  public:
   TrackBatch(ORBextractor& cur, ORBextractor& ref, int max_points, int max_batch, int pnp_max_iterations = 300)
-      : max_points_(max_points) {
+      : max_points_(max_points), cur_(&cur), ref_(&ref) {
     check(sd_track_create(cur.handle(), ref.handle(), max_points, max_batch, pnp_max_iterations, &h_));
   }
   ~TrackBatch() { sd_track_destroy(h_); }
@@ -170,11 +170,43 @@ class TrackBatch {
   }
   // stereo frames: mvuRight computed by the caller (-1 = no match)
   void SetURight(int frame, const float* mvuRight, int n) { check(sd_track_set_uright(h_, frame, 1, mvuRight, n)); }
+
+  // Sequential tracking: mLastFrame = Frame(mCurrentFrame) on the device (src/Tracking.cc:250-292).  Per frame:
+  //   CurrentExtractor() extracts -> SetPrior -> Tracking::TrackWithMotionModel -> Tracking::TrackLocalMap -> AdvanceLastFrame.
+  // ids: the caller's MapPoint identities (which 0: the last frame's points, 1: the local map's; -1 = none).  With both set,
+  // TrackLocalMap skips the local points TrackWithMotionModel saw (mnLastFrameSeen, :703, :900-918).
+  void SetMapIds(int frame, int which, const int32_t* ids, int n) { check(sd_track_set_map_ids(h_, frame, 1, which, ids, n)); }
+  // source 1: after TrackLocalMap; 0: after TrackWithMotionModel.  The extractors swap roles afterwards.
+  void AdvanceLastFrame(int n_frames, int source = 1) { check(sd_track_advance(h_, n_frames, source)); }
+  // CurrentFrame pose prior, 16 doubles column-major per frame: T (relative = false) or T * LastFrame.GetPose()
+  // (ConstantVelocity::GetPose, relative = true)
+  void SetPrior(int frame0, int n_frames, const double* T_cm, bool relative) {
+    check(sd_track_set_prior(h_, frame0, n_frames, T_cm, relative ? 1 : 0));
+  }
+  // the last frame of slot `frame` (what AdvanceLastFrame or SetLastFrame left); ids may be null
+  void GetLastFrame(int frame, LastFrameView& v, std::vector<int32_t>* ids = nullptr) {
+    const size_t M = max_points_;
+    int32_t n = 0;
+    v.valid.resize(M); v.Xw.resize(M * 3); v.desc.resize(M * 32); v.octave.resize(M); v.angle.resize(M); v.obs.resize(M);
+    if (ids) ids->resize(M);
+    check(sd_track_get_last(h_, frame, 1, &n, v.valid.data(), v.Xw.data(), v.desc.data(), v.octave.data(), v.angle.data(), v.obs.data(),
+                            ids ? ids->data() : nullptr));
+    v.valid.resize(n); v.Xw.resize((size_t)n * 3); v.desc.resize((size_t)n * 32); v.octave.resize(n); v.angle.resize(n); v.obs.resize(n);
+    if (ids) ids->resize(n);
+  }
+  // the extractor whose frames are tracked next (the two swap roles at every AdvanceLastFrame)
+  ORBextractor& CurrentExtractor() {
+    sd_orb* c = nullptr;
+    check(sd_track_get_extractors(h_, &c, nullptr));
+    return c == cur_->handle() ? *cur_ : *ref_;
+  }
   sd_track* handle() { return h_; }
 
  private:
   sd_track* h_ = nullptr;
   int max_points_;
+  ORBextractor* cur_;
+  ORBextractor* ref_;
 };
 
 class ImageAlign {

@@ -350,6 +350,40 @@ int sd_track_debug_features_in_area(sd_track* h, int frame, float x, float y, fl
  * sd_track_stream_fence orders the tracking stream against a caller's hipStream_t (the stream of its RCCL collective):
  * direction 0 = that stream waits for the tracking stream, 1 = the tracking stream waits for that stream. */
 int sd_track_pack_records(sd_track* h, int n_frames, int source, void* d_records);
+
+/* ------------------------------------------------------------------------------------------
+ * Sequential tracking: B camera streams tracked frame after frame, the hand-off on the device
+ *   mLastFrame = Frame(mCurrentFrame)             src/Tracking.cc:292, after
+ *     "Clean VO matches" (Observations() < 1)     src/Tracking.cc:250-257
+ *     outliers discarded                          src/Tracking.cc:272-275
+ *   mnLastFrameSeen skip of SearchLocalPoints     src/Tracking.cc:703, :900-918
+ *   ConstantVelocity::GetPose  Exp(vel) * last_pose_ (the prior; the velocity stays an input)
+ * One frame per call on every slot:
+ *   extract into sd_track_get_extractors' cur -> sd_track_set_prior -> sd_track_with_motion_model ->
+ *   [sd_track_local_map] -> sd_track_advance.
+ * sd_track_set_map_ids: the caller's identity of every map point, which = 0 last-frame arrays, 1 local-map arrays, [n][cap]
+ *   rows (cap <= max_points, the rest -1), -1 = none.  sd_track_set_last resets the last-frame ids of its slots to -1.  Once ids
+ *   are set, sd_track_local_map skips a local point whose id equals the id of a last-frame point that the final search of
+ *   sd_track_with_motion_model (run on this extraction) matched, before or after its outlier discard: the `cand` flags no
+ *   longer have to exclude them.  Points without ids (-1) are never skipped, so without ids nothing changes.
+ * sd_track_advance: for every slot < n_frames and current keypoint i < N, the last frame's point i becomes mvpMapPoints[i]
+ *   (source 0: after sd_track_with_motion_model's discard; 1: after sd_track_local_map, local points included, mvbOutlier
+ *   dropped), kept iff it has Observations() >= 1, with its Xw / descriptor / obs / id; octave = mvKeys[i].octave, angle =
+ *   mvKeysUn[i].angle; n_last = N; Tref = the frame's final pose (the prior when no pose solve ran).  Slots >= n_frames keep
+ *   their last frame.  Then the cur / ref extractors swap roles (this frame's pyramid and keypoints are the next reference):
+ *   extract the next frame into the new cur.  Queued on the tracking stream; that extraction waits for the kernels that
+ *   still read the set it overwrites.  SD_ERR_CAPACITY: keypoint capacity > max_points; SD_ERR_INVALID_ARG: the call named
+ *   by `source` has not run since the last extraction, or broadcast mode is on.
+ * sd_track_set_prior: Tprior = Tcur = T (relative 0) or T * Tref computed on the device (relative 1; each entry sums k = 0..3
+ *   in order, without FMA contraction), column-major, queued on the tracking stream without a host wait.  Tref is left alone.
+ * sd_track_get_last: the last-frame arrays in [n][max_points] layout; any pointer may be NULL.
+ * sd_track_get_extractors: the handles in the cur / ref roles now. */
+int sd_track_set_map_ids(sd_track* h, int frame0, int n_frames, int which, const int32_t* ids, int cap);
+int sd_track_advance(sd_track* h, int n_frames, int source);
+int sd_track_set_prior(sd_track* h, int frame0, int n_frames, const double* T_cm, int relative);
+int sd_track_get_last(sd_track* h, int frame0, int n_frames, int32_t* n_last, uint8_t* valid, double* Xw, uint8_t* desc, int32_t* octave,
+                      float* angle, int32_t* obs, int32_t* ids);
+int sd_track_get_extractors(sd_track* h, sd_orb** cur, sd_orb** ref);
 int sd_track_stream_fence(sd_track* h, void* hip_stream, int direction);
 int sd_track_set_profiling(sd_track* h, int on);
 int sd_track_stage_ms(sd_track* h, float* ms_out /* [0]=align, [1]=match, [2]=pnp */, int cap);

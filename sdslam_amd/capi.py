@@ -641,6 +641,50 @@ class Tracker:
         self.L.sd_track_stream_fence.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _check(self.L.sd_track_stream_fence(self.h, C.c_void_p(stream_ptr) if stream_ptr else None, int(direction)))
 
+    # --- sequential tracking: the last-frame hand-off on the device (src/Tracking.cc:250-292) ---
+    def set_map_ids(self, frame0, ids_list, which=0):
+        """The caller's identity of each map point, one array per slot (-1 = none); which 0: last-frame points, 1: local map."""
+        n, M = len(ids_list), self.M
+        ids = np.full((n, M), -1, np.int32)
+        for i, v in enumerate(ids_list):
+            v = np.asarray(v, np.int32)
+            assert len(v) <= M
+            ids[i, :len(v)] = v
+        self.L.sd_track_set_map_ids.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        _check(self.L.sd_track_set_map_ids(self.h, frame0, n, int(which), _p(ids), M))
+
+    def advance(self, n_frames, source=1):
+        """mLastFrame = Frame(mCurrentFrame) for every slot on the device; source 0: after track_with_motion_model, 1: after
+        track_local_map.  The extractors swap roles: extract the next frame into `self.cur`."""
+        self.L.sd_track_advance.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(self.L.sd_track_advance(self.h, n_frames, int(source)))
+        self._follow_extractors()
+
+    def _follow_extractors(self):
+        cur, ref = C.c_void_p(), C.c_void_p()
+        self.L.sd_track_get_extractors.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        _check(self.L.sd_track_get_extractors(self.h, C.byref(cur), C.byref(ref)))
+        if cur.value != self.cur.h.value:
+            self.cur, self.ref = self.ref, self.cur
+        assert cur.value == self.cur.h.value and ref.value == self.ref.h.value
+
+    def set_prior(self, frame0, T_list, relative=False):
+        """Tprior = Tcur = T (relative False) or T @ Tref computed on the device (ConstantVelocity::GetPose); Tref stays."""
+        a = np.ascontiguousarray(np.stack([_cm(T) for T in T_list]))
+        self.L.sd_track_set_prior.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        _check(self.L.sd_track_set_prior(self.h, frame0, len(T_list), _p(a), int(bool(relative))))
+
+    def get_last(self, frame0, n):
+        """The last-frame arrays, [n][max_points] layout."""
+        M = self.M
+        out = dict(n_last=np.zeros(n, np.int32), valid=np.zeros((n, M), np.uint8), Xw=np.zeros((n, M, 3)), desc=np.zeros((n, M, 32), np.uint8),
+                   octave=np.zeros((n, M), np.int32), angle=np.zeros((n, M), np.float32), obs=np.zeros((n, M), np.int32),
+                   ids=np.zeros((n, M), np.int32))
+        self.L.sd_track_get_last.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
+        _check(self.L.sd_track_get_last(self.h, frame0, n, *[_p(out[k]) for k in ("n_last", "valid", "Xw", "desc", "octave", "angle", "obs",
+                                                                                 "ids")]))
+        return out
+
     def set_profiling(self, on=True):
         _check(self.L.sd_track_set_profiling(self.h, int(on)))
 

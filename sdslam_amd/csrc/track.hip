@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <string>
 #include <vector>
 
@@ -49,6 +50,20 @@ struct sd_track {
   hipStream_t pnp_stream = nullptr;
   bool profiling = false;
   hipEvent_t ev_fence = nullptr;   // sd_track_stream_fence
+  // sequential tracking (sd_track_advance): the last call of each kind since the extraction of `cur` it read --
+  // [0] sd_track_with_motion_model, [1] sd_track_local_map -- as (extractor, its extraction serial, slots)
+  const sd_orb* ran_cur[2] = {nullptr, nullptr};
+  unsigned long long ran_serial[2] = {0, 0};
+  int ran_n[2] = {0, 0};
+  bool ids_on = false;             // sd_track_set_map_ids has been called: sd_track_local_map applies the seen-point exclusion
+  // sd_track_set_prior: host poses go through a ring of pinned buffers into d_prior, all on the tracking stream, so the call
+  // queues behind the hand-off that wrote Tref without a host wait (a slot is reused once the copy out of it has run)
+  static const int kPriorRing = 4;
+  double* prior_host[kPriorRing] = {};
+  hipEvent_t ev_prior[kPriorRing] = {};
+  bool prior_pending[kPriorRing] = {};
+  int prior_next = 0;
+  double* d_prior = nullptr;       // [max_batch][16]
   static const int kRing = 128;
   hipEvent_t ev[kRing][6] = {};
   int ev_calls[3] = {0, 0, 0};
@@ -81,6 +96,93 @@ __global__ void k_pack_records(TrackBuffers tb, int source, int n_frames, double
   else { ok = tb.al_ok[f]; }
   r[18] = inl;
   r[19] = ok;
+}
+
+// Tracking::Track's hand-off to the next frame (reference src/Tracking.cc:250-292), one workgroup per slot, into the second
+// last-frame SoA (the host swaps the two afterwards: what is read and what is written overlap).  Keypoint i < N of the current
+// frame keeps map point m = mvpMapPoints[i] -- source 0: cur_match after TrackWithMotionModel's outlier discard; 1: un_match
+// after TrackLocalMap, m >= M naming local point m - M -- iff it is there, not an outlier (mvbOutlier, source 1) and has
+// Observations() >= 1 ("Clean VO matches" :250-257, outliers :272-275).  Kept points carry Xw / descriptor / obs / id; the
+// others zeros and id -1.  octave = mvKeys[i].octave, angle = mvKeysUn[i].angle; n_last = N; Tref = the frame's final pose,
+// which both tracking tails leave in Tcur.  Slots >= n_frames keep their last frame (copied across).
+__global__ __launch_bounds__(256) void k_advance(const sd_keypoint* __restrict__ kps_all, const sd_keypoint* __restrict__ kps_un_all,
+                                                 const int32_t* __restrict__ nkp_all, TrackBuffers tb, int source, int n_frames) {
+  const int f = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
+  const int M = tb.max_points, cap = tb.kp_cap;
+  const size_t o = (size_t)f * M;
+  if (f >= n_frames) {
+    for (int i = tid; i < M; i += NT) {
+      const size_t e = o + i;
+      tb.valid2[e] = tb.valid[e];
+      for (int k = 0; k < 3; k++) tb.Xw2[e * 3 + k] = tb.Xw[e * 3 + k];
+      ((uint4*)tb.mp_desc2)[e * 2] = ((const uint4*)tb.mp_desc)[e * 2];
+      ((uint4*)tb.mp_desc2)[e * 2 + 1] = ((const uint4*)tb.mp_desc)[e * 2 + 1];
+      tb.octave2[e] = tb.octave[e];
+      tb.angle2[e] = tb.angle[e];
+      tb.obs2[e] = tb.obs[e];
+      tb.last_id2[e] = tb.last_id[e];
+    }
+    return;
+  }
+  const int N = min(nkp_all[f], cap);   // cap <= M (sd_track_advance)
+  const int32_t* match = (source == 0 ? tb.cur_match : tb.un_match) + (size_t)f * cap;
+  const uint8_t* outl = tb.po_outlier + (size_t)f * cap;
+  for (int i = tid; i < M; i += NT) {
+    uint8_t v = 0;
+    double X0 = 0, X1 = 0, X2 = 0;
+    int ob = 0, id = -1, oct = 0;
+    float ang = 0.f;
+    uint4 d0 = make_uint4(0, 0, 0, 0), d1 = d0;
+    if (i < N) {
+      oct = kps_all[(size_t)f * cap + i].octave;
+      ang = kps_un_all[(size_t)f * cap + i].angle;
+      const int m = match[i];
+      if (m >= 0 && !(source == 1 && outl[i])) {
+        const bool loc = m >= M;
+        const size_t e = o + (loc ? m - M : m);
+        const int n_obs = loc ? tb.lm_obs[e] : tb.obs[e];
+        if (n_obs >= 1) {
+          const double* X = (loc ? tb.lm_Xw : tb.Xw) + e * 3;
+          const uint4* d = (const uint4*)(loc ? tb.lm_desc : tb.mp_desc) + e * 2;
+          v = 1;
+          X0 = X[0]; X1 = X[1]; X2 = X[2];
+          d0 = d[0]; d1 = d[1];
+          ob = n_obs;
+          id = loc ? tb.lm_id[e] : tb.last_id[e];
+        }
+      }
+    }
+    const size_t e = o + i;
+    tb.valid2[e] = v;
+    tb.Xw2[e * 3] = X0;
+    tb.Xw2[e * 3 + 1] = X1;
+    tb.Xw2[e * 3 + 2] = X2;
+    ((uint4*)tb.mp_desc2)[e * 2] = d0;
+    ((uint4*)tb.mp_desc2)[e * 2 + 1] = d1;
+    tb.octave2[e] = oct;
+    tb.angle2[e] = ang;
+    tb.obs2[e] = ob;
+    tb.last_id2[e] = id;
+  }
+  if (tid == 0) tb.n_last[f] = N;
+  if (tid < 16) tb.Tref[(size_t)f * 16 + tid] = tb.Tcur[(size_t)f * 16 + tid];
+}
+
+// sd_track_set_prior: Tprior = Tcur = T (relative 0) or T * Tref (relative 1: ConstantVelocity::GetPose, Exp(vel) * last_pose_),
+// column-major; each entry sums k = 0..3 in order with explicit roundings (no FMA contraction), as a plain host loop does.
+__global__ void k_set_prior(const double* __restrict__ Tin, TrackBuffers tb, int frame0, int n, int relative) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * 16) return;
+  const int f = frame0 + t / 16, e = t % 16, c = e / 4, r = e % 4;
+  const double* T = Tin + (size_t)(t / 16) * 16;
+  double v = T[e];
+  if (relative) {
+    const double* R = tb.Tref + (size_t)f * 16;
+    v = __dmul_rn(T[r], R[c * 4]);
+    for (int k = 1; k < 4; k++) v = __dadd_rn(v, __dmul_rn(T[k * 4 + r], R[c * 4 + k]));
+  }
+  tb.Tprior[(size_t)f * 16 + e] = v;
+  tb.Tcur[(size_t)f * 16 + e] = v;
 }
 
 template <typename T>
@@ -133,6 +235,18 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &tb.angle, B * M));
   A(dalloc(h, &tb.obs, B * M));
   A(dalloc(h, &tb.n_last, B));
+  A(dalloc(h, &tb.last_id, B * M));
+  A(dalloc(h, &tb.valid2, B * M));
+  A(dalloc(h, &tb.Xw2, B * M * 3));
+  A(dalloc(h, &tb.mp_desc2, B * M * 32));
+  A(dalloc(h, &tb.octave2, B * M));
+  A(dalloc(h, &tb.angle2, B * M));
+  A(dalloc(h, &tb.obs2, B * M));
+  A(dalloc(h, &tb.last_id2, B * M));
+  A(dalloc(h, &tb.tw_seen, B * K));
+  A(dalloc(h, &tb.tw_seen_ids, B * K));
+  A(dalloc(h, &tb.lm_id, B * M));
+  A(dalloc(h, &h->d_prior, B * 16));
   A(dalloc(h, &tb.Tref, B * 16));
   A(dalloc(h, &tb.Tprior, B * 16));
   A(dalloc(h, &tb.Tcur, B * 16));
@@ -198,6 +312,11 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
     if (e0 == hipSuccess) e0 = hipMemset(tb.cur_match, 0xFF, (size_t)B * K * 4);
     if (e0 == hipSuccess) e0 = hipMemset(tb.lm_match, 0xFF, (size_t)B * K * 4);
     if (e0 == hipSuccess) e0 = hipMemset(tb.un_match, 0xFF, (size_t)B * K * 4);
+    if (e0 == hipSuccess) e0 = hipMemset(tb.tw_seen, 0xFF, (size_t)B * K * 4);
+    // no ids: the seen-point exclusion never fires and the hand-off carries -1
+    if (e0 == hipSuccess) e0 = hipMemset(tb.last_id, 0xFF, (size_t)B * M * 4);
+    if (e0 == hipSuccess) e0 = hipMemset(tb.last_id2, 0xFF, (size_t)B * M * 4);
+    if (e0 == hipSuccess) e0 = hipMemset(tb.lm_id, 0xFF, (size_t)B * M * 4);
     if (e0 != hipSuccess) { set_error(std::string("sd_track_create: ") + hipGetErrorString(e0)); rc = SD_ERR_HIP; }
   }
   if (rc == SD_OK) {
@@ -228,6 +347,10 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
     }
     for (int r = 0; r < sd_track::kRing && e == hipSuccess; r++)
       for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipEventCreate(&h->ev[r][i]);
+    for (int r = 0; r < sd_track::kPriorRing && e == hipSuccess; r++) {
+      e = hipHostMalloc((void**)&h->prior_host[r], B * 16 * sizeof(double), hipHostMallocDefault);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_prior[r], hipEventDisableTiming);
+    }
     if (e == hipSuccess) {
       // Priority of the tracking stream.  Round 1 (extraction kernels at 6-7 waves per SIMD): lowest was best (122.3 k vs
       // 119.2 k frames/s at highest) -- the few, long-running, latency-bound tracking workgroups filled what the extraction
@@ -263,6 +386,10 @@ void sd_track_destroy(sd_track* h) {
   if (h->pnp_stream) (void)hipStreamDestroy(h->pnp_stream);
   for (void* p : h->allocs) (void)hipFree(p);
   if (h->ev_fence) (void)hipEventDestroy(h->ev_fence);
+  for (int r = 0; r < sd_track::kPriorRing; r++) {
+    if (h->prior_host[r]) (void)hipHostFree(h->prior_host[r]);
+    if (h->ev_prior[r]) (void)hipEventDestroy(h->ev_prior[r]);
+  }
   for (int r = 0; r < sd_track::kRing; r++)
     for (int i = 0; i < 6; i++)
       if (h->ev[r][i]) (void)hipEventDestroy(h->ev[r][i]);
@@ -310,6 +437,7 @@ int sd_track_set_last(sd_track* h, int frame0, int n_frames, const int32_t* n_la
   SD_HIP_CHECK(hipMemcpyAsync(tb.octave + o * M, octave, n_frames * M * 4, hipMemcpyHostToDevice, s));
   SD_HIP_CHECK(hipMemcpyAsync(tb.angle + o * M, angle, n_frames * M * 4, hipMemcpyHostToDevice, s));
   SD_HIP_CHECK(hipMemcpyAsync(tb.obs + o * M, obs, n_frames * M * 4, hipMemcpyHostToDevice, s));
+  SD_HIP_CHECK(hipMemsetAsync(tb.last_id + o * M, 0xFF, n_frames * M * 4, s));   // new points: no ids until sd_track_set_map_ids
   SD_HIP_CHECK(hipStreamSynchronize(s));
   return SD_OK;
 }
@@ -366,6 +494,16 @@ static int mark_reads(sd_track* h, bool used_ref) {
     r->set_busy[r->set] = true;
   }
   return SD_OK;
+}
+
+// sequential tracking: which whole-function call last ran on the current extraction of `cur` (sd_track_advance's source)
+static void note_run(sd_track* h, int which, int n_frames) {
+  h->ran_cur[which] = h->cur;
+  h->ran_serial[which] = h->cur->extract_serial;
+  h->ran_n[which] = n_frames;
+}
+static bool ran_since_extract(const sd_track* h, int which, int n_frames) {
+  return h->ran_cur[which] == h->cur && h->ran_serial[which] == h->cur->extract_serial && n_frames <= h->ran_n[which];
 }
 
 // per_cur_frame: the call walks the frames of `cur` themselves (not tracker slots), so the broadcast does not apply
@@ -588,6 +726,7 @@ int sd_track_with_motion_model(sd_track* h, int n_frames, int align_mode, float 
   rc = launch_pose_opt(h->cur, tb, h->cam, h->d_inv_sigma2, 0, n_frames, s, min_matches, min_inliers);
   if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev2[5], s)); h->ev_calls[2]++; }
   if (rc == SD_OK) rc = mark_reads(h, false);
+  if (rc == SD_OK) note_run(h, 0, n_frames);
   return rc;
 }
 
@@ -607,13 +746,17 @@ int sd_track_local_map(sd_track* h, int n_frames, float th, float nnratio, float
   hipEvent_t* ev1 = h->ev[h->ev_calls[1] % sd_track::kRing];
   hipEvent_t* ev2 = h->ev[h->ev_calls[2] % sd_track::kRing];
   if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev1[2], s));
-  rc = launch_match_local(h->cur, h->tb, h->cam, h->d_sf, h->d_scale_thr, h->cur->nlevels, n_frames, th, nnratio, viewing_cos_limit, s, 1);
+  // seen-point exclusion: ids given, and tw_seen holds this extraction's TrackWithMotionModel result for these slots
+  const int exclude = h->ids_on && ran_since_extract(h, 0, n_frames) ? 1 : 0;
+  rc = launch_match_local(h->cur, h->tb, h->cam, h->d_sf, h->d_scale_thr, h->cur->nlevels, n_frames, th, nnratio, viewing_cos_limit, s, 1, 0,
+                          exclude);
   if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev1[3], s)); h->ev_calls[1]++; }
   if (rc != SD_OK) return rc;
   if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev2[4], s));
   rc = launch_pose_opt(h->cur, h->tb, h->cam, h->d_inv_sigma2, 2, n_frames, s, 0, min_inliers);
   if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev2[5], s)); h->ev_calls[2]++; }
   if (rc == SD_OK) rc = mark_reads(h, false);
+  if (rc == SD_OK) note_run(h, 1, n_frames);
   return rc;
 }
 
@@ -1055,6 +1198,105 @@ int sd_track_stream_fence(sd_track* h, void* hip_stream, int direction) {
     SD_HIP_CHECK(hipEventRecord(h->ev_fence, ext));
     SD_HIP_CHECK(hipStreamWaitEvent(h->pnp_stream, h->ev_fence, 0));
   }
+  return SD_OK;
+}
+
+// ---- sequential tracking: the last-frame hand-off on the device (Tracking::Track, src/Tracking.cc:250-292)
+
+int sd_track_set_map_ids(sd_track* h, int frame0, int n_frames, int which, const int32_t* ids, int cap) {
+  TRACK_RANGE(h, frame0, n_frames);
+  SD_REQUIRE(which == 0 || which == 1, SD_ERR_INVALID_ARG, "which must be 0 (last-frame points) or 1 (local map points)");
+  SD_REQUIRE(ids && cap >= 1 && cap <= h->max_points, SD_ERR_INVALID_ARG, "bad id array (cap must be 1..max_points)");
+  const size_t M = h->max_points;
+  int32_t* dst = (which == 0 ? h->tb.last_id : h->tb.lm_id) + (size_t)frame0 * M;
+  hipStream_t s = h->cur->stream;
+  SD_HIP_CHECK(hipMemsetAsync(dst, 0xFF, (size_t)n_frames * M * 4, s));
+  SD_HIP_CHECK(hipMemcpy2DAsync(dst, M * 4, ids, (size_t)cap * 4, (size_t)cap * 4, n_frames, hipMemcpyHostToDevice, s));
+  SD_HIP_CHECK(hipStreamSynchronize(s));
+  h->ids_on = true;
+  return SD_OK;
+}
+
+int sd_track_advance(sd_track* h, int n_frames, int source) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
+  SD_REQUIRE(source == 0 || source == 1, SD_ERR_INVALID_ARG, "source must be 0 (sd_track_with_motion_model) or 1 (sd_track_local_map)");
+  SD_REQUIRE(h->kp_cap <= h->max_points, SD_ERR_CAPACITY, "the keypoint capacity exceeds max_points: a last frame would not fit");
+  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
+  SD_REQUIRE(ran_since_extract(h, source, n_frames), SD_ERR_INVALID_ARG,
+             source == 0 ? "sd_track_with_motion_model has not run on these slots since the last extraction"
+                         : "sd_track_local_map has not run on these slots since the last extraction");
+  int nsel_ref = 0;
+  for (int q : h->ref->hp.quota) nsel_ref += q;
+  SD_REQUIRE(nsel_ref == h->kp_cap && h->cur->max_batch >= h->max_batch, SD_ERR_INVALID_ARG,
+             "cur / ref extractors must share the keypoint capacity and hold max_batch frames to swap roles");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  // the new `cur` is extracted into next while tracking kernels may still read its last output set: it needs two
+  int rc = orb_enable_double_buffer(h->ref);
+  if (rc != SD_OK) return rc;
+  hipStream_t s = h->pnp_stream;
+  rc = wait_inputs(h, false);
+  if (rc != SD_OK) return rc;
+  const sd_orb* c = h->cur;
+  hipLaunchKernelGGL(k_advance, dim3(h->max_batch), dim3(256), 0, s, c->d_kps, c->have_dist ? c->d_kps_un : c->d_kps, c->d_nout, h->tb, source,
+                     n_frames);
+  SD_HIP_CHECK(hipGetLastError());
+  rc = mark_reads(h, false);
+  if (rc != SD_OK) return rc;
+  TrackBuffers& tb = h->tb;   // launches queued from now on see the new last frame
+  std::swap(tb.valid, tb.valid2);
+  std::swap(tb.Xw, tb.Xw2);
+  std::swap(tb.mp_desc, tb.mp_desc2);
+  std::swap(tb.octave, tb.octave2);
+  std::swap(tb.angle, tb.angle2);
+  std::swap(tb.obs, tb.obs2);
+  std::swap(tb.last_id, tb.last_id2);
+  std::swap(h->cur, h->ref);   // this frame's pyramid and keypoints are the next ImageAlign / match reference
+  h->have_pnp = false;
+  h->ran_cur[0] = h->ran_cur[1] = nullptr;
+  return SD_OK;
+}
+
+int sd_track_set_prior(sd_track* h, int frame0, int n_frames, const double* T_cm, int relative) {
+  SD_REQUIRE(h && T_cm, SD_ERR_INVALID_ARG, "NULL argument");
+  SD_REQUIRE(frame0 >= 0 && n_frames >= 1 && frame0 + n_frames <= h->max_batch, SD_ERR_CAPACITY, "frame range exceeds max_batch");
+  SD_REQUIRE(relative == 0 || relative == 1, SD_ERR_INVALID_ARG, "relative must be 0 or 1");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  const int r = h->prior_next;
+  h->prior_next = (r + 1) % sd_track::kPriorRing;
+  if (h->prior_pending[r]) SD_HIP_CHECK(hipEventSynchronize(h->ev_prior[r]));   // its copy of kPriorRing calls ago has run
+  std::memcpy(h->prior_host[r], T_cm, (size_t)n_frames * 128);
+  hipStream_t s = h->pnp_stream;
+  SD_HIP_CHECK(hipMemcpyAsync(h->d_prior, h->prior_host[r], (size_t)n_frames * 128, hipMemcpyHostToDevice, s));
+  SD_HIP_CHECK(hipEventRecord(h->ev_prior[r], s));
+  h->prior_pending[r] = true;
+  hipLaunchKernelGGL(k_set_prior, dim3((n_frames * 16 + 255) / 256), dim3(256), 0, s, h->d_prior, h->tb, frame0, n_frames, relative);
+  SD_HIP_CHECK(hipGetLastError());
+  return SD_OK;
+}
+
+int sd_track_get_last(sd_track* h, int frame0, int n_frames, int32_t* n_last, uint8_t* valid, double* Xw, uint8_t* desc, int32_t* octave,
+                      float* angle, int32_t* obs, int32_t* ids) {
+  TRACK_RANGE(h, frame0, n_frames);
+  hipStream_t s = h->cur->stream;
+  const TrackBuffers& tb = h->tb;
+  const size_t M = h->max_points, o = frame0, n = n_frames;
+  if (n_last) SD_HIP_CHECK(hipMemcpyAsync(n_last, tb.n_last + o, n * 4, hipMemcpyDeviceToHost, s));
+  if (valid) SD_HIP_CHECK(hipMemcpyAsync(valid, tb.valid + o * M, n * M, hipMemcpyDeviceToHost, s));
+  if (Xw) SD_HIP_CHECK(hipMemcpyAsync(Xw, tb.Xw + o * M * 3, n * M * 24, hipMemcpyDeviceToHost, s));
+  if (desc) SD_HIP_CHECK(hipMemcpyAsync(desc, tb.mp_desc + o * M * 32, n * M * 32, hipMemcpyDeviceToHost, s));
+  if (octave) SD_HIP_CHECK(hipMemcpyAsync(octave, tb.octave + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
+  if (angle) SD_HIP_CHECK(hipMemcpyAsync(angle, tb.angle + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
+  if (obs) SD_HIP_CHECK(hipMemcpyAsync(obs, tb.obs + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
+  if (ids) SD_HIP_CHECK(hipMemcpyAsync(ids, tb.last_id + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
+  SD_HIP_CHECK(hipStreamSynchronize(s));
+  return SD_OK;
+}
+
+int sd_track_get_extractors(sd_track* h, sd_orb** cur, sd_orb** ref) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  if (cur) *cur = h->cur;
+  if (ref) *ref = h->ref;
   return SD_OK;
 }
 

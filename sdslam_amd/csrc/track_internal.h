@@ -21,6 +21,15 @@ struct TrackBuffers {
   float* angle;          // [B][M]   LastFrame.mvKeysUn[i].angle
   int32_t* obs;          // [B][M]   pMP->Observations()
   int32_t* n_last;       // [B]
+  int32_t* last_id;      // [B][M]   caller's identity of the point (sd_track_set_map_ids 0), -1: none
+  // second last-frame SoA: sd_track_advance writes the next last frame here, then the handle swaps the two
+  uint8_t* valid2;
+  double* Xw2;
+  uint8_t* mp_desc2;
+  int32_t* octave2;
+  float* angle2;
+  int32_t* obs2;
+  int32_t* last_id2;
   // poses, 16 doubles column-major (Eigen::Matrix4d::data())
   double* Tref;          // [B][16]  LastFrame.GetPose()
   double* Tprior;        // [B][16]  CurrentFrame pose before alignment (motion-model prediction)
@@ -66,6 +75,7 @@ struct TrackBuffers {
   float* lm_mfmax;       // [B][M]   mfMaxDistance
   uint8_t* lm_desc;      // [B][M][32]
   int32_t* lm_obs;       // [B][M]
+  int32_t* lm_id;        // [B][M]   caller's identity of the point (sd_track_set_map_ids 1), -1: none
   int32_t* lm_n;         // [B]
   uint8_t* lm_kclaim;    // [B][kp_cap] keypoint already holds a point with Observations() > 0
   // outputs
@@ -82,6 +92,9 @@ struct TrackBuffers {
   // Tracking::TrackWithMotionModel outcome (sd_track_with_motion_model)
   int32_t* tw_info;      // [B][4]: status (0 few matches, 1 few inliers, 2 tracked), nmatches after the outlier discard,
                          //         nmatchesMap, 1 if the wider-window retry ran
+  int32_t* tw_seen;      // [B][kp_cap] the final search's matches BEFORE the outlier discard: the points whose mnLastFrameSeen
+                         //             TrackWithMotionModel sets, which SearchLocalPoints skips (src/Tracking.cc:703, :900-918)
+  uint32_t* tw_seen_ids; // [B][kp_cap] their ids (last_id), ascending, 0xFFFFFFFF for none (k_seen_ids, sd_track_local_map)
   // Tracking::TrackLocalMap (sd_track_local_map): mvpMapPoints after SearchLocalPoints = frame matches + local matches
   int32_t* un_match;     // [B][kp_cap] -1 | v < M: last-frame point v | v >= M: local map point v - M
   int32_t* tl_info;      // [B][4]: status (1 failed, 2 tracked), points in mvpMapPoints, mnMatchesInliers, local matches
@@ -114,9 +127,10 @@ int launch_pose_opt(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& c
                     hipStream_t s, int min_matches = 0, int min_inliers = 0);
 // claim_from_matches: "keypoint already holds a point with Observations() > 0" is read off the frame-to-frame matches
 // (tb.cur_match / tb.obs) instead of the caller's lm_kclaim flags
+// exclude_seen: a local point whose id (lm_id) equals the id of a last-frame point in tw_seen is no candidate
 int launch_match_local(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_sf, const float* d_scale_thr,
                        int nlevels, int n_frames, float th, float nnratio, float cos_limit, hipStream_t s, int claim_from_matches = 0,
-                       int frustum_given = 0);
+                       int frustum_given = 0, int exclude_seen = 0);
 int launch_features_in_area(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, int frame, float x, float y, float r,
                             int min_level, int max_level, int32_t* d_out, int out_cap, int32_t* d_n, int32_t* d_grid, hipStream_t s);
 int launch_search_points(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, int n_frames, float nnratio, int check_ori,

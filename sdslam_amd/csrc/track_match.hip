@@ -808,12 +808,41 @@ __global__ __launch_bounds__(64) void k_match_assign_retry(const sd_keypoint* __
 // Same two phases as k_match; the per-point result needs the two smallest keys (best / second best for the
 // mfNNratio test), which are the reference's bestDist / bestDist2 because both are updated with strict `<` in
 // vIndices order.
-// Dynamic LDS: the k_match layout + u32 s_kclaim[KP2/32] + u8 s_koct[KP2].
+// k_seen_ids: per frame, the ids (tb.last_id) of the points in tb.tw_seen, ascending, -1 (none) last as 0xFFFFFFFF, into
+// tb.tw_seen_ids -- k_match_local's seen-point exclusion binary-searches them.  A kernel of its own: the sort's loop nest
+// inside k_match_local raised that kernel from 57 to 75 VGPRs.  KP2 (a power of two >= kp_cap) u32 of LDS.
+__global__ __launch_bounds__(256) void k_seen_ids(TrackBuffers tb, int KP2) {
+  extern __shared__ uint32_t s_ids[];
+  const int f = blockIdx.x, tid = threadIdx.x, NT = blockDim.x, cap = tb.kp_cap;
+  for (int i = tid; i < KP2; i += NT) {
+    const int v = i < cap ? tb.tw_seen[(size_t)f * cap + i] : -1;
+    s_ids[i] = (uint32_t)(v >= 0 ? tb.last_id[(size_t)f * tb.max_points + v] : -1);
+  }
+  __syncthreads();
+  for (int k = 2; k <= KP2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < KP2; i += NT) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const uint32_t a = s_ids[i], b = s_ids[ixj];
+          if ((a > b) == ((i & k) == 0)) {
+            s_ids[i] = b;
+            s_ids[ixj] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  for (int i = tid; i < cap; i += NT) tb.tw_seen_ids[(size_t)f * cap + i] = s_ids[i];
+}
+
+// Dynamic LDS: the k_match layout + u32 s_kclaim[KP2/32] + u8 s_koct[KP2].  The seen-point exclusion borrows s_list for KP2 ids.
+static_assert(MT_LIST_CAP >= MT_MAXKP, "k_match_local keeps the sorted seen ids in s_list");
 __global__ __launch_bounds__(64 * MT_WAVES) void k_match_local(const sd_keypoint* __restrict__ kps_all, const uint8_t* __restrict__ desc_all,
                                                                 const int32_t* __restrict__ nkp_all, TrackBuffers tb, TrackCam cam,
                                                                 const float* __restrict__ sf, const float* __restrict__ scale_thr,
                                                                 int nlevels, float th, float nnratio, float cos_limit, int KP2,
-                                                                int claim_from_matches, int frustum_given) {
+                                                                int claim_from_matches, int frustum_given, int exclude_seen) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int MP = tb.max_points;
   uint32_t* s_key = (uint32_t*)smem;
@@ -890,9 +919,32 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match_local(const sd_keypoint
       if (w + 1 < ((MP + 31) >> 5)) s_obs[w + 1] = (uint32_t)(bo >> 32);
     }
   }
+  // seen-point exclusion (exclude_seen): the sorted ids of the last-frame points TrackWithMotionModel's final search matched,
+  // before its outlier discard (k_seen_ids) -- pMP->mnLastFrameSeen == mCurrentFrame.mnId (src/Tracking.cc:703, :900-918).
+  // They go into s_list, which phase 1 fills only after the isInFrustum pass.
+  if (exclude_seen)
+    for (int i = tid; i < KP2; i += NT) s_list[i] = i < cap ? tb.tw_seen_ids[(size_t)f * cap + i] : 0xFFFFFFFFu;
   if (tid == 0) *s_nlist = 0;
   __syncthreads();
   grid_sort_and_starts(s_key, s_cstart, KP2, tid, NT);
+  if (exclude_seen) {   // binary search of every point's id among the sorted seen ids; the flags borrow s_pt, which phase 1
+                        // overwrites for every point < n_loc (the same thread reads its flag below: no barrier needed)
+    const int32_t* l_id = tb.lm_id + (size_t)f * M;
+    for (int i = tid; i < M; i += NT) {
+      const int id = i < n_loc ? l_id[i] : -1;
+      uint32_t seen = 0;
+      if (id >= 0) {
+        int lo = 0, hi = KP2;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (s_list[mid] < (uint32_t)id) lo = mid + 1;
+          else hi = mid;
+        }
+        seen = lo < KP2 && s_list[lo] == (uint32_t)id;
+      }
+      s_pt[i] = seen;
+    }
+  }
   // ---- isInFrustum, one thread per point (frustum_given: the caller's own Frame::isInFrustum results -- mbTrackInView,
   // mTrackProjX / Y / XR, mnTrackScaleLevel, mTrackViewCos, uploaded by sd_track_set_local_view -- are used as they are, which is
   // what ORBmatcher::SearchByProjection(F, vpMapPoints, th) itself reads, src/ORBmatcher.cc:48-60)
@@ -908,7 +960,7 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match_local(const sd_keypoint
       uint8_t inview = 0;
       float pu = 0, pv = 0, pxr = 0, vc = 0;
       int lvl = 0;
-      if (i < n_loc && cand[i]) {
+      if (i < n_loc && cand[i] && !(exclude_seen && s_pt[i])) {
         const double P0 = Xw[(size_t)i * 3], P1 = Xw[(size_t)i * 3 + 1], P2 = Xw[(size_t)i * 3 + 2];
         const double PcX = (R[0][0] * P0 + R[0][1] * P1 + R[0][2] * P2) + t[0];
         const double PcY = (R[1][0] * P0 + R[1][1] * P1 + R[1][2] * P2) + t[1];
@@ -1133,15 +1185,21 @@ int launch_features_in_area(const sd_orb* cur, const TrackBuffers& tb, const Tra
 
 int launch_match_local(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_sf, const float* d_scale_thr,
                        int nlevels, int n_frames, float th, float nnratio, float cos_limit, hipStream_t s, int claim_from_matches,
-                       int frustum_given) {
+                       int frustum_given, int exclude_seen) {
   int KP2 = 64;
   while (KP2 < tb.kp_cap) KP2 <<= 1;
   SD_REQUIRE(KP2 <= MT_MAXKP && tb.max_points <= 2048, SD_ERR_CAPACITY, "matcher supports at most 2048 keypoints / map points per frame");
   const int MP = tb.max_points;
+  exclude_seen = exclude_seen && !frustum_given;
+  if (exclude_seen) {
+    hipLaunchKernelGGL(k_seen_ids, dim3(n_frames), dim3(256), (size_t)KP2 * 4, s, tb, KP2);
+    SD_HIP_CHECK(hipGetLastError());
+  }
   const size_t lds = (size_t)KP2 * 4 + MT_LIST_CAP * 4 + (size_t)MP * 4 + (size_t)((MP + 31) >> 5) * 4 + (size_t)(KP2 >> 5) * 4 + (size_t)KP2 * 2 +
                      (GRID_COLS * GRID_ROWS + 2) * 2 + (size_t)KP2 + 4 + 8;
   hipLaunchKernelGGL(k_match_local, dim3(n_frames), dim3(64 * MT_WAVES), lds, s, (cur->have_dist ? cur->d_kps_un : cur->d_kps), cur->d_desc,
-                     cur->d_nout, tb, cam, d_sf, d_scale_thr, nlevels, th, nnratio, cos_limit, KP2, claim_from_matches, frustum_given);
+                     cur->d_nout, tb, cam, d_sf, d_scale_thr, nlevels, th, nnratio, cos_limit, KP2, claim_from_matches, frustum_given,
+                     exclude_seen ? 1 : 0);
   SD_HIP_CHECK(hipGetLastError());
   return SD_OK;
 }

@@ -441,6 +441,13 @@ __global__ __launch_bounds__(64 * W) void k_pose_opt(const sd_keypoint* __restri
       for (int k = 0; k < 8; k++) info[k] = 0;
       info[0] = nInitial;
     }
+    // TrackWithMotionModel: the final search's matches before the outlier discard -- the points it marks mnLastFrameSeen
+    // (src/Tracking.cc:703), which sd_track_local_map's seen-point exclusion reads.  Thread tid owns keypoints i = tid (mod
+    // PO_THREADS) here and in the discard below, so each entry is read before its owner clears it.
+    if (min_matches > 0 && source == 0) {
+      int32_t* seen = tb.tw_seen + (size_t)f * cap;
+      for (int i = tid; i < cap; i += PO_THREADS) seen[i] = i < nkp ? match[i] : -1;
+    }
     // TrackWithMotionModel: "Not enough matches, tracking failed" returns before PoseOptimization (src/Tracking.cc:691-694)
     const int nm_search = min_matches > 0 ? tb.n_matches[f] : 0;
     if (min_matches > 0 && nm_search < min_matches) {

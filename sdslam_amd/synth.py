@@ -228,3 +228,71 @@ def local_map_case(seed, kps, desc, T_cur, n_extra=300, scale_factor=1.2, nlevel
     out = {k: np.concatenate([pts[k], extra[k]]) for k in pts}
     perm = rng.permutation(n + ex)
     return {k: np.ascontiguousarray(v[perm]) for k, v in out.items()}
+
+
+# ----------------------------------------------------------------------------------------
+# Sequences: B camera streams tracked frame after frame (sd_track_advance)
+# ----------------------------------------------------------------------------------------
+def render_view_and_depth(tex, Tcw, w=640, h=480, depth=2.0):
+    """render_plane_view plus the camera-frame depth of the surface along every pixel's ray (what an RGB-D sensor reports)."""
+    R, t = Tcw[:3, :3], Tcw[:3, 3]
+    v, u = np.mgrid[0:h, 0:w].astype(np.float64)
+    rays = np.stack([(u - CX) / FX, (v - CY) / FY, np.ones_like(u)], -1)
+    Ow = -R.T @ t
+    Xw = intersect_surface(Ow, rays @ R, depth)
+    img = _bilinear(tex, 2.0 * (FX * Xw[..., 0] / depth + CX) + 0.5, 2.0 * (FY * Xw[..., 1] / depth + CY) + 0.5)
+    return img, (Xw @ R.T + t)[..., 2].astype(np.float32)
+
+
+def make_sequence(seed: int, n_frames: int, w=640, h=480, speed=1.0, with_depth=False):
+    """A smooth camera trajectory over the textured scene surface: frame t sits at Exp(upsilon(t), omega(t)) -- about a
+    centimetre and a third of a degree per frame at speed 1, turning gently -- with its rendered view and true pose Tcw
+    (and, with_depth, its true depth image).  The seed picks the texture and the phase of the motion."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    tex = make_image(seed, 2 * w, 2 * h)
+    ph = rng.uniform(0, 2 * np.pi, 6)
+    poses, views, depths = [], [], []
+    for t in range(n_frames):
+        s = speed * t
+        ups = (0.010 * s + 0.004 * np.sin(0.4 * s + ph[0]) - 0.004 * np.sin(ph[0]),
+               -0.006 * s + 0.003 * np.sin(0.5 * s + ph[1]) - 0.003 * np.sin(ph[1]),
+               0.004 * np.sin(0.3 * s + ph[2]) - 0.004 * np.sin(ph[2]))
+        om = (0.15 * np.sin(0.35 * s + ph[3]) - 0.15 * np.sin(ph[3]), -0.2 * s * 0.5 + 0.1 * np.sin(0.45 * s + ph[4]) - 0.1 * np.sin(ph[4]),
+              0.25 * np.sin(0.3 * s + ph[5]) - 0.25 * np.sin(ph[5]))
+        T = se3_exp(ups, om)
+        img, d = render_view_and_depth(tex, T, w, h)
+        poses.append(T)
+        views.append(img)
+        depths.append(d)
+    out = dict(views=np.stack(views), T=poses, K=(FX, FY, CX, CY))
+    if with_depth:
+        out["depth"] = np.stack(depths)
+    return out
+
+
+def static_map(kps, desc, T_cw, scale_factor=1.2, nlevels=8, seed=0):
+    """A map made of one point per keypoint of a frame seen at T_cw (the surface point it sees), as MapPoint would hold it
+    after that frame created it: id = keypoint index, normal = the viewing direction, mfMaxDistance = distance * scale
+    factor of the octave, mfMinDistance = mfMaxDistance / scale^(nlevels-1), invariance interval [0.8 min, 1.2 max]
+    (src/MapPoint.cc GetMin/MaxDistanceInvariance), the keypoint's descriptor, Observations() in 1..3 -- 0 for every
+    7th point (a VO point, dropped by the hand-off's "Clean VO matches").
+    Returns (local, last, ids): the dict Tracker.set_local / the oracle take (cand = 1), the dict Tracker.set_last takes
+    (the frame itself as the first last frame), and the ids."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = len(kps)
+    R, t = T_cw[:3, :3], T_cw[:3, 3]
+    Ow = -R.T @ t
+    rays = np.stack([(kps["x"].astype(np.float64) - CX) / FX, (kps["y"].astype(np.float64) - CY) / FY, np.ones(n)], -1)
+    Xw = np.ascontiguousarray(intersect_surface(Ow, rays @ R, 2.0))
+    PO = Xw - Ow
+    d = np.linalg.norm(PO, axis=1)
+    mf_max = (d * scale_factor ** kps["octave"].astype(np.float64)).astype(np.float32)
+    mf_min = (mf_max / np.float32(scale_factor ** (nlevels - 1))).astype(np.float32)
+    obs = rng.integers(1, 4, n).astype(np.int32)
+    obs[::7] = 0
+    ids = np.arange(n, dtype=np.int32)
+    local = dict(cand=np.ones(n, np.uint8), Xw=Xw, normal=np.ascontiguousarray(PO / d[:, None]), min_dist=np.float32(0.8) * mf_min,
+                 max_dist=np.float32(1.2) * mf_max, mf_max_dist=mf_max, desc=np.ascontiguousarray(desc), obs=obs)
+    last = dict(valid=np.ones(n, np.uint8), Xw=Xw.copy(), desc=np.ascontiguousarray(desc).copy(), octave=kps["octave"].astype(np.int32).copy(),
+                angle=kps["angle"].astype(np.float32).copy(), obs=obs.copy())
+    return local, last, ids

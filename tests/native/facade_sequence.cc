@@ -1,0 +1,90 @@
+// The C++ facade's sequential-tracking loop (TrackBatch::SetMapIds / SetPrior / AdvanceLastFrame / GetLastFrame /
+// CurrentExtractor) on one camera stream.
+//   facade_sequence                 link check: prints "facade sequence ok" (no GPU work)
+//   facade_sequence IN OUT          runs the loop on the frames and static map in IN, writes the per-frame results and the
+//                                   final last frame to OUT (layout: tests/test_sequence_facade_gpu.py)
+#include <sdslam/sdslam.hpp>
+
+#include <cstdio>
+#include <vector>
+
+template <typename T>
+static bool rd(FILE* f, std::vector<T>& v, size_t n) {
+  v.resize(n);
+  return fread(v.data(), sizeof(T), n, f) == n;
+}
+template <typename T>
+static void wr(FILE* f, const T* p, size_t n) { fwrite(p, sizeof(T), n, f); }
+
+int main(int argc, char** argv) {
+  using namespace SD_SLAM;
+  if (argc < 3) {
+    auto ids = &TrackBatch::SetMapIds;
+    auto adv = &TrackBatch::AdvanceLastFrame;
+    auto pri = &TrackBatch::SetPrior;
+    auto get = &TrackBatch::GetLastFrame;
+    auto cur = &TrackBatch::CurrentExtractor;
+    if (!ids || !adv || !pri || !get || !cur) return 1;
+    std::printf("facade sequence ok\n");
+    return 0;
+  }
+  FILE* f = std::fopen(argv[1], "rb");
+  if (!f) return 2;
+  std::vector<int32_t> hdr;   // W, H, T, n (map points), max_points
+  if (!rd(f, hdr, 5)) return 3;
+  const int W = hdr[0], H = hdr[1], T = hdr[2], n = hdr[3], M = hdr[4];
+  std::vector<uint8_t> frames, desc, valid;
+  std::vector<double> T0, vel, Xw, normal;
+  std::vector<float> mind, maxd, mfmax, angle;
+  std::vector<int32_t> obs, ids, octave;
+  bool ok = rd(f, frames, (size_t)T * W * H) && rd(f, T0, 16) && rd(f, vel, (size_t)(T - 1) * 16) && rd(f, Xw, (size_t)n * 3) &&
+            rd(f, normal, (size_t)n * 3) && rd(f, mind, n) && rd(f, maxd, n) && rd(f, mfmax, n) && rd(f, desc, (size_t)n * 32) &&
+            rd(f, obs, n) && rd(f, ids, n) && rd(f, valid, n) && rd(f, octave, n) && rd(f, angle, n);
+  std::fclose(f);
+  if (!ok) return 4;
+  ORBextractor a(1000, 1.2f, 8, 20, W, H, 1), b(1000, 1.2f, 8, 20, W, H, 1);
+  TrackBatch batch(a, b, M, 1, 100);
+  batch.SetCamera(500.f, 500.f, 320.f, 240.f, 0.f, 0.f, (float)W, 0.f, (float)H);
+  std::vector<KeyPoint> kps;
+  std::vector<uint8_t> dsc;
+  b(frames.data(), W, H, W, kps, dsc);   // frame 0 is the first last frame
+  LastFrameView last{valid, Xw, desc, octave, angle, obs};
+  batch.SetLastFrame(0, last);
+  TrackBatch::LocalMapView local{std::vector<uint8_t>(n, 1), Xw, normal, mind, maxd, mfmax, desc, obs};
+  batch.SetLocalMap(0, local, nullptr);
+  batch.SetMapIds(0, 0, ids.data(), n);
+  batch.SetMapIds(0, 1, ids.data(), n);
+  batch.SetPoses(0, T0.data(), T0.data());
+  FILE* o = std::fopen(argv[2], "wb");
+  if (!o) return 5;
+  for (int t = 1; t < T; t++) {
+    batch.CurrentExtractor()(frames.data() + (size_t)t * W * H, W, H, W, kps, dsc);
+    batch.SetPrior(0, 1, vel.data() + (size_t)(t - 1) * 16, true);
+    Tracking::TrackWithMotionModel(batch, 1, 15.f, true);
+    Tracking::TrackLocalMap(batch, 1, 1.f);
+    const Tracking::Tracked r = Tracking::Result(batch, 0);
+    int inliers = 0;
+    const bool tracked = Tracking::LocalMapResult(batch, 0, &inliers);
+    double Tcw[16];
+    ImageAlign().Result(batch, 0, Tcw);   // the frame's final pose
+    const int32_t rec[5] = {(int32_t)r.ok, r.nmatches, r.nmatchesMap, (int32_t)tracked, inliers};
+    wr(o, rec, 5);
+    wr(o, Tcw, 16);
+    batch.AdvanceLastFrame(1, 1);
+  }
+  LastFrameView v;
+  std::vector<int32_t> vid;
+  batch.GetLastFrame(0, v, &vid);
+  const int32_t nl = v.size();
+  wr(o, &nl, 1);
+  wr(o, v.valid.data(), nl);
+  wr(o, v.Xw.data(), (size_t)nl * 3);
+  wr(o, v.desc.data(), (size_t)nl * 32);
+  wr(o, v.octave.data(), nl);
+  wr(o, v.angle.data(), nl);
+  wr(o, v.obs.data(), nl);
+  wr(o, vid.data(), nl);
+  std::fclose(o);
+  std::printf("facade sequence ran %d frames\n", T - 1);
+  return 0;
+}

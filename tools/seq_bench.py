@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""Sequential tracking: B camera streams x T frames, TrackWithMotionModel + TrackLocalMap every frame, in two modes.
+
+  device   the hand-off on the device: sd_track_set_prior (relative) -> track -> sd_track_advance; no host round trip
+  host     the hand-off a caller had to do before sd_track_advance: synchronise, download sd_track_get_local_map /
+           sd_track_get_pose_opt / the last frame, rebuild the next last frame on the host (numpy gather), re-upload it with
+           sd_track_set_last + sd_track_set_map_ids + sd_track_set_poses.  Two trackers with swapped extractor roles
+           alternate, so the previous frame's pyramid is the reference without a second extraction.
+
+python tools/seq_bench.py [T=8] [B list=1,1024]  -> one JSON line per (B, mode), all of them in profiles/seq_bench.json
+Frames are resident in HBM (extraction from device memory); the timed region is frames 1..T-1 including extraction, ended
+by a synchronisation.  NU distinct sequences are tiled over the B streams.
+"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+import sdslam_amd  # noqa: E402
+from sdslam_amd import synth  # noqa: E402
+
+T = int(sys.argv[1]) if len(sys.argv) > 1 else 8
+BS = [int(b) for b in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1, 1024]
+NU = 8
+M = 1000
+CFG = (1000, 1.2, 8, 20)
+K = (synth.FX, synth.FY, synth.CX, synth.CY)
+BOUNDS = (0.0, 640.0, 0.0, 480.0)
+F = 640 * 480
+
+
+def setup(B, seqs):
+    views = np.stack([np.stack([seqs[b % NU]["views"][t] for b in range(B)]) for t in range(T)])   # [T][B][H][W]
+    frames = sdslam_amd.DeviceBuffer(views.nbytes)
+    frames.upload(views)
+    ext = [sdslam_amd.ORBextractor(*CFG, 640, 480, B) for _ in range(2)]
+    k, d, n = ext[1].extract_batch(views[0])
+    maps = [synth.static_map(k[b, :n[b]], d[b, :n[b]], seqs[b % NU]["T"][0], seed=b % NU) for b in range(min(B, NU))]
+    maps = [maps[b % NU] for b in range(B)]
+    vel = [[seqs[b % NU]["T"][t] @ np.linalg.inv(seqs[b % NU]["T"][t - 1]) for b in range(B)] for t in range(1, T)]
+    return frames, ext, maps, vel
+
+
+def new_tracker(cur, ref, B, maps, seqs):
+    trk = sdslam_amd.Tracker(cur, ref, max_points=M, max_batch=B, pnp_max_iterations=100)
+    trk.set_camera(*K, 0.0, BOUNDS)
+    trk.set_last(0, [m[1] for m in maps])
+    trk.set_local(0, [m[0] for m in maps])
+    trk.set_map_ids(0, [m[2] for m in maps], 0)
+    trk.set_map_ids(0, [m[2] for m in maps], 1)
+    T0 = [seqs[b % NU]["T"][0] for b in range(B)]
+    trk.set_poses(0, T0, T0)
+    return trk
+
+
+def track(trk, frames, B, t, vel=None):
+    trk.cur.extract_batch_device(frames.ptr.value + t * B * F, B, 640, 480)
+    if vel is not None:
+        trk.set_prior(0, vel, relative=True)
+    trk.track_with_motion_model(B, th=15.0)
+    trk.track_local_map(B, th=1.0)
+
+
+def run_device(B, seqs):
+    frames, ext, maps, vel = setup(B, seqs)
+    trk = new_tracker(ext[0], ext[1], B, maps, seqs)
+    t0 = time.perf_counter()
+    for t in range(1, T):
+        track(trk, frames, B, t, vel[t - 1])
+        trk.advance(B, 1)
+    st = trk.get_local_map(0, B)["status"]        # synchronises
+    dt = time.perf_counter() - t0
+    trk.close()
+    frames.free()
+    return dt, st
+
+
+def run_host(B, seqs):
+    frames, ext, maps, vel = setup(B, seqs)
+    trks = [new_tracker(ext[0], ext[1], B, maps, seqs), new_tracker(ext[1], ext[0], B, maps, seqs)]
+    local_ids = np.stack([np.pad(m[2], (0, M - len(m[2])), constant_values=-1) for m in maps])
+    lXw = np.zeros((B, M, 3))
+    ldesc = np.zeros((B, M, 32), np.uint8)
+    lobs = np.zeros((B, M), np.int32)
+    for b, m in enumerate(maps):
+        n = len(m[2])
+        lXw[b, :n], ldesc[b, :n], lobs[b, :n] = m[0]["Xw"], m[0]["desc"], m[0]["obs"]
+    T_last = [seqs[b % NU]["T"][0] for b in range(B)]
+    t0 = time.perf_counter()
+    for t in range(1, T):
+        trk = trks[(t - 1) % 2]
+        nxt = trks[t % 2]
+        prior = [v @ Tl for v, Tl in zip(vel[t - 1], T_last)]
+        trk.set_poses(0, T_last, prior)
+        track(trk, frames, B, t)
+        # the host hand-off
+        lm, po, last = trk.get_local_map(0, B), trk.get_pose_opt(0, B), trk.get_last(0, B)
+        kps, _, nk = trk.cur.download(0, B)
+        m = lm["match"][:, :M]
+        keep = (m >= 0) & ~po["outlier"][:, :M]
+        loc = m >= M
+        j = np.clip(np.where(loc, m - M, m), 0, M - 1)
+        bi = np.arange(B)[:, None]
+        obs = np.where(loc, lobs[bi, j], last["obs"][bi, j])
+        keep &= obs >= 1
+        Xw = np.where(loc[..., None], lXw[bi, j], last["Xw"][bi, j]) * keep[..., None]
+        desc = np.where(loc[..., None], ldesc[bi, j], last["desc"][bi, j]) * keep[..., None]
+        ids = np.where(keep, np.where(loc, local_ids[bi, j], last["ids"][bi, j]), -1)
+        cases = [dict(valid=keep[b, :nk[b]].astype(np.uint8), Xw=Xw[b, :nk[b]], desc=desc[b, :nk[b]], octave=kps["octave"][b, :nk[b]],
+                      angle=kps["angle"][b, :nk[b]], obs=(obs * keep)[b, :nk[b]]) for b in range(B)]
+        nxt.set_last(0, cases)
+        nxt.set_map_ids(0, [ids[b, :nk[b]] for b in range(B)], 0)
+        T_last = po["T"]
+    st = trks[(T - 2) % 2].get_local_map(0, B)["status"]
+    dt = time.perf_counter() - t0
+    for trk in trks:
+        trk.close()
+    frames.free()
+    return dt, st
+
+
+def main():
+    seqs = [synth.make_sequence(100 + i, T) for i in range(NU)]
+    out = []
+    for B in BS:
+        for mode, fn in (("device", run_device), ("host", run_host)):
+            dt, st = fn(B, seqs)
+            r = dict(metric="seq_track", mode=mode, B=B, T=T, seconds=round(dt, 4), frames_per_s=round(B * (T - 1) / dt, 1),
+                     ms_per_step=round(1e3 * dt / (T - 1), 3), tracked_last_frame=float(np.mean(st == 2)))
+            print(json.dumps(r), flush=True)
+            out.append(r)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "seq_bench.json"), "w") as f:
+        json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
