@@ -150,6 +150,12 @@ class TrackBatch {
   void ComputeStereoFromRGBD(int n_frames, const float* imDepth, int cols, int rows, int step_elems, size_t frame_step_elems) {
     check(sd_track_stereo_from_depth(h_, n_frames, imDepth, cols, rows, step_elems, frame_step_elems));
   }
+  // the same on depth maps already in device memory (dtype SD_DEPTH_F32 / SD_DEPTH_U16), converted as Tracking::GrabImageRGBD
+  // does with depthMapFactor = Config::DepthMapFactor(); queued without a host wait (ordering: sdslam_hip.h)
+  void ComputeStereoFromRGBD(int n_frames, const void* d_imDepth, int dtype, int cols, int rows, int step_elems, size_t frame_step_elems,
+                             float depthMapFactor) {
+    check(sd_track_stereo_from_depth_device(h_, n_frames, d_imDepth, dtype, cols, rows, step_elems, frame_step_elems, depthMapFactor));
+  }
   // TrackLocalMap: local map points of one frame (src/Tracking.cc:898-939), flattened in mvpLocalMapPoints order
   struct LocalMapView {
     std::vector<uint8_t> cand;                 // reaches isInFrustum: !isBad() && mnLastFrameSeen != frame id
@@ -193,6 +199,15 @@ class TrackBatch {
                             ids ? ids->data() : nullptr));
     v.valid.resize(n); v.Xw.resize((size_t)n * 3); v.desc.resize((size_t)n * 32); v.octave.resize(n); v.angle.resize(n); v.obs.resize(n);
     if (ids) ids->resize(n);
+  }
+  // Tracking::NeedNewKeyFrame's RGB-D counts (src/Tracking.cc:776-789), queued: keypoints with 0 < mvDepth < thDepth (mThDepth)
+  // whose map point AdvanceLastFrame(n_frames, source) would keep, and the others; CloseTrackedPointsResult reads them
+  void CloseTrackedPoints(int n_frames, int source, float thDepth) { check(sd_track_close_points(h_, n_frames, source, thDepth)); }
+  void CloseTrackedPointsResult(int frame, int& nTrackedClose, int& nNonTrackedClose) {
+    int32_t out2[2];
+    check(sd_track_get_close_points(h_, frame, 1, out2));
+    nTrackedClose = out2[0];
+    nNonTrackedClose = out2[1];
   }
   // the extractor whose frames are tracked next (the two swap roles at every AdvanceLastFrame)
   ORBextractor& CurrentExtractor() {

@@ -211,6 +211,21 @@ int sd_track_set_uright(sd_track* h, int frame0, int n_frames, const float* urig
 int sd_track_stereo_from_depth(sd_track* h, int n_frames, const float* depth, int w, int hgt,
                                int stride_elems, size_t frame_stride_elems);
 int sd_track_get_stereo(sd_track* h, int frame0, int n_frames, float* uright, float* depth, int cap);
+/* sd_track_stereo_from_depth_device: the same mvuRight / mvDepth from depth maps already in DEVICE memory, converted as
+ * Tracking::GrabImageRGBD does (src/Tracking.cc:113-117, 147-148).  d_depth holds n_frames maps of w x hgt elements of
+ * `dtype`, rows stride_elems apart, frames frame_stride_elems apart (both in elements), aligned to the element size.
+ * depth_map_factor = Config::DepthMapFactor(): scale = 1 if |factor| < 1e-5, else 1.0f / factor; the depth is
+ * (float)raw * scale, one float product, when |scale - 1| > 1e-5 or dtype is SD_DEPTH_U16, raw otherwise (raw 0: no depth).
+ * Queued on the tracking stream (the one sd_track_stream_fence orders) behind the current extraction and the tracking calls
+ * queued before it: no host wait, no allocation, no copy of the maps.  A producer on another stream S is ordered with
+ * sd_track_stream_fence(h, S, 1) before the call; the maps may be rewritten or freed after sd_track_stream_fence(h, S, 0)
+ * (S then waits for the call) or after any synchronising getter.  Slots >= n_frames are left alone; in broadcast mode the
+ * call walks the frames of the cur extractor, as sd_track_stereo_from_depth does.  SD_ERR_INVALID_ARG: NULL pointer, unknown
+ * dtype, w / hgt < 1, stride < w, a misaligned pointer, no camera, no extraction; SD_ERR_CAPACITY: n_frames > max_batch. */
+#define SD_DEPTH_F32 0  /* float    */
+#define SD_DEPTH_U16 1  /* uint16_t */
+int sd_track_stereo_from_depth_device(sd_track* h, int n_frames, const void* d_depth, int dtype, int w, int hgt,
+                                      int stride_elems, size_t frame_stride_elems, float depth_map_factor);
 
 /* TrackLocalMap's search (reference src/Tracking.cc:898-939): Frame::isInFrustum (src/Frame.cc:215-269, incl.
  * MapPoint::PredictScale src/MapPoint.cc:371-385) for every local map point with cand != 0, then
@@ -377,13 +392,24 @@ int sd_track_pack_records(sd_track* h, int n_frames, int source, void* d_records
  * sd_track_set_prior: Tprior = Tcur = T (relative 0) or T * Tref computed on the device (relative 1; each entry sums k = 0..3
  *   in order, without FMA contraction), column-major, queued on the tracking stream without a host wait.  Tref is left alone.
  * sd_track_get_last: the last-frame arrays in [n][max_points] layout; any pointer may be NULL.
- * sd_track_get_extractors: the handles in the cur / ref roles now. */
+ * sd_track_get_extractors: the handles in the cur / ref roles now.
+ * sd_track_close_points: the RGB-D counts of Tracking::NeedNewKeyFrame (src/Tracking.cc:776-789) for slots < n_frames, queued
+ *   on the tracking stream without a host wait.  Over keypoints i < N with 0 < mvDepth[i] < th_depth (mThDepth = mbf * ThDepth
+ *   / fx, passed in), a keypoint is tracked when sd_track_advance with the same
+ *   `source` would keep its map point (after "Clean VO matches": present, Observations() >= 1, not an outlier), non-tracked
+ *   otherwise.  SD_ERR_CAPACITY: n_frames > max_batch; SD_ERR_INVALID_ARG: a bad source, the call named by `source` has not
+ *   run on these slots since the last extraction, or broadcast mode is on.  Slots >= n_frames keep their counts.
+ *   Precondition (not checked): mvDepth of this extraction has been computed by sd_track_stereo_from_depth(_device) before
+ *   the call; otherwise the counts read whatever depth the slots last received (-1 everywhere for a new handle).
+ * sd_track_get_close_points: out2 = [n_frames][2] {nTrackedClose, nNonTrackedClose}; synchronises. */
 int sd_track_set_map_ids(sd_track* h, int frame0, int n_frames, int which, const int32_t* ids, int cap);
 int sd_track_advance(sd_track* h, int n_frames, int source);
 int sd_track_set_prior(sd_track* h, int frame0, int n_frames, const double* T_cm, int relative);
 int sd_track_get_last(sd_track* h, int frame0, int n_frames, int32_t* n_last, uint8_t* valid, double* Xw, uint8_t* desc, int32_t* octave,
                       float* angle, int32_t* obs, int32_t* ids);
 int sd_track_get_extractors(sd_track* h, sd_orb** cur, sd_orb** ref);
+int sd_track_close_points(sd_track* h, int n_frames, int source, float th_depth);
+int sd_track_get_close_points(sd_track* h, int frame0, int n_frames, int32_t* out2);
 int sd_track_stream_fence(sd_track* h, void* hip_stream, int direction);
 int sd_track_set_profiling(sd_track* h, int on);
 int sd_track_stage_ms(sd_track* h, float* ms_out /* [0]=align, [1]=match, [2]=pnp */, int cap);

@@ -445,6 +445,19 @@ class Tracker:
         self.L.sd_track_stereo_from_depth.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t]
         _check(self.L.sd_track_stereo_from_depth(self.h, d.shape[0], _p(d), d.shape[2], d.shape[1], d.shape[2], d.shape[1] * d.shape[2]))
 
+    DEPTH_F32, DEPTH_U16 = 0, 1
+
+    def stereo_from_depth_device(self, d_ptr, dtype, W, H, stride=None, frame_stride=None, depth_map_factor=1.0, n_frames=None):
+        """Frame::ComputeStereoFromRGBD on depth maps already in device memory at d_ptr, queued on the tracking stream (no host
+        wait, no copy); dtype DEPTH_F32 / DEPTH_U16; strides in elements; depth_map_factor = DepthMapFactor (converted as
+        Tracking::GrabImageRGBD does); n_frames defaults to the tracker's max_batch."""
+        stride = stride or W
+        frame_stride = frame_stride or stride * H
+        n = self.B if n_frames is None else n_frames
+        self.L.sd_track_stereo_from_depth_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t,
+                                                             C.c_float]
+        _check(self.L.sd_track_stereo_from_depth_device(self.h, n, d_ptr, int(dtype), W, H, stride, frame_stride, float(depth_map_factor)))
+
     def get_stereo(self, frame0, n):
         u = np.zeros((n, self.cap), np.float32)
         d = np.zeros((n, self.cap), np.float32)
@@ -684,6 +697,19 @@ class Tracker:
         _check(self.L.sd_track_get_last(self.h, frame0, n, *[_p(out[k]) for k in ("n_last", "valid", "Xw", "desc", "octave", "angle", "obs",
                                                                                  "ids")]))
         return out
+
+    def close_points(self, n_frames, source, th_depth):
+        """Queue Tracking::NeedNewKeyFrame's RGB-D counts (src/Tracking.cc:776-789) for slots < n_frames: keypoints with
+        0 < mvDepth < th_depth (mThDepth = mbf * ThDepth / fx) whose map point advance(source) would keep, and the others."""
+        self.L.sd_track_close_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float]
+        _check(self.L.sd_track_close_points(self.h, n_frames, int(source), float(th_depth)))
+
+    def get_close_points(self, frame0, n):
+        """dict(tracked=nTrackedClose, non_tracked=nNonTrackedClose), one entry per slot."""
+        out = np.zeros((n, 2), np.int32)
+        self.L.sd_track_get_close_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _check(self.L.sd_track_get_close_points(self.h, frame0, n, _p(out)))
+        return dict(tracked=out[:, 0].copy(), non_tracked=out[:, 1].copy())
 
     def set_profiling(self, on=True):
         _check(self.L.sd_track_set_profiling(self.h, int(on)))

@@ -64,6 +64,7 @@ struct sd_track {
   bool prior_pending[kPriorRing] = {};
   int prior_next = 0;
   double* d_prior = nullptr;       // [max_batch][16]
+  int32_t* d_close = nullptr;      // [max_batch][2] sd_track_close_points: nTrackedClose, nNonTrackedClose
   static const int kRing = 128;
   hipEvent_t ev[kRing][6] = {};
   int ev_calls[3] = {0, 0, 0};
@@ -96,6 +97,20 @@ __global__ void k_pack_records(TrackBuffers tb, int source, int n_frames, double
   else { ok = tb.al_ok[f]; }
   r[18] = inl;
   r[19] = ok;
+}
+
+// The map point mvpMapPoints[i] = m keeps after Tracking::Track's "Clean VO matches" (Observations() >= 1, reference
+// src/Tracking.cc:250-257) and outlier discard (:272-275): source 0 = cur_match after TrackWithMotionModel's discard (no
+// outlier flags left), 1 = un_match after TrackLocalMap, m >= M naming local point m - M, outl_i = &mvbOutlier[i].
+// Returns its Observations() if it is kept, else 0; *e / *loc locate it.  o = slot * M.  k_advance keeps these points and
+// k_close_points counts them as tracked: one test for both.
+__device__ __forceinline__ int kept_point_obs(const TrackBuffers& tb, int source, int m, const uint8_t* outl_i, size_t o, size_t* e,
+                                              bool* loc) {
+  if (m < 0 || (source == 1 && *outl_i)) return 0;
+  *loc = m >= tb.max_points;
+  *e = o + (*loc ? m - tb.max_points : m);
+  const int n_obs = *loc ? tb.lm_obs[*e] : tb.obs[*e];
+  return n_obs >= 1 ? n_obs : 0;
 }
 
 // Tracking::Track's hand-off to the next frame (reference src/Tracking.cc:250-292), one workgroup per slot, into the second
@@ -136,20 +151,17 @@ __global__ __launch_bounds__(256) void k_advance(const sd_keypoint* __restrict__
     if (i < N) {
       oct = kps_all[(size_t)f * cap + i].octave;
       ang = kps_un_all[(size_t)f * cap + i].angle;
-      const int m = match[i];
-      if (m >= 0 && !(source == 1 && outl[i])) {
-        const bool loc = m >= M;
-        const size_t e = o + (loc ? m - M : m);
-        const int n_obs = loc ? tb.lm_obs[e] : tb.obs[e];
-        if (n_obs >= 1) {
-          const double* X = (loc ? tb.lm_Xw : tb.Xw) + e * 3;
-          const uint4* d = (const uint4*)(loc ? tb.lm_desc : tb.mp_desc) + e * 2;
-          v = 1;
-          X0 = X[0]; X1 = X[1]; X2 = X[2];
-          d0 = d[0]; d1 = d[1];
-          ob = n_obs;
-          id = loc ? tb.lm_id[e] : tb.last_id[e];
-        }
+      bool loc = false;
+      size_t e = 0;
+      const int n_obs = kept_point_obs(tb, source, match[i], outl + i, o, &e, &loc);
+      if (n_obs >= 1) {
+        const double* X = (loc ? tb.lm_Xw : tb.Xw) + e * 3;
+        const uint4* d = (const uint4*)(loc ? tb.lm_desc : tb.mp_desc) + e * 2;
+        v = 1;
+        X0 = X[0]; X1 = X[1]; X2 = X[2];
+        d0 = d[0]; d1 = d[1];
+        ob = n_obs;
+        id = loc ? tb.lm_id[e] : tb.last_id[e];
       }
     }
     const size_t e = o + i;
@@ -166,6 +178,43 @@ __global__ __launch_bounds__(256) void k_advance(const sd_keypoint* __restrict__
   }
   if (tid == 0) tb.n_last[f] = N;
   if (tid < 16) tb.Tref[(size_t)f * 16 + tid] = tb.Tcur[(size_t)f * 16 + tid];
+}
+
+// Tracking::NeedNewKeyFrame's RGB-D counts (reference src/Tracking.cc:776-789), which run after "Clean VO matches"
+// (:250-257): over keypoints i < N with 0 < mvDepth[i] < th_depth, nTrackedClose = those whose map point k_advance keeps
+// (kept_point_obs) and nNonTrackedClose = the others.  One workgroup per slot; each wave counts with two ballots per 64
+// keypoints, the four waves' sums meet in LDS.
+__global__ __launch_bounds__(256) void k_close_points(const int32_t* __restrict__ nkp_all, TrackBuffers tb, int source, float th_depth,
+                                                      int32_t* __restrict__ out) {
+  __shared__ int s_n[2][4];
+  const int f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
+  const int M = tb.max_points, cap = tb.kp_cap;
+  const size_t o = (size_t)f * M;
+  const int N = min(nkp_all[f], cap);
+  const float* depth = tb.depth + (size_t)f * cap;
+  const int32_t* match = (source == 0 ? tb.cur_match : tb.un_match) + (size_t)f * cap;
+  const uint8_t* outl = tb.po_outlier + (size_t)f * cap;
+  int tracked = 0, other = 0;
+  for (int base = 0; base < N; base += 256) {   // trip count uniform over the workgroup: the ballots see every lane
+    const int i = base + tid;
+    bool close = false, kept = false;
+    if (i < N) {
+      const float d = depth[i];
+      close = d > 0 && d < th_depth;
+      bool loc;
+      size_t e;
+      if (close) kept = kept_point_obs(tb, source, match[i], outl + i, o, &e, &loc) >= 1;
+    }
+    const unsigned long long bc = __ballot(close), bk = __ballot(kept);
+    tracked += __popcll(bk);
+    other += __popcll(bc & ~bk);
+  }
+  if ((tid & 63) == 0) {
+    s_n[0][wave] = tracked;
+    s_n[1][wave] = other;
+  }
+  __syncthreads();
+  if (tid < 2) out[(size_t)f * 2 + tid] = s_n[tid][0] + s_n[tid][1] + s_n[tid][2] + s_n[tid][3];
 }
 
 // sd_track_set_prior: Tprior = Tcur = T (relative 0) or T * Tref (relative 1: ConstantVelocity::GetPose, Exp(vel) * last_pose_),
@@ -247,6 +296,7 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &tb.tw_seen_ids, B * K));
   A(dalloc(h, &tb.lm_id, B * M));
   A(dalloc(h, &h->d_prior, B * 16));
+  A(dalloc(h, &h->d_close, B * 2));
   A(dalloc(h, &tb.Tref, B * 16));
   A(dalloc(h, &tb.Tprior, B * 16));
   A(dalloc(h, &tb.Tcur, B * 16));
@@ -911,6 +961,27 @@ int sd_track_stereo_from_depth(sd_track* h, int n_frames, const float* depth, in
   return rc;
 }
 
+// The same on depth maps already in device memory, with Tracking::GrabImageRGBD's conversion (src/Tracking.cc:113-117,
+// 147-148) applied to the pixels read.  Queued on the tracking stream behind the current extraction: no host wait, no
+// allocation, no copy of the maps.
+int sd_track_stereo_from_depth_device(sd_track* h, int n_frames, const void* d_depth, int dtype, int w, int hgt, int stride_elems,
+                                      size_t frame_stride_elems, float depth_map_factor) {
+  int rc = check_ready(h, n_frames, true);
+  if (rc != SD_OK) return rc;
+  SD_REQUIRE(d_depth && (dtype == SD_DEPTH_F32 || dtype == SD_DEPTH_U16) && w >= 1 && hgt >= 1 && stride_elems >= w, SD_ERR_INVALID_ARG,
+             "bad depth image (NULL, unknown dtype, empty or stride < w)");
+  SD_REQUIRE((uintptr_t)d_depth % (dtype == SD_DEPTH_U16 ? 2 : 4) == 0, SD_ERR_INVALID_ARG, "depth pointer not aligned to its element size");
+  // mDepthMapFactor and the convertTo condition, in the reference's float arithmetic
+  const float scale = std::fabs(depth_map_factor) < 1e-5 ? 1.0f : 1.0f / depth_map_factor;
+  const bool convert = std::fabs(scale - 1.0f) > 1e-5 || dtype != SD_DEPTH_F32;
+  rc = wait_inputs(h, false);
+  if (rc != SD_OK) return rc;
+  rc = launch_stereo_from_depth_typed(h->cur, h->tb, h->cam, d_depth, dtype == SD_DEPTH_U16, convert, scale, w, hgt, stride_elems,
+                                      frame_stride_elems, n_frames, h->pnp_stream);
+  if (rc == SD_OK) rc = mark_reads(h, false);
+  return rc;
+}
+
 int sd_track_get_stereo(sd_track* h, int frame0, int n_frames, float* uright, float* depth, int cap) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(cap >= h->kp_cap, SD_ERR_CAPACITY, "cap smaller than the keypoint capacity");
@@ -1254,6 +1325,32 @@ int sd_track_advance(sd_track* h, int n_frames, int source) {
   std::swap(h->cur, h->ref);   // this frame's pyramid and keypoints are the next ImageAlign / match reference
   h->have_pnp = false;
   h->ran_cur[0] = h->ran_cur[1] = nullptr;
+  return SD_OK;
+}
+
+int sd_track_close_points(sd_track* h, int n_frames, int source, float th_depth) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
+  SD_REQUIRE(source == 0 || source == 1, SD_ERR_INVALID_ARG, "source must be 0 (sd_track_with_motion_model) or 1 (sd_track_local_map)");
+  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
+  // (a call that ran in broadcast mode may have covered more slots than `cur` holds frames: its keypoint counts end there)
+  SD_REQUIRE(ran_since_extract(h, source, n_frames) && h->cur->last_frames >= n_frames, SD_ERR_INVALID_ARG,
+             source == 0 ? "sd_track_with_motion_model has not run on these slots since the last extraction"
+                         : "sd_track_local_map has not run on these slots since the last extraction");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  hipStream_t s = h->pnp_stream;
+  int rc = wait_inputs(h, false);
+  if (rc != SD_OK) return rc;
+  hipLaunchKernelGGL(k_close_points, dim3(n_frames), dim3(256), 0, s, h->cur->d_nout, h->tb, source, th_depth, h->d_close);
+  SD_HIP_CHECK(hipGetLastError());
+  return mark_reads(h, false);
+}
+
+int sd_track_get_close_points(sd_track* h, int frame0, int n_frames, int32_t* out2) {
+  TRACK_RANGE(h, frame0, n_frames);
+  SD_REQUIRE(out2, SD_ERR_INVALID_ARG, "NULL argument");
+  SD_HIP_CHECK(hipMemcpyAsync(out2, h->d_close + (size_t)frame0 * 2, (size_t)n_frames * 8, hipMemcpyDeviceToHost, h->cur->stream));
+  SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
   return SD_OK;
 }
 

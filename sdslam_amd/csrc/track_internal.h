@@ -137,6 +137,10 @@ int launch_search_points(const sd_orb* cur, const sd_orb* ref, const TrackBuffer
                          hipStream_t s);
 int launch_stereo_from_depth(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_depth, int w, int h,
                              int stride_elems, size_t frame_stride_elems, int n_frames, hipStream_t s);
+// the same on a depth map of uint16_t (u16 != 0, always converted) or float elements; convert: d = (float)raw * scale
+int launch_stereo_from_depth_typed(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const void* d_depth, int u16,
+                                   int convert, float scale, int w, int h, int stride_elems, size_t frame_stride_elems, int n_frames,
+                                   hipStream_t s);
 int read_pnp_prof(unsigned long long* out32, int reset);
 int read_sel_prof(unsigned long long* out64, int reset);
 int read_align_prof(unsigned long long* out16, int reset);

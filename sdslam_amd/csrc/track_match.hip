@@ -1102,9 +1102,13 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match_local(const sd_keypoint
 
 // Frame::ComputeStereoFromRGBD (src/Frame.cc:399-417): d = imDepth.at<float>(kp.pt.y, kp.pt.x) at the
 // DISTORTED keypoint (coordinates truncated to int); mvDepth = d, mvuRight = kpU.pt.x - mbf / d if d > 0.
+// T = the depth map's element type; kConvert: Tracking::GrabImageRGBD's convertTo(CV_32F, mDepthMapFactor) applied to the
+// one pixel read (src/Tracking.cc:147-148; OpenCV's cvtScale to 32F: one float product, rounded once).  <float, false> is
+// the host call's kernel.
+template <typename T, bool kConvert>
 __global__ void k_stereo_from_depth(const sd_keypoint* __restrict__ kps, const sd_keypoint* __restrict__ kps_un,
-                                    const int32_t* __restrict__ nkp, TrackBuffers tb, TrackCam cam, const float* __restrict__ depth,
-                                    int w, int h, int stride, size_t frame_stride) {
+                                    const int32_t* __restrict__ nkp, TrackBuffers tb, TrackCam cam, const T* __restrict__ depth,
+                                    int w, int h, int stride, size_t frame_stride, float scale) {
   const int f = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x, cap = tb.kp_cap;
   if (i >= cap) return;
   float ur = -1.f, dd = -1.f;
@@ -1112,7 +1116,8 @@ __global__ void k_stereo_from_depth(const sd_keypoint* __restrict__ kps, const s
     const sd_keypoint kp = kps[(size_t)f * cap + i];
     const int v = (int)kp.y, u = (int)kp.x;
     if (u >= 0 && v >= 0 && u < w && v < h) {
-      const float d = depth[(size_t)f * frame_stride + (size_t)v * stride + u];
+      const T raw = depth[(size_t)f * frame_stride + (size_t)v * stride + u];
+      const float d = kConvert ? __fmul_rn((float)raw, scale) : (float)raw;
       if (d > 0) {
         dd = d;
         ur = kps_un[(size_t)f * cap + i].x - cam.bf / d;
@@ -1123,12 +1128,32 @@ __global__ void k_stereo_from_depth(const sd_keypoint* __restrict__ kps, const s
   tb.depth[(size_t)f * cap + i] = dd;
 }
 
-int launch_stereo_from_depth(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_depth, int w, int h,
-                             int stride_elems, size_t frame_stride_elems, int n_frames, hipStream_t s) {
-  hipLaunchKernelGGL(k_stereo_from_depth, dim3((tb.kp_cap + 255) / 256, n_frames), dim3(256), 0, s, cur->d_kps,
-                     (cur->have_dist ? cur->d_kps_un : cur->d_kps), cur->d_nout, tb, cam, d_depth, w, h, stride_elems, frame_stride_elems);
+template <typename T, bool kConvert>
+static int launch_stereo_from_depth_t(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const T* d_depth, int w, int h,
+                                      int stride_elems, size_t frame_stride_elems, float scale, int n_frames, hipStream_t s) {
+  hipLaunchKernelGGL((k_stereo_from_depth<T, kConvert>), dim3((tb.kp_cap + 255) / 256, n_frames), dim3(256), 0, s, cur->d_kps,
+                     (cur->have_dist ? cur->d_kps_un : cur->d_kps), cur->d_nout, tb, cam, d_depth, w, h, stride_elems, frame_stride_elems,
+                     scale);
   SD_HIP_CHECK(hipGetLastError());
   return SD_OK;
+}
+
+int launch_stereo_from_depth(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_depth, int w, int h,
+                             int stride_elems, size_t frame_stride_elems, int n_frames, hipStream_t s) {
+  return launch_stereo_from_depth_t<float, false>(cur, tb, cam, d_depth, w, h, stride_elems, frame_stride_elems, 1.f, n_frames, s);
+}
+
+int launch_stereo_from_depth_typed(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const void* d_depth, int u16,
+                                   int convert, float scale, int w, int h, int stride_elems, size_t frame_stride_elems, int n_frames,
+                                   hipStream_t s) {
+  if (u16)   // 16-bit depth is always converted (src/Tracking.cc:147: imD.type() != CV_32F)
+    return launch_stereo_from_depth_t<uint16_t, true>(cur, tb, cam, (const uint16_t*)d_depth, w, h, stride_elems, frame_stride_elems,
+                                                      scale, n_frames, s);
+  if (convert)
+    return launch_stereo_from_depth_t<float, true>(cur, tb, cam, (const float*)d_depth, w, h, stride_elems, frame_stride_elems, scale,
+                                                   n_frames, s);
+  return launch_stereo_from_depth_t<float, false>(cur, tb, cam, (const float*)d_depth, w, h, stride_elems, frame_stride_elems, 1.f,
+                                                  n_frames, s);
 }
 
 // ------------------------------------------------------------------------------------------------

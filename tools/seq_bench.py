@@ -7,7 +7,15 @@
            sd_track_set_last + sd_track_set_map_ids + sd_track_set_poses.  Two trackers with swapped extractor roles
            alternate, so the previous frame's pyramid is the reference without a second extraction.
 
-python tools/seq_bench.py [T=8] [B list=1,1024]  -> one JSON line per (B, mode), all of them in profiles/seq_bench.json
+RGB-D modes (device hand-off, bMono = false, TrackLocalMap at th 3, sd_track_close_points every frame):
+  host_f32    per frame: sd_track_stereo_from_depth on CV_32F maps in (pageable) host memory -- the call allocates, copies
+              the whole maps and synchronises
+  device_u16  per frame: sd_track_stereo_from_depth_device on 16-bit maps resident in HBM, DepthMapFactor 5000 (TUM)
+  mono        the monocular device loop above, as the baseline
+  (the mode list "rgbd" = host_f32,device_u16,mono)
+
+python tools/seq_bench.py [T=8] [B list=1,1024] [modes=device,host]  -> one JSON line per (B, mode), all of them in
+profiles/seq_bench.json (profiles/seq_bench_rgbd.json when RGB-D modes run).
 Frames are resident in HBM (extraction from device memory); the timed region is frames 1..T-1 including extraction, ended
 by a synchronisation.  NU distinct sequences are tiled over the B streams.
 """
@@ -25,7 +33,13 @@ from sdslam_amd import synth  # noqa: E402
 
 T = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 BS = [int(b) for b in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1, 1024]
+MODES = sys.argv[3].split(",") if len(sys.argv) > 3 else ["device", "host"]
+if MODES == ["rgbd"]:
+    MODES = ["host_f32", "device_u16", "mono"]
+RGBD = any(m in ("host_f32", "device_u16") for m in MODES)
 NU = 8
+BF = 4.0             # baseline x fx of the synthetic RGB-D camera (tests/test_sequence_gpu.py)
+TH_CLOSE = 2.0       # mThDepth handed to sd_track_close_points: about the median depth of the synthetic scenes
 M = 1000
 CFG = (1000, 1.2, 8, 20)
 K = (synth.FX, synth.FY, synth.CX, synth.CY)
@@ -79,6 +93,38 @@ def run_device(B, seqs):
     return dt, st
 
 
+def run_rgbd(B, seqs, mode):
+    frames, ext, maps, vel = setup(B, seqs)
+    raw = np.stack([np.stack([np.round(seqs[b % NU]["depth"][t] * 5000.0).astype(np.uint16) for b in range(B)]) for t in range(T)])
+    if mode == "device_u16":
+        dmaps = sdslam_amd.DeviceBuffer(raw.nbytes)
+        dmaps.upload(raw)
+    else:
+        conv = [raw[t].astype(np.float32) * (np.float32(1) / np.float32(5000)) for t in range(T)]
+    del raw
+    trk = new_tracker(ext[0], ext[1], B, maps, seqs)
+    trk.set_camera(*K, BF, BOUNDS)
+    t0 = time.perf_counter()
+    for t in range(1, T):
+        trk.cur.extract_batch_device(frames.ptr.value + t * B * F, B, 640, 480)
+        if mode == "device_u16":
+            trk.stereo_from_depth_device(dmaps.ptr.value + t * B * F * 2, trk.DEPTH_U16, 640, 480, depth_map_factor=5000.0)
+        else:
+            trk.stereo_from_depth(conv[t])
+        trk.set_prior(0, vel[t - 1], relative=True)
+        trk.track_with_motion_model(B, th=15.0, mono=False)
+        trk.track_local_map(B, th=3.0)
+        trk.close_points(B, 1, TH_CLOSE)
+        trk.advance(B, 1)
+    st = trk.get_local_map(0, B)["status"]        # synchronises
+    dt = time.perf_counter() - t0
+    trk.close()
+    frames.free()
+    if mode == "device_u16":
+        dmaps.free()
+    return dt, st
+
+
 def run_host(B, seqs):
     frames, ext, maps, vel = setup(B, seqs)
     trks = [new_tracker(ext[0], ext[1], B, maps, seqs), new_tracker(ext[1], ext[0], B, maps, seqs)]
@@ -124,17 +170,21 @@ def run_host(B, seqs):
 
 
 def main():
-    seqs = [synth.make_sequence(100 + i, T) for i in range(NU)]
+    seqs = [synth.make_sequence(100 + i, T, with_depth=RGBD) for i in range(NU)]
+    fns = dict(device=run_device, mono=run_device, host=run_host, host_f32=lambda B, s: run_rgbd(B, s, "host_f32"),
+               device_u16=lambda B, s: run_rgbd(B, s, "device_u16"))
     out = []
     for B in BS:
-        for mode, fn in (("device", run_device), ("host", run_host)):
-            dt, st = fn(B, seqs)
+        for mode in MODES:
+            dt, st = fns[mode](B, seqs)
             r = dict(metric="seq_track", mode=mode, B=B, T=T, seconds=round(dt, 4), frames_per_s=round(B * (T - 1) / dt, 1),
                      ms_per_step=round(1e3 * dt / (T - 1), 3), tracked_last_frame=float(np.mean(st == 2)))
+            if mode in ("host_f32", "device_u16"):
+                r["depth_bytes_copied_per_step"] = B * F * 4 if mode == "host_f32" else 0
             print(json.dumps(r), flush=True)
             out.append(r)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "seq_bench.json"), "w") as f:
+    with open(os.path.join(ROOT, "profiles", "seq_bench_rgbd.json" if RGBD else "seq_bench.json"), "w") as f:
         json.dump(out, f, indent=1)
 
 
