@@ -182,7 +182,7 @@ class TrackBatch {
   // ids: the caller's MapPoint identities (which 0: the last frame's points, 1: the local map's; -1 = none).  With both set,
   // TrackLocalMap skips the local points TrackWithMotionModel saw (mnLastFrameSeen, :703, :900-918).
   void SetMapIds(int frame, int which, const int32_t* ids, int n) { check(sd_track_set_map_ids(h_, frame, 1, which, ids, n)); }
-  // source 1: after TrackLocalMap; 0: after TrackWithMotionModel.  The extractors swap roles afterwards.
+  // source 1: after TrackLocalMap; 0: after TrackWithMotionModel; 2: after StereoInitialization.  The extractors swap roles afterwards.
   void AdvanceLastFrame(int n_frames, int source = 1) { check(sd_track_advance(h_, n_frames, source)); }
   // CurrentFrame pose prior, 16 doubles column-major per frame: T (relative = false) or T * LastFrame.GetPose()
   // (ConstantVelocity::GetPose, relative = true)
@@ -208,6 +208,44 @@ class TrackBatch {
     check(sd_track_get_close_points(h_, frame, 1, out2));
     nTrackedClose = out2[0];
     nNonTrackedClose = out2[1];
+  }
+  // RGB-D map points on the device (src/Tracking.cc:302-349, :753-896).  Frame 0: extract, ComputeStereoFromRGBD,
+  // StereoInitialization, AdvanceLastFrame(n, 2).  Later frames: ... Tracking::TrackLocalMap -> CloseTrackedPoints(n, 1, thDepth)
+  // -> Tracking::NeedNewKeyFrame -> Tracking::CreateNewKeyFrame(use_flags) -> AdvanceLastFrame(n, 1).
+  // Tracking::StereoInitialization (:302-349), queued: slots with more than min_keypoints keypoints get the identity pose and
+  // one map point per keypoint with depth, ids from SetNextMapPointId in keypoint order
+  void StereoInitialization(int n_frames, int min_keypoints = 500) { check(sd_track_stereo_init(h_, n_frames, min_keypoints)); }
+  // MapPoint::nNextId of the slots' maps
+  void SetNextMapPointId(int frame0, int n_frames, const int32_t* next_id) { check(sd_track_set_next_map_id(h_, frame0, n_frames, next_id)); }
+  // NeedNewKeyFrame's caller state, 8 ints per slot {KeyFramesInMap(), mpReferenceKF->TrackedMapPoints(nMinObs), mnLastKeyFrameId,
+  // mnLastRelocFrameId, flags (1 AcceptKeyFrames(), 2 isStopped() || stopRequested(), 4 KeyframesInQueue() < 3, 8 usePattern), 0, 0,
+  // 0}; SD_KF_KEEP leaves an entry as the device has it
+  void SetKeyFrameState(int frame0, int n_frames, const int32_t* state8) { check(sd_track_set_keyframe_state(h_, frame0, n_frames, state8)); }
+  // the decision bytes: bit 0 insert a keyframe, bit 1 wanted but the mapper is busy (call InterruptBA)
+  void SetKeyFrameFlags(int frame0, int n_frames, const uint8_t* flags) { check(sd_track_set_keyframe_flags(h_, frame0, n_frames, flags)); }
+  uint8_t KeyFrameFlags(int frame) {
+    uint8_t f = 0;
+    check(sd_track_get_keyframe_flags(h_, frame, 1, &f));
+    return f;
+  }
+  // the map points the last StereoInitialization / Tracking::CreateNewKeyFrame made in slot `frame`, in creation order (what
+  // the caller mirrors into its Map; KeyFrame construction and InsertKeyFrame stay with it).  Synchronises.
+  struct CreatedMapPoints {
+    int mode = 0;                   // 0 nothing created on the slot, 1 keyframe, 2 initialisation
+    int processed = 0, candidates = 0;
+    std::vector<int32_t> keypoint;  // index into the frame's keypoints
+    std::vector<int32_t> id;
+    std::vector<double> Xw;         // 3 per point
+  };
+  CreatedMapPoints CreatedPoints(int frame) {
+    const int cap = 2048;           // the tracker's keypoint limit
+    CreatedMapPoints c;
+    int32_t i4[4];
+    c.keypoint.resize(cap); c.id.resize(cap); c.Xw.resize((size_t)cap * 3);
+    check(sd_track_get_created(h_, frame, 1, i4, c.keypoint.data(), c.Xw.data(), c.id.data(), cap));
+    c.mode = i4[0]; c.processed = i4[2]; c.candidates = i4[3];
+    c.keypoint.resize(i4[1]); c.id.resize(i4[1]); c.Xw.resize((size_t)i4[1] * 3);
+    return c;
   }
   // the extractor whose frames are tracked next (the two swap roles at every AdvanceLastFrame)
   ORBextractor& CurrentExtractor() {
@@ -329,6 +367,17 @@ class Tracking {
     check(sd_track_get_local_map(batch.handle(), frame, 1, mvpMapPoints ? mvpMapPoints->data() : nullptr, kp_cap, i4));
     if (mnMatchesInliers) *mnMatchesInliers = i4[2];
     return i4[0] == 2;
+  }
+  // Tracking::NeedNewKeyFrame (src/Tracking.cc:753-826) for every slot, queued, on TrackLocalMap's mnMatchesInliers, the counts
+  // of TrackBatch::CloseTrackedPoints(n_frames, 1, mThDepth) and TrackBatch::SetKeyFrameState; frame_id = mCurrentFrame.mnId.
+  // The answer is TrackBatch::KeyFrameFlags, or feeds CreateNewKeyFrame directly.
+  static void NeedNewKeyFrame(TrackBatch& batch, int n_frames, bool rgbd, int frame_id, int mMinFrames, int mMaxFrames) {
+    check(sd_track_need_keyframe(batch.handle(), n_frames, rgbd ? 1 : 0, frame_id, mMinFrames, mMaxFrames));
+  }
+  // The RGB-D part of Tracking::CreateNewKeyFrame (:837-888, mnLastKeyFrameId :894) for the tracked slots (with use_flags: those
+  // whose decision bit 0 is set), queued; source as in AdvanceLastFrame, which then carries the points.
+  static void CreateNewKeyFrame(TrackBatch& batch, int n_frames, int source, float mThDepth, bool use_flags, int frame_id) {
+    check(sd_track_create_keyframe_points(batch.handle(), n_frames, source, mThDepth, use_flags ? 1 : 0, frame_id));
   }
   static Tracked Result(TrackBatch& batch, int frame) {
     int32_t i4[4];

@@ -383,7 +383,8 @@ int sd_track_pack_records(sd_track* h, int n_frames, int source, void* d_records
  *   longer have to exclude them.  Points without ids (-1) are never skipped, so without ids nothing changes.
  * sd_track_advance: for every slot < n_frames and current keypoint i < N, the last frame's point i becomes mvpMapPoints[i]
  *   (source 0: after sd_track_with_motion_model's discard; 1: after sd_track_local_map, local points included, mvbOutlier
- *   dropped), kept iff it has Observations() >= 1, with its Xw / descriptor / obs / id; octave = mvKeys[i].octave, angle =
+ *   dropped; 2: after sd_track_stereo_init, the created points only, Tref = the identity), kept iff it has Observations()
+ *   >= 1, with its Xw / descriptor / obs / id; octave = mvKeys[i].octave, angle =
  *   mvKeysUn[i].angle; n_last = N; Tref = the frame's final pose (the prior when no pose solve ran).  Slots >= n_frames keep
  *   their last frame.  Then the cur / ref extractors swap roles (this frame's pyramid and keypoints are the next reference):
  *   extract the next frame into the new cur.  Queued on the tracking stream; that extraction waits for the kernels that
@@ -413,6 +414,60 @@ int sd_track_get_close_points(sd_track* h, int frame0, int n_frames, int32_t* ou
 int sd_track_stream_fence(sd_track* h, void* hip_stream, int direction);
 int sd_track_set_profiling(sd_track* h, int on);
 int sd_track_stage_ms(sd_track* h, float* ms_out /* [0]=align, [1]=match, [2]=pnp */, int cap);
+
+/* ------------------------------------------------------------------------------------------
+ * RGB-D map points created on the device, so B streams bootstrap, track, decide and refill their points without a host wait
+ *   Tracking::StereoInitialization                src/Tracking.cc:302-349
+ *   Tracking::NeedNewKeyFrame                     src/Tracking.cc:753-826
+ *   Tracking::CreateNewKeyFrame, RGB-D part       src/Tracking.cc:837-888, mnLastKeyFrameId :894
+ *   Frame::UnprojectStereo                        src/Frame.cc:419-431
+ * Per frame:  ... -> sd_track_local_map -> sd_track_close_points -> sd_track_need_keyframe ->
+ *   sd_track_create_keyframe_points(use_flags = 1) -> sd_track_advance; frame 0: extract, depth, sd_track_stereo_init,
+ *   sd_track_advance(source = 2).  All calls but the two getters are queued on the tracking stream without a host wait; the
+ *   small host arrays travel through a ring of pinned buffers like sd_track_set_prior's.
+ * sd_track_set_next_map_id: MapPoint::nNextId per slot; created points get next_id, next_id + 1, ... in creation order and the
+ *   device advances it (0 for a new handle).
+ * sd_track_stereo_init: a slot with N = min(keypoints, capacity) > min_keypoints (reference: 500) sets its pose (Tcur) to the
+ *   identity and gives every keypoint with mvDepth > 0 a point, ids in keypoint order.  Other slots create nothing (info mode 0)
+ *   and sd_track_advance(source 2) leaves their last frame alone.
+ * sd_track_set_keyframe_state: state8 = [n][8] int32 {nKFs = KeyFramesInMap(), nRefMatches = mpReferenceKF->
+ *   TrackedMapPoints(nMinObs), mnLastKeyFrameId, mnLastRelocFrameId, flags, 3 reserved}; flags bit 0 AcceptKeyFrames() (mapper
+ *   idle), bit 1 isStopped() || stopRequested(), bit 2 KeyframesInQueue() < 3, bit 3 usePattern (enters nMinObs, which the caller
+ *   applied to nRefMatches: not read).  An entry equal to SD_KF_KEEP leaves the device's value: sd_track_create_keyframe_points
+ *   writes mnLastKeyFrameId itself.  nKFs and nRefMatches come from the KeyFrame graph and stay the caller's.
+ * sd_track_need_keyframe: the decision for slots < n_frames as one byte per slot: bit 0 insert a keyframe, bit 1 the conditions
+ *   held but the mapper is busy (where the reference calls InterruptBA; bit 0 is then KeyframesInQueue() < 3 for RGB-D).  Reads
+ *   mnMatchesInliers of sd_track_local_map and, for rgbd, the counts of sd_track_close_points(source 1): both must have run on
+ *   this extraction.  mnMatchesInliers < nRefMatches * 0.25 compares in double, < nRefMatches * thRefRatio in float (0.75f, 0.4f
+ *   for nKFs < 2, 0.9f when not rgbd).  A slot that is not tracked gets 0.
+ * sd_track_set_keyframe_flags / sd_track_get_keyframe_flags: the same bytes from / to the host (the getter synchronises).
+ * sd_track_create_keyframe_points: for every slot < n_frames that the call named by `source` (as in sd_track_advance) left
+ *   tracked and, with use_flags, whose flag bit 0 is set: keypoints with mvDepth > 0 sorted by (depth, index); the prefix up to
+ *   and including the first entry beyond th_depth (mThDepth) past the 100th is processed, and each of its keypoints that holds no
+ *   map point with Observations() >= 1 -- outlier flags not consulted, :861-867 -- gets a new point: Xw = UnprojectStereo from
+ *   the frame's final pose, Observations() = 1, the keypoint's descriptor, the next id.  mnLastKeyFrameId of the slot = frame_id.
+ *   The depth sort holds 2048 keys: SD_ERR_CAPACITY for a larger keypoint capacity.  UnprojectStereo: x = (u - cx) * z * invfx
+ *   in float, then Xw[r] = ((Rwc[r][0] * x + Rwc[r][1] * y) + Rwc[r][2] * z) + Ow[r], Ow[r] = -((Rwc[r][0] * t0 + Rwc[r][1] *
+ *   t1) + Rwc[r][2] * t2) in double, every operation rounded on its own.
+ *   A following sd_track_advance(source) hands each created point to the next frame in place of whatever the keypoint held.
+ *   The depth precondition is sd_track_close_points'.  A second creation call on one extraction replaces the first one's
+ *   record but has already advanced the ids.
+ * sd_track_get_created: per slot info4 = {mode (0 nothing created on the slot, 1 keyframe, 2 initialisation), created, P =
+ *   processed prefix (candidates for mode 2), candidates}, and [n][cap] rows in creation order: keypoint index, Xw ([n][cap][3]),
+ *   id; any of the three may be NULL.  Synchronises.  info4 is written even when the call returns SD_ERR_CAPACITY.  KeyFrame construction, InsertKeyFrame and later observations stay with
+ *   the caller.
+ * Errors: SD_ERR_INVALID_ARG for a bad source, when the call named by `source` (sd_track_need_keyframe: sd_track_local_map and
+ *   sd_track_close_points) has not run since the extraction, or in broadcast mode; SD_ERR_CAPACITY for n_frames > max_batch or
+ *   a cap smaller than a slot's number of created points. */
+#define SD_KF_KEEP INT32_MIN
+int sd_track_set_next_map_id(sd_track* h, int frame0, int n_frames, const int32_t* next_id);
+int sd_track_stereo_init(sd_track* h, int n_frames, int min_keypoints);
+int sd_track_set_keyframe_state(sd_track* h, int frame0, int n_frames, const int32_t* state8);
+int sd_track_need_keyframe(sd_track* h, int n_frames, int rgbd, int frame_id, int min_frames, int max_frames);
+int sd_track_set_keyframe_flags(sd_track* h, int frame0, int n_frames, const uint8_t* flags);
+int sd_track_get_keyframe_flags(sd_track* h, int frame0, int n_frames, uint8_t* flags);
+int sd_track_create_keyframe_points(sd_track* h, int n_frames, int source, float th_depth, int use_flags, int frame_id);
+int sd_track_get_created(sd_track* h, int frame0, int n_frames, int32_t* info4, int32_t* kp_index, double* Xw, int32_t* ids, int cap);
 
 /* ------------------------------------------------------------------------------------------
  * ORBmatcher::DescriptorDistance -- src/ORBmatcher.h:44, src/ORBmatcher.cc:1459-1473

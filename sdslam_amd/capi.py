@@ -668,7 +668,7 @@ class Tracker:
 
     def advance(self, n_frames, source=1):
         """mLastFrame = Frame(mCurrentFrame) for every slot on the device; source 0: after track_with_motion_model, 1: after
-        track_local_map.  The extractors swap roles: extract the next frame into `self.cur`."""
+        track_local_map, 2: after stereo_init.  The extractors swap roles: extract the next frame into `self.cur`."""
         self.L.sd_track_advance.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(self.L.sd_track_advance(self.h, n_frames, int(source)))
         self._follow_extractors()
@@ -710,6 +710,59 @@ class Tracker:
         self.L.sd_track_get_close_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _check(self.L.sd_track_get_close_points(self.h, frame0, n, _p(out)))
         return dict(tracked=out[:, 0].copy(), non_tracked=out[:, 1].copy())
+
+    # --- RGB-D map point creation and the keyframe decision on the device (src/Tracking.cc:302-349, :753-896) ---
+    KF_KEEP = -2 ** 31      # SD_KF_KEEP: a state entry that leaves the device's value
+
+    def set_next_map_id(self, frame0, next_ids):
+        """MapPoint::nNextId of every slot's map: the id the next created point receives."""
+        a = np.ascontiguousarray(next_ids, np.int32)
+        self.L.sd_track_set_next_map_id.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _check(self.L.sd_track_set_next_map_id(self.h, frame0, len(a), _p(a)))
+
+    def stereo_init(self, n_frames, min_keypoints=500):
+        """Queue Tracking::StereoInitialization for slots < n_frames: identity pose, one map point per keypoint with depth."""
+        self.L.sd_track_stereo_init.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(self.L.sd_track_stereo_init(self.h, n_frames, int(min_keypoints)))
+
+    def set_keyframe_state(self, frame0, state8):
+        """NeedNewKeyFrame's caller state, [n][8] int32: nKFs, nRefMatches, last_kf_id, last_reloc_id, flags, 3 reserved."""
+        a = np.ascontiguousarray(state8, np.int32)
+        assert a.ndim == 2 and a.shape[1] == 8
+        self.L.sd_track_set_keyframe_state.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _check(self.L.sd_track_set_keyframe_state(self.h, frame0, a.shape[0], _p(a)))
+
+    def need_keyframe(self, n_frames, rgbd, frame_id, min_frames, max_frames):
+        """Queue Tracking::NeedNewKeyFrame for slots < n_frames; the result is the slots' keyframe flags."""
+        self.L.sd_track_need_keyframe.argtypes = [C.c_void_p] + [C.c_int] * 5
+        _check(self.L.sd_track_need_keyframe(self.h, n_frames, int(bool(rgbd)), int(frame_id), int(min_frames), int(max_frames)))
+
+    def set_keyframe_flags(self, frame0, flags):
+        a = np.ascontiguousarray(flags, np.uint8)
+        self.L.sd_track_set_keyframe_flags.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _check(self.L.sd_track_set_keyframe_flags(self.h, frame0, len(a), _p(a)))
+
+    def get_keyframe_flags(self, frame0, n):
+        out = np.zeros(n, np.uint8)
+        self.L.sd_track_get_keyframe_flags.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _check(self.L.sd_track_get_keyframe_flags(self.h, frame0, n, _p(out)))
+        return out
+
+    def create_keyframe_points(self, n_frames, source, th_depth, use_flags=False, frame_id=0):
+        """Queue the RGB-D part of Tracking::CreateNewKeyFrame for slots < n_frames (use_flags: only where flag bit 0 is set)."""
+        self.L.sd_track_create_keyframe_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int]
+        _check(self.L.sd_track_create_keyframe_points(self.h, n_frames, int(source), float(th_depth), int(bool(use_flags)), int(frame_id)))
+
+    def get_created(self, frame0, n, cap=None):
+        """The points the last creation call made, per slot in creation order: dict(mode, created, P, candidates, kp_index, Xw, ids)
+        with [n][cap] rows (cap defaults to the keypoint capacity), entries >= created are -1 / 0."""
+        cap = self.cap if cap is None else cap
+        info = np.zeros((n, 4), np.int32)
+        idx, ids, Xw = np.full((n, cap), -1, np.int32), np.full((n, cap), -1, np.int32), np.zeros((n, cap, 3))
+        self.L.sd_track_get_created.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int]
+        _check(self.L.sd_track_get_created(self.h, frame0, n, _p(info), _p(idx), _p(Xw), _p(ids), cap))
+        return dict(mode=info[:, 0].copy(), created=info[:, 1].copy(), P=info[:, 2].copy(), candidates=info[:, 3].copy(), kp_index=idx,
+                    Xw=Xw, ids=ids)
 
     def set_profiling(self, on=True):
         _check(self.L.sd_track_set_profiling(self.h, int(on)))

@@ -65,6 +65,22 @@ struct sd_track {
   int prior_next = 0;
   double* d_prior = nullptr;       // [max_batch][16]
   int32_t* d_close = nullptr;      // [max_batch][2] sd_track_close_points: nTrackedClose, nNonTrackedClose
+  // ... and of sd_track_close_points (sd_track_need_keyframe reads its counts)
+  const sd_orb* close_cur = nullptr;
+  unsigned long long close_serial = 0;
+  int close_n = 0, close_source = -1;
+  // the last map point creation (sd_track_stereo_init / sd_track_create_keyframe_points) on the current extraction:
+  // sd_track_advance then takes the created keypoints' points from the np_* buffers
+  const sd_orb* made_cur = nullptr;
+  unsigned long long made_serial = 0;
+  int made_n = 0, made_mode = 0, made_source = -1;
+  // sd_track_set_keyframe_state / sd_track_set_keyframe_flags / sd_track_set_next_map_id: small host arrays through a ring
+  // of pinned buffers ([max_batch][8] int32 each) on the tracking stream, like the prior
+  int32_t* small_host[kPriorRing] = {};
+  hipEvent_t ev_small[kPriorRing] = {};
+  bool small_pending[kPriorRing] = {};
+  int small_next = 0;
+  int32_t* d_kf_stage = nullptr;   // [max_batch][8]
   static const int kRing = 128;
   hipEvent_t ev[kRing][6] = {};
   int ev_calls[3] = {0, 0, 0};
@@ -99,20 +115,6 @@ __global__ void k_pack_records(TrackBuffers tb, int source, int n_frames, double
   r[19] = ok;
 }
 
-// The map point mvpMapPoints[i] = m keeps after Tracking::Track's "Clean VO matches" (Observations() >= 1, reference
-// src/Tracking.cc:250-257) and outlier discard (:272-275): source 0 = cur_match after TrackWithMotionModel's discard (no
-// outlier flags left), 1 = un_match after TrackLocalMap, m >= M naming local point m - M, outl_i = &mvbOutlier[i].
-// Returns its Observations() if it is kept, else 0; *e / *loc locate it.  o = slot * M.  k_advance keeps these points and
-// k_close_points counts them as tracked: one test for both.
-__device__ __forceinline__ int kept_point_obs(const TrackBuffers& tb, int source, int m, const uint8_t* outl_i, size_t o, size_t* e,
-                                              bool* loc) {
-  if (m < 0 || (source == 1 && *outl_i)) return 0;
-  *loc = m >= tb.max_points;
-  *e = o + (*loc ? m - tb.max_points : m);
-  const int n_obs = *loc ? tb.lm_obs[*e] : tb.obs[*e];
-  return n_obs >= 1 ? n_obs : 0;
-}
-
 // Tracking::Track's hand-off to the next frame (reference src/Tracking.cc:250-292), one workgroup per slot, into the second
 // last-frame SoA (the host swaps the two afterwards: what is read and what is written overlap).  Keypoint i < N of the current
 // frame keeps map point m = mvpMapPoints[i] -- source 0: cur_match after TrackWithMotionModel's outlier discard; 1: un_match
@@ -120,12 +122,17 @@ __device__ __forceinline__ int kept_point_obs(const TrackBuffers& tb, int source
 // Observations() >= 1 ("Clean VO matches" :250-257, outliers :272-275).  Kept points carry Xw / descriptor / obs / id; the
 // others zeros and id -1.  octave = mvKeys[i].octave, angle = mvKeysUn[i].angle; n_last = N; Tref = the frame's final pose,
 // which both tracking tails leave in Tcur.  Slots >= n_frames keep their last frame (copied across).
+// created_n > 0: a creation call (track_newpoints.hip) ran on this extraction for slots < created_n; a keypoint it gave a new
+// point carries that point -- np_Xw, the keypoint's own descriptor (ComputeDistinctiveDescriptors with one observation),
+// Observations() = 1, np_id -- whatever mvbOutlier[i] says.  source 2: after StereoInitialization mvpMapPoints are the
+// created points only and Tref = the identity it left in Tcur; slots that did not initialise keep their last frame.
 __global__ __launch_bounds__(256) void k_advance(const sd_keypoint* __restrict__ kps_all, const sd_keypoint* __restrict__ kps_un_all,
-                                                 const int32_t* __restrict__ nkp_all, TrackBuffers tb, int source, int n_frames) {
+                                                 const int32_t* __restrict__ nkp_all, TrackBuffers tb, int source, int n_frames,
+                                                 const uint8_t* __restrict__ desc_all, int created_n) {
   const int f = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
   const int M = tb.max_points, cap = tb.kp_cap;
   const size_t o = (size_t)f * M;
-  if (f >= n_frames) {
+  if (f >= n_frames || (source == 2 && tb.np_info[(size_t)f * 4] != 2)) {
     for (int i = tid; i < M; i += NT) {
       const size_t e = o + i;
       tb.valid2[e] = tb.valid[e];
@@ -142,6 +149,7 @@ __global__ __launch_bounds__(256) void k_advance(const sd_keypoint* __restrict__
   const int N = min(nkp_all[f], cap);   // cap <= M (sd_track_advance)
   const int32_t* match = (source == 0 ? tb.cur_match : tb.un_match) + (size_t)f * cap;
   const uint8_t* outl = tb.po_outlier + (size_t)f * cap;
+  const uint8_t* made = f < created_n ? tb.np_flag + (size_t)f * cap : nullptr;
   for (int i = tid; i < M; i += NT) {
     uint8_t v = 0;
     double X0 = 0, X1 = 0, X2 = 0;
@@ -153,8 +161,17 @@ __global__ __launch_bounds__(256) void k_advance(const sd_keypoint* __restrict__
       ang = kps_un_all[(size_t)f * cap + i].angle;
       bool loc = false;
       size_t e = 0;
-      const int n_obs = kept_point_obs(tb, source, match[i], outl + i, o, &e, &loc);
-      if (n_obs >= 1) {
+      const bool is_new = made && made[i];
+      const int n_obs = (is_new || source == 2) ? 0 : kept_point_obs(tb, source, match[i], outl + i, o, &e, &loc);
+      if (is_new) {
+        const size_t k = (size_t)f * cap + i;
+        const uint4* d = (const uint4*)desc_all + k * 2;
+        v = 1;
+        X0 = tb.np_Xw[k * 3]; X1 = tb.np_Xw[k * 3 + 1]; X2 = tb.np_Xw[k * 3 + 2];
+        d0 = d[0]; d1 = d[1];
+        ob = 1;
+        id = tb.np_id[k];
+      } else if (n_obs >= 1) {
         const double* X = (loc ? tb.lm_Xw : tb.Xw) + e * 3;
         const uint4* d = (const uint4*)(loc ? tb.lm_desc : tb.mp_desc) + e * 2;
         v = 1;
@@ -297,6 +314,15 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &tb.lm_id, B * M));
   A(dalloc(h, &h->d_prior, B * 16));
   A(dalloc(h, &h->d_close, B * 2));
+  A(dalloc(h, &tb.np_flag, B * K));
+  A(dalloc(h, &tb.np_Xw, B * K * 3));
+  A(dalloc(h, &tb.np_id, B * K));
+  A(dalloc(h, &tb.np_list, B * K));
+  A(dalloc(h, &tb.np_info, B * 4));
+  A(dalloc(h, &tb.next_id, B));
+  A(dalloc(h, &tb.kf_state, B * 8));
+  A(dalloc(h, &tb.kf_flags, B));
+  A(dalloc(h, &h->d_kf_stage, B * 8));
   A(dalloc(h, &tb.Tref, B * 16));
   A(dalloc(h, &tb.Tprior, B * 16));
   A(dalloc(h, &tb.Tcur, B * 16));
@@ -400,6 +426,8 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
     for (int r = 0; r < sd_track::kPriorRing && e == hipSuccess; r++) {
       e = hipHostMalloc((void**)&h->prior_host[r], B * 16 * sizeof(double), hipHostMallocDefault);
       if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_prior[r], hipEventDisableTiming);
+      if (e == hipSuccess) e = hipHostMalloc((void**)&h->small_host[r], B * 8 * sizeof(int32_t), hipHostMallocDefault);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_small[r], hipEventDisableTiming);
     }
     if (e == hipSuccess) {
       // Priority of the tracking stream.  Round 1 (extraction kernels at 6-7 waves per SIMD): lowest was best (122.3 k vs
@@ -439,6 +467,8 @@ void sd_track_destroy(sd_track* h) {
   for (int r = 0; r < sd_track::kPriorRing; r++) {
     if (h->prior_host[r]) (void)hipHostFree(h->prior_host[r]);
     if (h->ev_prior[r]) (void)hipEventDestroy(h->ev_prior[r]);
+    if (h->small_host[r]) (void)hipHostFree(h->small_host[r]);
+    if (h->ev_small[r]) (void)hipEventDestroy(h->ev_small[r]);
   }
   for (int r = 0; r < sd_track::kRing; r++)
     for (int i = 0; i < 6; i++)
@@ -1291,12 +1321,23 @@ int sd_track_set_map_ids(sd_track* h, int frame0, int n_frames, int which, const
 int sd_track_advance(sd_track* h, int n_frames, int source) {
   SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
   SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
-  SD_REQUIRE(source == 0 || source == 1, SD_ERR_INVALID_ARG, "source must be 0 (sd_track_with_motion_model) or 1 (sd_track_local_map)");
+  SD_REQUIRE(source >= 0 && source <= 2, SD_ERR_INVALID_ARG,
+             "source must be 0 (sd_track_with_motion_model), 1 (sd_track_local_map) or 2 (sd_track_stereo_init)");
   SD_REQUIRE(h->kp_cap <= h->max_points, SD_ERR_CAPACITY, "the keypoint capacity exceeds max_points: a last frame would not fit");
   SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
-  SD_REQUIRE(ran_since_extract(h, source, n_frames), SD_ERR_INVALID_ARG,
-             source == 0 ? "sd_track_with_motion_model has not run on these slots since the last extraction"
-                         : "sd_track_local_map has not run on these slots since the last extraction");
+  // a creation call on this extraction: its points go with the keypoints that received them
+  const bool made = h->made_cur == h->cur && h->made_serial == h->cur->extract_serial;
+  if (source == 2) {
+    SD_REQUIRE(made && h->made_mode == 2 && n_frames <= h->made_n, SD_ERR_INVALID_ARG,
+               "sd_track_stereo_init has not run on these slots since the last extraction");
+  } else {
+    SD_REQUIRE(ran_since_extract(h, source, n_frames), SD_ERR_INVALID_ARG,
+               source == 0 ? "sd_track_with_motion_model has not run on these slots since the last extraction"
+                           : "sd_track_local_map has not run on these slots since the last extraction");
+    SD_REQUIRE(!made || (h->made_mode == 1 && h->made_source == source), SD_ERR_INVALID_ARG,
+               "map points were created on this extraction from another source (sd_track_stereo_init: advance with source 2)");
+  }
+  const int created_n = made ? h->made_n : 0;
   int nsel_ref = 0;
   for (int q : h->ref->hp.quota) nsel_ref += q;
   SD_REQUIRE(nsel_ref == h->kp_cap && h->cur->max_batch >= h->max_batch, SD_ERR_INVALID_ARG,
@@ -1310,7 +1351,7 @@ int sd_track_advance(sd_track* h, int n_frames, int source) {
   if (rc != SD_OK) return rc;
   const sd_orb* c = h->cur;
   hipLaunchKernelGGL(k_advance, dim3(h->max_batch), dim3(256), 0, s, c->d_kps, c->have_dist ? c->d_kps_un : c->d_kps, c->d_nout, h->tb, source,
-                     n_frames);
+                     n_frames, c->d_desc, created_n);
   SD_HIP_CHECK(hipGetLastError());
   rc = mark_reads(h, false);
   if (rc != SD_OK) return rc;
@@ -1325,6 +1366,7 @@ int sd_track_advance(sd_track* h, int n_frames, int source) {
   std::swap(h->cur, h->ref);   // this frame's pyramid and keypoints are the next ImageAlign / match reference
   h->have_pnp = false;
   h->ran_cur[0] = h->ran_cur[1] = nullptr;
+  h->made_cur = h->close_cur = nullptr;
   return SD_OK;
 }
 
@@ -1343,6 +1385,10 @@ int sd_track_close_points(sd_track* h, int n_frames, int source, float th_depth)
   if (rc != SD_OK) return rc;
   hipLaunchKernelGGL(k_close_points, dim3(n_frames), dim3(256), 0, s, h->cur->d_nout, h->tb, source, th_depth, h->d_close);
   SD_HIP_CHECK(hipGetLastError());
+  h->close_cur = h->cur;
+  h->close_serial = h->cur->extract_serial;
+  h->close_n = n_frames;
+  h->close_source = source;
   return mark_reads(h, false);
 }
 
@@ -1351,6 +1397,127 @@ int sd_track_get_close_points(sd_track* h, int frame0, int n_frames, int32_t* ou
   SD_REQUIRE(out2, SD_ERR_INVALID_ARG, "NULL argument");
   SD_HIP_CHECK(hipMemcpyAsync(out2, h->d_close + (size_t)frame0 * 2, (size_t)n_frames * 8, hipMemcpyDeviceToHost, h->cur->stream));
   SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
+  return SD_OK;
+}
+
+// ---- RGB-D map point creation and the keyframe decision on the device (kernels: track_newpoints.hip)
+
+// `bytes` (at most max_batch x 32, a ring buffer's size) from the host into `dst` on the tracking stream, through the pinned
+// ring: no host wait unless the ring slot's copy of kPriorRing calls ago is still pending
+static int small_upload(sd_track* h, void* dst, const void* src, size_t bytes) {
+  SD_REQUIRE(bytes <= (size_t)h->max_batch * 8 * sizeof(int32_t), SD_ERR_CAPACITY, "upload exceeds the pinned ring buffer");
+  const int r = h->small_next;
+  h->small_next = (r + 1) % sd_track::kPriorRing;
+  if (h->small_pending[r]) SD_HIP_CHECK(hipEventSynchronize(h->ev_small[r]));
+  std::memcpy(h->small_host[r], src, bytes);
+  SD_HIP_CHECK(hipMemcpyAsync(dst, h->small_host[r], bytes, hipMemcpyHostToDevice, h->pnp_stream));
+  SD_HIP_CHECK(hipEventRecord(h->ev_small[r], h->pnp_stream));
+  h->small_pending[r] = true;
+  return SD_OK;
+}
+
+#define SMALL_RANGE(h, frame0, n, p)                                                                                         \
+  SD_REQUIRE((h) && (p), SD_ERR_INVALID_ARG, "NULL argument");                                                             \
+  SD_REQUIRE((frame0) >= 0 && (n) >= 1 && (frame0) + (n) <= (h)->max_batch, SD_ERR_CAPACITY, "frame range exceeds max_batch"); \
+  SD_HIP_CHECK(hipSetDevice((h)->device))
+
+int sd_track_set_next_map_id(sd_track* h, int frame0, int n_frames, const int32_t* next_id) {
+  SMALL_RANGE(h, frame0, n_frames, next_id);
+  return small_upload(h, h->tb.next_id + frame0, next_id, (size_t)n_frames * 4);
+}
+
+int sd_track_set_keyframe_state(sd_track* h, int frame0, int n_frames, const int32_t* state8) {
+  SMALL_RANGE(h, frame0, n_frames, state8);
+  int rc = small_upload(h, h->d_kf_stage, state8, (size_t)n_frames * 32);
+  if (rc != SD_OK) return rc;
+  return launch_set_keyframe_state(h->tb, h->d_kf_stage, frame0, n_frames, h->pnp_stream);
+}
+
+int sd_track_set_keyframe_flags(sd_track* h, int frame0, int n_frames, const uint8_t* flags) {
+  SMALL_RANGE(h, frame0, n_frames, flags);
+  return small_upload(h, h->tb.kf_flags + frame0, flags, (size_t)n_frames);
+}
+
+int sd_track_get_keyframe_flags(sd_track* h, int frame0, int n_frames, uint8_t* flags) {
+  TRACK_RANGE(h, frame0, n_frames);
+  SD_REQUIRE(flags, SD_ERR_INVALID_ARG, "NULL argument");
+  SD_HIP_CHECK(hipMemcpyAsync(flags, h->tb.kf_flags + frame0, (size_t)n_frames, hipMemcpyDeviceToHost, h->cur->stream));
+  SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
+  return SD_OK;
+}
+
+int sd_track_need_keyframe(sd_track* h, int n_frames, int rgbd, int frame_id, int min_frames, int max_frames) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
+  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
+  SD_REQUIRE(ran_since_extract(h, 1, n_frames), SD_ERR_INVALID_ARG,
+             "sd_track_local_map has not run on these slots since the last extraction");
+  SD_REQUIRE(!rgbd || (h->close_cur == h->cur && h->close_serial == h->cur->extract_serial && n_frames <= h->close_n && h->close_source == 1),
+             SD_ERR_INVALID_ARG, "sd_track_close_points (source 1) has not run on these slots since the last extraction");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  return launch_need_keyframe(h->tb, h->d_close, n_frames, rgbd != 0, frame_id, min_frames, max_frames, h->pnp_stream);
+}
+
+static int new_points(sd_track* h, int n_frames, int mode, int source, float th_depth, int use_flags, int frame_id, int min_keypoints) {
+  hipStream_t s = h->pnp_stream;
+  int rc = wait_inputs(h, false);
+  if (rc != SD_OK) return rc;
+  // Frame::invfx = 1.0f / fx (src/Frame.cc:90), rounded on the host
+  rc = launch_new_points(h->cur, h->tb, h->cam, 1.0f / h->cam.ffx, 1.0f / h->cam.ffy, n_frames, mode, source, th_depth, use_flags, frame_id,
+                         min_keypoints, s);
+  if (rc != SD_OK) return rc;
+  h->made_cur = h->cur;
+  h->made_serial = h->cur->extract_serial;
+  h->made_n = n_frames;
+  h->made_mode = mode;
+  h->made_source = source;
+  return mark_reads(h, false);
+}
+
+int sd_track_stereo_init(sd_track* h, int n_frames, int min_keypoints) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
+  SD_REQUIRE(h->have_cam, SD_ERR_INVALID_ARG, "sd_track_set_camera has not been called");
+  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
+  SD_REQUIRE(h->cur->have_geom && h->cur->last_frames >= n_frames, SD_ERR_INVALID_ARG, "current frames have not been extracted");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  h->have_pnp = false;
+  return new_points(h, n_frames, 2, 0, 0.f, 0, 0, min_keypoints);
+}
+
+int sd_track_create_keyframe_points(sd_track* h, int n_frames, int source, float th_depth, int use_flags, int frame_id) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
+  SD_REQUIRE(source == 0 || source == 1, SD_ERR_INVALID_ARG, "source must be 0 (sd_track_with_motion_model) or 1 (sd_track_local_map)");
+  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
+  SD_REQUIRE(ran_since_extract(h, source, n_frames) && h->cur->last_frames >= n_frames, SD_ERR_INVALID_ARG,
+             source == 0 ? "sd_track_with_motion_model has not run on these slots since the last extraction"
+                         : "sd_track_local_map has not run on these slots since the last extraction");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  return new_points(h, n_frames, 1, source, th_depth, use_flags != 0, frame_id, 0);
+}
+
+int sd_track_get_created(sd_track* h, int frame0, int n_frames, int32_t* info4, int32_t* kp_index, double* Xw, int32_t* ids, int cap) {
+  TRACK_RANGE(h, frame0, n_frames);
+  SD_REQUIRE(info4 && cap >= 0, SD_ERR_INVALID_ARG, "bad arguments");
+  const size_t K = h->kp_cap, n = n_frames, o = frame0;
+  const TrackBuffers& tb = h->tb;
+  hipStream_t s = h->cur->stream;
+  std::vector<int32_t> list(n * K), id(n * K);
+  std::vector<double> X(n * K * 3);
+  SD_HIP_CHECK(hipMemcpyAsync(info4, tb.np_info + o * 4, n * 16, hipMemcpyDeviceToHost, s));
+  SD_HIP_CHECK(hipMemcpyAsync(list.data(), tb.np_list + o * K, n * K * 4, hipMemcpyDeviceToHost, s));
+  SD_HIP_CHECK(hipMemcpyAsync(id.data(), tb.np_id + o * K, n * K * 4, hipMemcpyDeviceToHost, s));
+  SD_HIP_CHECK(hipMemcpyAsync(X.data(), tb.np_Xw + o * K * 3, n * K * 24, hipMemcpyDeviceToHost, s));
+  SD_HIP_CHECK(hipStreamSynchronize(s));
+  for (size_t f = 0; f < n; f++) SD_REQUIRE(info4[f * 4 + 1] <= cap, SD_ERR_CAPACITY, "cap is smaller than a slot's number of created points");
+  for (size_t f = 0; f < n; f++)
+    for (int r = 0; r < info4[f * 4 + 1]; r++) {   // creation order
+      const size_t i = (size_t)list[f * K + r], d = f * (size_t)cap + r;
+      if (kp_index) kp_index[d] = (int32_t)i;
+      if (ids) ids[d] = id[f * K + i];
+      if (Xw) std::memcpy(Xw + d * 3, &X[(f * K + i) * 3], 24);
+    }
   return SD_OK;
 }
 

@@ -98,7 +98,32 @@ struct TrackBuffers {
   // Tracking::TrackLocalMap (sd_track_local_map): mvpMapPoints after SearchLocalPoints = frame matches + local matches
   int32_t* un_match;     // [B][kp_cap] -1 | v < M: last-frame point v | v >= M: local map point v - M
   int32_t* tl_info;      // [B][4]: status (1 failed, 2 tracked), points in mvpMapPoints, mnMatchesInliers, local matches
+  // map point creation (track_newpoints.hip): Tracking::StereoInitialization / CreateNewKeyFrame on the current frame
+  uint8_t* np_flag;      // [B][kp_cap] keypoint i received a new map point in the last creation call
+  double* np_Xw;         // [B][kp_cap][3] its world position (Frame::UnprojectStereo), valid where np_flag
+  int32_t* np_id;        // [B][kp_cap] its id (MapPoint::nNextId order), valid where np_flag
+  int32_t* np_list;      // [B][kp_cap] the created keypoint indices in creation order
+  int32_t* np_info;      // [B][4]: mode (0 nothing ran on the slot, 1 keyframe, 2 initialisation), created, P (entries of the
+                         //         depth-sorted list the loop processed), candidates (keypoints with mvDepth > 0)
+  int32_t* next_id;      // [B]    MapPoint::nNextId of the slot's map (sd_track_set_next_map_id)
+  int32_t* kf_state;     // [B][8] NeedNewKeyFrame's caller state: nKFs, nRefMatches, mnLastKeyFrameId, mnLastRelocFrameId, flags
+  uint8_t* kf_flags;     // [B]    bit 0 insert a keyframe, bit 1 wanted but the mapper is busy (InterruptBA)
 };
+
+// The map point mvpMapPoints[i] = m keeps after Tracking::Track's "Clean VO matches" (Observations() >= 1, reference
+// src/Tracking.cc:250-257) and outlier discard (:272-275): source 0 = cur_match after TrackWithMotionModel's discard (no
+// outlier flags left), 1 = un_match after TrackLocalMap, m >= M naming local point m - M, outl_i = &mvbOutlier[i].
+// Returns its Observations() if it is kept, else 0; *e / *loc locate it.  o = slot * M.  k_advance keeps these points and
+// k_close_points counts them as tracked: one test for both.  with_outliers: the state BEFORE the outlier discard, which
+// CreateNewKeyFrame sees (:861-867 run between :257 and :272) -- a flagged point with Observations() >= 1 is still there.
+__device__ __forceinline__ int kept_point_obs(const TrackBuffers& tb, int source, int m, const uint8_t* outl_i, size_t o, size_t* e,
+                                              bool* loc, bool with_outliers = false) {
+  if (m < 0 || (source == 1 && !with_outliers && *outl_i)) return 0;
+  *loc = m >= tb.max_points;
+  *e = o + (*loc ? m - tb.max_points : m);
+  const int n_obs = *loc ? tb.lm_obs[*e] : tb.obs[*e];
+  return n_obs >= 1 ? n_obs : 0;
+}
 
 struct TrackCam {
   double fx, fy, cx, cy;                 // (double)(float) like ImageAlign::cam_fx_
@@ -141,6 +166,14 @@ int launch_stereo_from_depth(const sd_orb* cur, const TrackBuffers& tb, const Tr
 int launch_stereo_from_depth_typed(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const void* d_depth, int u16,
                                    int convert, float scale, int w, int h, int stride_elems, size_t frame_stride_elems, int n_frames,
                                    hipStream_t s);
+// map point creation and the keyframe decision (track_newpoints.hip).  mode 1: CreateNewKeyFrame on the result of the
+// tracking call `source`; 2: StereoInitialization.  inv_fx / inv_fy = Frame::invfx / invfy.
+int launch_new_points(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, float inv_fx, float inv_fy, int n_frames, int mode,
+                      int source, float th_depth, int use_flags, int frame_id, int min_keypoints, hipStream_t s);
+int launch_need_keyframe(const TrackBuffers& tb, const int32_t* d_close, int n_frames, int rgbd, int frame_id, int min_frames,
+                         int max_frames, hipStream_t s);
+// entries of `staged` ([n][8]) equal to INT32_MIN leave the device's value
+int launch_set_keyframe_state(const TrackBuffers& tb, const int32_t* staged, int frame0, int n_frames, hipStream_t s);
 int read_pnp_prof(unsigned long long* out32, int reset);
 int read_sel_prof(unsigned long long* out64, int reset);
 int read_align_prof(unsigned long long* out16, int reset);

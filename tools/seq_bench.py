@@ -14,6 +14,15 @@ RGB-D modes (device hand-off, bMono = false, TrackLocalMap at th 3, sd_track_clo
   mono        the monocular device loop above, as the baseline
   (the mode list "rgbd" = host_f32,device_u16,mono)
 
+RGB-D keyframe modes (no static map: every stream starts from sd_track_stereo_init on frame 0 with an empty local map and lives
+on the points it creates; u16 depth in HBM; keyframe state nKFs 5, nRefMatches 700, idle mapper, MinFrames 3, MaxFrames 30):
+  kf_device   per frame: ... -> sd_track_close_points -> sd_track_need_keyframe -> sd_track_create_keyframe_points(use_flags)
+              -> sd_track_advance; the 32-byte keyframe state of every slot is uploaded each step; no host wait in the loop
+  kf_host     the host alternative: synchronise, download depth, matches, outlier flags, poses and the last frame, decide and
+              create the points in numpy, re-upload through sd_track_set_last (two trackers alternate, as in `host`)
+  (the mode list "rgbd_kf" = kf_device,kf_host,device_u16 -- the last one is the loop without creation, run in the same
+  session; results in profiles/seq_bench_rgbd_kf.json)
+
 python tools/seq_bench.py [T=8] [B list=1,1024] [modes=device,host]  -> one JSON line per (B, mode), all of them in
 profiles/seq_bench.json (profiles/seq_bench_rgbd.json when RGB-D modes run).
 Frames are resident in HBM (extraction from device memory); the timed region is frames 1..T-1 including extraction, ended
@@ -36,7 +45,12 @@ BS = [int(b) for b in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1, 1024
 MODES = sys.argv[3].split(",") if len(sys.argv) > 3 else ["device", "host"]
 if MODES == ["rgbd"]:
     MODES = ["host_f32", "device_u16", "mono"]
-RGBD = any(m in ("host_f32", "device_u16") for m in MODES)
+KF = MODES == ["rgbd_kf"] or any(m in ("kf_device", "kf_host") for m in MODES)
+if MODES == ["rgbd_kf"]:
+    MODES = ["kf_device", "kf_host", "device_u16"]
+RGBD = any(m in ("host_f32", "device_u16", "kf_device", "kf_host") for m in MODES)
+KF_STATE = (5, 700, 0, 0, 1, 0, 0, 0)
+KF_MIN_FRAMES, KF_MAX_FRAMES = 3, 30
 NU = 8
 BF = 4.0             # baseline x fx of the synthetic RGB-D camera (tests/test_sequence_gpu.py)
 TH_CLOSE = 2.0       # mThDepth handed to sd_track_close_points: about the median depth of the synthetic scenes
@@ -125,6 +139,142 @@ def run_rgbd(B, seqs, mode):
     return dt, st
 
 
+def kf_setup(B, seqs):
+    frames, ext, _, vel = setup(B, seqs)
+    raw = np.stack([np.stack([np.round(seqs[b % NU]["depth"][t] * 5000.0).astype(np.uint16) for b in range(B)]) for t in range(T)])
+    dmaps = sdslam_amd.DeviceBuffer(raw.nbytes)
+    dmaps.upload(raw)
+    return frames, ext, vel, dmaps
+
+
+def kf_tracker(cur, ref, B):
+    trk = sdslam_amd.Tracker(cur, ref, max_points=M, max_batch=B, pnp_max_iterations=100)
+    trk.set_camera(*K, BF, BOUNDS)
+    return trk
+
+
+def kf_frame(trk, frames, dmaps, B, t):
+    trk.cur.extract_batch_device(frames.ptr.value + t * B * F, B, 640, 480)
+    trk.stereo_from_depth_device(dmaps.ptr.value + t * B * F * 2, trk.DEPTH_U16, 640, 480, depth_map_factor=5000.0)
+
+
+def run_kf_device(B, seqs):
+    frames, ext, vel, dmaps = kf_setup(B, seqs)
+    trk = kf_tracker(ext[0], ext[1], B)
+    state = np.array([KF_STATE] * B, np.int32)
+    trk.set_keyframe_state(0, state)
+    state[:, 2] = trk.KF_KEEP
+    kf_frame(trk, frames, dmaps, B, 0)
+    trk.stereo_init(B, 500)
+    trk.advance(B, 2)
+    trk.get_last(0, 1)                            # synchronises
+    t0 = time.perf_counter()
+    for t in range(1, T):
+        kf_frame(trk, frames, dmaps, B, t)
+        trk.set_prior(0, vel[t - 1], relative=True)
+        trk.set_keyframe_state(0, state)
+        trk.track_with_motion_model(B, th=15.0, mono=False)
+        trk.track_local_map(B, th=3.0)
+        trk.close_points(B, 1, TH_CLOSE)
+        trk.need_keyframe(B, True, t, KF_MIN_FRAMES, KF_MAX_FRAMES)
+        trk.create_keyframe_points(B, 1, TH_CLOSE, use_flags=True, frame_id=t)
+        trk.advance(B, 1)
+    st = trk.get_local_map(0, B)["status"]        # synchronises
+    dt = time.perf_counter() - t0
+    trk.close()
+    frames.free()
+    dmaps.free()
+    return dt, st
+
+
+def unproject(u, v, z, Tcw):
+    """Frame::UnprojectStereo for arrays, in the operation order of include/sdslam_hip.h."""
+    f32 = np.float32
+    x = (u - f32(K[2])) * z * (f32(1) / f32(K[0]))
+    y = (v - f32(K[3])) * z * (f32(1) / f32(K[1]))
+    c = np.stack([x, y, z], 1).astype(np.float64)
+    Rwc, t = Tcw[:3, :3].T, Tcw[:3, 3]
+    Ow = -((Rwc[:, 0] * t[0] + Rwc[:, 1] * t[1]) + Rwc[:, 2] * t[2])
+    return ((c[:, 0:1] * Rwc[:, 0] + c[:, 1:2] * Rwc[:, 1]) + c[:, 2:3] * Rwc[:, 2]) + Ow
+
+
+def run_kf_host(B, seqs):
+    frames, ext, vel, dmaps = kf_setup(B, seqs)
+    trks = [kf_tracker(ext[0], ext[1], B), kf_tracker(ext[1], ext[0], B)]
+    th = np.float32(TH_CLOSE)
+    # frame 0 on the device, mirrored to the host once (outside the timed region)
+    kf_frame(trks[1], frames, dmaps, B, 0)
+    trks[1].stereo_init(B, 500)
+    c = trks[1].get_created(0, B)
+    kps, desc, nk = trks[1].cur.download(0, B)
+    cases, idl = [], []
+    for b in range(B):
+        n, k = nk[b], c["created"][b]
+        v = np.zeros(n, np.uint8)
+        X, ids = np.zeros((n, 3)), np.full(n, -1, np.int32)
+        i = c["kp_index"][b, :k]
+        v[i], X[i], ids[i] = 1, c["Xw"][b, :k], c["ids"][b, :k]
+        cases.append(dict(valid=v, Xw=X, desc=desc[b, :n] * v[:, None], octave=kps["octave"][b, :n], angle=kps["angle"][b, :n], obs=v.astype(np.int32)))
+        idl.append(ids)
+    trks[0].set_last(0, cases)
+    trks[0].set_map_ids(0, idl, 0)
+    next_id = c["created"].astype(np.int64).copy()
+    last_kf = np.zeros(B, np.int64)
+    T_last = [np.eye(4)] * B
+    bi = np.arange(B)[:, None]
+    t0 = time.perf_counter()
+    for t in range(1, T):
+        trk, nxt = trks[(t - 1) % 2], trks[t % 2]
+        trk.set_poses(0, T_last, [v @ Tl for v, Tl in zip(vel[t - 1], T_last)])
+        kf_frame(trk, frames, dmaps, B, t)
+        trk.track_with_motion_model(B, th=15.0, mono=False)
+        trk.track_local_map(B, th=3.0)
+        # the host round trip: decision, creation, hand-off
+        lm, po, last = trk.get_local_map(0, B), trk.get_pose_opt(0, B), trk.get_last(0, B)
+        _, dd = trk.get_stereo(0, B)
+        kps, desc, nk = trk.cur.download(0, B)
+        m = lm["match"][:, :M]
+        j = np.clip(m, 0, M - 1)
+        has = (m >= 0) & (last["obs"][bi, j] >= 1) & (np.arange(m.shape[1])[None] < nk[:, None])
+        keep = has & ~po["outlier"][:, :M]
+        close = (dd > 0) & (dd < th) & (np.arange(dd.shape[1])[None] < nk[:, None])
+        n_tr, n_non = (close & keep).sum(1), (close & ~keep).sum(1)
+        inl = lm["n_inliers"]
+        need_close = (n_tr < 100) & (n_non > 70)
+        c1 = (t >= last_kf + KF_MAX_FRAMES) | (t >= last_kf + KF_MIN_FRAMES) | (inl.astype(np.float64) < KF_STATE[1] * 0.25) | need_close
+        c2 = ((inl.astype(np.float32) < np.float32(KF_STATE[1]) * np.float32(0.75)) | need_close) & (inl > 15)
+        insert = c1 & c2 & (lm["status"] == 2)
+        Xw = last["Xw"][bi, j] * keep[..., None]
+        dsc = last["desc"][bi, j] * keep[..., None]
+        ids = np.where(keep, last["ids"][bi, j], -1)
+        obs = last["obs"][bi, j] * keep
+        valid = keep.copy()
+        for b in np.nonzero(insert)[0]:
+            n = nk[b]
+            d = dd[b, :n]
+            order = np.argsort(np.where(d > 0, d, np.inf), kind="stable")[:int((d > 0).sum())]
+            far = np.nonzero((d[order] > th) & (np.arange(len(order)) >= 100))[0]
+            pre = order[:far[0] + 1] if len(far) else order
+            new = pre[~has[b, pre]]
+            valid[b, new], obs[b, new], dsc[b, new] = True, 1, desc[b, new]
+            Xw[b, new] = unproject(kps["x"][b, new], kps["y"][b, new], d[new], po["T"][b])
+            ids[b, new] = next_id[b] + np.arange(len(new))
+            next_id[b] += len(new)
+            last_kf[b] = t
+        cases = [dict(valid=valid[b, :nk[b]].astype(np.uint8), Xw=Xw[b, :nk[b]], desc=dsc[b, :nk[b]], octave=kps["octave"][b, :nk[b]],
+                      angle=kps["angle"][b, :nk[b]], obs=obs[b, :nk[b]]) for b in range(B)]
+        nxt.set_last(0, cases)
+        nxt.set_map_ids(0, [ids[b, :nk[b]] for b in range(B)], 0)
+        T_last = po["T"]
+    st = trks[(T - 2) % 2].get_local_map(0, B)["status"]
+    dt = time.perf_counter() - t0
+    for trk in trks:
+        trk.close()
+    frames.free()
+    dmaps.free()
+    return dt, st
+
+
 def run_host(B, seqs):
     frames, ext, maps, vel = setup(B, seqs)
     trks = [new_tracker(ext[0], ext[1], B, maps, seqs), new_tracker(ext[1], ext[0], B, maps, seqs)]
@@ -172,7 +322,7 @@ def run_host(B, seqs):
 def main():
     seqs = [synth.make_sequence(100 + i, T, with_depth=RGBD) for i in range(NU)]
     fns = dict(device=run_device, mono=run_device, host=run_host, host_f32=lambda B, s: run_rgbd(B, s, "host_f32"),
-               device_u16=lambda B, s: run_rgbd(B, s, "device_u16"))
+               device_u16=lambda B, s: run_rgbd(B, s, "device_u16"), kf_device=run_kf_device, kf_host=run_kf_host)
     out = []
     for B in BS:
         for mode in MODES:
@@ -184,7 +334,7 @@ def main():
             print(json.dumps(r), flush=True)
             out.append(r)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "seq_bench_rgbd.json" if RGBD else "seq_bench.json"), "w") as f:
+    with open(os.path.join(ROOT, "profiles", "seq_bench_rgbd_kf.json" if KF else "seq_bench_rgbd.json" if RGBD else "seq_bench.json"), "w") as f:
         json.dump(out, f, indent=1)
 
 
