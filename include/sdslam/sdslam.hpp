@@ -178,7 +178,8 @@ class TrackBatch {
   void SetURight(int frame, const float* mvuRight, int n) { check(sd_track_set_uright(h_, frame, 1, mvuRight, n)); }
 
   // Sequential tracking: mLastFrame = Frame(mCurrentFrame) on the device (src/Tracking.cc:250-292).  Per frame:
-  //   CurrentExtractor() extracts -> SetPrior -> Tracking::TrackWithMotionModel -> Tracking::TrackLocalMap -> AdvanceLastFrame.
+  //   CurrentExtractor() extracts -> SetPrior | PredictMotion -> Tracking::TrackWithMotionModel -> Tracking::TrackLocalMap ->
+  //   [UpdateMotion] -> AdvanceLastFrame.
   // ids: the caller's MapPoint identities (which 0: the last frame's points, 1: the local map's; -1 = none).  With both set,
   // TrackLocalMap skips the local points TrackWithMotionModel saw (mnLastFrameSeen, :703, :900-918).
   void SetMapIds(int frame, int which, const int32_t* ids, int n) { check(sd_track_set_map_ids(h_, frame, 1, which, ids, n)); }
@@ -188,6 +189,22 @@ class TrackBatch {
   // (ConstantVelocity::GetPose, relative = true)
   void SetPrior(int frame0, int n_frames, const double* T_cm, bool relative) {
     check(sd_track_set_prior(h_, frame0, n_frames, T_cm, relative ? 1 : 0));
+  }
+  // The motion model on the device (EKF + ConstantVelocity per slot, src/sensors/EKF.cc, ConstantVelocity.cc), all queued:
+  // PredictMotion = motion_model_->Predict(mLastFrame.GetPose()) (src/Tracking.cc:661) as the prior of slots < n_frames, dt the
+  // time since the last update (the reference's timer_); UpdateMotion = :243-247 with the Restart() of :221 / :226 for the
+  // slots the call named by source (0 TrackWithMotionModel, 1 TrackLocalMap, -1 every slot) did not track, before
+  // AdvanceLastFrame; RestartMotion = motion_model_->Restart().  A slot that is not started gets the last pose as prior;
+  // running TrackReferenceKeyFrame or Relocalization on such slots stays with the caller.
+  void PredictMotion(int n_frames, double dt) { check(sd_track_motion_predict(h_, n_frames, dt)); }
+  void UpdateMotion(int n_frames, int source = 1) { check(sd_track_motion_update(h_, n_frames, source)); }
+  void RestartMotion(int frame0, int n_frames) { check(sd_track_motion_restart(h_, frame0, n_frames)); }
+  // the filter of slot `frame`: X (v, w), the diagonal of P, it_time and Exp(X) of the last prediction (16 doubles
+  // column-major); any pointer may be null.  Returns EKF::Started().  Synchronises.
+  bool MotionState(int frame, double X[6], double Pdiag[6] = nullptr, double* it_time = nullptr, double E_cm[16] = nullptr) {
+    int32_t started = 0;
+    check(sd_track_get_motion(h_, frame, 1, X, Pdiag, &started, it_time, E_cm, nullptr));
+    return started != 0;
   }
   // the last frame of slot `frame` (what AdvanceLastFrame or SetLastFrame left); ids may be null
   void GetLastFrame(int frame, LastFrameView& v, std::vector<int32_t>* ids = nullptr) {

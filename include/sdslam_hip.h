@@ -372,10 +372,11 @@ int sd_track_pack_records(sd_track* h, int n_frames, int source, void* d_records
  *     "Clean VO matches" (Observations() < 1)     src/Tracking.cc:250-257
  *     outliers discarded                          src/Tracking.cc:272-275
  *   mnLastFrameSeen skip of SearchLocalPoints     src/Tracking.cc:703, :900-918
- *   ConstantVelocity::GetPose  Exp(vel) * last_pose_ (the prior; the velocity stays an input)
+ *   ConstantVelocity::GetPose  Exp(vel) * last_pose_ (the prior: from the caller through sd_track_set_prior, or from the
+ *     device's own motion model, below)
  * One frame per call on every slot:
- *   extract into sd_track_get_extractors' cur -> sd_track_set_prior -> sd_track_with_motion_model ->
- *   [sd_track_local_map] -> sd_track_advance.
+ *   extract into sd_track_get_extractors' cur -> sd_track_set_prior | sd_track_motion_predict -> sd_track_with_motion_model ->
+ *   [sd_track_local_map] -> [sd_track_motion_update] -> sd_track_advance.
  * sd_track_set_map_ids: the caller's identity of every map point, which = 0 last-frame arrays, 1 local-map arrays, [n][cap]
  *   rows (cap <= max_points, the rest -1), -1 = none.  sd_track_set_last resets the last-frame ids of its slots to -1.  Once ids
  *   are set, sd_track_local_map skips a local point whose id equals the id of a last-frame point that the final search of
@@ -411,6 +412,44 @@ int sd_track_get_last(sd_track* h, int frame0, int n_frames, int32_t* n_last, ui
 int sd_track_get_extractors(sd_track* h, sd_orb** cur, sd_orb** ref);
 int sd_track_close_points(sd_track* h, int n_frames, int source, float th_depth);
 int sd_track_get_close_points(sd_track* h, int frame0, int n_frames, int32_t* out2);
+
+/* Motion model on the device: EKF + ConstantVelocity as per-slot state of the tracker, so the prior needs no host pose
+ *   EKF::Predict / Update / Restart               src/sensors/EKF.cc:44-66, :68-104, :106-109
+ *   ConstantVelocity (Init, Q, R, Z, Exp, Log)    src/sensors/ConstantVelocity.cc:34-46, :83-122, :151-263
+ *   COV_V_2, COV_W_2, SIGMA_V, SIGMA_W            src/sensors/Sensor.cc:24-32
+ *   motion_model_->Predict(mLastFrame.GetPose())  src/Tracking.cc:661
+ *   motion_model_->Update / Restart               src/Tracking.cc:243-247, :221, :226
+ * Per slot: X (v, w), the diagonal of P (jF = jH = G = I and Q, R, the initial P are diagonal, so the reference's dense P, S and
+ *   K stay exactly diagonal: six scalar filters), started (EKF::Started()), it_time, last_pose (Sensor::SetLastPose) and the
+ *   last E = Exp(X).  A new handle: started 0, X = 0, P = diag(COV_V_2 x3, COV_W_2 x3).
+ * sd_track_motion_predict: for slots < n_frames, it_time = started ? dt : 0; last_pose = Tref; P += Q(it_time);
+ *   Tprior = Tcur = Exp(X) * Tref through the product of sd_track_set_prior (k = 0..3 in order, no FMA contraction).  Tref is
+ *   left alone.  dt stands for the reference's wall-clock timer: one value for all slots of the step, which advance in
+ *   lock-step; per-slot timestamps are not supported.  A slot that is not started has X = 0, Exp(0) = I and so Tprior = Tref
+ *   bit for bit: the pose TrackReferenceKeyFrame starts from, which keeps the batch uniform.
+ * sd_track_motion_update: for slots < n_frames; a slot is tracked when source 0: sd_track_with_motion_model left status 2,
+ *   1: sd_track_local_map left status 2, -1: always (the caller vouches: its own pose solve).  Tracked and last_pose not zero
+ *   (Matrix4d::isZero(): every |entry| <= 1e-12): EKF::Update with the frame's final pose Tcur, Z = Log(Tcur *
+ *   inverse(last_pose)); the first update after a start only sets started (InitState: X = 0).  Otherwise EKF::Restart
+ *   (started 0, X = 0, the diagonal of P to its initial values).  Call it before sd_track_advance.
+ * sd_track_motion_restart: EKF::Restart for slots frame0 .. frame0 + n_frames - 1.
+ *   These three are queued on the tracking stream behind the calls whose results they read: no host wait, no allocation.
+ * sd_track_get_motion: [n][6] X, [n][6] diagonal of P, [n] started, [n] it_time, [n][16] E and last_pose column-major; any
+ *   pointer may be NULL; synchronises.  sd_track_set_motion: restores X / P / started / it_time of a stream's filter (NULL:
+ *   left alone); synchronises.
+ * Slots >= n_frames keep their state and prior.  sd_track_set_prior stays: either call may set the prior of a frame.
+ * Errors: SD_ERR_CAPACITY for n_frames > max_batch; SD_ERR_INVALID_ARG for a source outside -1..1, a dt that is negative or not
+ *   finite, broadcast mode, or when the call named by `source` (0 / 1) has not run on these slots since the last extraction.
+ * Not covered (the caller's, with the statuses that name the slots): running TrackReferenceKeyFrame's (Frame, KeyFrame)
+ *   overloads for slots that are not started or just relocalised (src/Tracking.cc:215-216), its retry after a failed
+ *   TrackWithMotionModel (:219-222), Relocalization, and the IMU sensor model. */
+int sd_track_motion_predict(sd_track* h, int n_frames, double dt);
+int sd_track_motion_update(sd_track* h, int n_frames, int source);
+int sd_track_motion_restart(sd_track* h, int frame0, int n_frames);
+int sd_track_get_motion(sd_track* h, int frame0, int n_frames, double* X6, double* Pdiag6, int32_t* started, double* it_time,
+                        double* E_cm, double* last_pose_cm);
+int sd_track_set_motion(sd_track* h, int frame0, int n_frames, const double* X6, const double* Pdiag6, const int32_t* started,
+                        const double* it_time);
 int sd_track_stream_fence(sd_track* h, void* hip_stream, int direction);
 int sd_track_set_profiling(sd_track* h, int on);
 int sd_track_stage_ms(sd_track* h, float* ms_out /* [0]=align, [1]=match, [2]=pnp */, int cap);

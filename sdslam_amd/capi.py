@@ -687,6 +687,39 @@ class Tracker:
         self.L.sd_track_set_prior.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         _check(self.L.sd_track_set_prior(self.h, frame0, len(T_list), _p(a), int(bool(relative))))
 
+    # --- motion model on the device: EKF + ConstantVelocity per slot (src/sensors/EKF.cc, ConstantVelocity.cc) ---
+    def motion_predict(self, n_frames, dt):
+        """Queue EKF::Predict for slots < n_frames: Tprior = Tcur = Exp(X) @ Tref; dt is the time since the last update."""
+        self.L.sd_track_motion_predict.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        _check(self.L.sd_track_motion_predict(self.h, n_frames, float(dt)))
+
+    def motion_update(self, n_frames, source=1):
+        """Queue EKF::Update with the frames' final poses for the slots the call named by `source` tracked (0
+        track_with_motion_model, 1 track_local_map, -1 every slot), EKF::Restart for the others.  Before advance()."""
+        self.L.sd_track_motion_update.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(self.L.sd_track_motion_update(self.h, n_frames, int(source)))
+
+    def motion_restart(self, frame0, n_frames):
+        self.L.sd_track_motion_restart.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(self.L.sd_track_motion_restart(self.h, frame0, n_frames))
+
+    def get_motion(self, frame0, n):
+        """dict(X [n][6], P [n][6] diagonal, started [n], it_time [n], E and last_pose as n 4x4 matrices); synchronises."""
+        X, P, st, it = np.zeros((n, 6)), np.zeros((n, 6)), np.zeros(n, np.int32), np.zeros(n)
+        E, Lp = np.zeros((n, 16)), np.zeros((n, 16))
+        self.L.sd_track_get_motion.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+        _check(self.L.sd_track_get_motion(self.h, frame0, n, _p(X), _p(P), _p(st), _p(it), _p(E), _p(Lp)))
+        return dict(X=X, P=P, started=st, it_time=it, E=[_from_cm(e) for e in E], last_pose=[_from_cm(t) for t in Lp])
+
+    def set_motion(self, frame0, X=None, P=None, started=None, it_time=None):
+        """Restore a stream's filter: [n][6] X, [n][6] diagonal of P, [n] started, [n] it_time; None leaves a field alone."""
+        a = [None if v is None else np.ascontiguousarray(v, dt) for v, dt in ((X, np.float64), (P, np.float64), (started, np.int32),
+                                                                              (it_time, np.float64))]
+        n = {len(v) for v in a if v is not None}
+        assert len(n) == 1
+        self.L.sd_track_set_motion.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+        _check(self.L.sd_track_set_motion(self.h, frame0, n.pop(), *[None if v is None else _p(v) for v in a]))
+
     def get_last(self, frame0, n):
         """The last-frame arrays, [n][max_points] layout."""
         M = self.M

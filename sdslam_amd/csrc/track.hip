@@ -242,11 +242,7 @@ __global__ void k_set_prior(const double* __restrict__ Tin, TrackBuffers tb, int
   const int f = frame0 + t / 16, e = t % 16, c = e / 4, r = e % 4;
   const double* T = Tin + (size_t)(t / 16) * 16;
   double v = T[e];
-  if (relative) {
-    const double* R = tb.Tref + (size_t)f * 16;
-    v = __dmul_rn(T[r], R[c * 4]);
-    for (int k = 1; k < 4; k++) v = __dadd_rn(v, __dmul_rn(T[k * 4 + r], R[c * 4 + k]));
-  }
+  if (relative) v = pose_product_entry(T, tb.Tref + (size_t)f * 16, r, c);
   tb.Tprior[(size_t)f * 16 + e] = v;
   tb.Tcur[(size_t)f * 16 + e] = v;
 }
@@ -323,6 +319,12 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &tb.kf_state, B * 8));
   A(dalloc(h, &tb.kf_flags, B));
   A(dalloc(h, &h->d_kf_stage, B * 8));
+  A(dalloc(h, &tb.mo_X, B * 6));
+  A(dalloc(h, &tb.mo_P, B * 6));
+  A(dalloc(h, &tb.mo_started, B));
+  A(dalloc(h, &tb.mo_it, B));
+  A(dalloc(h, &tb.mo_last, B * 16));
+  A(dalloc(h, &tb.mo_E, B * 16));
   A(dalloc(h, &tb.Tref, B * 16));
   A(dalloc(h, &tb.Tprior, B * 16));
   A(dalloc(h, &tb.Tcur, B * 16));
@@ -393,6 +395,9 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
     if (e0 == hipSuccess) e0 = hipMemset(tb.last_id, 0xFF, (size_t)B * M * 4);
     if (e0 == hipSuccess) e0 = hipMemset(tb.last_id2, 0xFF, (size_t)B * M * 4);
     if (e0 == hipSuccess) e0 = hipMemset(tb.lm_id, 0xFF, (size_t)B * M * 4);
+    // motion model: not started, X = 0, P = diag(COV_V_2 x3, COV_W_2 x3) (ConstantVelocity::Init; both 0.000625)
+    std::vector<double> p0((size_t)B * 6, 0.000625);
+    if (e0 == hipSuccess) e0 = hipMemcpy(tb.mo_P, p0.data(), p0.size() * 8, hipMemcpyHostToDevice);
     if (e0 != hipSuccess) { set_error(std::string("sd_track_create: ") + hipGetErrorString(e0)); rc = SD_ERR_HIP; }
   }
   if (rc == SD_OK) {
@@ -1536,6 +1541,67 @@ int sd_track_set_prior(sd_track* h, int frame0, int n_frames, const double* T_cm
   h->prior_pending[r] = true;
   hipLaunchKernelGGL(k_set_prior, dim3((n_frames * 16 + 255) / 256), dim3(256), 0, s, h->d_prior, h->tb, frame0, n_frames, relative);
   SD_HIP_CHECK(hipGetLastError());
+  return SD_OK;
+}
+
+// ---- motion model on the device (kernels: track_motion.hip)
+
+int sd_track_motion_predict(sd_track* h, int n_frames, double dt) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
+  SD_REQUIRE(std::isfinite(dt) && dt >= 0.0, SD_ERR_INVALID_ARG, "dt must be finite and not negative");
+  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  return launch_motion_predict(h->tb, n_frames, dt, h->pnp_stream);
+}
+
+int sd_track_motion_update(sd_track* h, int n_frames, int source) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
+  SD_REQUIRE(source >= -1 && source <= 1, SD_ERR_INVALID_ARG,
+             "source must be -1 (every slot tracked), 0 (sd_track_with_motion_model) or 1 (sd_track_local_map)");
+  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
+  SD_REQUIRE(source < 0 || ran_since_extract(h, source, n_frames), SD_ERR_INVALID_ARG,
+             source == 0 ? "sd_track_with_motion_model has not run on these slots since the last extraction"
+                         : "sd_track_local_map has not run on these slots since the last extraction");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  return launch_motion_update(h->tb, n_frames, source, h->pnp_stream);
+}
+
+int sd_track_motion_restart(sd_track* h, int frame0, int n_frames) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(frame0 >= 0 && n_frames >= 1 && frame0 + n_frames <= h->max_batch, SD_ERR_CAPACITY, "frame range exceeds max_batch");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  return launch_motion_init(h->tb, frame0, n_frames, h->pnp_stream);
+}
+
+int sd_track_get_motion(sd_track* h, int frame0, int n_frames, double* X6, double* Pdiag6, int32_t* started, double* it_time,
+                        double* E_cm, double* last_pose_cm) {
+  TRACK_RANGE(h, frame0, n_frames);
+  hipStream_t s = h->cur->stream;
+  const TrackBuffers& tb = h->tb;
+  const size_t o = frame0, n = n_frames;
+  if (X6) SD_HIP_CHECK(hipMemcpyAsync(X6, tb.mo_X + o * 6, n * 48, hipMemcpyDeviceToHost, s));
+  if (Pdiag6) SD_HIP_CHECK(hipMemcpyAsync(Pdiag6, tb.mo_P + o * 6, n * 48, hipMemcpyDeviceToHost, s));
+  if (started) SD_HIP_CHECK(hipMemcpyAsync(started, tb.mo_started + o, n * 4, hipMemcpyDeviceToHost, s));
+  if (it_time) SD_HIP_CHECK(hipMemcpyAsync(it_time, tb.mo_it + o, n * 8, hipMemcpyDeviceToHost, s));
+  if (E_cm) SD_HIP_CHECK(hipMemcpyAsync(E_cm, tb.mo_E + o * 16, n * 128, hipMemcpyDeviceToHost, s));
+  if (last_pose_cm) SD_HIP_CHECK(hipMemcpyAsync(last_pose_cm, tb.mo_last + o * 16, n * 128, hipMemcpyDeviceToHost, s));
+  SD_HIP_CHECK(hipStreamSynchronize(s));
+  return SD_OK;
+}
+
+int sd_track_set_motion(sd_track* h, int frame0, int n_frames, const double* X6, const double* Pdiag6, const int32_t* started,
+                        const double* it_time) {
+  TRACK_RANGE(h, frame0, n_frames);
+  hipStream_t s = h->cur->stream;
+  const TrackBuffers& tb = h->tb;
+  const size_t o = frame0, n = n_frames;
+  if (X6) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_X + o * 6, X6, n * 48, hipMemcpyHostToDevice, s));
+  if (Pdiag6) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_P + o * 6, Pdiag6, n * 48, hipMemcpyHostToDevice, s));
+  if (started) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_started + o, started, n * 4, hipMemcpyHostToDevice, s));
+  if (it_time) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_it + o, it_time, n * 8, hipMemcpyHostToDevice, s));
+  SD_HIP_CHECK(hipStreamSynchronize(s));
   return SD_OK;
 }
 

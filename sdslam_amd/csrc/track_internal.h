@@ -108,7 +108,24 @@ struct TrackBuffers {
   int32_t* next_id;      // [B]    MapPoint::nNextId of the slot's map (sd_track_set_next_map_id)
   int32_t* kf_state;     // [B][8] NeedNewKeyFrame's caller state: nKFs, nRefMatches, mnLastKeyFrameId, mnLastRelocFrameId, flags
   uint8_t* kf_flags;     // [B]    bit 0 insert a keyframe, bit 1 wanted but the mapper is busy (InterruptBA)
+  // motion model (track_motion.hip): EKF + ConstantVelocity of every slot
+  double* mo_X;          // [B][6]  X_ = (v, w)
+  double* mo_P;          // [B][6]  diagonal of P_ (the off-diagonals are exactly 0, see track_motion.hip)
+  int32_t* mo_started;   // [B]     updated_ (EKF::Started())
+  double* mo_it;         // [B]     it_time_
+  double* mo_last;       // [B][16] Sensor::last_pose_ (SetLastPose), column-major
+  double* mo_E;          // [B][16] Exp(X_) of the last prediction, column-major
 };
+
+// Entry (r, c) of the 4x4 product A * B, both column-major: k = 0..3 in order, every product and sum rounded on its own (no
+// FMA contraction), as a plain host loop does.  The one product behind every prior: k_set_prior (T * Tref) and
+// k_motion_predict (Exp(X) * Tref) must agree bit for bit.
+__device__ __forceinline__ double pose_product_entry(const double* __restrict__ A, const double* __restrict__ B, int r, int c) {
+  double v = __dmul_rn(A[r], B[c * 4]);
+#pragma unroll
+  for (int k = 1; k < 4; k++) v = __dadd_rn(v, __dmul_rn(A[k * 4 + r], B[c * 4 + k]));
+  return v;
+}
 
 // The map point mvpMapPoints[i] = m keeps after Tracking::Track's "Clean VO matches" (Observations() >= 1, reference
 // src/Tracking.cc:250-257) and outlier discard (:272-275): source 0 = cur_match after TrackWithMotionModel's discard (no
@@ -174,6 +191,10 @@ int launch_need_keyframe(const TrackBuffers& tb, const int32_t* d_close, int n_f
                          int max_frames, hipStream_t s);
 // entries of `staged` ([n][8]) equal to INT32_MIN leave the device's value
 int launch_set_keyframe_state(const TrackBuffers& tb, const int32_t* staged, int frame0, int n_frames, hipStream_t s);
+// motion model (track_motion.hip).  source -1: every slot < n counts as tracked; 0 / 1: tw_info / tl_info status 2
+int launch_motion_init(const TrackBuffers& tb, int frame0, int n_frames, hipStream_t s);   // EKF::Restart
+int launch_motion_predict(const TrackBuffers& tb, int n_frames, double dt, hipStream_t s);
+int launch_motion_update(const TrackBuffers& tb, int n_frames, int source, hipStream_t s);
 int read_pnp_prof(unsigned long long* out32, int reset);
 int read_sel_prof(unsigned long long* out64, int reset);
 int read_align_prof(unsigned long long* out16, int reset);

@@ -23,6 +23,14 @@ on the points it creates; u16 depth in HBM; keyframe state nKFs 5, nRefMatches 7
   (the mode list "rgbd_kf" = kf_device,kf_host,device_u16 -- the last one is the loop without creation, run in the same
   session; results in profiles/seq_bench_rgbd_kf.json)
 
+Motion-model modes (monocular, the `device` loop with the prior from the filter instead of ground-truth velocities; dt 1/30):
+  ekf_device  per frame: sd_track_motion_predict -> track -> sd_track_motion_update(1) -> sd_track_advance: the EKF +
+              ConstantVelocity state lives on the device, no pose crosses the bus and the host decides nothing
+  ekf_host    what a caller had to do before: synchronise, download the B final poses and statuses (sd_track_get_align /
+              sd_track_get_local_map), run the filter for B streams on the host (vectorised numpy, the textbook SE(3) Exp / Log),
+              upload B matrices through sd_track_set_prior
+  (results in profiles/seq_bench_motion.json when one of them is in the mode list)
+
 python tools/seq_bench.py [T=8] [B list=1,1024] [modes=device,host]  -> one JSON line per (B, mode), all of them in
 profiles/seq_bench.json (profiles/seq_bench_rgbd.json when RGB-D modes run).
 Frames are resident in HBM (extraction from device memory); the timed region is frames 1..T-1 including extraction, ended
@@ -48,6 +56,8 @@ if MODES == ["rgbd"]:
 KF = MODES == ["rgbd_kf"] or any(m in ("kf_device", "kf_host") for m in MODES)
 if MODES == ["rgbd_kf"]:
     MODES = ["kf_device", "kf_host", "device_u16"]
+EKF = any(m in ("ekf_device", "ekf_host") for m in MODES)
+EKF_DT = 1.0 / 30.0
 RGBD = any(m in ("host_f32", "device_u16", "kf_device", "kf_host") for m in MODES)
 KF_STATE = (5, 700, 0, 0, 1, 0, 0, 0)
 KF_MIN_FRAMES, KF_MAX_FRAMES = 3, 30
@@ -101,6 +111,99 @@ def run_device(B, seqs):
         track(trk, frames, B, t, vel[t - 1])
         trk.advance(B, 1)
     st = trk.get_local_map(0, B)["status"]        # synchronises
+    dt = time.perf_counter() - t0
+    trk.close()
+    frames.free()
+    return dt, st
+
+
+def run_ekf_device(B, seqs):
+    frames, ext, maps, _ = setup(B, seqs)
+    trk = new_tracker(ext[0], ext[1], B, maps, seqs)
+    t0 = time.perf_counter()
+    for t in range(1, T):
+        trk.cur.extract_batch_device(frames.ptr.value + t * B * F, B, 640, 480)
+        trk.motion_predict(B, EKF_DT)
+        trk.track_with_motion_model(B, th=15.0)
+        trk.track_local_map(B, th=1.0)
+        trk.motion_update(B, 1)
+        trk.advance(B, 1)
+    st = trk.get_local_map(0, B)["status"]        # synchronises
+    dt = time.perf_counter() - t0
+    trk.close()
+    frames.free()
+    return dt, st
+
+
+def _hat(w):
+    O = np.zeros(w.shape[:-1] + (3, 3))
+    O[..., 0, 1], O[..., 0, 2], O[..., 1, 0] = -w[..., 2], w[..., 1], w[..., 2]
+    O[..., 1, 2], O[..., 2, 0], O[..., 2, 1] = -w[..., 0], -w[..., 1], w[..., 0]
+    return O
+
+
+def se3_exp(x):
+    """[B][6] (v, w) -> [B][4][4], Rodrigues; series below 1e-6 rad."""
+    w = x[:, 3:]
+    th = np.linalg.norm(w, axis=1)[:, None, None]
+    small = th < 1e-6
+    ths = np.where(small, 1.0, th)
+    a = np.where(small, 1.0 - th * th / 6, np.sin(ths) / ths)
+    b = np.where(small, 0.5 - th * th / 24, (1 - np.cos(ths)) / ths ** 2)
+    c = np.where(small, 1.0 / 6 - th * th / 120, (ths - np.sin(ths)) / ths ** 3)
+    O = _hat(w)
+    O2 = O @ O
+    E = np.tile(np.eye(4), (len(x), 1, 1))
+    E[:, :3, :3] = np.eye(3) + a * O + b * O2
+    E[:, :3, 3] = ((np.eye(3) + b * O + c * O2) @ x[:, :3, None])[..., 0]
+    return E
+
+
+def se3_log(T):
+    """[B][4][4] -> [B][6] (v, w), rotations below pi."""
+    Rm = T[:, :3, :3]
+    cos = np.clip((np.trace(Rm, axis1=1, axis2=2) - 1) / 2, -1, 1)
+    th = np.arccos(cos)
+    small = th < 1e-6
+    ths = np.where(small, 1.0, th)
+    f = np.where(small, 0.5 + th * th / 12, ths / (2 * np.sin(ths)))
+    w = f[:, None] * np.stack([Rm[:, 2, 1] - Rm[:, 1, 2], Rm[:, 0, 2] - Rm[:, 2, 0], Rm[:, 1, 0] - Rm[:, 0, 1]], 1)
+    c = np.where(small, 1.0 / 12, (1 - ths / (2 * np.tan(ths / 2))) / ths ** 2)[:, None, None]
+    O = _hat(w)
+    v = ((np.eye(3) - 0.5 * O + c * (O @ O)) @ T[:, :3, 3:4])[..., 0]
+    return np.concatenate([v, w], 1)
+
+
+def run_ekf_host(B, seqs):
+    frames, ext, maps, _ = setup(B, seqs)
+    trk = new_tracker(ext[0], ext[1], B, maps, seqs)
+    X = np.zeros((B, 6))
+    P = np.tile(np.array([0.000625] * 6), (B, 1))
+    sig2 = np.array([16.0] * 3 + [36.0] * 3)
+    started = np.zeros(B, bool)
+    T_last = np.stack([seqs[b % NU]["T"][0] for b in range(B)])
+    t0 = time.perf_counter()
+    for t in range(1, T):
+        it = np.where(started, EKF_DT, 0.0)[:, None]
+        Q = sig2 * it * it
+        P = P + Q
+        trk.cur.extract_batch_device(frames.ptr.value + t * B * F, B, 640, 480)
+        trk.set_prior(0, list(se3_exp(X)), relative=True)
+        trk.track_with_motion_model(B, th=15.0)
+        trk.track_local_map(B, th=1.0)
+        # the host round trip of the motion model: poses and statuses down, the filter in numpy
+        pose = np.stack(trk.get_align(0, B)["T"])
+        ok = trk.get_local_map(0, B)["status"] == 2
+        Z = se3_log(pose @ np.linalg.inv(T_last))
+        S = P + Q
+        Kg = P / S
+        upd = (ok & started)[:, None]
+        X = np.where(upd, X + Kg * (Z - X), np.where(ok[:, None], X * started[:, None], 0.0))
+        P = np.where(upd, P - Kg * S * Kg, np.where(ok[:, None], P, 0.000625))
+        started = ok
+        trk.advance(B, 1)
+        T_last = pose
+    st = trk.get_local_map(0, B)["status"]
     dt = time.perf_counter() - t0
     trk.close()
     frames.free()
@@ -322,7 +425,8 @@ def run_host(B, seqs):
 def main():
     seqs = [synth.make_sequence(100 + i, T, with_depth=RGBD) for i in range(NU)]
     fns = dict(device=run_device, mono=run_device, host=run_host, host_f32=lambda B, s: run_rgbd(B, s, "host_f32"),
-               device_u16=lambda B, s: run_rgbd(B, s, "device_u16"), kf_device=run_kf_device, kf_host=run_kf_host)
+               device_u16=lambda B, s: run_rgbd(B, s, "device_u16"), kf_device=run_kf_device, kf_host=run_kf_host,
+               ekf_device=run_ekf_device, ekf_host=run_ekf_host)
     out = []
     for B in BS:
         for mode in MODES:
@@ -334,7 +438,7 @@ def main():
             print(json.dumps(r), flush=True)
             out.append(r)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "seq_bench_rgbd_kf.json" if KF else "seq_bench_rgbd.json" if RGBD else "seq_bench.json"), "w") as f:
+    with open(os.path.join(ROOT, "profiles", "seq_bench_motion.json" if EKF else "seq_bench_rgbd_kf.json" if KF else "seq_bench_rgbd.json" if RGBD else "seq_bench.json"), "w") as f:
         json.dump(out, f, indent=1)
 
 
