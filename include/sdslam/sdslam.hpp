@@ -195,7 +195,10 @@ class TrackBatch {
   // time since the last update (the reference's timer_); UpdateMotion = :243-247 with the Restart() of :221 / :226 for the
   // slots the call named by source (0 TrackWithMotionModel, 1 TrackLocalMap, -1 every slot) did not track, before
   // AdvanceLastFrame; RestartMotion = motion_model_->Restart().  A slot that is not started gets the last pose as prior;
-  // running TrackReferenceKeyFrame or Relocalization on such slots stays with the caller.
+  // running TrackReferenceKeyFrame or Relocalization on such slots stays with the caller.  Which Sensor the three run is
+  // SetSensorModel's choice, as Tracking chooses at construction (src/Tracking.cc:134-138): SD_SENSOR_CONSTANT_VELOCITY (the
+  // default) or SD_SENSOR_IMU, the 16-state filter of System::MONOCULAR_IMU (src/sensors/IMU.cc), whose prior is the filter's
+  // own absolute pose and whose UpdateMotion reads the measurements of SetMeasurements.
   void PredictMotion(int n_frames, double dt) { check(sd_track_motion_predict(h_, n_frames, dt)); }
   void UpdateMotion(int n_frames, int source = 1) { check(sd_track_motion_update(h_, n_frames, source)); }
   void RestartMotion(int frame0, int n_frames) { check(sd_track_motion_restart(h_, frame0, n_frames)); }
@@ -204,6 +207,18 @@ class TrackBatch {
   bool MotionState(int frame, double X[6], double Pdiag[6] = nullptr, double* it_time = nullptr, double E_cm[16] = nullptr) {
     int32_t started = 0;
     check(sd_track_get_motion(h_, frame, 1, X, Pdiag, &started, it_time, E_cm, nullptr));
+    return started != 0;
+  }
+  // the Sensor of the motion model; every slot's filter of the chosen model restarts
+  void SetSensorModel(int model) { check(sd_track_set_sensor_model(h_, model)); }
+  // Tracking::SetMeasurements for slots frame0 .. frame0 + n - 1: [n][6] doubles (gyro xyz, accelerometer xyz), queued; they
+  // persist until replaced.  SD_SENSOR_IMU only.
+  void SetMeasurements(int frame0, int n, const double* wa6) { check(sd_track_set_measurements(h_, frame0, n, wa6)); }
+  // the IMU filter of slot `frame`: X (x, q as w x y z, v, w, a), the dense P row-major, gravity_ and it_time; any pointer
+  // may be null.  Returns EKF::Started().  Synchronises.
+  bool ImuState(int frame, double X[16], double P[256] = nullptr, double gravity[3] = nullptr, double* it_time = nullptr) {
+    int32_t started = 0;
+    check(sd_track_get_imu(h_, frame, 1, X, P, gravity, &started, it_time, nullptr, nullptr));
     return started != 0;
   }
   // the last frame of slot `frame` (what AdvanceLastFrame or SetLastFrame left); ids may be null

@@ -442,7 +442,8 @@ int sd_track_get_close_points(sd_track* h, int frame0, int n_frames, int32_t* ou
  *   finite, broadcast mode, or when the call named by `source` (0 / 1) has not run on these slots since the last extraction.
  * Not covered (the caller's, with the statuses that name the slots): running TrackReferenceKeyFrame's (Frame, KeyFrame)
  *   overloads for slots that are not started or just relocalised (src/Tracking.cc:215-216), its retry after a failed
- *   TrackWithMotionModel (:219-222), Relocalization, and the IMU sensor model. */
+ *   TrackWithMotionModel (:219-222), and Relocalization.  The IMU sensor model is the other value of
+ *   sd_track_set_sensor_model, below; everything in this comment describes SD_SENSOR_CONSTANT_VELOCITY, the default. */
 int sd_track_motion_predict(sd_track* h, int n_frames, double dt);
 int sd_track_motion_update(sd_track* h, int n_frames, int source);
 int sd_track_motion_restart(sd_track* h, int frame0, int n_frames);
@@ -450,6 +451,54 @@ int sd_track_get_motion(sd_track* h, int frame0, int n_frames, double* X6, doubl
                         double* E_cm, double* last_pose_cm);
 int sd_track_set_motion(sd_track* h, int frame0, int n_frames, const double* X6, const double* Pdiag6, const int32_t* started,
                         const double* it_time);
+
+/* IMU sensor model on the device: the 16-state EKF of Monocular-IMU tracking (System::MONOCULAR_IMU, System::TrackFusion,
+ * Tracking::SetMeasurements) as per-slot state, chosen per handle as Tracking chooses its Sensor (src/Tracking.cc:134-138)
+ *   EKF::Predict / Update / Restart               src/sensors/EKF.cc:44-109
+ *   IMU (Init, InitState, F, jF, Q, Z, H, jH, R, UpdateGravity)   src/sensors/IMU.cc:26-240
+ *   Sensor (GetPose, PoseToVector, QuaternionFromAngularVelocity, QuaternionJacobian(Right), dq_by_dw)   src/sensors/Sensor.cc:24-159
+ * Per slot: X[16] = (x, q as w x y z, v, w, a), the dense P[16][16] row-major, gravity_[3], started, it_time, last_pose and
+ *   the last measurements [6] = (gyro xyz, accelerometer xyz); about 2.3 KB, allocated with the tracker.  A new handle: model
+ *   SD_SENSOR_CONSTANT_VELOCITY; IMU state started 0, X = (0, 1 0 0 0, 0, 0, 0), P = diag(COV_X_2 x3, COV_Q_2 x4, COV_V_2 x3,
+ *   COV_W_2 x3, COV_A_2 x3), gravity_ = 0.
+ * sd_track_set_sensor_model: the filter that sd_track_motion_predict / _update / _restart run from now on.  Every slot's
+ *   filter of the chosen model restarts (a new Tracking constructs a new EKF), and under SD_SENSOR_IMU every slot's
+ *   measurements count as not set.  With SD_SENSOR_CONSTANT_VELOCITY every call behaves as described above.
+ * Under SD_SENSOR_IMU:
+ *   sd_track_motion_predict, slots < n_frames: last_pose = Tref.  A started slot: it_time = dt; jF and Q on the old X, then
+ *     X = F(X), P = jF P jF^T + Q, Tprior = Tcur = Sensor::GetPose(X) -- the filter's own absolute pose (the rotation of a
+ *     normalised copy of q, and x), not a product with Tref.  A slot that is not started is not predicted: the reference never
+ *     calls Predict for it (it runs TrackReferenceKeyFrame from the last pose), so Tprior = Tcur = Tref bit for bit, X and P
+ *     are left alone and it_time = 0 -- the same convention as the constant-velocity model.
+ *   sd_track_motion_update, slots < n_frames: tracked (source as above) and last_pose not zero: EKF::Update with the pose in
+ *     Tcur and the slot's stored measurements -- Z = (x, normalised q of the pose, gyro, accelerometer - gravity_) after
+ *     UpdateGravity(it_time); the first update after a start is InitState (X = the pose part of Z, zeros elsewhere, gravity_ =
+ *     0, P left alone).  Otherwise EKF::Restart = IMU::Init, gravity_ = 0 included; IMU::Init assigns the five diagonal
+ *     blocks of P (x, q, v, w, a) and leaves the off-diagonal blocks as they are, so only a filter that never updated, or
+ *     one sd_track_set_sensor_model rebuilt, has all of them zero.  The reference's quirks are kept: P = P -
+ *     K S K^T without symmetrisation, quaternions subtracted componentwise in Y = Z - h(X), R = sigma^2 it_time^2 (zero for dt
+ *     = 0), the state's q never normalised.  S^-1 is a Gauss-Jordan inverse with partial pivoting.
+ *   sd_track_motion_restart: EKF::Restart for its range.  Measurements, it_time and last_pose stay.
+ *   sd_track_set_measurements: Tracking::SetMeasurements for slots frame0 .. frame0 + n_frames - 1, [n][6] doubles (gyro xyz,
+ *     accelerometer xyz); they persist until replaced, as the reference's vector does.  Queued on the tracking stream through
+ *     the pinned ring of sd_track_set_prior: no host wait, no allocation.
+ *   sd_track_get_imu: [n][16] X, [n][256] P, [n][3] gravity_, [n] started, [n] it_time, [n][16] last_pose column-major, [n][6]
+ *     measurements; any pointer may be NULL; synchronises.  sd_track_set_imu restores X / P / gravity_ / started / it_time
+ *     (NULL: left alone); synchronises.
+ * Slots >= n_frames keep everything.  Errors, all leaving state untouched: SD_ERR_INVALID_ARG for an unknown model;
+ *   sd_track_set_measurements or sd_track_set_imu under SD_SENSOR_CONSTANT_VELOCITY; sd_track_get_motion / _set_motion under
+ *   SD_SENSOR_IMU; measurements that are not finite; sd_track_motion_update under SD_SENSOR_IMU for slots whose measurements
+ *   have not been set since the model was chosen (the reference asserts there); and everything the motion calls refuse above.
+ * Not covered: per-slot timestamps, orientation filters (Madgwick), and what the constant-velocity model leaves to the caller. */
+#define SD_SENSOR_CONSTANT_VELOCITY 0
+#define SD_SENSOR_IMU 1
+int sd_track_set_sensor_model(sd_track* h, int model);
+int sd_track_get_sensor_model(sd_track* h, int* model);
+int sd_track_set_measurements(sd_track* h, int frame0, int n_frames, const double* wa6);
+int sd_track_get_imu(sd_track* h, int frame0, int n_frames, double* X16, double* P256, double* gravity3, int32_t* started, double* it_time,
+                     double* last_pose_cm, double* measurements6);
+int sd_track_set_imu(sd_track* h, int frame0, int n_frames, const double* X16, const double* P256, const double* gravity3,
+                     const int32_t* started, const double* it_time);
 int sd_track_stream_fence(sd_track* h, void* hip_stream, int direction);
 int sd_track_set_profiling(sd_track* h, int on);
 int sd_track_stage_ms(sd_track* h, float* ms_out /* [0]=align, [1]=match, [2]=pnp */, int cap);

@@ -720,6 +720,44 @@ class Tracker:
         self.L.sd_track_set_motion.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
         _check(self.L.sd_track_set_motion(self.h, frame0, n.pop(), *[None if v is None else _p(v) for v in a]))
 
+    # --- IMU sensor model: the 16-state EKF of Monocular-IMU tracking (src/sensors/IMU.cc), chosen per tracker ---
+    SENSOR_CONSTANT_VELOCITY, SENSOR_IMU = 0, 1
+
+    def set_sensor_model(self, model):
+        """The filter motion_predict / motion_update / motion_restart run; every slot's filter of that model restarts."""
+        self.L.sd_track_set_sensor_model.argtypes = [C.c_void_p, C.c_int]
+        _check(self.L.sd_track_set_sensor_model(self.h, int(model)))
+
+    def get_sensor_model(self):
+        m = C.c_int(-1)
+        self.L.sd_track_get_sensor_model.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        _check(self.L.sd_track_get_sensor_model(self.h, C.byref(m)))
+        return m.value
+
+    def set_measurements(self, frame0, wa):
+        """Tracking::SetMeasurements for slots frame0 ..: [n][6] (gyro xyz, accelerometer xyz); queued, persists until replaced."""
+        a = np.ascontiguousarray(wa, np.float64).reshape(-1, 6)
+        self.L.sd_track_set_measurements.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _check(self.L.sd_track_set_measurements(self.h, frame0, len(a), _p(a)))
+
+    def get_imu(self, frame0, n):
+        """dict(X [n][16], P [n][16][16], gravity [n][3], started [n], it_time [n], last_pose as n 4x4 matrices, measurements
+        [n][6]); synchronises."""
+        X, P, g, st, it = np.zeros((n, 16)), np.zeros((n, 16, 16)), np.zeros((n, 3)), np.zeros(n, np.int32), np.zeros(n)
+        Lp, me = np.zeros((n, 16)), np.zeros((n, 6))
+        self.L.sd_track_get_imu.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
+        _check(self.L.sd_track_get_imu(self.h, frame0, n, _p(X), _p(P), _p(g), _p(st), _p(it), _p(Lp), _p(me)))
+        return dict(X=X, P=P, gravity=g, started=st, it_time=it, last_pose=[_from_cm(t) for t in Lp], measurements=me)
+
+    def set_imu(self, frame0, X=None, P=None, gravity=None, started=None, it_time=None):
+        """Restore a stream's IMU filter: [n][16] X, [n][16][16] P, [n][3] gravity, [n] started, [n] it_time; None leaves a field."""
+        a = [None if v is None else np.ascontiguousarray(v, dt) for v, dt in ((X, np.float64), (P, np.float64), (gravity, np.float64),
+                                                                              (started, np.int32), (it_time, np.float64))]
+        n = {len(v) for v in a if v is not None}
+        assert len(n) == 1
+        self.L.sd_track_set_imu.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+        _check(self.L.sd_track_set_imu(self.h, frame0, n.pop(), *[None if v is None else _p(v) for v in a]))
+
     def get_last(self, frame0, n):
         """The last-frame arrays, [n][max_points] layout."""
         M = self.M

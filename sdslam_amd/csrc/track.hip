@@ -81,6 +81,9 @@ struct sd_track {
   bool small_pending[kPriorRing] = {};
   int small_next = 0;
   int32_t* d_kf_stage = nullptr;   // [max_batch][8]
+  // sd_track_set_sensor_model: which filter sd_track_motion_predict / _update / _restart run (per handle, as per Tracking)
+  int sensor_model = SD_SENSOR_CONSTANT_VELOCITY;
+  std::vector<uint8_t> meas_set;   // [max_batch] sd_track_set_measurements has covered the slot since the model was chosen
   static const int kRing = 128;
   hipEvent_t ev[kRing][6] = {};
   int ev_calls[3] = {0, 0, 0};
@@ -325,6 +328,13 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &tb.mo_it, B));
   A(dalloc(h, &tb.mo_last, B * 16));
   A(dalloc(h, &tb.mo_E, B * 16));
+  A(dalloc(h, &tb.im_X, B * 16));
+  A(dalloc(h, &tb.im_P, B * 256));
+  A(dalloc(h, &tb.im_g, B * 3));
+  A(dalloc(h, &tb.im_started, B));
+  A(dalloc(h, &tb.im_it, B));
+  A(dalloc(h, &tb.im_last, B * 16));
+  A(dalloc(h, &tb.im_meas, B * 6));
   A(dalloc(h, &tb.Tref, B * 16));
   A(dalloc(h, &tb.Tprior, B * 16));
   A(dalloc(h, &tb.Tcur, B * 16));
@@ -398,6 +408,16 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
     // motion model: not started, X = 0, P = diag(COV_V_2 x3, COV_W_2 x3) (ConstantVelocity::Init; both 0.000625)
     std::vector<double> p0((size_t)B * 6, 0.000625);
     if (e0 == hipSuccess) e0 = hipMemcpy(tb.mo_P, p0.data(), p0.size() * 8, hipMemcpyHostToDevice);
+    // IMU sensor model: not started, X = (0, q = 1 0 0 0, 0, 0, 0), P = diag(COV_X_2 x3, COV_Q_2 x4, COV_V_2 x3, COV_W_2 x3,
+    // COV_A_2 x3) (IMU::Init), gravity_ = 0
+    std::vector<double> ix((size_t)B * 16, 0.0), ip((size_t)B * 256, 0.0);
+    for (size_t f = 0; f < (size_t)B; f++) {
+      ix[f * 16 + 3] = 1.0;
+      for (int i = 0; i < 16; i++) ip[f * 256 + i * 17] = i < 3 ? 0.0025 : (i < 7 ? 0.00001 : 0.000625);
+    }
+    if (e0 == hipSuccess) e0 = hipMemcpy(tb.im_X, ix.data(), ix.size() * 8, hipMemcpyHostToDevice);
+    if (e0 == hipSuccess) e0 = hipMemcpy(tb.im_P, ip.data(), ip.size() * 8, hipMemcpyHostToDevice);
+    h->meas_set.assign((size_t)B, 0);
     if (e0 != hipSuccess) { set_error(std::string("sd_track_create: ") + hipGetErrorString(e0)); rc = SD_ERR_HIP; }
   }
   if (rc == SD_OK) {
@@ -1552,6 +1572,7 @@ int sd_track_motion_predict(sd_track* h, int n_frames, double dt) {
   SD_REQUIRE(std::isfinite(dt) && dt >= 0.0, SD_ERR_INVALID_ARG, "dt must be finite and not negative");
   SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
   SD_HIP_CHECK(hipSetDevice(h->device));
+  if (h->sensor_model == SD_SENSOR_IMU) return launch_imu_predict(h->tb, n_frames, dt, h->pnp_stream);
   return launch_motion_predict(h->tb, n_frames, dt, h->pnp_stream);
 }
 
@@ -1564,7 +1585,11 @@ int sd_track_motion_update(sd_track* h, int n_frames, int source) {
   SD_REQUIRE(source < 0 || ran_since_extract(h, source, n_frames), SD_ERR_INVALID_ARG,
              source == 0 ? "sd_track_with_motion_model has not run on these slots since the last extraction"
                          : "sd_track_local_map has not run on these slots since the last extraction");
+  if (h->sensor_model == SD_SENSOR_IMU)   // the reference asserts on the size of measurements_ (IMU::Z)
+    for (int f = 0; f < n_frames; f++)
+      SD_REQUIRE(h->meas_set[f], SD_ERR_INVALID_ARG, "sd_track_set_measurements has not covered these slots since the IMU model was chosen");
   SD_HIP_CHECK(hipSetDevice(h->device));
+  if (h->sensor_model == SD_SENSOR_IMU) return launch_imu_update(h->tb, n_frames, source, h->pnp_stream);
   return launch_motion_update(h->tb, n_frames, source, h->pnp_stream);
 }
 
@@ -1572,11 +1597,13 @@ int sd_track_motion_restart(sd_track* h, int frame0, int n_frames) {
   SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
   SD_REQUIRE(frame0 >= 0 && n_frames >= 1 && frame0 + n_frames <= h->max_batch, SD_ERR_CAPACITY, "frame range exceeds max_batch");
   SD_HIP_CHECK(hipSetDevice(h->device));
+  if (h->sensor_model == SD_SENSOR_IMU) return launch_imu_init(h->tb, frame0, n_frames, 0, h->pnp_stream);
   return launch_motion_init(h->tb, frame0, n_frames, h->pnp_stream);
 }
 
 int sd_track_get_motion(sd_track* h, int frame0, int n_frames, double* X6, double* Pdiag6, int32_t* started, double* it_time,
                         double* E_cm, double* last_pose_cm) {
+  SD_REQUIRE(!h || h->sensor_model == SD_SENSOR_CONSTANT_VELOCITY, SD_ERR_INVALID_ARG, "the IMU sensor model is selected: sd_track_get_imu");
   TRACK_RANGE(h, frame0, n_frames);
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
@@ -1593,6 +1620,7 @@ int sd_track_get_motion(sd_track* h, int frame0, int n_frames, double* X6, doubl
 
 int sd_track_set_motion(sd_track* h, int frame0, int n_frames, const double* X6, const double* Pdiag6, const int32_t* started,
                         const double* it_time) {
+  SD_REQUIRE(!h || h->sensor_model == SD_SENSOR_CONSTANT_VELOCITY, SD_ERR_INVALID_ARG, "the IMU sensor model is selected: sd_track_set_imu");
   TRACK_RANGE(h, frame0, n_frames);
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
@@ -1601,6 +1629,80 @@ int sd_track_set_motion(sd_track* h, int frame0, int n_frames, const double* X6,
   if (Pdiag6) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_P + o * 6, Pdiag6, n * 48, hipMemcpyHostToDevice, s));
   if (started) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_started + o, started, n * 4, hipMemcpyHostToDevice, s));
   if (it_time) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_it + o, it_time, n * 8, hipMemcpyHostToDevice, s));
+  SD_HIP_CHECK(hipStreamSynchronize(s));
+  return SD_OK;
+}
+
+// ---- the IMU sensor model (kernels: track_imu.hip)
+
+int sd_track_set_sensor_model(sd_track* h, int model) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(model == SD_SENSOR_CONSTANT_VELOCITY || model == SD_SENSOR_IMU, SD_ERR_INVALID_ARG,
+             "model must be SD_SENSOR_CONSTANT_VELOCITY or SD_SENSOR_IMU");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  // a new Tracking constructs its EKF: every slot's filter of the chosen model restarts
+  int rc = model == SD_SENSOR_IMU ? launch_imu_init(h->tb, 0, h->max_batch, 1, h->pnp_stream)
+                                  : launch_motion_init(h->tb, 0, h->max_batch, h->pnp_stream);
+  if (rc != SD_OK) return rc;
+  h->sensor_model = model;
+  h->meas_set.assign((size_t)h->max_batch, 0);
+  return SD_OK;
+}
+
+int sd_track_get_sensor_model(sd_track* h, int* model) {
+  SD_REQUIRE(h && model, SD_ERR_INVALID_ARG, "NULL argument");
+  *model = h->sensor_model;
+  return SD_OK;
+}
+
+// Tracking::SetMeasurements for slots frame0 .. frame0 + n_frames - 1, through the pinned ring of sd_track_set_prior
+int sd_track_set_measurements(sd_track* h, int frame0, int n_frames, const double* wa6) {
+  SD_REQUIRE(h && wa6, SD_ERR_INVALID_ARG, "NULL argument");
+  SD_REQUIRE(frame0 >= 0 && n_frames >= 1 && frame0 + n_frames <= h->max_batch, SD_ERR_CAPACITY, "frame range exceeds max_batch");
+  SD_REQUIRE(h->sensor_model == SD_SENSOR_IMU, SD_ERR_INVALID_ARG, "the constant-velocity model takes no measurements (sd_track_set_sensor_model)");
+  for (size_t i = 0; i < (size_t)n_frames * 6; i++) SD_REQUIRE(std::isfinite(wa6[i]), SD_ERR_INVALID_ARG, "measurements must be finite");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  const int r = h->prior_next;
+  h->prior_next = (r + 1) % sd_track::kPriorRing;
+  if (h->prior_pending[r]) SD_HIP_CHECK(hipEventSynchronize(h->ev_prior[r]));   // its copy of kPriorRing calls ago has run
+  std::memcpy(h->prior_host[r], wa6, (size_t)n_frames * 48);
+  hipStream_t s = h->pnp_stream;
+  SD_HIP_CHECK(hipMemcpyAsync(h->tb.im_meas + (size_t)frame0 * 6, h->prior_host[r], (size_t)n_frames * 48, hipMemcpyHostToDevice, s));
+  SD_HIP_CHECK(hipEventRecord(h->ev_prior[r], s));
+  h->prior_pending[r] = true;
+  for (int f = frame0; f < frame0 + n_frames; f++) h->meas_set[f] = 1;
+  return SD_OK;
+}
+
+int sd_track_get_imu(sd_track* h, int frame0, int n_frames, double* X16, double* P256, double* gravity3, int32_t* started, double* it_time,
+                     double* last_pose_cm, double* measurements6) {
+  TRACK_RANGE(h, frame0, n_frames);
+  hipStream_t s = h->cur->stream;
+  const TrackBuffers& tb = h->tb;
+  const size_t o = frame0, n = n_frames;
+  if (X16) SD_HIP_CHECK(hipMemcpyAsync(X16, tb.im_X + o * 16, n * 128, hipMemcpyDeviceToHost, s));
+  if (P256) SD_HIP_CHECK(hipMemcpyAsync(P256, tb.im_P + o * 256, n * 2048, hipMemcpyDeviceToHost, s));
+  if (gravity3) SD_HIP_CHECK(hipMemcpyAsync(gravity3, tb.im_g + o * 3, n * 24, hipMemcpyDeviceToHost, s));
+  if (started) SD_HIP_CHECK(hipMemcpyAsync(started, tb.im_started + o, n * 4, hipMemcpyDeviceToHost, s));
+  if (it_time) SD_HIP_CHECK(hipMemcpyAsync(it_time, tb.im_it + o, n * 8, hipMemcpyDeviceToHost, s));
+  if (last_pose_cm) SD_HIP_CHECK(hipMemcpyAsync(last_pose_cm, tb.im_last + o * 16, n * 128, hipMemcpyDeviceToHost, s));
+  if (measurements6) SD_HIP_CHECK(hipMemcpyAsync(measurements6, tb.im_meas + o * 6, n * 48, hipMemcpyDeviceToHost, s));
+  SD_HIP_CHECK(hipStreamSynchronize(s));
+  return SD_OK;
+}
+
+int sd_track_set_imu(sd_track* h, int frame0, int n_frames, const double* X16, const double* P256, const double* gravity3,
+                     const int32_t* started, const double* it_time) {
+  SD_REQUIRE(!h || h->sensor_model == SD_SENSOR_IMU, SD_ERR_INVALID_ARG, "the constant-velocity model is selected: sd_track_set_motion");
+  TRACK_RANGE(h, frame0, n_frames);
+  hipStream_t s = h->cur->stream;
+  const TrackBuffers& tb = h->tb;
+  const size_t o = frame0, n = n_frames;
+  if (X16) SD_HIP_CHECK(hipMemcpyAsync(tb.im_X + o * 16, X16, n * 128, hipMemcpyHostToDevice, s));
+  if (P256) SD_HIP_CHECK(hipMemcpyAsync(tb.im_P + o * 256, P256, n * 2048, hipMemcpyHostToDevice, s));
+  if (gravity3) SD_HIP_CHECK(hipMemcpyAsync(tb.im_g + o * 3, gravity3, n * 24, hipMemcpyHostToDevice, s));
+  if (started) SD_HIP_CHECK(hipMemcpyAsync(tb.im_started + o, started, n * 4, hipMemcpyHostToDevice, s));
+  if (it_time) SD_HIP_CHECK(hipMemcpyAsync(tb.im_it + o, it_time, n * 8, hipMemcpyHostToDevice, s));
   SD_HIP_CHECK(hipStreamSynchronize(s));
   return SD_OK;
 }

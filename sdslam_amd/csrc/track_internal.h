@@ -115,6 +115,14 @@ struct TrackBuffers {
   double* mo_it;         // [B]     it_time_
   double* mo_last;       // [B][16] Sensor::last_pose_ (SetLastPose), column-major
   double* mo_E;          // [B][16] Exp(X_) of the last prediction, column-major
+  // IMU sensor model (track_imu.hip): EKF + IMU of every slot, used instead of mo_* under SD_SENSOR_IMU
+  double* im_X;          // [B][16] X_ = (x, q as w x y z, v, w, a)
+  double* im_P;          // [B][256] P_, dense, row-major
+  double* im_g;          // [B][3]  IMU::gravity_
+  int32_t* im_started;   // [B]     updated_
+  double* im_it;         // [B]     it_time_
+  double* im_last;       // [B][16] Sensor::last_pose_, column-major
+  double* im_meas;       // [B][6]  Tracking::measurements_ (SetMeasurements): gyro xyz, accelerometer xyz
 };
 
 // Entry (r, c) of the 4x4 product A * B, both column-major: k = 0..3 in order, every product and sum rounded on its own (no
@@ -195,6 +203,11 @@ int launch_set_keyframe_state(const TrackBuffers& tb, const int32_t* staged, int
 int launch_motion_init(const TrackBuffers& tb, int frame0, int n_frames, hipStream_t s);   // EKF::Restart
 int launch_motion_predict(const TrackBuffers& tb, int n_frames, double dt, hipStream_t s);
 int launch_motion_update(const TrackBuffers& tb, int n_frames, int source, hipStream_t s);
+// IMU sensor model (track_imu.hip), one wave per slot; source as above
+// full 0: EKF::Restart (IMU::Init: the diagonal blocks of P only); 1: a newly constructed EKF (all of P)
+int launch_imu_init(const TrackBuffers& tb, int frame0, int n_frames, int full, hipStream_t s);
+int launch_imu_predict(const TrackBuffers& tb, int n_frames, double dt, hipStream_t s);
+int launch_imu_update(const TrackBuffers& tb, int n_frames, int source, hipStream_t s);
 int read_pnp_prof(unsigned long long* out32, int reset);
 int read_sel_prof(unsigned long long* out64, int reset);
 int read_align_prof(unsigned long long* out16, int reset);

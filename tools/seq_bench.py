@@ -31,6 +31,15 @@ Motion-model modes (monocular, the `device` loop with the prior from the filter 
               upload B matrices through sd_track_set_prior
   (results in profiles/seq_bench_motion.json when one of them is in the mode list)
 
+IMU sensor-model modes (the 16-state EKF of Monocular-IMU tracking; gyro readings from the ground-truth poses, a constant
+accelerometer reading; dt 1/30):
+  imu_device  the ekf_device loop under sd_track_set_sensor_model(SD_SENSOR_IMU) with one sd_track_set_measurements per step
+              (48 bytes per slot through the pinned ring): no host wait in the loop
+  imu_host    what a caller had to do before: synchronise, download the B final poses and statuses, run the dense filter for
+              B streams on the host (batched numpy, numpy.linalg.inv for the 13 x 13 S), upload B priors through
+              sd_track_set_prior(relative = 0)
+  (results in profiles/seq_bench_imu.json when one of them is in the mode list)
+
 python tools/seq_bench.py [T=8] [B list=1,1024] [modes=device,host]  -> one JSON line per (B, mode), all of them in
 profiles/seq_bench.json (profiles/seq_bench_rgbd.json when RGB-D modes run).
 Frames are resident in HBM (extraction from device memory); the timed region is frames 1..T-1 including extraction, ended
@@ -57,7 +66,9 @@ KF = MODES == ["rgbd_kf"] or any(m in ("kf_device", "kf_host") for m in MODES)
 if MODES == ["rgbd_kf"]:
     MODES = ["kf_device", "kf_host", "device_u16"]
 EKF = any(m in ("ekf_device", "ekf_host") for m in MODES)
+IMU = any(m in ("imu_device", "imu_host") for m in MODES)
 EKF_DT = 1.0 / 30.0
+IMU_A = (0.05, -0.03, 0.02)
 RGBD = any(m in ("host_f32", "device_u16", "kf_device", "kf_host") for m in MODES)
 KF_STATE = (5, 700, 0, 0, 1, 0, 0, 0)
 KF_MIN_FRAMES, KF_MAX_FRAMES = 3, 30
@@ -200,6 +211,158 @@ def run_ekf_host(B, seqs):
         upd = (ok & started)[:, None]
         X = np.where(upd, X + Kg * (Z - X), np.where(ok[:, None], X * started[:, None], 0.0))
         P = np.where(upd, P - Kg * S * Kg, np.where(ok[:, None], P, 0.000625))
+        started = ok
+        trk.advance(B, 1)
+        T_last = pose
+    st = trk.get_local_map(0, B)["status"]
+    dt = time.perf_counter() - t0
+    trk.close()
+    frames.free()
+    return dt, st
+
+
+def _rot_quat(Rm):
+    """[B][3][3] -> [B][4] (w, x, y, z), rotations with a positive trace (the sequences')."""
+    t = np.sqrt(np.trace(Rm, axis1=1, axis2=2) + 1.0)
+    q = np.stack([0.5 * t, (Rm[:, 2, 1] - Rm[:, 1, 2]) * 0.5 / t, (Rm[:, 0, 2] - Rm[:, 2, 0]) * 0.5 / t, (Rm[:, 1, 0] - Rm[:, 0, 1]) * 0.5 / t], 1)
+    return q / np.linalg.norm(q, axis=1, keepdims=True)
+
+
+def _quat_mul(a, b):
+    return np.stack([a[:, 0] * b[:, 0] - a[:, 1] * b[:, 1] - a[:, 2] * b[:, 2] - a[:, 3] * b[:, 3],
+                     a[:, 0] * b[:, 1] + a[:, 1] * b[:, 0] + a[:, 2] * b[:, 3] - a[:, 3] * b[:, 2],
+                     a[:, 0] * b[:, 2] + a[:, 2] * b[:, 0] + a[:, 3] * b[:, 1] - a[:, 1] * b[:, 3],
+                     a[:, 0] * b[:, 3] + a[:, 3] * b[:, 0] + a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1]], 1)
+
+
+def _quat_w(wt):
+    ang = np.linalg.norm(wt, axis=1)
+    safe = np.where(ang > 0, ang, 1.0)
+    return np.concatenate([np.where(ang > 0, np.cos(ang / 2), 1.0)[:, None], (np.where(ang > 0, np.sin(ang / 2) / safe, 0.0))[:, None] * wt], 1)
+
+
+def _quat_rot(q):
+    w, x, y, z = (q / np.linalg.norm(q, axis=1, keepdims=True)).T
+    return np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], 1),
+                     np.stack([2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)], 1),
+                     np.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], 1)], 1)
+
+
+def _dq_by_dw(q, w, t):
+    """Sensor::dq_by_dw for [B] filters, both branches."""
+    modw = np.linalg.norm(w, axis=1)
+    zero = modw == 0
+    m = np.where(zero, 1.0, modw)[:, None, None]
+    sb, cb = np.sin(m * t / 2), np.cos(m * t / 2)
+    mdw = np.zeros((len(w), 4, 3))
+    mdw[:, 0, :] = (-t / 2 * sb[:, 0] * w / m[:, 0])
+    mdw[:, 1:, :] = w[:, :, None] * w[:, None, :] / (m * m) * (t / 2 * cb - sb / m) + np.eye(3) * (sb / m)
+    w_, x, y, z = q.T
+    JR = np.stack([np.stack([w_, -x, -y, -z], 1), np.stack([x, w_, -z, y], 1), np.stack([y, z, w_, -x], 1), np.stack([z, -y, x, w_], 1)], 1)
+    res = JR @ mdw
+    res[zero] = np.vstack([np.zeros((1, 3)), np.eye(3) * t / 2])
+    return res
+
+
+def imu_measurements(B, seqs):
+    """[T][B][6]: gyro w_t = 2 log(q_{t-1}^-1 q_t) / dt from the ground-truth poses, the constant accelerometer reading."""
+    out = np.zeros((T, B, 6))
+    out[:, :, 3:] = IMU_A
+    for u in range(min(B, NU)):
+        q = _rot_quat(np.stack([seqs[u]["T"][t][:3, :3] for t in range(T)]))
+        d = _quat_mul(q[:-1] * np.array([1.0, -1.0, -1.0, -1.0]), q[1:])
+        nv = np.linalg.norm(d[:, 1:], axis=1)
+        w = np.where(nv[:, None] > 0, 2 * np.arctan2(nv, d[:, 0])[:, None] * d[:, 1:] / np.where(nv > 0, nv, 1.0)[:, None], 0.0) / EKF_DT
+        out[1:, u::NU, :3] = w[:, None, :]
+    return out
+
+
+def run_imu_device(B, seqs):
+    frames, ext, maps, _ = setup(B, seqs)
+    trk = new_tracker(ext[0], ext[1], B, maps, seqs)
+    trk.set_sensor_model(trk.SENSOR_IMU)
+    meas = imu_measurements(B, seqs)
+    t0 = time.perf_counter()
+    for t in range(1, T):
+        trk.cur.extract_batch_device(frames.ptr.value + t * B * F, B, 640, 480)
+        trk.set_measurements(0, meas[t])
+        trk.motion_predict(B, EKF_DT)
+        trk.track_with_motion_model(B, th=15.0)
+        trk.track_local_map(B, th=1.0)
+        trk.motion_update(B, 1)
+        trk.advance(B, 1)
+    st = trk.get_local_map(0, B)["status"]        # synchronises
+    dt = time.perf_counter() - t0
+    trk.close()
+    frames.free()
+    return dt, st
+
+
+IMU_SEL = np.array([0, 1, 2, 3, 4, 5, 6, 10, 11, 12, 13, 14, 15])
+IMU_P0 = np.diag([0.0025] * 3 + [0.00001] * 4 + [0.000625] * 9)
+IMU_R = np.array([0.05 ** 2] * 3 + [0.02 ** 2] * 4 + [2.60 ** 2] * 3 + [8.94 ** 2] * 3)
+IMU_PN = np.array([16.0] * 3 + [36.0] * 3 + [8.94 ** 2] * 3)
+
+
+def run_imu_host(B, seqs):
+    frames, ext, maps, _ = setup(B, seqs)
+    trk = new_tracker(ext[0], ext[1], B, maps, seqs)
+    meas = imu_measurements(B, seqs)
+    X = np.zeros((B, 16))
+    X[:, 3] = 1.0
+    P = np.tile(IMU_P0, (B, 1, 1))
+    g = np.zeros((B, 3))
+    started = np.zeros(B, bool)
+    T_last = np.stack([seqs[b % NU]["T"][0] for b in range(B)])
+    dt_, I3 = EKF_DT, np.eye(3)
+    t0 = time.perf_counter()
+    for t in range(1, T):
+        # EKF::Predict for the started filters; the last pose for the others
+        q, w = X[:, 3:7], X[:, 10:13]
+        qwt, D = _quat_w(w * dt_), _dq_by_dw(q, w, dt_)
+        jF = np.tile(np.eye(16), (B, 1, 1))
+        jF[:, 0:3, 7:10] = I3 * dt_
+        jF[:, 7:10, 13:16] = I3 * dt_
+        a_, b_, c_, d_ = qwt.T
+        jF[:, 3:7, 3:7] = np.stack([np.stack([a_, -b_, -c_, -d_], 1), np.stack([b_, a_, d_, -c_], 1), np.stack([c_, -d_, a_, b_], 1),
+                                    np.stack([d_, c_, -b_, a_], 1)], 1)
+        jF[:, 3:7, 10:13] = D
+        G = np.zeros((B, 16, 9))
+        G[:, 0:3, 0:3], G[:, 7:10, 0:3], G[:, 7:10, 6:9], G[:, 10:13, 3:6], G[:, 13:16, 6:9] = I3 * dt_, I3, I3 * dt_, I3, I3
+        G[:, 3:7, 3:6] = D
+        Xp = X.copy()
+        Xp[:, 0:3] += X[:, 7:10] * dt_
+        Xp[:, 3:7] = _quat_mul(q, qwt)
+        Xp[:, 7:10] += X[:, 13:16] * dt_
+        Pp = jF @ P @ jF.transpose(0, 2, 1) + (G * (IMU_PN * dt_ * dt_)) @ G.transpose(0, 2, 1)
+        X = np.where(started[:, None], Xp, X)
+        P = np.where(started[:, None, None], Pp, P)
+        prior = np.tile(np.eye(4), (B, 1, 1))
+        prior[:, :3, :3], prior[:, :3, 3] = _quat_rot(X[:, 3:7]), X[:, 0:3]
+        prior = np.where(started[:, None, None], prior, T_last)
+        trk.cur.extract_batch_device(frames.ptr.value + t * B * F, B, 640, 480)
+        trk.set_prior(0, list(prior), relative=False)
+        trk.track_with_motion_model(B, th=15.0)
+        trk.track_local_map(B, th=1.0)
+        # the host round trip of the motion model: poses and statuses down, the filter in numpy
+        pose = np.stack(trk.get_align(0, B)["T"])
+        ok = trk.get_local_map(0, B)["status"] == 2
+        it = np.where(started, dt_, 0.0)
+        alpha = (0.27 / (0.27 + it))[:, None]
+        g = alpha * g + (1 - alpha) * meas[t][:, 3:]
+        Z = np.concatenate([pose[:, :3, 3], _rot_quat(pose[:, :3, :3]), meas[t][:, :3], meas[t][:, 3:] - g], 1)
+        S = P[:, IMU_SEL][:, :, IMU_SEL] + np.eye(13) * (IMU_R * dt_ * dt_)
+        Kg = P[:, :, IMU_SEL] @ np.linalg.inv(S)
+        Xu = X + (Kg @ (Z - X[:, IMU_SEL])[..., None])[..., 0]
+        Pu = P - Kg @ S @ Kg.transpose(0, 2, 1)
+        Xi = np.zeros((B, 16))
+        Xi[:, :7] = Z[:, :7]
+        upd, init = (ok & started), (ok & ~started)
+        X0 = np.zeros(16)
+        X0[3] = 1.0
+        X = np.where(upd[:, None], Xu, np.where(init[:, None], Xi, X0))
+        P = np.where(upd[:, None, None], Pu, np.where(init[:, None, None], P, IMU_P0))
+        g = np.where(upd[:, None], g, 0.0)
         started = ok
         trk.advance(B, 1)
         T_last = pose
@@ -426,7 +589,7 @@ def main():
     seqs = [synth.make_sequence(100 + i, T, with_depth=RGBD) for i in range(NU)]
     fns = dict(device=run_device, mono=run_device, host=run_host, host_f32=lambda B, s: run_rgbd(B, s, "host_f32"),
                device_u16=lambda B, s: run_rgbd(B, s, "device_u16"), kf_device=run_kf_device, kf_host=run_kf_host,
-               ekf_device=run_ekf_device, ekf_host=run_ekf_host)
+               ekf_device=run_ekf_device, ekf_host=run_ekf_host, imu_device=run_imu_device, imu_host=run_imu_host)
     out = []
     for B in BS:
         for mode in MODES:
@@ -438,7 +601,7 @@ def main():
             print(json.dumps(r), flush=True)
             out.append(r)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "seq_bench_motion.json" if EKF else "seq_bench_rgbd_kf.json" if KF else "seq_bench_rgbd.json" if RGBD else "seq_bench.json"), "w") as f:
+    with open(os.path.join(ROOT, "profiles", "seq_bench_imu.json" if IMU else "seq_bench_motion.json" if EKF else "seq_bench_rgbd_kf.json" if KF else "seq_bench_rgbd.json" if RGBD else "seq_bench.json"), "w") as f:
         json.dump(out, f, indent=1)
 
 
