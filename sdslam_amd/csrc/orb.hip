@@ -1619,7 +1619,7 @@ static int pipeline_body(sd_orb* h, const uint8_t* d_imgs, int n, int stride, si
     SD_HIP_CHECK(hipEventRecord(ev[2], h->fast_stream));
     h->evf_n[ring_slot] = h->evf_ready ? nfp : 0;
   }
-  // ev_fast_done stands for "pyramid AND FAST complete" (a tracker's ImageAlign waits for it alone, track.hip wait_inputs): a
+  // ev_fast_done stands for "pyramid AND FAST complete" (a tracker's ImageAlign waits for it alone, track_handle.h wait_inputs): a
   // level without grid cells launches no FAST, so the FAST stream has not necessarily waited for that level's resize
   // (few features: no cells at all on the merged small levels) -- order it behind the whole pyramid explicitly
   SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_pyr_done, 0));

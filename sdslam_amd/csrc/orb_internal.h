@@ -1,4 +1,4 @@
-// Internal layout of the sd_orb handle (shared by orb.hip and track.hip; not part of the ABI).
+// Internal layout of the sd_orb handle (shared by orb.hip and the sd_track sources through track_handle.h; not part of the ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 

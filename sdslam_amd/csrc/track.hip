@@ -4,6 +4,8 @@
 // Besides the stage calls: whole-function calls that keep the reference's per-frame decisions on
 // the device (sd_track_with_motion_model, sd_track_local_map) and the one-frame-against-all-
 // keyframes calls (sd_track_relocalize, sd_track_detect_loop) built on the broadcast current frame.
+// The sequential loop around them (hand-off, keyframes, new points, motion models) is track_seq.hip; the handle itself and the
+// helpers both files share are track_handle.h.
 //
 // Call sequence of the reference this mirrors (src/Tracking.cc:654-718):
 //   ImageAlign::ComputePose(cur, last)            -> sd_track_align
@@ -15,79 +17,12 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <utility>
 #include <string>
 #include <vector>
 
-#include "orb_internal.h"
-#include "track_internal.h"
+#include "track_handle.h"
 
 using namespace sd;
-
-struct sd_track {
-  sd_orb* cur = nullptr;
-  sd_orb* ref = nullptr;
-  int max_points = 0, max_batch = 0, kp_cap = 0, device = 0;
-  int rand_per_frame = 0;
-  std::vector<int> rand_len;      // rand() values actually supplied per slot (sd_track_set_rand)
-  bool have_pnp = false;          // sd_track_pnp has constructed the solvers sd_track_pnp_iterate continues ...
-  unsigned long long pnp_serial = 0;   // ... on the keypoints of THIS extraction of `cur` (the reference's solver owns copies of its inputs)
-  PnpParams pnp_params{};
-  int pnp_frames = 0, pnp_iter_upper = 0;   // slots / upper bound of mnIterations of those solvers
-  TrackBuffers tb{};
-  TrackCam cam{};
-  bool have_cam = false;
-  float* d_sf = nullptr;
-  float* d_inv_sf = nullptr;
-  float* d_sigma2 = nullptr;
-  float* d_inv_sigma2 = nullptr;
-  float* d_scale_thr = nullptr;   // MapPoint::PredictScale breakpoints (see k_match_local)
-  std::vector<void*> allocs;
-  // The tracking kernels (align, match, PnP: latency-bound, few waves) run on their own stream, so
-  // the extraction of the next batch on cur->stream overlaps them; `cur` is double-buffered
-  // (orb_internal.h: output sets) and every tracking launch waits for the extraction it consumes
-  // (ev_extract_done) and marks the sets it read (ev_set_free).
-  hipStream_t pnp_stream = nullptr;
-  bool profiling = false;
-  hipEvent_t ev_fence = nullptr;   // sd_track_stream_fence
-  // sequential tracking (sd_track_advance): the last call of each kind since the extraction of `cur` it read --
-  // [0] sd_track_with_motion_model, [1] sd_track_local_map -- as (extractor, its extraction serial, slots)
-  const sd_orb* ran_cur[2] = {nullptr, nullptr};
-  unsigned long long ran_serial[2] = {0, 0};
-  int ran_n[2] = {0, 0};
-  bool ids_on = false;             // sd_track_set_map_ids has been called: sd_track_local_map applies the seen-point exclusion
-  // sd_track_set_prior: host poses go through a ring of pinned buffers into d_prior, all on the tracking stream, so the call
-  // queues behind the hand-off that wrote Tref without a host wait (a slot is reused once the copy out of it has run)
-  static const int kPriorRing = 4;
-  double* prior_host[kPriorRing] = {};
-  hipEvent_t ev_prior[kPriorRing] = {};
-  bool prior_pending[kPriorRing] = {};
-  int prior_next = 0;
-  double* d_prior = nullptr;       // [max_batch][16]
-  int32_t* d_close = nullptr;      // [max_batch][2] sd_track_close_points: nTrackedClose, nNonTrackedClose
-  // ... and of sd_track_close_points (sd_track_need_keyframe reads its counts)
-  const sd_orb* close_cur = nullptr;
-  unsigned long long close_serial = 0;
-  int close_n = 0, close_source = -1;
-  // the last map point creation (sd_track_stereo_init / sd_track_create_keyframe_points) on the current extraction:
-  // sd_track_advance then takes the created keypoints' points from the np_* buffers
-  const sd_orb* made_cur = nullptr;
-  unsigned long long made_serial = 0;
-  int made_n = 0, made_mode = 0, made_source = -1;
-  // sd_track_set_keyframe_state / sd_track_set_keyframe_flags / sd_track_set_next_map_id: small host arrays through a ring
-  // of pinned buffers ([max_batch][8] int32 each) on the tracking stream, like the prior
-  int32_t* small_host[kPriorRing] = {};
-  hipEvent_t ev_small[kPriorRing] = {};
-  bool small_pending[kPriorRing] = {};
-  int small_next = 0;
-  int32_t* d_kf_stage = nullptr;   // [max_batch][8]
-  // sd_track_set_sensor_model: which filter sd_track_motion_predict / _update / _restart run (per handle, as per Tracking)
-  int sensor_model = SD_SENSOR_CONSTANT_VELOCITY;
-  std::vector<uint8_t> meas_set;   // [max_batch] sd_track_set_measurements has covered the slot since the model was chosen
-  static const int kRing = 128;
-  hipEvent_t ev[kRing][6] = {};
-  int ev_calls[3] = {0, 0, 0};
-};
 
 // Per-frame result record (the only data that crosses xGMI in the batched-frames mode), 20 doubles:
 // pose 4x4 column-major | ImageAlign ok | nmatches | pose-solver inliers | pose-solver ok
@@ -116,138 +51,6 @@ __global__ void k_pack_records(TrackBuffers tb, int source, int n_frames, double
   else { ok = tb.al_ok[f]; }
   r[18] = inl;
   r[19] = ok;
-}
-
-// Tracking::Track's hand-off to the next frame (reference src/Tracking.cc:250-292), one workgroup per slot, into the second
-// last-frame SoA (the host swaps the two afterwards: what is read and what is written overlap).  Keypoint i < N of the current
-// frame keeps map point m = mvpMapPoints[i] -- source 0: cur_match after TrackWithMotionModel's outlier discard; 1: un_match
-// after TrackLocalMap, m >= M naming local point m - M -- iff it is there, not an outlier (mvbOutlier, source 1) and has
-// Observations() >= 1 ("Clean VO matches" :250-257, outliers :272-275).  Kept points carry Xw / descriptor / obs / id; the
-// others zeros and id -1.  octave = mvKeys[i].octave, angle = mvKeysUn[i].angle; n_last = N; Tref = the frame's final pose,
-// which both tracking tails leave in Tcur.  Slots >= n_frames keep their last frame (copied across).
-// created_n > 0: a creation call (track_newpoints.hip) ran on this extraction for slots < created_n; a keypoint it gave a new
-// point carries that point -- np_Xw, the keypoint's own descriptor (ComputeDistinctiveDescriptors with one observation),
-// Observations() = 1, np_id -- whatever mvbOutlier[i] says.  source 2: after StereoInitialization mvpMapPoints are the
-// created points only and Tref = the identity it left in Tcur; slots that did not initialise keep their last frame.
-__global__ __launch_bounds__(256) void k_advance(const sd_keypoint* __restrict__ kps_all, const sd_keypoint* __restrict__ kps_un_all,
-                                                 const int32_t* __restrict__ nkp_all, TrackBuffers tb, int source, int n_frames,
-                                                 const uint8_t* __restrict__ desc_all, int created_n) {
-  const int f = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
-  const int M = tb.max_points, cap = tb.kp_cap;
-  const size_t o = (size_t)f * M;
-  if (f >= n_frames || (source == 2 && tb.np_info[(size_t)f * 4] != 2)) {
-    for (int i = tid; i < M; i += NT) {
-      const size_t e = o + i;
-      tb.valid2[e] = tb.valid[e];
-      for (int k = 0; k < 3; k++) tb.Xw2[e * 3 + k] = tb.Xw[e * 3 + k];
-      ((uint4*)tb.mp_desc2)[e * 2] = ((const uint4*)tb.mp_desc)[e * 2];
-      ((uint4*)tb.mp_desc2)[e * 2 + 1] = ((const uint4*)tb.mp_desc)[e * 2 + 1];
-      tb.octave2[e] = tb.octave[e];
-      tb.angle2[e] = tb.angle[e];
-      tb.obs2[e] = tb.obs[e];
-      tb.last_id2[e] = tb.last_id[e];
-    }
-    return;
-  }
-  const int N = min(nkp_all[f], cap);   // cap <= M (sd_track_advance)
-  const int32_t* match = (source == 0 ? tb.cur_match : tb.un_match) + (size_t)f * cap;
-  const uint8_t* outl = tb.po_outlier + (size_t)f * cap;
-  const uint8_t* made = f < created_n ? tb.np_flag + (size_t)f * cap : nullptr;
-  for (int i = tid; i < M; i += NT) {
-    uint8_t v = 0;
-    double X0 = 0, X1 = 0, X2 = 0;
-    int ob = 0, id = -1, oct = 0;
-    float ang = 0.f;
-    uint4 d0 = make_uint4(0, 0, 0, 0), d1 = d0;
-    if (i < N) {
-      oct = kps_all[(size_t)f * cap + i].octave;
-      ang = kps_un_all[(size_t)f * cap + i].angle;
-      bool loc = false;
-      size_t e = 0;
-      const bool is_new = made && made[i];
-      const int n_obs = (is_new || source == 2) ? 0 : kept_point_obs(tb, source, match[i], outl + i, o, &e, &loc);
-      if (is_new) {
-        const size_t k = (size_t)f * cap + i;
-        const uint4* d = (const uint4*)desc_all + k * 2;
-        v = 1;
-        X0 = tb.np_Xw[k * 3]; X1 = tb.np_Xw[k * 3 + 1]; X2 = tb.np_Xw[k * 3 + 2];
-        d0 = d[0]; d1 = d[1];
-        ob = 1;
-        id = tb.np_id[k];
-      } else if (n_obs >= 1) {
-        const double* X = (loc ? tb.lm_Xw : tb.Xw) + e * 3;
-        const uint4* d = (const uint4*)(loc ? tb.lm_desc : tb.mp_desc) + e * 2;
-        v = 1;
-        X0 = X[0]; X1 = X[1]; X2 = X[2];
-        d0 = d[0]; d1 = d[1];
-        ob = n_obs;
-        id = loc ? tb.lm_id[e] : tb.last_id[e];
-      }
-    }
-    const size_t e = o + i;
-    tb.valid2[e] = v;
-    tb.Xw2[e * 3] = X0;
-    tb.Xw2[e * 3 + 1] = X1;
-    tb.Xw2[e * 3 + 2] = X2;
-    ((uint4*)tb.mp_desc2)[e * 2] = d0;
-    ((uint4*)tb.mp_desc2)[e * 2 + 1] = d1;
-    tb.octave2[e] = oct;
-    tb.angle2[e] = ang;
-    tb.obs2[e] = ob;
-    tb.last_id2[e] = id;
-  }
-  if (tid == 0) tb.n_last[f] = N;
-  if (tid < 16) tb.Tref[(size_t)f * 16 + tid] = tb.Tcur[(size_t)f * 16 + tid];
-}
-
-// Tracking::NeedNewKeyFrame's RGB-D counts (reference src/Tracking.cc:776-789), which run after "Clean VO matches"
-// (:250-257): over keypoints i < N with 0 < mvDepth[i] < th_depth, nTrackedClose = those whose map point k_advance keeps
-// (kept_point_obs) and nNonTrackedClose = the others.  One workgroup per slot; each wave counts with two ballots per 64
-// keypoints, the four waves' sums meet in LDS.
-__global__ __launch_bounds__(256) void k_close_points(const int32_t* __restrict__ nkp_all, TrackBuffers tb, int source, float th_depth,
-                                                      int32_t* __restrict__ out) {
-  __shared__ int s_n[2][4];
-  const int f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
-  const int M = tb.max_points, cap = tb.kp_cap;
-  const size_t o = (size_t)f * M;
-  const int N = min(nkp_all[f], cap);
-  const float* depth = tb.depth + (size_t)f * cap;
-  const int32_t* match = (source == 0 ? tb.cur_match : tb.un_match) + (size_t)f * cap;
-  const uint8_t* outl = tb.po_outlier + (size_t)f * cap;
-  int tracked = 0, other = 0;
-  for (int base = 0; base < N; base += 256) {   // trip count uniform over the workgroup: the ballots see every lane
-    const int i = base + tid;
-    bool close = false, kept = false;
-    if (i < N) {
-      const float d = depth[i];
-      close = d > 0 && d < th_depth;
-      bool loc;
-      size_t e;
-      if (close) kept = kept_point_obs(tb, source, match[i], outl + i, o, &e, &loc) >= 1;
-    }
-    const unsigned long long bc = __ballot(close), bk = __ballot(kept);
-    tracked += __popcll(bk);
-    other += __popcll(bc & ~bk);
-  }
-  if ((tid & 63) == 0) {
-    s_n[0][wave] = tracked;
-    s_n[1][wave] = other;
-  }
-  __syncthreads();
-  if (tid < 2) out[(size_t)f * 2 + tid] = s_n[tid][0] + s_n[tid][1] + s_n[tid][2] + s_n[tid][3];
-}
-
-// sd_track_set_prior: Tprior = Tcur = T (relative 0) or T * Tref (relative 1: ConstantVelocity::GetPose, Exp(vel) * last_pose_),
-// column-major; each entry sums k = 0..3 in order with explicit roundings (no FMA contraction), as a plain host loop does.
-__global__ void k_set_prior(const double* __restrict__ Tin, TrackBuffers tb, int frame0, int n, int relative) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n * 16) return;
-  const int f = frame0 + t / 16, e = t % 16, c = e / 4, r = e % 4;
-  const double* T = Tin + (size_t)(t / 16) * 16;
-  double v = T[e];
-  if (relative) v = pose_product_entry(T, tb.Tref + (size_t)f * 16, r, c);
-  tb.Tprior[(size_t)f * 16 + e] = v;
-  tb.Tcur[(size_t)f * 16 + e] = v;
 }
 
 template <typename T>
@@ -405,18 +208,6 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
     if (e0 == hipSuccess) e0 = hipMemset(tb.last_id, 0xFF, (size_t)B * M * 4);
     if (e0 == hipSuccess) e0 = hipMemset(tb.last_id2, 0xFF, (size_t)B * M * 4);
     if (e0 == hipSuccess) e0 = hipMemset(tb.lm_id, 0xFF, (size_t)B * M * 4);
-    // motion model: not started, X = 0, P = diag(COV_V_2 x3, COV_W_2 x3) (ConstantVelocity::Init; both 0.000625)
-    std::vector<double> p0((size_t)B * 6, 0.000625);
-    if (e0 == hipSuccess) e0 = hipMemcpy(tb.mo_P, p0.data(), p0.size() * 8, hipMemcpyHostToDevice);
-    // IMU sensor model: not started, X = (0, q = 1 0 0 0, 0, 0, 0), P = diag(COV_X_2 x3, COV_Q_2 x4, COV_V_2 x3, COV_W_2 x3,
-    // COV_A_2 x3) (IMU::Init), gravity_ = 0
-    std::vector<double> ix((size_t)B * 16, 0.0), ip((size_t)B * 256, 0.0);
-    for (size_t f = 0; f < (size_t)B; f++) {
-      ix[f * 16 + 3] = 1.0;
-      for (int i = 0; i < 16; i++) ip[f * 256 + i * 17] = i < 3 ? 0.0025 : (i < 7 ? 0.00001 : 0.000625);
-    }
-    if (e0 == hipSuccess) e0 = hipMemcpy(tb.im_X, ix.data(), ix.size() * 8, hipMemcpyHostToDevice);
-    if (e0 == hipSuccess) e0 = hipMemcpy(tb.im_P, ip.data(), ip.size() * 8, hipMemcpyHostToDevice);
     h->meas_set.assign((size_t)B, 0);
     if (e0 != hipSuccess) { set_error(std::string("sd_track_create: ") + hipGetErrorString(e0)); rc = SD_ERR_HIP; }
   }
@@ -448,12 +239,8 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
     }
     for (int r = 0; r < sd_track::kRing && e == hipSuccess; r++)
       for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipEventCreate(&h->ev[r][i]);
-    for (int r = 0; r < sd_track::kPriorRing && e == hipSuccess; r++) {
-      e = hipHostMalloc((void**)&h->prior_host[r], B * 16 * sizeof(double), hipHostMallocDefault);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_prior[r], hipEventDisableTiming);
-      if (e == hipSuccess) e = hipHostMalloc((void**)&h->small_host[r], B * 8 * sizeof(int32_t), hipHostMallocDefault);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_small[r], hipEventDisableTiming);
-    }
+    if (e == hipSuccess) e = h->pose_ring.create(B * 16 * sizeof(double));
+    if (e == hipSuccess) e = h->small_ring.create(B * 8 * sizeof(int32_t));
     if (e == hipSuccess) {
       // Priority of the tracking stream.  Round 1 (extraction kernels at 6-7 waves per SIMD): lowest was best (122.3 k vs
       // 119.2 k frames/s at highest) -- the few, long-running, latency-bound tracking workgroups filled what the extraction
@@ -471,6 +258,11 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
       set_error(std::string("sd_track_create: ") + hipGetErrorString(e));
       rc = SD_ERR_HIP;
     }
+    // both motion models as their constructors leave them (ConstantVelocity::Init, IMU::Init on a zeroed P).  These kernels
+    // must stay behind the blocking hipMemcpy calls above, which drain the null stream of dalloc's hipMemset (the tracking
+    // stream does not wait for it); every reader of the filters runs on the tracking stream or waits for it (TRACK_RANGE)
+    if (rc == SD_OK) rc = launch_motion_init(tb, 0, max_batch, h->pnp_stream);
+    if (rc == SD_OK) rc = launch_imu_init(tb, 0, max_batch, /*full*/ 1, h->pnp_stream);
     if (rc == SD_OK) rc = orb_enable_double_buffer(cur);
   }
   if (rc != SD_OK) {
@@ -489,12 +281,8 @@ void sd_track_destroy(sd_track* h) {
   if (h->pnp_stream) (void)hipStreamDestroy(h->pnp_stream);
   for (void* p : h->allocs) (void)hipFree(p);
   if (h->ev_fence) (void)hipEventDestroy(h->ev_fence);
-  for (int r = 0; r < sd_track::kPriorRing; r++) {
-    if (h->prior_host[r]) (void)hipHostFree(h->prior_host[r]);
-    if (h->ev_prior[r]) (void)hipEventDestroy(h->ev_prior[r]);
-    if (h->small_host[r]) (void)hipHostFree(h->small_host[r]);
-    if (h->ev_small[r]) (void)hipEventDestroy(h->ev_small[r]);
-  }
+  h->pose_ring.destroy();
+  h->small_ring.destroy();
   for (int r = 0; r < sd_track::kRing; r++)
     for (int i = 0; i < 6; i++)
       if (h->ev[r][i]) (void)hipEventDestroy(h->ev[r][i]);
@@ -514,12 +302,6 @@ int sd_track_set_camera(sd_track* h, float fx, float fy, float cx, float cy, flo
   h->have_cam = true;
   return SD_OK;
 }
-
-#define TRACK_RANGE(h, frame0, n)                                                                        \
-  SD_REQUIRE((h), SD_ERR_INVALID_ARG, "handle is NULL");                                                 \
-  SD_REQUIRE((frame0) >= 0 && (n) >= 1 && (frame0) + (n) <= (h)->max_batch, SD_ERR_CAPACITY, "frame range exceeds max_batch"); \
-  SD_HIP_CHECK(hipSetDevice((h)->device));                                                               \
-  SD_HIP_CHECK(hipStreamSynchronize((h)->pnp_stream))
 
 int sd_track_set_last(sd_track* h, int frame0, int n_frames, const int32_t* n_last, const uint8_t* valid, const double* Xw,
                       const uint8_t* desc, const int32_t* octave, const float* angle, const int32_t* obs) {
@@ -566,59 +348,6 @@ int sd_track_set_rand(sd_track* h, int frame0, int n_frames, const int32_t* rand
                                 (size_t)per_frame * 4, (size_t)per_frame * 4, n_frames, hipMemcpyHostToDevice, h->cur->stream));
   SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
   for (int f = 0; f < n_frames; f++) h->rand_len[(size_t)frame0 + f] = per_frame;
-  return SD_OK;
-}
-
-// Order the tracking stream behind the extractions it consumes ...
-static int wait_inputs(sd_track* h, bool need_ref, bool pyramid_only = false) {
-  // ImageAlign reads pyramids only: it may start as soon as the current batch's pyramid exists, beside FAST / selection /
-  // descriptors of the same batch (option "track.align_start" = 0 restores the wait for the whole extraction)
-  const int align_start = opt(OPT_ALIGN_START);
-  const bool early = align_start != 0;
-  // ... but not beside FAST: k_align holds 30 KB of LDS per frame (4 frames per CU), FAST wants 24-39 KB per workgroup, while
-  // selection + descriptors, which follow FAST, use next to none.  Waiting for the end of the batch's FAST launches instead of
-  // its pyramid: full step 175.2 -> 178.8 k frames/s (three alternating runs; k_align 1.38 -> 0.84 ms in the pipeline).
-  // "track.align_start" = 1: wait for the pyramid only; 2 (default): for the FAST launches.
-  const bool after_fast = align_start == 2;
-  if (h->cur->extract_recorded) {
-    hipEvent_t ev = h->cur->ev_extract_done;
-    if (pyramid_only && early && h->cur->pyr_event_live) ev = after_fast ? h->cur->ev_fast_done : h->cur->ev_pyr_done;
-    SD_HIP_CHECK(hipStreamWaitEvent(h->pnp_stream, ev, 0));
-  }
-  if (need_ref && h->ref->extract_recorded) SD_HIP_CHECK(hipStreamWaitEvent(h->pnp_stream, h->ref->ev_extract_done, 0));
-  return SD_OK;
-}
-// ... and tell the extractors which output sets the kernel just queued is reading.
-static int mark_reads(sd_track* h, bool used_ref) {
-  sd_orb* c = h->cur;
-  SD_HIP_CHECK(hipEventRecord(c->ev_set_free[c->set], h->pnp_stream));
-  c->set_busy[c->set] = true;
-  if (used_ref && h->ref != h->cur) {
-    sd_orb* r = h->ref;
-    SD_HIP_CHECK(hipEventRecord(r->ev_set_free[r->set], h->pnp_stream));
-    r->set_busy[r->set] = true;
-  }
-  return SD_OK;
-}
-
-// sequential tracking: which whole-function call last ran on the current extraction of `cur` (sd_track_advance's source)
-static void note_run(sd_track* h, int which, int n_frames) {
-  h->ran_cur[which] = h->cur;
-  h->ran_serial[which] = h->cur->extract_serial;
-  h->ran_n[which] = n_frames;
-}
-static bool ran_since_extract(const sd_track* h, int which, int n_frames) {
-  return h->ran_cur[which] == h->cur && h->ran_serial[which] == h->cur->extract_serial && n_frames <= h->ran_n[which];
-}
-
-// per_cur_frame: the call walks the frames of `cur` themselves (not tracker slots), so the broadcast does not apply
-static int check_ready(sd_track* h, int n_frames, bool per_cur_frame = false) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_REQUIRE(h->have_cam, SD_ERR_INVALID_ARG, "sd_track_set_camera has not been called");
-  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
-  const int need = (h->tb.cur_bcast >= 0 && !per_cur_frame) ? h->tb.cur_bcast + 1 : n_frames;
-  SD_REQUIRE(h->cur->have_geom && h->cur->last_frames >= need, SD_ERR_INVALID_ARG, "current frames have not been extracted");
-  SD_HIP_CHECK(hipSetDevice(h->device));
   return SD_OK;
 }
 
@@ -831,7 +560,7 @@ int sd_track_with_motion_model(sd_track* h, int n_frames, int align_mode, float 
   rc = launch_pose_opt(h->cur, tb, h->cam, h->d_inv_sigma2, 0, n_frames, s, min_matches, min_inliers);
   if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev2[5], s)); h->ev_calls[2]++; }
   if (rc == SD_OK) rc = mark_reads(h, false);
-  if (rc == SD_OK) note_run(h, 0, n_frames);
+  if (rc == SD_OK) h->ran[0].set(h, n_frames);
   return rc;
 }
 
@@ -852,7 +581,7 @@ int sd_track_local_map(sd_track* h, int n_frames, float th, float nnratio, float
   hipEvent_t* ev2 = h->ev[h->ev_calls[2] % sd_track::kRing];
   if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev1[2], s));
   // seen-point exclusion: ids given, and tw_seen holds this extraction's TrackWithMotionModel result for these slots
-  const int exclude = h->ids_on && ran_since_extract(h, 0, n_frames) ? 1 : 0;
+  const int exclude = h->ids_on && h->ran[0].covers(h, n_frames) ? 1 : 0;
   rc = launch_match_local(h->cur, h->tb, h->cam, h->d_sf, h->d_scale_thr, h->cur->nlevels, n_frames, th, nnratio, viewing_cos_limit, s, 1, 0,
                           exclude);
   if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev1[3], s)); h->ev_calls[1]++; }
@@ -861,7 +590,7 @@ int sd_track_local_map(sd_track* h, int n_frames, float th, float nnratio, float
   rc = launch_pose_opt(h->cur, h->tb, h->cam, h->d_inv_sigma2, 2, n_frames, s, 0, min_inliers);
   if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev2[5], s)); h->ev_calls[2]++; }
   if (rc == SD_OK) rc = mark_reads(h, false);
-  if (rc == SD_OK) note_run(h, 1, n_frames);
+  if (rc == SD_OK) h->ran[1].set(h, n_frames);
   return rc;
 }
 
@@ -1324,404 +1053,6 @@ int sd_track_stream_fence(sd_track* h, void* hip_stream, int direction) {
     SD_HIP_CHECK(hipEventRecord(h->ev_fence, ext));
     SD_HIP_CHECK(hipStreamWaitEvent(h->pnp_stream, h->ev_fence, 0));
   }
-  return SD_OK;
-}
-
-// ---- sequential tracking: the last-frame hand-off on the device (Tracking::Track, src/Tracking.cc:250-292)
-
-int sd_track_set_map_ids(sd_track* h, int frame0, int n_frames, int which, const int32_t* ids, int cap) {
-  TRACK_RANGE(h, frame0, n_frames);
-  SD_REQUIRE(which == 0 || which == 1, SD_ERR_INVALID_ARG, "which must be 0 (last-frame points) or 1 (local map points)");
-  SD_REQUIRE(ids && cap >= 1 && cap <= h->max_points, SD_ERR_INVALID_ARG, "bad id array (cap must be 1..max_points)");
-  const size_t M = h->max_points;
-  int32_t* dst = (which == 0 ? h->tb.last_id : h->tb.lm_id) + (size_t)frame0 * M;
-  hipStream_t s = h->cur->stream;
-  SD_HIP_CHECK(hipMemsetAsync(dst, 0xFF, (size_t)n_frames * M * 4, s));
-  SD_HIP_CHECK(hipMemcpy2DAsync(dst, M * 4, ids, (size_t)cap * 4, (size_t)cap * 4, n_frames, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  h->ids_on = true;
-  return SD_OK;
-}
-
-int sd_track_advance(sd_track* h, int n_frames, int source) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
-  SD_REQUIRE(source >= 0 && source <= 2, SD_ERR_INVALID_ARG,
-             "source must be 0 (sd_track_with_motion_model), 1 (sd_track_local_map) or 2 (sd_track_stereo_init)");
-  SD_REQUIRE(h->kp_cap <= h->max_points, SD_ERR_CAPACITY, "the keypoint capacity exceeds max_points: a last frame would not fit");
-  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
-  // a creation call on this extraction: its points go with the keypoints that received them
-  const bool made = h->made_cur == h->cur && h->made_serial == h->cur->extract_serial;
-  if (source == 2) {
-    SD_REQUIRE(made && h->made_mode == 2 && n_frames <= h->made_n, SD_ERR_INVALID_ARG,
-               "sd_track_stereo_init has not run on these slots since the last extraction");
-  } else {
-    SD_REQUIRE(ran_since_extract(h, source, n_frames), SD_ERR_INVALID_ARG,
-               source == 0 ? "sd_track_with_motion_model has not run on these slots since the last extraction"
-                           : "sd_track_local_map has not run on these slots since the last extraction");
-    SD_REQUIRE(!made || (h->made_mode == 1 && h->made_source == source), SD_ERR_INVALID_ARG,
-               "map points were created on this extraction from another source (sd_track_stereo_init: advance with source 2)");
-  }
-  const int created_n = made ? h->made_n : 0;
-  int nsel_ref = 0;
-  for (int q : h->ref->hp.quota) nsel_ref += q;
-  SD_REQUIRE(nsel_ref == h->kp_cap && h->cur->max_batch >= h->max_batch, SD_ERR_INVALID_ARG,
-             "cur / ref extractors must share the keypoint capacity and hold max_batch frames to swap roles");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  // the new `cur` is extracted into next while tracking kernels may still read its last output set: it needs two
-  int rc = orb_enable_double_buffer(h->ref);
-  if (rc != SD_OK) return rc;
-  hipStream_t s = h->pnp_stream;
-  rc = wait_inputs(h, false);
-  if (rc != SD_OK) return rc;
-  const sd_orb* c = h->cur;
-  hipLaunchKernelGGL(k_advance, dim3(h->max_batch), dim3(256), 0, s, c->d_kps, c->have_dist ? c->d_kps_un : c->d_kps, c->d_nout, h->tb, source,
-                     n_frames, c->d_desc, created_n);
-  SD_HIP_CHECK(hipGetLastError());
-  rc = mark_reads(h, false);
-  if (rc != SD_OK) return rc;
-  TrackBuffers& tb = h->tb;   // launches queued from now on see the new last frame
-  std::swap(tb.valid, tb.valid2);
-  std::swap(tb.Xw, tb.Xw2);
-  std::swap(tb.mp_desc, tb.mp_desc2);
-  std::swap(tb.octave, tb.octave2);
-  std::swap(tb.angle, tb.angle2);
-  std::swap(tb.obs, tb.obs2);
-  std::swap(tb.last_id, tb.last_id2);
-  std::swap(h->cur, h->ref);   // this frame's pyramid and keypoints are the next ImageAlign / match reference
-  h->have_pnp = false;
-  h->ran_cur[0] = h->ran_cur[1] = nullptr;
-  h->made_cur = h->close_cur = nullptr;
-  return SD_OK;
-}
-
-int sd_track_close_points(sd_track* h, int n_frames, int source, float th_depth) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
-  SD_REQUIRE(source == 0 || source == 1, SD_ERR_INVALID_ARG, "source must be 0 (sd_track_with_motion_model) or 1 (sd_track_local_map)");
-  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
-  // (a call that ran in broadcast mode may have covered more slots than `cur` holds frames: its keypoint counts end there)
-  SD_REQUIRE(ran_since_extract(h, source, n_frames) && h->cur->last_frames >= n_frames, SD_ERR_INVALID_ARG,
-             source == 0 ? "sd_track_with_motion_model has not run on these slots since the last extraction"
-                         : "sd_track_local_map has not run on these slots since the last extraction");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  hipStream_t s = h->pnp_stream;
-  int rc = wait_inputs(h, false);
-  if (rc != SD_OK) return rc;
-  hipLaunchKernelGGL(k_close_points, dim3(n_frames), dim3(256), 0, s, h->cur->d_nout, h->tb, source, th_depth, h->d_close);
-  SD_HIP_CHECK(hipGetLastError());
-  h->close_cur = h->cur;
-  h->close_serial = h->cur->extract_serial;
-  h->close_n = n_frames;
-  h->close_source = source;
-  return mark_reads(h, false);
-}
-
-int sd_track_get_close_points(sd_track* h, int frame0, int n_frames, int32_t* out2) {
-  TRACK_RANGE(h, frame0, n_frames);
-  SD_REQUIRE(out2, SD_ERR_INVALID_ARG, "NULL argument");
-  SD_HIP_CHECK(hipMemcpyAsync(out2, h->d_close + (size_t)frame0 * 2, (size_t)n_frames * 8, hipMemcpyDeviceToHost, h->cur->stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
-  return SD_OK;
-}
-
-// ---- RGB-D map point creation and the keyframe decision on the device (kernels: track_newpoints.hip)
-
-// `bytes` (at most max_batch x 32, a ring buffer's size) from the host into `dst` on the tracking stream, through the pinned
-// ring: no host wait unless the ring slot's copy of kPriorRing calls ago is still pending
-static int small_upload(sd_track* h, void* dst, const void* src, size_t bytes) {
-  SD_REQUIRE(bytes <= (size_t)h->max_batch * 8 * sizeof(int32_t), SD_ERR_CAPACITY, "upload exceeds the pinned ring buffer");
-  const int r = h->small_next;
-  h->small_next = (r + 1) % sd_track::kPriorRing;
-  if (h->small_pending[r]) SD_HIP_CHECK(hipEventSynchronize(h->ev_small[r]));
-  std::memcpy(h->small_host[r], src, bytes);
-  SD_HIP_CHECK(hipMemcpyAsync(dst, h->small_host[r], bytes, hipMemcpyHostToDevice, h->pnp_stream));
-  SD_HIP_CHECK(hipEventRecord(h->ev_small[r], h->pnp_stream));
-  h->small_pending[r] = true;
-  return SD_OK;
-}
-
-#define SMALL_RANGE(h, frame0, n, p)                                                                                         \
-  SD_REQUIRE((h) && (p), SD_ERR_INVALID_ARG, "NULL argument");                                                             \
-  SD_REQUIRE((frame0) >= 0 && (n) >= 1 && (frame0) + (n) <= (h)->max_batch, SD_ERR_CAPACITY, "frame range exceeds max_batch"); \
-  SD_HIP_CHECK(hipSetDevice((h)->device))
-
-int sd_track_set_next_map_id(sd_track* h, int frame0, int n_frames, const int32_t* next_id) {
-  SMALL_RANGE(h, frame0, n_frames, next_id);
-  return small_upload(h, h->tb.next_id + frame0, next_id, (size_t)n_frames * 4);
-}
-
-int sd_track_set_keyframe_state(sd_track* h, int frame0, int n_frames, const int32_t* state8) {
-  SMALL_RANGE(h, frame0, n_frames, state8);
-  int rc = small_upload(h, h->d_kf_stage, state8, (size_t)n_frames * 32);
-  if (rc != SD_OK) return rc;
-  return launch_set_keyframe_state(h->tb, h->d_kf_stage, frame0, n_frames, h->pnp_stream);
-}
-
-int sd_track_set_keyframe_flags(sd_track* h, int frame0, int n_frames, const uint8_t* flags) {
-  SMALL_RANGE(h, frame0, n_frames, flags);
-  return small_upload(h, h->tb.kf_flags + frame0, flags, (size_t)n_frames);
-}
-
-int sd_track_get_keyframe_flags(sd_track* h, int frame0, int n_frames, uint8_t* flags) {
-  TRACK_RANGE(h, frame0, n_frames);
-  SD_REQUIRE(flags, SD_ERR_INVALID_ARG, "NULL argument");
-  SD_HIP_CHECK(hipMemcpyAsync(flags, h->tb.kf_flags + frame0, (size_t)n_frames, hipMemcpyDeviceToHost, h->cur->stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
-  return SD_OK;
-}
-
-int sd_track_need_keyframe(sd_track* h, int n_frames, int rgbd, int frame_id, int min_frames, int max_frames) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
-  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
-  SD_REQUIRE(ran_since_extract(h, 1, n_frames), SD_ERR_INVALID_ARG,
-             "sd_track_local_map has not run on these slots since the last extraction");
-  SD_REQUIRE(!rgbd || (h->close_cur == h->cur && h->close_serial == h->cur->extract_serial && n_frames <= h->close_n && h->close_source == 1),
-             SD_ERR_INVALID_ARG, "sd_track_close_points (source 1) has not run on these slots since the last extraction");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  return launch_need_keyframe(h->tb, h->d_close, n_frames, rgbd != 0, frame_id, min_frames, max_frames, h->pnp_stream);
-}
-
-static int new_points(sd_track* h, int n_frames, int mode, int source, float th_depth, int use_flags, int frame_id, int min_keypoints) {
-  hipStream_t s = h->pnp_stream;
-  int rc = wait_inputs(h, false);
-  if (rc != SD_OK) return rc;
-  // Frame::invfx = 1.0f / fx (src/Frame.cc:90), rounded on the host
-  rc = launch_new_points(h->cur, h->tb, h->cam, 1.0f / h->cam.ffx, 1.0f / h->cam.ffy, n_frames, mode, source, th_depth, use_flags, frame_id,
-                         min_keypoints, s);
-  if (rc != SD_OK) return rc;
-  h->made_cur = h->cur;
-  h->made_serial = h->cur->extract_serial;
-  h->made_n = n_frames;
-  h->made_mode = mode;
-  h->made_source = source;
-  return mark_reads(h, false);
-}
-
-int sd_track_stereo_init(sd_track* h, int n_frames, int min_keypoints) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
-  SD_REQUIRE(h->have_cam, SD_ERR_INVALID_ARG, "sd_track_set_camera has not been called");
-  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
-  SD_REQUIRE(h->cur->have_geom && h->cur->last_frames >= n_frames, SD_ERR_INVALID_ARG, "current frames have not been extracted");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  h->have_pnp = false;
-  return new_points(h, n_frames, 2, 0, 0.f, 0, 0, min_keypoints);
-}
-
-int sd_track_create_keyframe_points(sd_track* h, int n_frames, int source, float th_depth, int use_flags, int frame_id) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
-  SD_REQUIRE(source == 0 || source == 1, SD_ERR_INVALID_ARG, "source must be 0 (sd_track_with_motion_model) or 1 (sd_track_local_map)");
-  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
-  SD_REQUIRE(ran_since_extract(h, source, n_frames) && h->cur->last_frames >= n_frames, SD_ERR_INVALID_ARG,
-             source == 0 ? "sd_track_with_motion_model has not run on these slots since the last extraction"
-                         : "sd_track_local_map has not run on these slots since the last extraction");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  return new_points(h, n_frames, 1, source, th_depth, use_flags != 0, frame_id, 0);
-}
-
-int sd_track_get_created(sd_track* h, int frame0, int n_frames, int32_t* info4, int32_t* kp_index, double* Xw, int32_t* ids, int cap) {
-  TRACK_RANGE(h, frame0, n_frames);
-  SD_REQUIRE(info4 && cap >= 0, SD_ERR_INVALID_ARG, "bad arguments");
-  const size_t K = h->kp_cap, n = n_frames, o = frame0;
-  const TrackBuffers& tb = h->tb;
-  hipStream_t s = h->cur->stream;
-  std::vector<int32_t> list(n * K), id(n * K);
-  std::vector<double> X(n * K * 3);
-  SD_HIP_CHECK(hipMemcpyAsync(info4, tb.np_info + o * 4, n * 16, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipMemcpyAsync(list.data(), tb.np_list + o * K, n * K * 4, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipMemcpyAsync(id.data(), tb.np_id + o * K, n * K * 4, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipMemcpyAsync(X.data(), tb.np_Xw + o * K * 3, n * K * 24, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  for (size_t f = 0; f < n; f++) SD_REQUIRE(info4[f * 4 + 1] <= cap, SD_ERR_CAPACITY, "cap is smaller than a slot's number of created points");
-  for (size_t f = 0; f < n; f++)
-    for (int r = 0; r < info4[f * 4 + 1]; r++) {   // creation order
-      const size_t i = (size_t)list[f * K + r], d = f * (size_t)cap + r;
-      if (kp_index) kp_index[d] = (int32_t)i;
-      if (ids) ids[d] = id[f * K + i];
-      if (Xw) std::memcpy(Xw + d * 3, &X[(f * K + i) * 3], 24);
-    }
-  return SD_OK;
-}
-
-int sd_track_set_prior(sd_track* h, int frame0, int n_frames, const double* T_cm, int relative) {
-  SD_REQUIRE(h && T_cm, SD_ERR_INVALID_ARG, "NULL argument");
-  SD_REQUIRE(frame0 >= 0 && n_frames >= 1 && frame0 + n_frames <= h->max_batch, SD_ERR_CAPACITY, "frame range exceeds max_batch");
-  SD_REQUIRE(relative == 0 || relative == 1, SD_ERR_INVALID_ARG, "relative must be 0 or 1");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  const int r = h->prior_next;
-  h->prior_next = (r + 1) % sd_track::kPriorRing;
-  if (h->prior_pending[r]) SD_HIP_CHECK(hipEventSynchronize(h->ev_prior[r]));   // its copy of kPriorRing calls ago has run
-  std::memcpy(h->prior_host[r], T_cm, (size_t)n_frames * 128);
-  hipStream_t s = h->pnp_stream;
-  SD_HIP_CHECK(hipMemcpyAsync(h->d_prior, h->prior_host[r], (size_t)n_frames * 128, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipEventRecord(h->ev_prior[r], s));
-  h->prior_pending[r] = true;
-  hipLaunchKernelGGL(k_set_prior, dim3((n_frames * 16 + 255) / 256), dim3(256), 0, s, h->d_prior, h->tb, frame0, n_frames, relative);
-  SD_HIP_CHECK(hipGetLastError());
-  return SD_OK;
-}
-
-// ---- motion model on the device (kernels: track_motion.hip)
-
-int sd_track_motion_predict(sd_track* h, int n_frames, double dt) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
-  SD_REQUIRE(std::isfinite(dt) && dt >= 0.0, SD_ERR_INVALID_ARG, "dt must be finite and not negative");
-  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  if (h->sensor_model == SD_SENSOR_IMU) return launch_imu_predict(h->tb, n_frames, dt, h->pnp_stream);
-  return launch_motion_predict(h->tb, n_frames, dt, h->pnp_stream);
-}
-
-int sd_track_motion_update(sd_track* h, int n_frames, int source) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
-  SD_REQUIRE(source >= -1 && source <= 1, SD_ERR_INVALID_ARG,
-             "source must be -1 (every slot tracked), 0 (sd_track_with_motion_model) or 1 (sd_track_local_map)");
-  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
-  SD_REQUIRE(source < 0 || ran_since_extract(h, source, n_frames), SD_ERR_INVALID_ARG,
-             source == 0 ? "sd_track_with_motion_model has not run on these slots since the last extraction"
-                         : "sd_track_local_map has not run on these slots since the last extraction");
-  if (h->sensor_model == SD_SENSOR_IMU)   // the reference asserts on the size of measurements_ (IMU::Z)
-    for (int f = 0; f < n_frames; f++)
-      SD_REQUIRE(h->meas_set[f], SD_ERR_INVALID_ARG, "sd_track_set_measurements has not covered these slots since the IMU model was chosen");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  if (h->sensor_model == SD_SENSOR_IMU) return launch_imu_update(h->tb, n_frames, source, h->pnp_stream);
-  return launch_motion_update(h->tb, n_frames, source, h->pnp_stream);
-}
-
-int sd_track_motion_restart(sd_track* h, int frame0, int n_frames) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_REQUIRE(frame0 >= 0 && n_frames >= 1 && frame0 + n_frames <= h->max_batch, SD_ERR_CAPACITY, "frame range exceeds max_batch");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  if (h->sensor_model == SD_SENSOR_IMU) return launch_imu_init(h->tb, frame0, n_frames, 0, h->pnp_stream);
-  return launch_motion_init(h->tb, frame0, n_frames, h->pnp_stream);
-}
-
-int sd_track_get_motion(sd_track* h, int frame0, int n_frames, double* X6, double* Pdiag6, int32_t* started, double* it_time,
-                        double* E_cm, double* last_pose_cm) {
-  SD_REQUIRE(!h || h->sensor_model == SD_SENSOR_CONSTANT_VELOCITY, SD_ERR_INVALID_ARG, "the IMU sensor model is selected: sd_track_get_imu");
-  TRACK_RANGE(h, frame0, n_frames);
-  hipStream_t s = h->cur->stream;
-  const TrackBuffers& tb = h->tb;
-  const size_t o = frame0, n = n_frames;
-  if (X6) SD_HIP_CHECK(hipMemcpyAsync(X6, tb.mo_X + o * 6, n * 48, hipMemcpyDeviceToHost, s));
-  if (Pdiag6) SD_HIP_CHECK(hipMemcpyAsync(Pdiag6, tb.mo_P + o * 6, n * 48, hipMemcpyDeviceToHost, s));
-  if (started) SD_HIP_CHECK(hipMemcpyAsync(started, tb.mo_started + o, n * 4, hipMemcpyDeviceToHost, s));
-  if (it_time) SD_HIP_CHECK(hipMemcpyAsync(it_time, tb.mo_it + o, n * 8, hipMemcpyDeviceToHost, s));
-  if (E_cm) SD_HIP_CHECK(hipMemcpyAsync(E_cm, tb.mo_E + o * 16, n * 128, hipMemcpyDeviceToHost, s));
-  if (last_pose_cm) SD_HIP_CHECK(hipMemcpyAsync(last_pose_cm, tb.mo_last + o * 16, n * 128, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
-}
-
-int sd_track_set_motion(sd_track* h, int frame0, int n_frames, const double* X6, const double* Pdiag6, const int32_t* started,
-                        const double* it_time) {
-  SD_REQUIRE(!h || h->sensor_model == SD_SENSOR_CONSTANT_VELOCITY, SD_ERR_INVALID_ARG, "the IMU sensor model is selected: sd_track_set_imu");
-  TRACK_RANGE(h, frame0, n_frames);
-  hipStream_t s = h->cur->stream;
-  const TrackBuffers& tb = h->tb;
-  const size_t o = frame0, n = n_frames;
-  if (X6) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_X + o * 6, X6, n * 48, hipMemcpyHostToDevice, s));
-  if (Pdiag6) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_P + o * 6, Pdiag6, n * 48, hipMemcpyHostToDevice, s));
-  if (started) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_started + o, started, n * 4, hipMemcpyHostToDevice, s));
-  if (it_time) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_it + o, it_time, n * 8, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
-}
-
-// ---- the IMU sensor model (kernels: track_imu.hip)
-
-int sd_track_set_sensor_model(sd_track* h, int model) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_REQUIRE(model == SD_SENSOR_CONSTANT_VELOCITY || model == SD_SENSOR_IMU, SD_ERR_INVALID_ARG,
-             "model must be SD_SENSOR_CONSTANT_VELOCITY or SD_SENSOR_IMU");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  // a new Tracking constructs its EKF: every slot's filter of the chosen model restarts
-  int rc = model == SD_SENSOR_IMU ? launch_imu_init(h->tb, 0, h->max_batch, 1, h->pnp_stream)
-                                  : launch_motion_init(h->tb, 0, h->max_batch, h->pnp_stream);
-  if (rc != SD_OK) return rc;
-  h->sensor_model = model;
-  h->meas_set.assign((size_t)h->max_batch, 0);
-  return SD_OK;
-}
-
-int sd_track_get_sensor_model(sd_track* h, int* model) {
-  SD_REQUIRE(h && model, SD_ERR_INVALID_ARG, "NULL argument");
-  *model = h->sensor_model;
-  return SD_OK;
-}
-
-// Tracking::SetMeasurements for slots frame0 .. frame0 + n_frames - 1, through the pinned ring of sd_track_set_prior
-int sd_track_set_measurements(sd_track* h, int frame0, int n_frames, const double* wa6) {
-  SD_REQUIRE(h && wa6, SD_ERR_INVALID_ARG, "NULL argument");
-  SD_REQUIRE(frame0 >= 0 && n_frames >= 1 && frame0 + n_frames <= h->max_batch, SD_ERR_CAPACITY, "frame range exceeds max_batch");
-  SD_REQUIRE(h->sensor_model == SD_SENSOR_IMU, SD_ERR_INVALID_ARG, "the constant-velocity model takes no measurements (sd_track_set_sensor_model)");
-  for (size_t i = 0; i < (size_t)n_frames * 6; i++) SD_REQUIRE(std::isfinite(wa6[i]), SD_ERR_INVALID_ARG, "measurements must be finite");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  const int r = h->prior_next;
-  h->prior_next = (r + 1) % sd_track::kPriorRing;
-  if (h->prior_pending[r]) SD_HIP_CHECK(hipEventSynchronize(h->ev_prior[r]));   // its copy of kPriorRing calls ago has run
-  std::memcpy(h->prior_host[r], wa6, (size_t)n_frames * 48);
-  hipStream_t s = h->pnp_stream;
-  SD_HIP_CHECK(hipMemcpyAsync(h->tb.im_meas + (size_t)frame0 * 6, h->prior_host[r], (size_t)n_frames * 48, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipEventRecord(h->ev_prior[r], s));
-  h->prior_pending[r] = true;
-  for (int f = frame0; f < frame0 + n_frames; f++) h->meas_set[f] = 1;
-  return SD_OK;
-}
-
-int sd_track_get_imu(sd_track* h, int frame0, int n_frames, double* X16, double* P256, double* gravity3, int32_t* started, double* it_time,
-                     double* last_pose_cm, double* measurements6) {
-  TRACK_RANGE(h, frame0, n_frames);
-  hipStream_t s = h->cur->stream;
-  const TrackBuffers& tb = h->tb;
-  const size_t o = frame0, n = n_frames;
-  if (X16) SD_HIP_CHECK(hipMemcpyAsync(X16, tb.im_X + o * 16, n * 128, hipMemcpyDeviceToHost, s));
-  if (P256) SD_HIP_CHECK(hipMemcpyAsync(P256, tb.im_P + o * 256, n * 2048, hipMemcpyDeviceToHost, s));
-  if (gravity3) SD_HIP_CHECK(hipMemcpyAsync(gravity3, tb.im_g + o * 3, n * 24, hipMemcpyDeviceToHost, s));
-  if (started) SD_HIP_CHECK(hipMemcpyAsync(started, tb.im_started + o, n * 4, hipMemcpyDeviceToHost, s));
-  if (it_time) SD_HIP_CHECK(hipMemcpyAsync(it_time, tb.im_it + o, n * 8, hipMemcpyDeviceToHost, s));
-  if (last_pose_cm) SD_HIP_CHECK(hipMemcpyAsync(last_pose_cm, tb.im_last + o * 16, n * 128, hipMemcpyDeviceToHost, s));
-  if (measurements6) SD_HIP_CHECK(hipMemcpyAsync(measurements6, tb.im_meas + o * 6, n * 48, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
-}
-
-int sd_track_set_imu(sd_track* h, int frame0, int n_frames, const double* X16, const double* P256, const double* gravity3,
-                     const int32_t* started, const double* it_time) {
-  SD_REQUIRE(!h || h->sensor_model == SD_SENSOR_IMU, SD_ERR_INVALID_ARG, "the constant-velocity model is selected: sd_track_set_motion");
-  TRACK_RANGE(h, frame0, n_frames);
-  hipStream_t s = h->cur->stream;
-  const TrackBuffers& tb = h->tb;
-  const size_t o = frame0, n = n_frames;
-  if (X16) SD_HIP_CHECK(hipMemcpyAsync(tb.im_X + o * 16, X16, n * 128, hipMemcpyHostToDevice, s));
-  if (P256) SD_HIP_CHECK(hipMemcpyAsync(tb.im_P + o * 256, P256, n * 2048, hipMemcpyHostToDevice, s));
-  if (gravity3) SD_HIP_CHECK(hipMemcpyAsync(tb.im_g + o * 3, gravity3, n * 24, hipMemcpyHostToDevice, s));
-  if (started) SD_HIP_CHECK(hipMemcpyAsync(tb.im_started + o, started, n * 4, hipMemcpyHostToDevice, s));
-  if (it_time) SD_HIP_CHECK(hipMemcpyAsync(tb.im_it + o, it_time, n * 8, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
-}
-
-int sd_track_get_last(sd_track* h, int frame0, int n_frames, int32_t* n_last, uint8_t* valid, double* Xw, uint8_t* desc, int32_t* octave,
-                      float* angle, int32_t* obs, int32_t* ids) {
-  TRACK_RANGE(h, frame0, n_frames);
-  hipStream_t s = h->cur->stream;
-  const TrackBuffers& tb = h->tb;
-  const size_t M = h->max_points, o = frame0, n = n_frames;
-  if (n_last) SD_HIP_CHECK(hipMemcpyAsync(n_last, tb.n_last + o, n * 4, hipMemcpyDeviceToHost, s));
-  if (valid) SD_HIP_CHECK(hipMemcpyAsync(valid, tb.valid + o * M, n * M, hipMemcpyDeviceToHost, s));
-  if (Xw) SD_HIP_CHECK(hipMemcpyAsync(Xw, tb.Xw + o * M * 3, n * M * 24, hipMemcpyDeviceToHost, s));
-  if (desc) SD_HIP_CHECK(hipMemcpyAsync(desc, tb.mp_desc + o * M * 32, n * M * 32, hipMemcpyDeviceToHost, s));
-  if (octave) SD_HIP_CHECK(hipMemcpyAsync(octave, tb.octave + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
-  if (angle) SD_HIP_CHECK(hipMemcpyAsync(angle, tb.angle + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
-  if (obs) SD_HIP_CHECK(hipMemcpyAsync(obs, tb.obs + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
-  if (ids) SD_HIP_CHECK(hipMemcpyAsync(ids, tb.last_id + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
   return SD_OK;
 }
 

@@ -1,0 +1,190 @@
+// The sd_track handle and the host helpers its entry points share (track.hip: creation and the batched stages;
+// track_seq.hip: sequential tracking).  Not part of the ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "orb_internal.h"
+#include "track_internal.h"
+
+#define SD_TRY(call) do { const int _rc = (call); if (_rc != SD_OK) return _rc; } while (0)
+
+// Small host arrays on their way into device memory without a host wait: the next of kSlots pinned buffers takes a copy, which
+// goes to the device on the caller's stream, behind whatever that stream has queued.  A buffer is written again once the copy
+// out of it has run (kSlots calls later: only then can the host wait).
+struct UploadRing {
+  static const int kSlots = 4;
+  void* host[kSlots] = {};
+  hipEvent_t ev[kSlots] = {};
+  bool pending[kSlots] = {};
+  int next = 0;
+  size_t slot_bytes = 0;
+
+  hipError_t create(size_t bytes) {
+    slot_bytes = bytes;
+    hipError_t e = hipSuccess;
+    for (int r = 0; r < kSlots && e == hipSuccess; r++) {
+      e = hipHostMalloc(&host[r], bytes, hipHostMallocDefault);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[r], hipEventDisableTiming);
+    }
+    return e;
+  }
+  void destroy() {
+    for (int r = 0; r < kSlots; r++) {
+      if (host[r]) (void)hipHostFree(host[r]);
+      if (ev[r]) (void)hipEventDestroy(ev[r]);
+    }
+  }
+  int upload(void* dst, const void* src, size_t bytes, hipStream_t s) {
+    SD_REQUIRE(bytes <= slot_bytes, SD_ERR_CAPACITY, "upload exceeds the pinned ring buffer");
+    const int r = next;
+    next = (r + 1) % kSlots;
+    if (pending[r]) SD_HIP_CHECK(hipEventSynchronize(ev[r]));   // its copy of kSlots calls ago has run
+    std::memcpy(host[r], src, bytes);
+    SD_HIP_CHECK(hipMemcpyAsync(dst, host[r], bytes, hipMemcpyHostToDevice, s));
+    SD_HIP_CHECK(hipEventRecord(ev[r], s));
+    pending[r] = true;
+    return SD_OK;
+  }
+};
+
+// "This call ran on this extraction of `cur`, for slots < n" (mode / source: what the call was asked for, where a later call
+// has to know).  An extraction of `cur` ends it, and sd_track_advance resets it.
+struct RunStamp {
+  const sd_orb* cur = nullptr;
+  unsigned long long serial = 0;
+  int n = 0, mode = 0, source = -1;
+  inline void set(const sd_track* h, int n_frames, int mode_ = 0, int source_ = -1);
+  inline bool covers(const sd_track* h, int n_frames) const;
+};
+
+struct sd_track {
+  sd_orb* cur = nullptr;
+  sd_orb* ref = nullptr;
+  int max_points = 0, max_batch = 0, kp_cap = 0, device = 0;
+  int rand_per_frame = 0;
+  std::vector<int> rand_len;      // rand() values actually supplied per slot (sd_track_set_rand)
+  bool have_pnp = false;          // sd_track_pnp has constructed the solvers sd_track_pnp_iterate continues ...
+  unsigned long long pnp_serial = 0;   // ... on the keypoints of THIS extraction of `cur` (the reference's solver owns copies of its inputs)
+  sd::PnpParams pnp_params{};
+  int pnp_frames = 0, pnp_iter_upper = 0;   // slots / upper bound of mnIterations of those solvers
+  sd::TrackBuffers tb{};
+  sd::TrackCam cam{};
+  bool have_cam = false;
+  float* d_sf = nullptr;
+  float* d_inv_sf = nullptr;
+  float* d_sigma2 = nullptr;
+  float* d_inv_sigma2 = nullptr;
+  float* d_scale_thr = nullptr;   // MapPoint::PredictScale breakpoints (see k_match_local)
+  std::vector<void*> allocs;
+  // The tracking kernels (align, match, PnP: latency-bound, few waves) run on their own stream, so
+  // the extraction of the next batch on cur->stream overlaps them; `cur` is double-buffered
+  // (orb_internal.h: output sets) and every tracking launch waits for the extraction it consumes
+  // (ev_extract_done) and marks the sets it read (ev_set_free).
+  hipStream_t pnp_stream = nullptr;
+  bool profiling = false;
+  hipEvent_t ev_fence = nullptr;   // sd_track_stream_fence
+  // sequential tracking: what ran on the current extraction of `cur` --
+  RunStamp ran[2];                 // [0] sd_track_with_motion_model, [1] sd_track_local_map (sd_track_advance's source)
+  RunStamp close;                  // sd_track_close_points (sd_track_need_keyframe reads its counts)
+  RunStamp made;                   // point creation (mode 2 sd_track_stereo_init, 1 sd_track_create_keyframe_points): advance hands its np_* on
+  bool ids_on = false;             // sd_track_set_map_ids has been called: sd_track_local_map applies the seen-point exclusion
+  // Both feed the tracking stream, so a setter queues behind the hand-off that wrote Tref without a host wait.  Two, because a
+  // loop step issues several uploads behind the same tracking kernels: one shared ring would make the host wait within a step.
+  UploadRing pose_ring;            // [max_batch][16] double: sd_track_set_prior, sd_track_set_measurements
+  UploadRing small_ring;           // [max_batch][8] int32: sd_track_set_keyframe_state / _flags, sd_track_set_next_map_id
+  double* d_prior = nullptr;       // [max_batch][16]
+  int32_t* d_close = nullptr;      // [max_batch][2] sd_track_close_points: nTrackedClose, nNonTrackedClose
+  int32_t* d_kf_stage = nullptr;   // [max_batch][8]
+  // sd_track_set_sensor_model: which filter sd_track_motion_predict / _update / _restart run (per handle, as per Tracking)
+  int sensor_model = SD_SENSOR_CONSTANT_VELOCITY;
+  std::vector<uint8_t> meas_set;   // [max_batch] sd_track_set_measurements has covered the slot since the model was chosen
+  static const int kRing = 128;
+  hipEvent_t ev[kRing][6] = {};
+  int ev_calls[3] = {0, 0, 0};
+};
+
+inline void RunStamp::set(const sd_track* h, int n_frames, int mode_, int source_) {
+  *this = RunStamp{h->cur, h->cur->extract_serial, n_frames, mode_, source_};
+}
+inline bool RunStamp::covers(const sd_track* h, int n_frames) const {
+  return cur == h->cur && serial == h->cur->extract_serial && n_frames <= n;
+}
+
+// "<the call `source` names> has not run on these slots since the last extraction"; 2: sd_track_stereo_init
+static inline const char* not_run_msg(int source) {
+  return source == 0   ? "sd_track_with_motion_model has not run on these slots since the last extraction"
+         : source == 1 ? "sd_track_local_map has not run on these slots since the last extraction"
+                       : "sd_track_stereo_init has not run on these slots since the last extraction";
+}
+
+// Order the tracking stream behind the extractions it consumes ...
+static inline int wait_inputs(sd_track* h, bool need_ref, bool pyramid_only = false) {
+  // ImageAlign reads pyramids only: it may start as soon as the current batch's pyramid exists, beside FAST / selection /
+  // descriptors of the same batch (option "track.align_start" = 0 restores the wait for the whole extraction)
+  const int align_start = sd::opt(sd::OPT_ALIGN_START);
+  const bool early = align_start != 0;
+  // ... but not beside FAST: k_align holds 30 KB of LDS per frame (4 frames per CU), FAST wants 24-39 KB per workgroup, while
+  // selection + descriptors, which follow FAST, use next to none.  Waiting for the end of the batch's FAST launches instead of
+  // its pyramid: full step 175.2 -> 178.8 k frames/s (three alternating runs; k_align 1.38 -> 0.84 ms in the pipeline).
+  // "track.align_start" = 1: wait for the pyramid only; 2 (default): for the FAST launches.
+  const bool after_fast = align_start == 2;
+  if (h->cur->extract_recorded) {
+    hipEvent_t ev = h->cur->ev_extract_done;
+    if (pyramid_only && early && h->cur->pyr_event_live) ev = after_fast ? h->cur->ev_fast_done : h->cur->ev_pyr_done;
+    SD_HIP_CHECK(hipStreamWaitEvent(h->pnp_stream, ev, 0));
+  }
+  if (need_ref && h->ref->extract_recorded) SD_HIP_CHECK(hipStreamWaitEvent(h->pnp_stream, h->ref->ev_extract_done, 0));
+  return SD_OK;
+}
+// ... and tell the extractors which output sets the kernel just queued is reading.
+static inline int mark_reads(sd_track* h, bool used_ref) {
+  sd_orb* c = h->cur;
+  SD_HIP_CHECK(hipEventRecord(c->ev_set_free[c->set], h->pnp_stream));
+  c->set_busy[c->set] = true;
+  if (used_ref && h->ref != h->cur) {
+    sd_orb* r = h->ref;
+    SD_HIP_CHECK(hipEventRecord(r->ev_set_free[r->set], h->pnp_stream));
+    r->set_busy[r->set] = true;
+  }
+  return SD_OK;
+}
+
+// per_cur_frame: the call walks the frames of `cur` themselves (not tracker slots), so the broadcast does not apply
+static inline int check_ready(sd_track* h, int n_frames, bool per_cur_frame = false) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(h->have_cam, SD_ERR_INVALID_ARG, "sd_track_set_camera has not been called");
+  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
+  const int need = (h->tb.cur_bcast >= 0 && !per_cur_frame) ? h->tb.cur_bcast + 1 : n_frames;
+  SD_REQUIRE(h->cur->have_geom && h->cur->last_frames >= need, SD_ERR_INVALID_ARG, "current frames have not been extracted");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  return SD_OK;
+}
+
+// The preamble of the sequential calls on slots < n_frames comes in pieces, because every entry point keeps the order of its
+// checks and has argument and state checks of its own between them: the handle and the batch ...
+static inline int check_batch(const sd_track* h, int n_frames) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
+  return SD_OK;
+}
+// ... "slot f pairs with current frame f" (the sequential loop never runs in broadcast mode) ... and hipSetDevice, last.
+static inline int check_paired(const sd_track* h) {
+  SD_REQUIRE(h->tb.cur_bcast < 0, SD_ERR_INVALID_ARG, "broadcast mode is on (sd_track_set_current_broadcast)");
+  return SD_OK;
+}
+
+// The preamble of the calls on slots frame0 .. frame0 + n - 1: the range alone (the caller checks more before it sets the device),
+// or the device too (the call queues on the tracking stream), or also a wait for that stream (the call touches what it uses).
+enum RangeUse { RANGE_CHECK, RANGE_QUEUE, RANGE_SYNC };
+static inline int check_range(const sd_track* h, int frame0, int n, RangeUse use) {
+  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(frame0 >= 0 && n >= 1 && frame0 + n <= h->max_batch, SD_ERR_CAPACITY, "frame range exceeds max_batch");
+  if (use != RANGE_CHECK) SD_HIP_CHECK(hipSetDevice(h->device));
+  if (use == RANGE_SYNC) SD_HIP_CHECK(hipStreamSynchronize(h->pnp_stream));
+  return SD_OK;
+}
+#define TRACK_RANGE(h, frame0, n) SD_TRY(check_range((h), (frame0), (n), RANGE_SYNC))
+#define QUEUE_RANGE(h, frame0, n) SD_TRY(check_range((h), (frame0), (n), RANGE_QUEUE))

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "orb_internal.h"
+#include "sd_quat.h"
 #include "track_internal.h"
 
 namespace sd {
@@ -109,37 +110,11 @@ __device__ __forceinline__ void im_dq_by_dw(const double (&q)[4], const double (
     for (int c = 0; c < 3; c++) res[r][c] = ((J[r][0] * mdw[0][c] + J[r][1] * mdw[1][c]) + J[r][2] * mdw[2][c]) + J[r][3] * mdw[3][c];
 }
 
-// Eigen::Quaterniond(Matrix3d) and normalize() as in track_motion.hip, on the rotation of a column-major pose
+// Eigen::Quaterniond(Matrix3d) and normalize() on the rotation of a column-major pose
 __device__ __forceinline__ void im_pose_quat(const double (&T)[16], double (&q)[4]) {
-  const double m00 = T[0], m10 = T[1], m20 = T[2], m01 = T[4], m11 = T[5], m21 = T[6], m02 = T[8], m12 = T[9], m22 = T[10];
-  double t = m00 + m11 + m22, w, x, y, z;
-  if (t > 0.0) {
-    t = sqrt(t + 1.0);
-    w = 0.5 * t;
-    t = 0.5 / t;
-    x = (m21 - m12) * t; y = (m02 - m20) * t; z = (m10 - m01) * t;
-  } else if (m22 > (m11 > m00 ? m11 : m00)) {
-    t = sqrt(m22 - m00 - m11 + 1.0);
-    z = 0.5 * t;
-    t = 0.5 / t;
-    w = (m10 - m01) * t; x = (m02 + m20) * t; y = (m12 + m21) * t;
-  } else if (m11 > m00) {
-    t = sqrt(m11 - m22 - m00 + 1.0);
-    y = 0.5 * t;
-    t = 0.5 / t;
-    w = (m02 - m20) * t; z = (m21 + m12) * t; x = (m01 + m10) * t;
-  } else {
-    t = sqrt(m00 - m11 - m22 + 1.0);
-    x = 0.5 * t;
-    t = 0.5 / t;
-    w = (m21 - m12) * t; y = (m10 + m01) * t; z = (m20 + m02) * t;
-  }
-  const double n2 = ((x * x + y * y) + z * z) + w * w;
-  if (n2 > 0.0) {
-    const double n = sqrt(n2);
-    w /= n; x /= n; y /= n; z /= n;
-  }
-  q[0] = w; q[1] = x; q[2] = y; q[3] = z;
+  const double m[3][3] = {{T[0], T[4], T[8]}, {T[1], T[5], T[9]}, {T[2], T[6], T[10]}};
+  mat_to_quat(m, q[0], q[1], q[2], q[3]);
+  quat_normalize(q[0], q[1], q[2], q[3]);
 }
 
 // EKF::Restart (full 0) or a newly constructed EKF (full 1) for slots frame0 .. frame0 + n - 1, one wave per slot
@@ -227,17 +202,11 @@ __global__ __launch_bounds__(64) void k_imu_predict(TrackBuffers tb, int n, doub
 #pragma unroll
     for (int i = 0; i < 16; i++) tb.im_X[(size_t)f * 16 + i] = Xn[i];
     // Sensor::GetPose: the rotation of a normalised copy of q, column-major
-    double pw = Xn[3], px = Xn[4], py = Xn[5], pz = Xn[6];
-    const double n2 = ((px * px + py * py) + pz * pz) + pw * pw;
-    if (n2 > 0.0) {
-      const double nn = sqrt(n2);
-      pw /= nn; px /= nn; py /= nn; pz /= nn;
-    }
-    const double tx = 2.0 * px, ty = 2.0 * py, tz = 2.0 * pz;
-    const double twx = tx * pw, twy = ty * pw, twz = tz * pw, txx = tx * px, txy = ty * px, txz = tz * px;
-    const double tyy = ty * py, tyz = tz * py, tzz = tz * pz;
-    const double T[16] = {1.0 - (tyy + tzz), txy + twz, txz - twy, 0.0, txy - twz, 1.0 - (txx + tzz), tyz + twx, 0.0,
-                          txz + twy, tyz - twx, 1.0 - (txx + tyy), 0.0, Xn[0], Xn[1], Xn[2], 1.0};
+    double pw = Xn[3], px = Xn[4], py = Xn[5], pz = Xn[6], R[3][3];
+    quat_normalize(pw, px, py, pz);
+    quat_to_mat(pw, px, py, pz, R);
+    const double T[16] = {R[0][0], R[1][0], R[2][0], 0.0, R[0][1], R[1][1], R[2][1], 0.0,
+                          R[0][2], R[1][2], R[2][2], 0.0, Xn[0], Xn[1], Xn[2], 1.0};
 #pragma unroll
     for (int i = 0; i < 16; i++) {
       tb.Tprior[(size_t)f * 16 + i] = T[i];
@@ -272,9 +241,7 @@ __global__ __launch_bounds__(64) void k_imu_update(TrackBuffers tb, int n, int s
   __shared__ double sP[256], sS[169], sM[13 * 26], sK[208], sKS[208], sY[13], sCol[13];
   const int f = blockIdx.x, lane = threadIdx.x;
   if (f >= n) return;
-  bool tracked = true;
-  if (source == 0) tracked = tb.tw_info[(size_t)f * 4] == 2;
-  else if (source == 1) tracked = tb.tl_info[(size_t)f * 4] == 2;
+  const bool tracked = slot_tracked(tb, source, f);
   const bool nz = lane < 16 && !(fabs(tb.im_last[(size_t)f * 16 + lane]) <= 1e-12);   // !Matrix4d::isZero()
   if (!tracked || __ballot(nz) == 0ull) {
     im_restart(tb, f, lane, false);

@@ -150,6 +150,13 @@ __device__ __forceinline__ int kept_point_obs(const TrackBuffers& tb, int source
   return n_obs >= 1 ? n_obs : 0;
 }
 
+// Whether the tracking call `source` left slot f tracked: -1 every slot counts, 0 tw_info status 2, 1 tl_info status 2
+__device__ __forceinline__ bool slot_tracked(const TrackBuffers& tb, int source, int f) {
+  if (source == 0) return tb.tw_info[(size_t)f * 4] == 2;
+  if (source == 1) return tb.tl_info[(size_t)f * 4] == 2;
+  return true;
+}
+
 struct TrackCam {
   double fx, fy, cx, cy;                 // (double)(float) like ImageAlign::cam_fx_
   float ffx, ffy, fcx, fcy;              // Frame::fx ... (static floats)

@@ -2,7 +2,7 @@
 // the RGB-D part of Tracking::CreateNewKeyFrame (:837-888) and the decision Tracking::NeedNewKeyFrame (:753-826).
 // Everything they read is resident: mvDepth (tb.depth), mvKeysUn, the frame's final pose (tb.Tcur), mvpMapPoints
 // (cur_match / un_match) and Observations() (tb.obs / tb.lm_obs).  The created points reach the next frame through
-// k_advance (track.hip); KeyFrame objects and the covisibility graph stay with the caller.
+// k_advance (track_seq.hip); KeyFrame objects and the covisibility graph stay with the caller.
 #include <hip/hip_runtime.h>
 
 #include "orb_internal.h"
