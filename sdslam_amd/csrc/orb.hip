@@ -1750,9 +1750,7 @@ int orb_enable_double_buffer(sd_orb* h) {
   if (h->nsets == 2) return SD_OK;
   SD_HIP_CHECK(hipSetDevice(h->device));
   SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  int nsel = 0;
-  for (int q : h->hp.quota) nsel += q;
-  const size_t cap = std::max(nsel, 1), B = h->max_batch;
+  const size_t cap = std::max(keypoint_capacity(h), 1), B = h->max_batch;
   SD_HIP_CHECK(hipMalloc(&h->kps_set[1], cap * B * sizeof(sd_keypoint)));
   SD_HIP_CHECK(hipMalloc(&h->kps_un_set[1], cap * B * sizeof(sd_keypoint)));
   SD_HIP_CHECK(hipMalloc(&h->desc_set[1], cap * B * 32));
@@ -1828,9 +1826,7 @@ int sd_orb_create(int nfeatures, float scale_factor, int nlevels, int th_fast, i
   h->max_batch = max_batch;
   h->device = device;
   plan_tables(nfeatures, scale_factor, nlevels, h->hp);
-  int nsel = 0;
-  for (int q : h->hp.quota) nsel += q;
-  const size_t cap = std::max(nsel, 1);
+  const size_t cap = std::max(keypoint_capacity(h), 1);
   hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipMalloc(&h->d_plan, sizeof(OrbPlan));
   if (e == hipSuccess) e = hipMalloc(&h->d_img, (size_t)max_w * max_h * max_batch);

@@ -96,6 +96,13 @@ struct sd_orb {
   int ev_calls = 0;   // calls recorded since profiling was (re-)enabled
 };
 
+// Keypoints a frame can hold: the sum of the per-level quotas (hp.plan.nsel is the same number, but only once a geometry is planned)
+static inline int keypoint_capacity(const sd_orb* h) {
+  int n = 0;
+  for (int q : h->hp.quota) n += q;
+  return n;
+}
+
 namespace sd {
 int orb_enable_double_buffer(sd_orb* h);   // orb.hip; idempotent
 }

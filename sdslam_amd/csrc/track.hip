@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "track_handle.h"
@@ -53,14 +54,32 @@ __global__ void k_pack_records(TrackBuffers tb, int source, int n_frames, double
   r[19] = ok;
 }
 
-template <typename T>
+// What a buffer holds when sd_track_create returns: zeros | 0xFF bytes (-1 in an int32) | -1.f in every float
+enum Fill { FILL_ZERO, FILL_FF, FILL_MINUS_ONE };
+
+// The fill runs on the null stream: sd_track_create waits for it before it queues anything that reads a buffer
+template <Fill F = FILL_ZERO, typename T>
 static int dalloc(sd_track* h, T** p, size_t count) {
+  static_assert(F != FILL_MINUS_ONE || std::is_same<T, float>::value, "FILL_MINUS_ONE is a float value");
+  const size_t n = std::max<size_t>(count, 1);
   void* q = nullptr;
-  SD_HIP_CHECK(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-  SD_HIP_CHECK(hipMemset(q, 0, std::max<size_t>(count, 1) * sizeof(T)));
+  SD_HIP_CHECK(hipMalloc(&q, n * sizeof(T)));
   h->allocs.push_back(q);
+  if (F == FILL_MINUS_ONE) SD_HIP_CHECK(hipMemsetD32(q, (int)0xBF800000u /* -1.f */, n));
+  else SD_HIP_CHECK(hipMemset(q, F == FILL_FF ? 0xFF : 0, n * sizeof(T)));
   *p = (T*)q;
   return SD_OK;
+}
+
+// Run `stages` with every slot paired to frame `cur_frame` of the cur extractor (sd_track_set_current_broadcast), and put the
+// caller's pairing back whatever they return
+template <typename Stages>
+static int with_broadcast(sd_track* h, int cur_frame, Stages&& stages) {
+  const int saved = h->tb.cur_bcast;
+  SD_TRY(sd_track_set_current_broadcast(h, cur_frame));
+  const int rc = stages();
+  h->tb.cur_bcast = saved;
+  return rc;
 }
 
 extern "C" {
@@ -76,8 +95,7 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   SD_REQUIRE(max_points >= 1 && max_points <= 2048 && max_batch >= 1 && max_batch <= ref->max_batch, SD_ERR_INVALID_ARG,
              "bad capacities (max_points <= 2048, max_batch <= the ref extractor's max_batch)");
   SD_REQUIRE(pnp_max_iterations >= 1 && pnp_max_iterations <= 4096, SD_ERR_INVALID_ARG, "bad pnp_max_iterations");
-  int nsel = 0;
-  for (int q : cur->hp.quota) nsel += q;
+  const int nsel = keypoint_capacity(cur);
   SD_REQUIRE(nsel >= 1 && nsel <= 2048, SD_ERR_INVALID_ARG, "tracking supports at most 2048 keypoints per frame");
   SD_HIP_CHECK(hipSetDevice(cur->device));
   sd_track* h = new sd_track();
@@ -89,11 +107,14 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   h->device = cur->device;
   h->rand_per_frame = 4 * pnp_max_iterations;
   h->rand_len.assign((size_t)max_batch, 0);
+  h->meas_set.assign((size_t)max_batch, 0);
   const size_t B = max_batch, M = max_points, K = nsel;
   TrackBuffers& tb = h->tb;
   tb.max_points = max_points;
   tb.kp_cap = nsel;
   tb.cur_bcast = -1;
+  // FILL_FF on the match / seen arrays: "no map point" until a search has run (a TrackLocalMap / PoseOptimization called first
+  // must not see index 0 everywhere); on the id arrays: no ids, the seen-point exclusion never fires and the hand-off carries -1
   int rc = SD_OK;
   auto A = [&](int r) { if (rc == SD_OK) rc = r; };
   A(dalloc(h, &tb.valid, B * M));
@@ -103,17 +124,17 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &tb.angle, B * M));
   A(dalloc(h, &tb.obs, B * M));
   A(dalloc(h, &tb.n_last, B));
-  A(dalloc(h, &tb.last_id, B * M));
+  A(dalloc<FILL_FF>(h, &tb.last_id, B * M));
   A(dalloc(h, &tb.valid2, B * M));
   A(dalloc(h, &tb.Xw2, B * M * 3));
   A(dalloc(h, &tb.mp_desc2, B * M * 32));
   A(dalloc(h, &tb.octave2, B * M));
   A(dalloc(h, &tb.angle2, B * M));
   A(dalloc(h, &tb.obs2, B * M));
-  A(dalloc(h, &tb.last_id2, B * M));
-  A(dalloc(h, &tb.tw_seen, B * K));
+  A(dalloc<FILL_FF>(h, &tb.last_id2, B * M));
+  A(dalloc<FILL_FF>(h, &tb.tw_seen, B * K));
   A(dalloc(h, &tb.tw_seen_ids, B * K));
-  A(dalloc(h, &tb.lm_id, B * M));
+  A(dalloc<FILL_FF>(h, &tb.lm_id, B * M));
   A(dalloc(h, &h->d_prior, B * 16));
   A(dalloc(h, &h->d_close, B * 2));
   A(dalloc(h, &tb.np_flag, B * K));
@@ -145,15 +166,15 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &tb.al_err, B));
   A(dalloc(h, &tb.al_chi2, B));
   A(dalloc(h, &tb.al_iters, B * 16));
-  A(dalloc(h, &tb.cur_match, B * K));
+  A(dalloc<FILL_FF>(h, &tb.cur_match, B * K));
   A(dalloc(h, &tb.n_matches, B));
   A(dalloc(h, &tb.mt_list, B * 8192));
   A(dalloc(h, &tb.mt_pt, B * M));
   A(dalloc(h, &tb.mt_key, B * 2048));
   A(dalloc(h, &tb.mt_cstart, B * (64 * 48 + 4)));
   A(dalloc(h, &tb.retry_list, B + 1));
-  A(dalloc(h, &tb.uright, B * K));
-  A(dalloc(h, &tb.depth, B * K));
+  A(dalloc<FILL_MINUS_ONE>(h, &tb.uright, B * K));
+  A(dalloc<FILL_MINUS_ONE>(h, &tb.depth, B * K));
   A(dalloc(h, &tb.rand_stream, B * (size_t)h->rand_per_frame));
   A(dalloc(h, &tb.pnp_T, B * 16));
   A(dalloc(h, &tb.pnp_inliers, B * K));
@@ -182,13 +203,13 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &tb.lm_proj, B * M * 3));
   A(dalloc(h, &tb.lm_level, B * M));
   A(dalloc(h, &tb.lm_cos, B * M));
-  A(dalloc(h, &tb.lm_match, B * K));
+  A(dalloc<FILL_FF>(h, &tb.lm_match, B * K));
   A(dalloc(h, &tb.lm_nmatch, B));
   A(dalloc(h, &tb.po_T, B * 16));
   A(dalloc(h, &tb.po_outlier, B * K));
   A(dalloc(h, &tb.po_info, B * 8));
   A(dalloc(h, &tb.tw_info, B * 4));
-  A(dalloc(h, &tb.un_match, B * K));
+  A(dalloc<FILL_FF>(h, &tb.un_match, B * K));
   A(dalloc(h, &tb.tl_info, B * 4));
   A(dalloc(h, &h->d_inv_sigma2, (size_t)cur->nlevels));
   A(dalloc(h, &h->d_scale_thr, (size_t)SD_MAX_LEVELS));
@@ -196,26 +217,14 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &h->d_inv_sf, (size_t)cur->nlevels));
   A(dalloc(h, &h->d_sigma2, (size_t)cur->nlevels));
   if (rc == SD_OK) {
-    std::vector<float> neg((size_t)B * K, -1.f);
-    hipError_t e0 = hipMemcpy(tb.uright, neg.data(), neg.size() * 4, hipMemcpyHostToDevice);
-    if (e0 == hipSuccess) e0 = hipMemcpy(tb.depth, neg.data(), neg.size() * 4, hipMemcpyHostToDevice);
-    // "no map point" until a search has run (a TrackLocalMap / PoseOptimization called first must not see index 0 everywhere)
-    if (e0 == hipSuccess) e0 = hipMemset(tb.cur_match, 0xFF, (size_t)B * K * 4);
-    if (e0 == hipSuccess) e0 = hipMemset(tb.lm_match, 0xFF, (size_t)B * K * 4);
-    if (e0 == hipSuccess) e0 = hipMemset(tb.un_match, 0xFF, (size_t)B * K * 4);
-    if (e0 == hipSuccess) e0 = hipMemset(tb.tw_seen, 0xFF, (size_t)B * K * 4);
-    // no ids: the seen-point exclusion never fires and the hand-off carries -1
-    if (e0 == hipSuccess) e0 = hipMemset(tb.last_id, 0xFF, (size_t)B * M * 4);
-    if (e0 == hipSuccess) e0 = hipMemset(tb.last_id2, 0xFF, (size_t)B * M * 4);
-    if (e0 == hipSuccess) e0 = hipMemset(tb.lm_id, 0xFF, (size_t)B * M * 4);
-    h->meas_set.assign((size_t)B, 0);
-    if (e0 != hipSuccess) { set_error(std::string("sd_track_create: ") + hipGetErrorString(e0)); rc = SD_ERR_HIP; }
-  }
-  if (rc == SD_OK) {
-    hipError_t e = hipMemcpy(h->d_sf, cur->hp.sf.data(), cur->nlevels * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->d_inv_sf, cur->hp.inv_sf.data(), cur->nlevels * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->d_sigma2, cur->hp.sigma2.data(), cur->nlevels * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->d_inv_sigma2, cur->hp.inv_sigma2.data(), cur->nlevels * 4, hipMemcpyHostToDevice);
+    hipError_t e = hipSuccess;
+    auto table = [&](float* dst, const float* src) {
+      if (e == hipSuccess) e = hipMemcpy(dst, src, cur->nlevels * sizeof(float), hipMemcpyHostToDevice);
+    };
+    table(h->d_sf, cur->hp.sf.data());
+    table(h->d_inv_sf, cur->hp.inv_sf.data());
+    table(h->d_sigma2, cur->hp.sigma2.data());
+    table(h->d_inv_sigma2, cur->hp.inv_sigma2.data());
     if (e == hipSuccess) {
       // MapPoint::PredictScale (src/MapPoint.cc:371-385): nScale = ceil(log(ratio) / mfLogScaleFactor), float overloads,
       // mfLogScaleFactor = log(mfScaleFactor) (src/Frame.cc:80).  thr[n] = smallest float ratio that reaches level n,
@@ -259,8 +268,9 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
       rc = SD_ERR_HIP;
     }
     // both motion models as their constructors leave them (ConstantVelocity::Init, IMU::Init on a zeroed P).  These kernels
-    // must stay behind the blocking hipMemcpy calls above, which drain the null stream of dalloc's hipMemset (the tracking
-    // stream does not wait for it); every reader of the filters runs on the tracking stream or waits for it (TRACK_RANGE)
+    // must stay behind the blocking hipMemcpy calls of the tables above (d_scale_thr's is the last), which drain the null stream
+    // of dalloc's fills (the tracking stream does not wait for it); every reader of the filters runs on the tracking stream or
+    // waits for it (TRACK_RANGE)
     if (rc == SD_OK) rc = launch_motion_init(tb, 0, max_batch, h->pnp_stream);
     if (rc == SD_OK) rc = launch_imu_init(tb, 0, max_batch, /*full*/ 1, h->pnp_stream);
     if (rc == SD_OK) rc = orb_enable_double_buffer(cur);
@@ -308,7 +318,7 @@ int sd_track_set_last(sd_track* h, int frame0, int n_frames, const int32_t* n_la
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(n_last && valid && Xw && desc && octave && angle && obs, SD_ERR_INVALID_ARG, "NULL argument");
   h->have_pnp = false;   // the solvers' 3-D points are being replaced
-  const size_t M = h->max_points, o = (size_t)frame0;
+  const size_t M = h->max_points, o = (size_t)frame0, n = (size_t)n_frames;
   for (int f = 0; f < n_frames; f++) SD_REQUIRE(n_last[f] >= 0 && n_last[f] <= h->max_points, SD_ERR_CAPACITY, "n_last exceeds max_points");
   // the octave indexes mvScaleFactors / mvLevelSigma2 on the device (search radius, level window)
   for (int f = 0; f < n_frames; f++)
@@ -317,35 +327,32 @@ int sd_track_set_last(sd_track* h, int frame0, int n_frames, const int32_t* n_la
                  SD_ERR_INVALID_ARG, "octave of a valid last-frame point outside [0, nlevels)");
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
-  SD_HIP_CHECK(hipMemcpyAsync(tb.n_last + o, n_last, (size_t)n_frames * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.valid + o * M, valid, n_frames * M, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.Xw + o * M * 3, Xw, n_frames * M * 3 * 8, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.mp_desc + o * M * 32, desc, n_frames * M * 32, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.octave + o * M, octave, n_frames * M * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.angle + o * M, angle, n_frames * M * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.obs + o * M, obs, n_frames * M * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemsetAsync(tb.last_id + o * M, 0xFF, n_frames * M * 4, s));   // new points: no ids until sd_track_set_map_ids
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(upload(tb.n_last, n_last, o, n, 1, s));
+  SD_TRY(upload(tb.valid, valid, o, n, M, s));
+  SD_TRY(upload(tb.Xw, Xw, o, n, M * 3, s));
+  SD_TRY(upload(tb.mp_desc, desc, o, n, M * 32, s));
+  SD_TRY(upload(tb.octave, octave, o, n, M, s));
+  SD_TRY(upload(tb.angle, angle, o, n, M, s));
+  SD_TRY(upload(tb.obs, obs, o, n, M, s));
+  SD_HIP_CHECK(hipMemsetAsync(tb.last_id + o * M, 0xFF, n * M * sizeof(int32_t), s));   // new points: no ids until sd_track_set_map_ids
+  return wait_for(s);
 }
 
 int sd_track_set_poses(sd_track* h, int frame0, int n_frames, const double* Tref_cm, const double* Tcur_cm) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(Tref_cm && Tcur_cm, SD_ERR_INVALID_ARG, "NULL argument");
   hipStream_t s = h->cur->stream;
-  SD_HIP_CHECK(hipMemcpyAsync(h->tb.Tref + (size_t)frame0 * 16, Tref_cm, (size_t)n_frames * 128, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(h->tb.Tprior + (size_t)frame0 * 16, Tcur_cm, (size_t)n_frames * 128, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(h->tb.Tcur + (size_t)frame0 * 16, Tcur_cm, (size_t)n_frames * 128, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(upload(h->tb.Tref, Tref_cm, frame0, n_frames, 16, s));
+  SD_TRY(upload(h->tb.Tprior, Tcur_cm, frame0, n_frames, 16, s));
+  SD_TRY(upload(h->tb.Tcur, Tcur_cm, frame0, n_frames, 16, s));
+  return wait_for(s);
 }
 
 int sd_track_set_rand(sd_track* h, int frame0, int n_frames, const int32_t* rand_values, int per_frame) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(rand_values && per_frame >= 1 && per_frame <= h->rand_per_frame, SD_ERR_INVALID_ARG, "bad rand stream");
   h->have_pnp = false;   // a resumed iterate() continues at a position of the OLD stream
-  SD_HIP_CHECK(hipMemcpy2DAsync(h->tb.rand_stream + (size_t)frame0 * h->rand_per_frame, (size_t)h->rand_per_frame * 4, rand_values,
-                                (size_t)per_frame * 4, (size_t)per_frame * 4, n_frames, hipMemcpyHostToDevice, h->cur->stream));
+  SD_TRY(upload_rows(h->tb.rand_stream, h->rand_per_frame, rand_values, per_frame, frame0, n_frames, h->cur->stream));
   SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
   for (int f = 0; f < n_frames; f++) h->rand_len[(size_t)frame0 + f] = per_frame;
   return SD_OK;
@@ -363,35 +370,20 @@ int sd_track_set_current_broadcast(sd_track* h, int cur_frame) {
 }
 
 int sd_track_align(sd_track* h, int n_frames, int mode) {
-  int rc = check_ready(h, n_frames);
-  if (rc != SD_OK) return rc;
+  SD_TRY(check_ready(h, n_frames));
   SD_REQUIRE(mode >= 0 && mode <= 3, SD_ERR_INVALID_ARG, "bad mode");
-  SD_REQUIRE(h->ref->have_geom && h->ref->last_frames >= n_frames && h->ref->cur_w == h->cur->cur_w && h->ref->cur_h == h->cur->cur_h,
-             SD_ERR_INVALID_ARG, "reference frames not extracted or of different size");
-  hipStream_t s = h->pnp_stream;
-  rc = wait_inputs(h, true, true);
-  if (rc != SD_OK) return rc;
-  hipEvent_t* ev = h->ev[h->ev_calls[0] % sd_track::kRing];
-  if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev[0], s));
-  rc = launch_align(h->cur, h->ref, h->tb, h->cam, h->d_inv_sf, h->d_sf, n_frames, mode, s);
-  if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev[1], s)); h->ev_calls[0]++; }
-  if (rc == SD_OK) rc = mark_reads(h, true);
-  return rc;
+  SD_TRY(require_ref_frames(h, n_frames, true));
+  return run_stage(h, true, true, STAGE_ALIGN, [&](hipStream_t s) {
+    return launch_align(h->cur, h->ref, h->tb, h->cam, h->d_inv_sf, h->d_sf, n_frames, mode, s);
+  });
 }
 
 int sd_track_match(sd_track* h, int n_frames, float th, int mono, int check_ori) {
-  int rc = check_ready(h, n_frames);
-  if (rc != SD_OK) return rc;
-  hipStream_t s = h->pnp_stream;
+  SD_TRY(check_ready(h, n_frames));
   h->have_pnp = false;   // mvpMapPoints is rewritten: solvers built on the old vector cannot be continued
-  rc = wait_inputs(h, false);
-  if (rc != SD_OK) return rc;
-  hipEvent_t* ev = h->ev[h->ev_calls[1] % sd_track::kRing];
-  if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev[2], s));
-  rc = launch_match(h->cur, h->tb, h->cam, h->d_sf, n_frames, th, mono, check_ori, s);
-  if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev[3], s)); h->ev_calls[1]++; }
-  if (rc == SD_OK) rc = mark_reads(h, false);
-  return rc;
+  return run_stage(h, false, false, STAGE_MATCH, [&](hipStream_t s) {
+    return launch_match(h->cur, h->tb, h->cam, h->d_sf, n_frames, th, mono, check_ori, s);
+  });
 }
 
 // TrackLocalMap's search.  Local map points of every frame, flattened in mvpLocalMapPoints order.
@@ -400,23 +392,22 @@ int sd_track_set_local(sd_track* h, int frame0, int n_frames, const int32_t* n_l
                        const int32_t* obs, const uint8_t* kp_claimed) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(n_local && cand && Xw && normal && min_dist && max_dist && mf_max_dist && desc && obs, SD_ERR_INVALID_ARG, "NULL argument");
-  const size_t M = h->max_points, o = (size_t)frame0, K = h->kp_cap;
+  const size_t M = h->max_points, K = h->kp_cap, o = (size_t)frame0, n = (size_t)n_frames;
   for (int f = 0; f < n_frames; f++) SD_REQUIRE(n_local[f] >= 0 && n_local[f] <= h->max_points, SD_ERR_CAPACITY, "n_local exceeds max_points");
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_n + o, n_local, (size_t)n_frames * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_cand + o * M, cand, n_frames * M, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_Xw + o * M * 3, Xw, n_frames * M * 3 * 8, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_normal + o * M * 3, normal, n_frames * M * 3 * 8, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_min + o * M, min_dist, n_frames * M * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_max + o * M, max_dist, n_frames * M * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_mfmax + o * M, mf_max_dist, n_frames * M * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_desc + o * M * 32, desc, n_frames * M * 32, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_obs + o * M, obs, n_frames * M * 4, hipMemcpyHostToDevice, s));
-  if (kp_claimed) SD_HIP_CHECK(hipMemcpyAsync(tb.lm_kclaim + o * K, kp_claimed, n_frames * K, hipMemcpyHostToDevice, s));
-  else SD_HIP_CHECK(hipMemsetAsync(tb.lm_kclaim + o * K, 0, n_frames * K, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(upload(tb.lm_n, n_local, o, n, 1, s));
+  SD_TRY(upload(tb.lm_cand, cand, o, n, M, s));
+  SD_TRY(upload(tb.lm_Xw, Xw, o, n, M * 3, s));
+  SD_TRY(upload(tb.lm_normal, normal, o, n, M * 3, s));
+  SD_TRY(upload(tb.lm_min, min_dist, o, n, M, s));
+  SD_TRY(upload(tb.lm_max, max_dist, o, n, M, s));
+  SD_TRY(upload(tb.lm_mfmax, mf_max_dist, o, n, M, s));
+  SD_TRY(upload(tb.lm_desc, desc, o, n, M * 32, s));
+  SD_TRY(upload(tb.lm_obs, obs, o, n, M, s));
+  if (kp_claimed) SD_TRY(upload(tb.lm_kclaim, kp_claimed, o, n, K, s));
+  else SD_HIP_CHECK(hipMemsetAsync(tb.lm_kclaim + o * K, 0, n * K, s));
+  return wait_for(s);
 }
 
 // ORBmatcher::SearchByProjection(Frame& F, const vector<MapPoint*>& vpMapPoints, th) on the caller's OWN isInFrustum results
@@ -427,7 +418,7 @@ int sd_track_set_local_view(sd_track* h, int frame0, int n_frames, const int32_t
                             const int32_t* level, const float* view_cos, const uint8_t* desc, const int32_t* obs, const uint8_t* kp_claimed) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(n_local && in_view && proj3 && level && view_cos && desc && obs, SD_ERR_INVALID_ARG, "NULL argument");
-  const size_t M = h->max_points, o = (size_t)frame0, K = h->kp_cap;
+  const size_t M = h->max_points, K = h->kp_cap, o = (size_t)frame0, n = (size_t)n_frames;
   for (int f = 0; f < n_frames; f++) {
     SD_REQUIRE(n_local[f] >= 0 && n_local[f] <= h->max_points, SD_ERR_CAPACITY, "n_local exceeds max_points");
     for (int i = 0; i < n_local[f]; i++)
@@ -436,41 +427,32 @@ int sd_track_set_local_view(sd_track* h, int frame0, int n_frames, const int32_t
   }
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_n + o, n_local, (size_t)n_frames * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_inview + o * M, in_view, n_frames * M, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_proj + o * M * 3, proj3, n_frames * M * 12, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_level + o * M, level, n_frames * M * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_cos + o * M, view_cos, n_frames * M * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_desc + o * M * 32, desc, n_frames * M * 32, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(tb.lm_obs + o * M, obs, n_frames * M * 4, hipMemcpyHostToDevice, s));
-  if (kp_claimed) SD_HIP_CHECK(hipMemcpyAsync(tb.lm_kclaim + o * K, kp_claimed, n_frames * K, hipMemcpyHostToDevice, s));
-  else SD_HIP_CHECK(hipMemsetAsync(tb.lm_kclaim + o * K, 0, n_frames * K, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(upload(tb.lm_n, n_local, o, n, 1, s));
+  SD_TRY(upload(tb.lm_inview, in_view, o, n, M, s));
+  SD_TRY(upload(tb.lm_proj, proj3, o, n, M * 3, s));
+  SD_TRY(upload(tb.lm_level, level, o, n, M, s));
+  SD_TRY(upload(tb.lm_cos, view_cos, o, n, M, s));
+  SD_TRY(upload(tb.lm_desc, desc, o, n, M * 32, s));
+  SD_TRY(upload(tb.lm_obs, obs, o, n, M, s));
+  if (kp_claimed) SD_TRY(upload(tb.lm_kclaim, kp_claimed, o, n, K, s));
+  else SD_HIP_CHECK(hipMemsetAsync(tb.lm_kclaim + o * K, 0, n * K, s));
+  return wait_for(s);
 }
 
 int sd_track_match_local_view(sd_track* h, int n_frames, float th, float nnratio) {
-  int rc = check_ready(h, n_frames);
-  if (rc != SD_OK) return rc;
-  hipStream_t s = h->pnp_stream;
-  rc = wait_inputs(h, false);
-  if (rc != SD_OK) return rc;
-  rc = launch_match_local(h->cur, h->tb, h->cam, h->d_sf, h->d_scale_thr, h->cur->nlevels, n_frames, th, nnratio, 0.f, s, 0, 1);
-  if (rc == SD_OK) rc = mark_reads(h, false);
-  return rc;
+  SD_TRY(check_ready(h, n_frames));
+  return run_stage(h, false, false, STAGE_NONE, [&](hipStream_t s) {
+    return launch_match_local(h->cur, h->tb, h->cam, h->d_sf, h->d_scale_thr, h->cur->nlevels, n_frames, th, nnratio, 0.f, s, 0, 1);
+  });
 }
 
 // Frame::isInFrustum for every candidate + ORBmatcher::SearchByProjection(F, vpMapPoints, th) with mfNNratio = nnratio,
 // at the frames' current poses (sd_track_set_poses / the ImageAlign result)
 int sd_track_match_local(sd_track* h, int n_frames, float th, float nnratio, float viewing_cos_limit) {
-  int rc = check_ready(h, n_frames);
-  if (rc != SD_OK) return rc;
-  hipStream_t s = h->pnp_stream;
-  rc = wait_inputs(h, false);
-  if (rc != SD_OK) return rc;
-  rc = launch_match_local(h->cur, h->tb, h->cam, h->d_sf, h->d_scale_thr, h->cur->nlevels, n_frames, th, nnratio, viewing_cos_limit, s);
-  if (rc == SD_OK) rc = mark_reads(h, false);
-  return rc;
+  SD_TRY(check_ready(h, n_frames));
+  return run_stage(h, false, false, STAGE_NONE, [&](hipStream_t s) {
+    return launch_match_local(h->cur, h->tb, h->cam, h->d_sf, h->d_scale_thr, h->cur->nlevels, n_frames, th, nnratio, viewing_cos_limit, s);
+  });
 }
 
 int sd_track_get_local(sd_track* h, int frame0, int n_frames, int32_t* local_match, int cap, int32_t* n_matches, uint8_t* in_view,
@@ -480,33 +462,23 @@ int sd_track_get_local(sd_track* h, int frame0, int n_frames, int32_t* local_mat
   hipStream_t s = h->cur->stream;
   const size_t M = h->max_points, o = frame0, n = n_frames;
   const TrackBuffers& tb = h->tb;
-  if (local_match)
-    SD_HIP_CHECK(hipMemcpy2DAsync(local_match, (size_t)cap * 4, tb.lm_match + o * h->kp_cap, (size_t)h->kp_cap * 4, (size_t)h->kp_cap * 4, n_frames,
-                                  hipMemcpyDeviceToHost, s));
-  if (n_matches) SD_HIP_CHECK(hipMemcpyAsync(n_matches, tb.lm_nmatch + o, n * 4, hipMemcpyDeviceToHost, s));
-  if (in_view) SD_HIP_CHECK(hipMemcpyAsync(in_view, tb.lm_inview + o * M, n * M, hipMemcpyDeviceToHost, s));
-  if (proj3) SD_HIP_CHECK(hipMemcpyAsync(proj3, tb.lm_proj + o * M * 3, n * M * 12, hipMemcpyDeviceToHost, s));
-  if (level) SD_HIP_CHECK(hipMemcpyAsync(level, tb.lm_level + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
-  if (view_cos) SD_HIP_CHECK(hipMemcpyAsync(view_cos, tb.lm_cos + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(download_rows(local_match, cap, tb.lm_match, o, n, h->kp_cap, s));
+  SD_TRY(download(n_matches, tb.lm_nmatch, o, n, 1, s));
+  SD_TRY(download(in_view, tb.lm_inview, o, n, M, s));
+  SD_TRY(download(proj3, tb.lm_proj, o, n, M * 3, s));
+  SD_TRY(download(level, tb.lm_level, o, n, M, s));
+  SD_TRY(download(view_cos, tb.lm_cos, o, n, M, s));
+  return wait_for(s);
 }
 
 // Optimizer::PoseOptimization(&CurrentFrame) at the frames' current poses (tb.Tcur: sd_track_set_poses / ImageAlign result).
 // source 0: mvpMapPoints = the frame-to-frame matches (sd_track_match); 1: the local-map matches (sd_track_match_local).
 int sd_track_pose_opt(sd_track* h, int n_frames, int source) {
-  int rc = check_ready(h, n_frames);
-  if (rc != SD_OK) return rc;
+  SD_TRY(check_ready(h, n_frames));
   SD_REQUIRE(source >= 0 && source <= 2, SD_ERR_INVALID_ARG, "source must be 0 (frame matches), 1 (local-map matches) or 2 (both, as after SearchLocalPoints)");
-  hipStream_t s = h->pnp_stream;
-  rc = wait_inputs(h, false);
-  if (rc != SD_OK) return rc;
-  hipEvent_t* ev = h->ev[h->ev_calls[2] % sd_track::kRing];   // timed in the pose-solve slot, like sd_track_pnp
-  if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev[4], s));
-  rc = launch_pose_opt(h->cur, h->tb, h->cam, h->d_inv_sigma2, source, n_frames, s);
-  if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev[5], s)); h->ev_calls[2]++; }
-  if (rc == SD_OK) rc = mark_reads(h, false);
-  return rc;
+  return run_stage(h, false, false, STAGE_SOLVE, [&](hipStream_t s) {   // timed in the pose-solve slot, like sd_track_pnp
+    return launch_pose_opt(h->cur, h->tb, h->cam, h->d_inv_sigma2, source, n_frames, s);
+  });
 }
 
 // Tracking::TrackWithMotionModel (reference src/Tracking.cc:654-718) / TrackReferenceKeyFrame (:583-644) for the batch, as
@@ -523,45 +495,38 @@ int sd_track_pose_opt(sd_track* h, int n_frames, int source) {
 // goes to mLastFrame, not to the keyframe (src/Tracking.cc:610): with align_mode 1 it equals the reference when the slot's
 // points serve both, otherwise run the stages separately.
 int sd_track_with_motion_model(sd_track* h, int n_frames, int align_mode, float th, int mono, int min_matches, int min_inliers) {
-  int rc = check_ready(h, n_frames);
-  if (rc != SD_OK) return rc;
+  SD_TRY(check_ready(h, n_frames));
   SD_REQUIRE(align_mode >= -1 && align_mode <= 1, SD_ERR_INVALID_ARG, "align_mode must be -1 (off), 0 (last frame) or 1 (reference keyframe)");
   SD_REQUIRE(min_matches >= 3 && min_inliers >= 0, SD_ERR_INVALID_ARG, "bad gates (reference: 20 matches, 10 inliers)");
   hipStream_t s = h->pnp_stream;
   const TrackBuffers& tb = h->tb;
   h->have_pnp = false;
   const bool use_ref = align_mode >= 0;
-  if (use_ref)
-    SD_REQUIRE(h->ref->have_geom && h->ref->last_frames >= n_frames && h->ref->cur_w == h->cur->cur_w && h->ref->cur_h == h->cur->cur_h,
-               SD_ERR_INVALID_ARG, "reference frames not extracted or of different size");
-  rc = wait_inputs(h, use_ref, use_ref);
-  if (rc != SD_OK) return rc;
-  hipEvent_t* ev = h->ev[h->ev_calls[0] % sd_track::kRing];
-  hipEvent_t* ev1 = h->ev[h->ev_calls[1] % sd_track::kRing];
-  hipEvent_t* ev2 = h->ev[h->ev_calls[2] % sd_track::kRing];
-  SD_HIP_CHECK(hipMemsetAsync(tb.tw_info, 0, (size_t)n_frames * 16, s));
-  if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev[0], s));
+  if (use_ref) SD_TRY(require_ref_frames(h, n_frames, true));
+  SD_TRY(wait_inputs(h, use_ref, use_ref));
+  SD_HIP_CHECK(hipMemsetAsync(tb.tw_info, 0, (size_t)n_frames * 4 * sizeof(int32_t), s));
+  SD_TRY(stage_begin(h, STAGE_ALIGN));
+  int rc = SD_OK;
   if (use_ref) rc = launch_align(h->cur, h->ref, tb, h->cam, h->d_inv_sf, h->d_sf, n_frames, align_mode, s);
-  else SD_HIP_CHECK(hipMemcpyAsync(tb.Tcur, tb.Tprior, (size_t)n_frames * 128, hipMemcpyDeviceToDevice, s));
-  if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev[1], s)); h->ev_calls[0]++; }
-  if (rc != SD_OK) return rc;
+  else SD_HIP_CHECK(hipMemcpyAsync(tb.Tcur, tb.Tprior, (size_t)n_frames * 16 * sizeof(double), hipMemcpyDeviceToDevice, s));
+  SD_TRY(stage_end(h, STAGE_ALIGN));
+  SD_TRY(rc);
   if (use_ref) {
-    rc = mark_reads(h, true);
-    if (rc != SD_OK) return rc;
-    rc = wait_inputs(h, false);   // the matcher needs the keypoints, not only the pyramid
-    if (rc != SD_OK) return rc;
+    SD_TRY(mark_reads(h, true));
+    SD_TRY(wait_inputs(h, false));   // the matcher needs the keypoints, not only the pyramid
   }
-  if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev1[2], s));
+  SD_TRY(stage_begin(h, STAGE_MATCH));
   rc = launch_match(h->cur, tb, h->cam, h->d_sf, n_frames, th, mono, 1, s, 0, min_matches);   // (lists the frames that need the retry)
   if (rc == SD_OK) rc = launch_match(h->cur, tb, h->cam, h->d_sf, n_frames, 2.f * th, mono, 1, s, min_matches);
-  if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev1[3], s)); h->ev_calls[1]++; }
-  if (rc != SD_OK) return rc;
-  if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev2[4], s));
+  SD_TRY(stage_end(h, STAGE_MATCH));
+  SD_TRY(rc);
+  SD_TRY(stage_begin(h, STAGE_SOLVE));
   rc = launch_pose_opt(h->cur, tb, h->cam, h->d_inv_sigma2, 0, n_frames, s, min_matches, min_inliers);
-  if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev2[5], s)); h->ev_calls[2]++; }
-  if (rc == SD_OK) rc = mark_reads(h, false);
-  if (rc == SD_OK) h->ran[0].set(h, n_frames);
-  return rc;
+  SD_TRY(stage_end(h, STAGE_SOLVE));
+  SD_TRY(rc);
+  SD_TRY(mark_reads(h, false));
+  h->ran[0].set(h, n_frames);
+  return SD_OK;
 }
 
 // Tracking::TrackLocalMap (reference src/Tracking.cc:720-751) for the batch, after sd_track_with_motion_model (or any
@@ -571,27 +536,24 @@ int sd_track_with_motion_model(sd_track* h, int n_frames, int align_mode, float 
 // The local map (sd_track_set_local) is the caller's UpdateLocalMap(); its `cand` flags carry the "already matched in this
 // frame / isBad" skips of :916-921, kp_claimed is ignored here.  th: 1, 3 for RGB-D, 5 after a relocalisation (:929-934).
 int sd_track_local_map(sd_track* h, int n_frames, float th, float nnratio, float viewing_cos_limit, int min_inliers) {
-  int rc = check_ready(h, n_frames);
-  if (rc != SD_OK) return rc;
+  SD_TRY(check_ready(h, n_frames));
   SD_REQUIRE(min_inliers >= 0, SD_ERR_INVALID_ARG, "bad min_inliers (reference: 30)");
   hipStream_t s = h->pnp_stream;
-  rc = wait_inputs(h, false);
-  if (rc != SD_OK) return rc;
-  hipEvent_t* ev1 = h->ev[h->ev_calls[1] % sd_track::kRing];
-  hipEvent_t* ev2 = h->ev[h->ev_calls[2] % sd_track::kRing];
-  if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev1[2], s));
+  SD_TRY(wait_inputs(h, false));
+  SD_TRY(stage_begin(h, STAGE_MATCH));
   // seen-point exclusion: ids given, and tw_seen holds this extraction's TrackWithMotionModel result for these slots
   const int exclude = h->ids_on && h->ran[0].covers(h, n_frames) ? 1 : 0;
-  rc = launch_match_local(h->cur, h->tb, h->cam, h->d_sf, h->d_scale_thr, h->cur->nlevels, n_frames, th, nnratio, viewing_cos_limit, s, 1, 0,
-                          exclude);
-  if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev1[3], s)); h->ev_calls[1]++; }
-  if (rc != SD_OK) return rc;
-  if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev2[4], s));
+  int rc = launch_match_local(h->cur, h->tb, h->cam, h->d_sf, h->d_scale_thr, h->cur->nlevels, n_frames, th, nnratio, viewing_cos_limit, s, 1, 0,
+                              exclude);
+  SD_TRY(stage_end(h, STAGE_MATCH));
+  SD_TRY(rc);
+  SD_TRY(stage_begin(h, STAGE_SOLVE));
   rc = launch_pose_opt(h->cur, h->tb, h->cam, h->d_inv_sigma2, 2, n_frames, s, 0, min_inliers);
-  if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev2[5], s)); h->ev_calls[2]++; }
-  if (rc == SD_OK) rc = mark_reads(h, false);
-  if (rc == SD_OK) h->ran[1].set(h, n_frames);
-  return rc;
+  SD_TRY(stage_end(h, STAGE_SOLVE));
+  SD_TRY(rc);
+  SD_TRY(mark_reads(h, false));
+  h->ran[1].set(h, n_frames);
+  return SD_OK;
 }
 
 // map_match (may be NULL): mvpMapPoints after SearchLocalPoints, -1 | v < max_points: last-frame point v | v >= max_points:
@@ -600,21 +562,17 @@ int sd_track_get_local_map(sd_track* h, int frame0, int n_frames, int32_t* map_m
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(!map_match || cap >= h->kp_cap, SD_ERR_CAPACITY, "cap smaller than the keypoint capacity");
   hipStream_t s = h->cur->stream;
-  if (map_match)
-    SD_HIP_CHECK(hipMemcpy2DAsync(map_match, (size_t)cap * 4, h->tb.un_match + (size_t)frame0 * h->kp_cap, (size_t)h->kp_cap * 4,
-                                  (size_t)h->kp_cap * 4, n_frames, hipMemcpyDeviceToHost, s));
-  if (info4) SD_HIP_CHECK(hipMemcpyAsync(info4, h->tb.tl_info + (size_t)frame0 * 4, (size_t)n_frames * 16, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(download_rows(map_match, cap, h->tb.un_match, frame0, n_frames, h->kp_cap, s));
+  SD_TRY(download(info4, h->tb.tl_info, frame0, n_frames, 4, s));
+  return wait_for(s);
 }
 
 // info4 per frame: status (0 few matches, 1 few inliers, 2 tracked), nmatches after the discard, nmatchesMap, retried
 int sd_track_get_tracked(sd_track* h, int frame0, int n_frames, int32_t* info4) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(info4, SD_ERR_INVALID_ARG, "NULL argument");
-  SD_HIP_CHECK(hipMemcpyAsync(info4, h->tb.tw_info + (size_t)frame0 * 4, (size_t)n_frames * 16, hipMemcpyDeviceToHost, h->cur->stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
-  return SD_OK;
+  SD_TRY(download(info4, h->tb.tw_info, frame0, n_frames, 4, h->cur->stream));
+  return wait_for(h->cur->stream);
 }
 
 // Tracking::Relocalization (reference src/Tracking.cc:1064-1097) over all keyframes at once.  The reference walks the
@@ -631,19 +589,16 @@ int sd_track_relocalize(sd_track* h, int n_keyframes, int cur_frame, float th, i
   SD_REQUIRE(h && winner, SD_ERR_INVALID_ARG, "NULL argument");
   *winner = -1;
   SD_REQUIRE(cur_frame >= 0, SD_ERR_INVALID_ARG, "cur_frame must name a frame of the cur extractor");
-  const int saved = h->tb.cur_bcast;
-  int rc = sd_track_set_current_broadcast(h, cur_frame);
-  if (rc != SD_OK) return rc;
-  rc = sd_track_align(h, n_keyframes, 2);
-  if (rc == SD_OK) rc = sd_track_match(h, n_keyframes, th, mono, 1);   // ORBmatcher matcher(0.75, true)
-  if (rc == SD_OK) rc = sd_track_pose_opt(h, n_keyframes, 0);
-  h->tb.cur_bcast = saved;
-  if (rc != SD_OK) return rc;
+  SD_TRY(with_broadcast(h, cur_frame, [&] {
+    SD_TRY(sd_track_align(h, n_keyframes, 2));
+    SD_TRY(sd_track_match(h, n_keyframes, th, mono, 1));   // ORBmatcher matcher(0.75, true)
+    return sd_track_pose_opt(h, n_keyframes, 0);
+  }));
   std::vector<int32_t> ok(n_keyframes), nm(n_keyframes), info((size_t)n_keyframes * 8);
   hipStream_t s = h->pnp_stream;
-  SD_HIP_CHECK(hipMemcpyAsync(ok.data(), h->tb.al_ok, (size_t)n_keyframes * 4, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipMemcpyAsync(nm.data(), h->tb.n_matches, (size_t)n_keyframes * 4, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipMemcpyAsync(info.data(), h->tb.po_info, (size_t)n_keyframes * 32, hipMemcpyDeviceToHost, s));
+  SD_TRY(download(ok.data(), h->tb.al_ok, 0, n_keyframes, 1, s));
+  SD_TRY(download(nm.data(), h->tb.n_matches, 0, n_keyframes, 1, s));
+  SD_TRY(download(info.data(), h->tb.po_info, 0, n_keyframes, 8, s));
   SD_HIP_CHECK(hipStreamSynchronize(s));
   for (int i = 0; i < n_keyframes; i++) {
     const int good = info[(size_t)i * 8 + 5];
@@ -666,19 +621,14 @@ int sd_track_detect_loop(sd_track* h, int n_keyframes, int cur_frame, const uint
   SD_REQUIRE(h && candidates && n_candidates && cap >= 0, SD_ERR_INVALID_ARG, "NULL argument");
   *n_candidates = 0;
   SD_REQUIRE(cur_frame >= 0, SD_ERR_INVALID_ARG, "cur_frame must name a frame of the cur extractor");
-  const int saved = h->tb.cur_bcast;
-  int rc = sd_track_set_current_broadcast(h, cur_frame);
-  if (rc != SD_OK) return rc;
-  rc = sd_track_align(h, n_keyframes, 3);
-  h->tb.cur_bcast = saved;
-  if (rc != SD_OK) return rc;
+  SD_TRY(with_broadcast(h, cur_frame, [&] { return sd_track_align(h, n_keyframes, 3); }));
   std::vector<int32_t> ok(n_keyframes);
   std::vector<double> err(n_keyframes);
   hipStream_t s = h->pnp_stream;
-  SD_HIP_CHECK(hipMemcpyAsync(ok.data(), h->tb.al_ok, (size_t)n_keyframes * 4, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipMemcpyAsync(err.data(), h->tb.al_err, (size_t)n_keyframes * 8, hipMemcpyDeviceToHost, s));
+  SD_TRY(download(ok.data(), h->tb.al_ok, 0, n_keyframes, 1, s));
+  SD_TRY(download(err.data(), h->tb.al_err, 0, n_keyframes, 1, s));
   SD_HIP_CHECK(hipStreamSynchronize(s));
-  if (errors) std::memcpy(errors, err.data(), (size_t)n_keyframes * 8);
+  if (errors) std::memcpy(errors, err.data(), (size_t)n_keyframes * sizeof(double));
   double best = 1e10;
   std::vector<int32_t> kept;
   for (int i = 0; i < n_keyframes; i++) {
@@ -702,39 +652,34 @@ int sd_track_get_pose_opt(sd_track* h, int frame0, int n_frames, double* Tcw_cm,
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(!outlier || cap >= h->kp_cap, SD_ERR_CAPACITY, "cap smaller than the keypoint capacity");
   hipStream_t s = h->cur->stream;
-  if (Tcw_cm) SD_HIP_CHECK(hipMemcpyAsync(Tcw_cm, h->tb.po_T + (size_t)frame0 * 16, (size_t)n_frames * 128, hipMemcpyDeviceToHost, s));
-  if (outlier)
-    SD_HIP_CHECK(hipMemcpy2DAsync(outlier, cap, h->tb.po_outlier + (size_t)frame0 * h->kp_cap, h->kp_cap, h->kp_cap, n_frames,
-                                  hipMemcpyDeviceToHost, s));
-  if (info8) SD_HIP_CHECK(hipMemcpyAsync(info8, h->tb.po_info + (size_t)frame0 * 8, (size_t)n_frames * 32, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(download(Tcw_cm, h->tb.po_T, frame0, n_frames, 16, s));
+  SD_TRY(download_rows(outlier, cap, h->tb.po_outlier, frame0, n_frames, h->kp_cap, s));
+  SD_TRY(download(info8, h->tb.po_info, frame0, n_frames, 8, s));
+  return wait_for(s);
 }
 
 // CurrentFrame.mvuRight supplied by the caller (stereo) -- [n_frames][kp_cap] floats, -1 = none
 int sd_track_set_uright(sd_track* h, int frame0, int n_frames, const float* uright, int cap) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(uright && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad uright array");
-  SD_HIP_CHECK(hipMemcpy2DAsync(h->tb.uright + (size_t)frame0 * h->kp_cap, (size_t)h->kp_cap * 4, uright, (size_t)cap * 4, (size_t)cap * 4,
-                                n_frames, hipMemcpyHostToDevice, h->cur->stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
-  return SD_OK;
+  SD_TRY(upload_rows(h->tb.uright, h->kp_cap, uright, cap, frame0, n_frames, h->cur->stream));
+  return wait_for(h->cur->stream);
 }
 
 // Frame::ComputeStereoFromRGBD on the current frames of the batch: depth images (CV_32F, host memory)
 int sd_track_stereo_from_depth(sd_track* h, int n_frames, const float* depth, int w, int hgt, int stride_elems, size_t frame_stride_elems) {
-  int rc = check_ready(h, n_frames, true);
-  if (rc != SD_OK) return rc;
+  SD_TRY(check_ready(h, n_frames, true));
   SD_REQUIRE(depth && w >= 1 && hgt >= 1 && stride_elems >= w, SD_ERR_INVALID_ARG, "bad depth image");
   SD_HIP_CHECK(hipStreamSynchronize(h->pnp_stream));   // a queued match may still read the stereo arrays
   float* d_depth = nullptr;
   const size_t total = (size_t)n_frames * w * hgt;
-  SD_HIP_CHECK(hipMalloc(&d_depth, total * 4));
+  SD_HIP_CHECK(hipMalloc(&d_depth, total * sizeof(float)));
   hipStream_t s = h->cur->stream;
   hipError_t e = hipSuccess;
+  int rc = SD_OK;
   for (int f = 0; f < n_frames && e == hipSuccess; f++)
-    e = hipMemcpy2DAsync(d_depth + (size_t)f * w * hgt, (size_t)w * 4, depth + (size_t)f * frame_stride_elems, (size_t)stride_elems * 4,
-                         (size_t)w * 4, hgt, hipMemcpyHostToDevice, s);
+    e = hipMemcpy2DAsync(d_depth + (size_t)f * w * hgt, w * sizeof(float), depth + (size_t)f * frame_stride_elems, stride_elems * sizeof(float),
+                         w * sizeof(float), hgt, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) rc = launch_stereo_from_depth(h->cur, h->tb, h->cam, d_depth, w, hgt, w, (size_t)w * hgt, n_frames, s);
   hipError_t e2 = hipStreamSynchronize(s);
   (void)hipFree(d_depth);
@@ -750,30 +695,26 @@ int sd_track_stereo_from_depth(sd_track* h, int n_frames, const float* depth, in
 // allocation, no copy of the maps.
 int sd_track_stereo_from_depth_device(sd_track* h, int n_frames, const void* d_depth, int dtype, int w, int hgt, int stride_elems,
                                       size_t frame_stride_elems, float depth_map_factor) {
-  int rc = check_ready(h, n_frames, true);
-  if (rc != SD_OK) return rc;
+  SD_TRY(check_ready(h, n_frames, true));
   SD_REQUIRE(d_depth && (dtype == SD_DEPTH_F32 || dtype == SD_DEPTH_U16) && w >= 1 && hgt >= 1 && stride_elems >= w, SD_ERR_INVALID_ARG,
              "bad depth image (NULL, unknown dtype, empty or stride < w)");
   SD_REQUIRE((uintptr_t)d_depth % (dtype == SD_DEPTH_U16 ? 2 : 4) == 0, SD_ERR_INVALID_ARG, "depth pointer not aligned to its element size");
   // mDepthMapFactor and the convertTo condition, in the reference's float arithmetic
   const float scale = std::fabs(depth_map_factor) < 1e-5 ? 1.0f : 1.0f / depth_map_factor;
   const bool convert = std::fabs(scale - 1.0f) > 1e-5 || dtype != SD_DEPTH_F32;
-  rc = wait_inputs(h, false);
-  if (rc != SD_OK) return rc;
-  rc = launch_stereo_from_depth_typed(h->cur, h->tb, h->cam, d_depth, dtype == SD_DEPTH_U16, convert, scale, w, hgt, stride_elems,
-                                      frame_stride_elems, n_frames, h->pnp_stream);
-  if (rc == SD_OK) rc = mark_reads(h, false);
-  return rc;
+  return run_stage(h, false, false, STAGE_NONE, [&](hipStream_t s) {
+    return launch_stereo_from_depth_typed(h->cur, h->tb, h->cam, d_depth, dtype == SD_DEPTH_U16, convert, scale, w, hgt, stride_elems,
+                                          frame_stride_elems, n_frames, s);
+  });
 }
 
 int sd_track_get_stereo(sd_track* h, int frame0, int n_frames, float* uright, float* depth, int cap) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(cap >= h->kp_cap, SD_ERR_CAPACITY, "cap smaller than the keypoint capacity");
   hipStream_t s = h->cur->stream;
-  if (uright) SD_HIP_CHECK(hipMemcpy2DAsync(uright, (size_t)cap * 4, h->tb.uright + (size_t)frame0 * h->kp_cap, (size_t)h->kp_cap * 4, (size_t)h->kp_cap * 4, n_frames, hipMemcpyDeviceToHost, s));
-  if (depth) SD_HIP_CHECK(hipMemcpy2DAsync(depth, (size_t)cap * 4, h->tb.depth + (size_t)frame0 * h->kp_cap, (size_t)h->kp_cap * 4, (size_t)h->kp_cap * 4, n_frames, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(download_rows(uright, cap, h->tb.uright, frame0, n_frames, h->kp_cap, s));
+  SD_TRY(download_rows(depth, cap, h->tb.depth, frame0, n_frames, h->kp_cap, s));
+  return wait_for(s);
 }
 
 // ORBmatcher::SearchByPoints(currentKF, pKF, matches) (reference src/ORBmatcher.cc:1209-1301) for the batch: slot f matches
@@ -787,40 +728,27 @@ int sd_track_set_point_flags(sd_track* h, int frame0, int n_frames, const uint8_
   const size_t K = h->kp_cap, o = (size_t)frame0 * K;
   SD_HIP_CHECK(hipMemsetAsync(h->tb.sp_valid1 + o, 0, (size_t)n_frames * K, s));
   SD_HIP_CHECK(hipMemsetAsync(h->tb.sp_valid2 + o, 0, (size_t)n_frames * K, s));
-  SD_HIP_CHECK(hipMemcpy2DAsync(h->tb.sp_valid1 + o, K, has_mp_cur, (size_t)cap, (size_t)cap, n_frames, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpy2DAsync(h->tb.sp_valid2 + o, K, has_mp_ref, (size_t)cap, (size_t)cap, n_frames, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(upload_rows(h->tb.sp_valid1, K, has_mp_cur, cap, frame0, n_frames, s));
+  SD_TRY(upload_rows(h->tb.sp_valid2, K, has_mp_ref, cap, frame0, n_frames, s));
+  return wait_for(s);
 }
 
 int sd_track_search_by_points(sd_track* h, int n_frames, float nnratio, int check_ori) {
-  int rc = check_ready(h, n_frames);
-  if (rc != SD_OK) return rc;
-  SD_REQUIRE(h->ref->have_geom && h->ref->last_frames >= n_frames, SD_ERR_INVALID_ARG, "keyframes of the ref extractor have not been extracted");
-  int nsel_ref = 0;
-  for (int q : h->ref->hp.quota) nsel_ref += q;
-  SD_REQUIRE(nsel_ref == h->kp_cap, SD_ERR_INVALID_ARG, "cur / ref extractors must share the keypoint capacity");
-  hipStream_t s = h->pnp_stream;
-  rc = wait_inputs(h, true);
-  if (rc != SD_OK) return rc;
-  hipEvent_t* ev = h->ev[h->ev_calls[1] % sd_track::kRing];   // timed in the matcher's slot
-  if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev[2], s));
-  rc = launch_search_points(h->cur, h->ref, h->tb, n_frames, nnratio, check_ori, s);
-  if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev[3], s)); h->ev_calls[1]++; }
-  if (rc == SD_OK) rc = mark_reads(h, true);
-  return rc;
+  SD_TRY(check_ready(h, n_frames));
+  SD_TRY(require_ref_frames(h, n_frames, false));
+  SD_REQUIRE(keypoint_capacity(h->ref) == h->kp_cap, SD_ERR_INVALID_ARG, "cur / ref extractors must share the keypoint capacity");
+  return run_stage(h, true, false, STAGE_MATCH, [&](hipStream_t s) {   // timed in the matcher's slot
+    return launch_search_points(h->cur, h->ref, h->tb, n_frames, nnratio, check_ori, s);
+  });
 }
 
 int sd_track_get_point_matches(sd_track* h, int frame0, int n_frames, int32_t* matches12, int cap, int32_t* n_matches) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(!matches12 || cap >= h->kp_cap, SD_ERR_CAPACITY, "cap smaller than the keypoint capacity");
   hipStream_t s = h->cur->stream;
-  if (matches12)
-    SD_HIP_CHECK(hipMemcpy2DAsync(matches12, (size_t)cap * 4, h->tb.sp_match + (size_t)frame0 * h->kp_cap, (size_t)h->kp_cap * 4,
-                                  (size_t)h->kp_cap * 4, n_frames, hipMemcpyDeviceToHost, s));
-  if (n_matches) SD_HIP_CHECK(hipMemcpyAsync(n_matches, h->tb.sp_n + frame0, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(download_rows(matches12, cap, h->tb.sp_match, frame0, n_frames, h->kp_cap, s));
+  SD_TRY(download(n_matches, h->tb.sp_n, frame0, n_frames, 1, s));
+  return wait_for(s);
 }
 
 // PnPsolver(F, vpMapPointMatches) accepts ANY match vector (reference src/PnPsolver.cc:71-110), and so does
@@ -839,22 +767,13 @@ int sd_track_set_matches(sd_track* h, int frame0, int n_frames, const int32_t* c
       cnt[f] += m >= 0;
     }
   hipStream_t s = h->cur->stream;
-  SD_HIP_CHECK(hipMemcpyAsync(h->tb.cur_match + (size_t)frame0 * h->kp_cap, full.data(), full.size() * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipMemcpyAsync(h->tb.n_matches + frame0, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(upload(h->tb.cur_match, full.data(), frame0, n_frames, h->kp_cap, s));
+  SD_TRY(upload(h->tb.n_matches, cnt.data(), frame0, n_frames, 1, s));
+  return wait_for(s);
 }
 
 static int run_pnp(sd_track* h, int n_frames, const PnpParams& pp) {
-  hipStream_t s = h->pnp_stream;
-  int rc = wait_inputs(h, false);
-  if (rc != SD_OK) return rc;
-  hipEvent_t* ev = h->ev[h->ev_calls[2] % sd_track::kRing];
-  if (h->profiling) SD_HIP_CHECK(hipEventRecord(ev[4], s));
-  rc = launch_pnp(h->cur, h->tb, h->cam, h->d_sigma2, pp, n_frames, s);
-  if (h->profiling) { SD_HIP_CHECK(hipEventRecord(ev[5], s)); h->ev_calls[2]++; }
-  if (rc == SD_OK) rc = mark_reads(h, false);
-  return rc;
+  return run_stage(h, false, false, STAGE_SOLVE, [&](hipStream_t s) { return launch_pnp(h->cur, h->tb, h->cam, h->d_sigma2, pp, n_frames, s); });
 }
 
 // every slot must have been given the rand() values the call can consume: minSet per RANSAC iteration
@@ -869,8 +788,7 @@ static int check_rand(sd_track* h, int n_frames, long long need) {
 // PnPsolver ctor + SetRansacParameters + iterate(n_iterations) (reference src/PnPsolver.cc:71-244)
 int sd_track_pnp(sd_track* h, int n_frames, double probability, int min_inliers, int max_iterations, int min_set, float epsilon,
                  float th2, int n_iterations) {
-  int rc = check_ready(h, n_frames);
-  if (rc != SD_OK) return rc;
+  SD_TRY(check_ready(h, n_frames));
   // the reference's default is 4 (src/PnPsolver.h:74); other sizes go through the general (one hypothesis at a time) path.
   // Fewer than 4 correspondences leave EPnP's 12 x 12 system rank deficient beyond its 4-D null space: the reference's own
   // hypotheses are then rounding noise of its summation order.  minSet 3 is accepted because its OUTCOME is pinned against
@@ -879,8 +797,7 @@ int sd_track_pnp(sd_track* h, int n_frames, double probability, int min_inliers,
   SD_REQUIRE(min_set >= 3 && min_set <= 64, SD_ERR_INVALID_ARG, "minSet must be in [3, 64]");
   SD_REQUIRE(max_iterations >= 1 && n_iterations >= 0 && min_inliers >= 0, SD_ERR_INVALID_ARG, "bad RANSAC parameters");
   const long long upper = std::max(max_iterations, n_iterations);
-  rc = check_rand(h, n_frames, (long long)min_set * upper);
-  if (rc != SD_OK) return rc;
+  SD_TRY(check_rand(h, n_frames, (long long)min_set * upper));
   PnpParams pp;
   pp.probability = probability;
   pp.min_inliers = min_inliers;
@@ -891,15 +808,13 @@ int sd_track_pnp(sd_track* h, int n_frames, double probability, int min_inliers,
   pp.n_iterations = n_iterations;
   pp.rand_per_frame = h->rand_per_frame;
   pp.resume = 0;
-  rc = run_pnp(h, n_frames, pp);
-  if (rc == SD_OK) {
-    h->have_pnp = true;
-    h->pnp_serial = h->cur->extract_serial;
-    h->pnp_params = pp;
-    h->pnp_frames = n_frames;
-    h->pnp_iter_upper = (int)upper;
-  }
-  return rc;
+  SD_TRY(run_pnp(h, n_frames, pp));
+  h->have_pnp = true;
+  h->pnp_serial = h->cur->extract_serial;
+  h->pnp_params = pp;
+  h->pnp_frames = n_frames;
+  h->pnp_iter_upper = (int)upper;
+  return SD_OK;
 }
 
 // A further PnPsolver::iterate(n_iterations) on the solvers the last sd_track_pnp constructed: mnIterations, the best
@@ -907,8 +822,7 @@ int sd_track_pnp(sd_track* h, int n_frames, double probability, int min_inliers,
 // mnIterations < mRansacMaxIts OR nCurrentIterations < nIterations, so after the first call every call adds exactly
 // n_iterations).  The match vector must not have been changed in between (the reference's solver holds its own copy).
 int sd_track_pnp_iterate(sd_track* h, int n_frames, int n_iterations) {
-  int rc = check_ready(h, n_frames);
-  if (rc != SD_OK) return rc;
+  SD_TRY(check_ready(h, n_frames));
   SD_REQUIRE(h->have_pnp && n_frames <= h->pnp_frames, SD_ERR_INVALID_ARG,
              "sd_track_pnp has not constructed solvers for these slots (or their matches / map points / rand stream were replaced since)");
   SD_REQUIRE(h->pnp_serial == h->cur->extract_serial, SD_ERR_INVALID_ARG,
@@ -916,13 +830,12 @@ int sd_track_pnp_iterate(sd_track* h, int n_frames, int n_iterations) {
   SD_REQUIRE(n_iterations >= 0, SD_ERR_INVALID_ARG, "bad n_iterations");
   PnpParams pp = h->pnp_params;
   const long long upper = std::max<long long>(pp.max_iterations, (long long)h->pnp_iter_upper + n_iterations);
-  rc = check_rand(h, n_frames, (long long)pp.min_set * upper);
-  if (rc != SD_OK) return rc;
+  SD_TRY(check_rand(h, n_frames, (long long)pp.min_set * upper));
   pp.n_iterations = n_iterations;
   pp.resume = 1;
-  rc = run_pnp(h, n_frames, pp);
-  if (rc == SD_OK) h->pnp_iter_upper = (int)upper;
-  return rc;
+  SD_TRY(run_pnp(h, n_frames, pp));
+  h->pnp_iter_upper = (int)upper;
+  return SD_OK;
 }
 
 int sd_track_get_align(sd_track* h, int frame0, int n_frames, double* Tcur_cm, double* error, int32_t* ok, int32_t* iters,
@@ -930,38 +843,31 @@ int sd_track_get_align(sd_track* h, int frame0, int n_frames, double* Tcur_cm, d
   TRACK_RANGE(h, frame0, n_frames);
   hipStream_t s = h->cur->stream;
   const size_t o = frame0, n = n_frames;
-  if (Tcur_cm) SD_HIP_CHECK(hipMemcpyAsync(Tcur_cm, h->tb.Tcur + o * 16, n * 128, hipMemcpyDeviceToHost, s));
-  if (error) SD_HIP_CHECK(hipMemcpyAsync(error, h->tb.al_err + o, n * 8, hipMemcpyDeviceToHost, s));
-  if (ok) SD_HIP_CHECK(hipMemcpyAsync(ok, h->tb.al_ok + o, n * 4, hipMemcpyDeviceToHost, s));
-  if (iters) SD_HIP_CHECK(hipMemcpyAsync(iters, h->tb.al_iters + o * 16, n * 64, hipMemcpyDeviceToHost, s));
-  if (chi2) SD_HIP_CHECK(hipMemcpyAsync(chi2, h->tb.al_chi2 + o, n * 8, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(download(Tcur_cm, h->tb.Tcur, o, n, 16, s));
+  SD_TRY(download(error, h->tb.al_err, o, n, 1, s));
+  SD_TRY(download(ok, h->tb.al_ok, o, n, 1, s));
+  SD_TRY(download(iters, h->tb.al_iters, o, n, 16, s));
+  SD_TRY(download(chi2, h->tb.al_chi2, o, n, 1, s));
+  return wait_for(s);
 }
 
 int sd_track_get_matches(sd_track* h, int frame0, int n_frames, int32_t* cur_match, int cap, int32_t* n_matches) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(!cur_match || cap >= h->kp_cap, SD_ERR_CAPACITY, "cap smaller than the keypoint capacity");
   hipStream_t s = h->cur->stream;
-  if (cur_match)
-    SD_HIP_CHECK(hipMemcpy2DAsync(cur_match, (size_t)cap * 4, h->tb.cur_match + (size_t)frame0 * h->kp_cap, (size_t)h->kp_cap * 4,
-                                  (size_t)h->kp_cap * 4, n_frames, hipMemcpyDeviceToHost, s));
-  if (n_matches) SD_HIP_CHECK(hipMemcpyAsync(n_matches, h->tb.n_matches + frame0, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(download_rows(cur_match, cap, h->tb.cur_match, frame0, n_frames, h->kp_cap, s));
+  SD_TRY(download(n_matches, h->tb.n_matches, frame0, n_frames, 1, s));
+  return wait_for(s);
 }
 
 int sd_track_get_pnp(sd_track* h, int frame0, int n_frames, float* Tcw_rowmajor, uint8_t* inliers, int cap, int32_t* info8) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(!inliers || cap >= h->kp_cap, SD_ERR_CAPACITY, "cap smaller than the keypoint capacity");
   hipStream_t s = h->cur->stream;
-  if (Tcw_rowmajor) SD_HIP_CHECK(hipMemcpyAsync(Tcw_rowmajor, h->tb.pnp_T + (size_t)frame0 * 16, (size_t)n_frames * 64, hipMemcpyDeviceToHost, s));
-  if (inliers)
-    SD_HIP_CHECK(hipMemcpy2DAsync(inliers, cap, h->tb.pnp_inliers + (size_t)frame0 * h->kp_cap, h->kp_cap, h->kp_cap, n_frames,
-                                  hipMemcpyDeviceToHost, s));
-  if (info8) SD_HIP_CHECK(hipMemcpyAsync(info8, h->tb.pnp_info + (size_t)frame0 * 8, (size_t)n_frames * 32, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(download(Tcw_rowmajor, h->tb.pnp_T, frame0, n_frames, 16, s));
+  SD_TRY(download_rows(inliers, cap, h->tb.pnp_inliers, frame0, n_frames, h->kp_cap, s));
+  SD_TRY(download(info8, h->tb.pnp_info, frame0, n_frames, 8, s));
+  return wait_for(s);
 }
 
 // EPnP (compute_pose, src/PnPsolver.cc:445-492) alone on explicit correspondences -- parity diagnostics
@@ -1002,27 +908,25 @@ int sd_track_debug_read(sd_track* h, int which, int frame, void* out, size_t byt
 // indices in the reference's order; grid_counts (may be NULL): mGrid[x][y].size() as [64][48] ints.
 int sd_track_debug_features_in_area(sd_track* h, int frame, float x, float y, float r, int min_level, int max_level, int32_t* indices,
                                     int cap, int32_t* n_out, int32_t* grid_counts) {
-  int rc = check_ready(h, frame + 1, true);
-  if (rc != SD_OK) return rc;
+  SD_TRY(check_ready(h, frame + 1, true));
   SD_REQUIRE(frame >= 0 && indices && n_out && cap >= 0, SD_ERR_INVALID_ARG, "bad arguments");
   hipStream_t s = h->pnp_stream;
-  rc = wait_inputs(h, false);
-  if (rc != SD_OK) return rc;
+  SD_TRY(wait_inputs(h, false));
   int32_t* d = nullptr;
   const size_t n_ints = (size_t)h->kp_cap + 1 + 64 * 48;
-  SD_HIP_CHECK(hipMalloc(&d, n_ints * 4));
-  rc = launch_features_in_area(h->cur, h->tb, h->cam, frame, x, y, r, min_level, max_level, d, h->kp_cap, d + h->kp_cap, d + h->kp_cap + 1, s);
+  SD_HIP_CHECK(hipMalloc(&d, n_ints * sizeof(int32_t)));
+  const int rc = launch_features_in_area(h->cur, h->tb, h->cam, frame, x, y, r, min_level, max_level, d, h->kp_cap, d + h->kp_cap, d + h->kp_cap + 1, s);
   std::vector<int32_t> host(n_ints);
-  hipError_t e = hipMemcpyAsync(host.data(), d, n_ints * 4, hipMemcpyDeviceToHost, s);
+  hipError_t e = hipMemcpyAsync(host.data(), d, n_ints * sizeof(int32_t), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   (void)hipFree(d);
-  if (rc != SD_OK) return rc;
+  SD_TRY(rc);
   if (e != hipSuccess) { set_error(std::string("sd_track_debug_features_in_area: ") + hipGetErrorString(e)); return SD_ERR_HIP; }
   const int n = host[h->kp_cap];
   *n_out = n;
   SD_REQUIRE(n <= cap, SD_ERR_CAPACITY, "indices array too small");
-  std::memcpy(indices, host.data(), (size_t)n * 4);
-  if (grid_counts) std::memcpy(grid_counts, host.data() + h->kp_cap + 1, 64 * 48 * 4);
+  std::memcpy(indices, host.data(), (size_t)n * sizeof(int32_t));
+  if (grid_counts) std::memcpy(grid_counts, host.data() + h->kp_cap + 1, 64 * 48 * sizeof(int32_t));
   return SD_OK;
 }
 
@@ -1082,8 +986,8 @@ int sd_track_stage_ms(sd_track* h, float* ms_out, int cap) {
     const int n = std::min(h->ev_calls[k], (int)sd_track::kRing);
     for (int r = 0; r < n; r++) {
       float ms = 0;
-      const int slot = (h->ev_calls[k] - 1 - r) % sd_track::kRing;
-      SD_HIP_CHECK(hipEventElapsedTime(&ms, h->ev[slot][2 * k], h->ev[slot][2 * k + 1]));
+      const hipEvent_t* ev = stage_events(h, k, h->ev_calls[k] - 1 - r);
+      SD_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
       ms_out[k] += ms / n;
     }
   }

@@ -1,5 +1,9 @@
 // The sd_track handle and the host helpers its entry points share (track.hip: creation and the batched stages;
-// track_seq.hip: sequential tracking).  Not part of the ABI.
+// track_seq.hip: sequential tracking).  Not part of the ABI.  In order: UploadRing and RunStamp (the sequential loop's two
+// small types), the handle, wait_inputs / mark_reads (ordering against the extractors), the argument preambles (check_ready,
+// check_batch / check_paired, check_range with TRACK_RANGE / QUEUE_RANGE, require_ref_frames), the stage timers and run_stage
+// (the bracket every batched stage launches in), and the typed copies between host arrays and the per-slot device buffers
+// (download / upload, download_rows / upload_rows), whose byte counts come from the buffer's element type.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,7 +41,9 @@ struct UploadRing {
       if (ev[r]) (void)hipEventDestroy(ev[r]);
     }
   }
-  int upload(void* dst, const void* src, size_t bytes, hipStream_t s) {
+  template <typename T>
+  int upload(T* dst, const T* src, size_t count, hipStream_t s) {
+    const size_t bytes = count * sizeof(T);
     SD_REQUIRE(bytes <= slot_bytes, SD_ERR_CAPACITY, "upload exceeds the pinned ring buffer");
     const int r = next;
     next = (r + 1) % kSlots;
@@ -188,3 +194,74 @@ static inline int check_range(const sd_track* h, int frame0, int n, RangeUse use
 }
 #define TRACK_RANGE(h, frame0, n) SD_TRY(check_range((h), (frame0), (n), RANGE_SYNC))
 #define QUEUE_RANGE(h, frame0, n) SD_TRY(check_range((h), (frame0), (n), RANGE_QUEUE))
+
+// Frames 0 .. n_frames - 1 of the `ref` extractor exist; same_size: and have the geometry of the current frames (ImageAlign)
+static inline int require_ref_frames(const sd_track* h, int n_frames, bool same_size) {
+  const bool extracted = h->ref->have_geom && h->ref->last_frames >= n_frames;
+  if (same_size)
+    SD_REQUIRE(extracted && h->ref->cur_w == h->cur->cur_w && h->ref->cur_h == h->cur->cur_h, SD_ERR_INVALID_ARG,
+               "reference frames not extracted or of different size");
+  else
+    SD_REQUIRE(extracted, SD_ERR_INVALID_ARG, "keyframes of the ref extractor have not been extracted");
+  return SD_OK;
+}
+
+// Stage timers (sd_track_set_profiling / sd_track_stage_ms): call number c of stage k records its start and stop on the tracking
+// stream into events 2k and 2k + 1 of ring slot c % kRing.  stage_end counts the call whether or not its launch succeeded.
+enum { STAGE_NONE = -1, STAGE_ALIGN = 0, STAGE_MATCH = 1, STAGE_SOLVE = 2 };
+static inline hipEvent_t* stage_events(sd_track* h, int k, int call) { return &h->ev[call % sd_track::kRing][2 * k]; }
+static inline int stage_begin(sd_track* h, int k) {
+  if (h->profiling) SD_HIP_CHECK(hipEventRecord(stage_events(h, k, h->ev_calls[k])[0], h->pnp_stream));
+  return SD_OK;
+}
+static inline int stage_end(sd_track* h, int k) {
+  if (!h->profiling) return SD_OK;
+  SD_HIP_CHECK(hipEventRecord(stage_events(h, k, h->ev_calls[k])[1], h->pnp_stream));
+  h->ev_calls[k]++;
+  return SD_OK;
+}
+
+// What every single-launch stage does once its entry point has checked its arguments (check_ready first, then its own checks:
+// they stay in the entry point, in its order): wait for the extractions, launch(tracking stream) between the timer records of
+// stage `timer` (STAGE_NONE: untimed), mark the output sets as read.  need_ref: the launch reads the ref extractor's frames too.
+template <typename Launch>
+static inline int run_stage(sd_track* h, bool need_ref, bool pyramid_only, int timer, Launch&& launch) {
+  SD_TRY(wait_inputs(h, need_ref, pyramid_only));
+  if (timer != STAGE_NONE) SD_TRY(stage_begin(h, timer));
+  const int rc = launch(h->pnp_stream);
+  if (timer != STAGE_NONE) SD_TRY(stage_end(h, timer));
+  SD_TRY(rc);
+  return mark_reads(h, need_ref);
+}
+
+// The host wait that ends a getter or setter: its copies have run
+static inline int wait_for(hipStream_t s) {
+  SD_HIP_CHECK(hipStreamSynchronize(s));
+  return SD_OK;
+}
+
+// Slots frame0 .. frame0 + n - 1 of a device buffer with per_slot elements a slot, to / from a dense host array.  A NULL host
+// pointer is an output the caller does not want / an input it leaves as it is: no copy.
+template <typename T>
+static inline int download(T* dst, const T* src, size_t frame0, size_t n, size_t per_slot, hipStream_t s) {
+  if (dst) SD_HIP_CHECK(hipMemcpyAsync(dst, src + frame0 * per_slot, n * per_slot * sizeof(T), hipMemcpyDeviceToHost, s));
+  return SD_OK;
+}
+template <typename T>
+static inline int upload(T* dst, const T* src, size_t frame0, size_t n, size_t per_slot, hipStream_t s) {
+  if (src) SD_HIP_CHECK(hipMemcpyAsync(dst + frame0 * per_slot, src, n * per_slot * sizeof(T), hipMemcpyHostToDevice, s));
+  return SD_OK;
+}
+// The same where the host rows have a pitch of their own: n rows, the device's of K elements, the caller's of `cap` (>= K to
+// read whole rows, <= K to write the first `cap` elements of each).  Pitches in elements, of any size.
+template <typename T>
+static inline int download_rows(T* dst, size_t cap, const T* src, size_t frame0, size_t n, size_t K, hipStream_t s) {
+  if (dst)
+    SD_HIP_CHECK(hipMemcpy2DAsync(dst, cap * sizeof(T), src + frame0 * K, K * sizeof(T), K * sizeof(T), n, hipMemcpyDeviceToHost, s));
+  return SD_OK;
+}
+template <typename T>
+static inline int upload_rows(T* dst, size_t K, const T* src, size_t cap, size_t frame0, size_t n, hipStream_t s) {
+  SD_HIP_CHECK(hipMemcpy2DAsync(dst + frame0 * K, K * sizeof(T), src, cap * sizeof(T), cap * sizeof(T), n, hipMemcpyHostToDevice, s));
+  return SD_OK;
+}

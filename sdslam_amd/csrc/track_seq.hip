@@ -150,10 +150,10 @@ int sd_track_set_map_ids(sd_track* h, int frame0, int n_frames, int which, const
   SD_REQUIRE(which == 0 || which == 1, SD_ERR_INVALID_ARG, "which must be 0 (last-frame points) or 1 (local map points)");
   SD_REQUIRE(ids && cap >= 1 && cap <= h->max_points, SD_ERR_INVALID_ARG, "bad id array (cap must be 1..max_points)");
   const size_t M = h->max_points;
-  int32_t* dst = (which == 0 ? h->tb.last_id : h->tb.lm_id) + (size_t)frame0 * M;
+  int32_t* dst = which == 0 ? h->tb.last_id : h->tb.lm_id;
   hipStream_t s = h->cur->stream;
-  SD_HIP_CHECK(hipMemsetAsync(dst, 0xFF, (size_t)n_frames * M * 4, s));
-  SD_HIP_CHECK(hipMemcpy2DAsync(dst, M * 4, ids, (size_t)cap * 4, (size_t)cap * 4, n_frames, hipMemcpyHostToDevice, s));
+  SD_HIP_CHECK(hipMemsetAsync(dst + (size_t)frame0 * M, 0xFF, (size_t)n_frames * M * sizeof(int32_t), s));
+  SD_TRY(upload_rows(dst, M, ids, cap, frame0, n_frames, s));
   SD_HIP_CHECK(hipStreamSynchronize(s));
   h->ids_on = true;
   return SD_OK;
@@ -175,9 +175,7 @@ int sd_track_advance(sd_track* h, int n_frames, int source) {
                "map points were created on this extraction from another source (sd_track_stereo_init: advance with source 2)");
   }
   const int created_n = made ? h->made.n : 0;
-  int nsel_ref = 0;
-  for (int q : h->ref->hp.quota) nsel_ref += q;
-  SD_REQUIRE(nsel_ref == h->kp_cap && h->cur->max_batch >= h->max_batch, SD_ERR_INVALID_ARG,
+  SD_REQUIRE(keypoint_capacity(h->ref) == h->kp_cap && h->cur->max_batch >= h->max_batch, SD_ERR_INVALID_ARG,
              "cur / ref extractors must share the keypoint capacity and hold max_batch frames to swap roles");
   SD_HIP_CHECK(hipSetDevice(h->device));
   // the new `cur` is extracted into next while tracking kernels may still read its last output set: it needs two
@@ -219,9 +217,8 @@ int sd_track_close_points(sd_track* h, int n_frames, int source, float th_depth)
 int sd_track_get_close_points(sd_track* h, int frame0, int n_frames, int32_t* out2) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(out2, SD_ERR_INVALID_ARG, "NULL argument");
-  SD_HIP_CHECK(hipMemcpyAsync(out2, h->d_close + (size_t)frame0 * 2, (size_t)n_frames * 8, hipMemcpyDeviceToHost, h->cur->stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
-  return SD_OK;
+  SD_TRY(download(out2, h->d_close, frame0, n_frames, 2, h->cur->stream));
+  return wait_for(h->cur->stream);
 }
 
 // ---- RGB-D map point creation and the keyframe decision on the device (kernels: track_newpoints.hip)
@@ -229,13 +226,13 @@ int sd_track_get_close_points(sd_track* h, int frame0, int n_frames, int32_t* ou
 int sd_track_set_next_map_id(sd_track* h, int frame0, int n_frames, const int32_t* next_id) {
   SD_REQUIRE(h && next_id, SD_ERR_INVALID_ARG, "NULL argument");
   QUEUE_RANGE(h, frame0, n_frames);
-  return h->small_ring.upload(h->tb.next_id + frame0, next_id, (size_t)n_frames * 4, h->pnp_stream);
+  return h->small_ring.upload(h->tb.next_id + frame0, next_id, (size_t)n_frames, h->pnp_stream);
 }
 
 int sd_track_set_keyframe_state(sd_track* h, int frame0, int n_frames, const int32_t* state8) {
   SD_REQUIRE(h && state8, SD_ERR_INVALID_ARG, "NULL argument");
   QUEUE_RANGE(h, frame0, n_frames);
-  SD_TRY(h->small_ring.upload(h->d_kf_stage, state8, (size_t)n_frames * 32, h->pnp_stream));
+  SD_TRY(h->small_ring.upload(h->d_kf_stage, state8, (size_t)n_frames * 8, h->pnp_stream));
   return launch_set_keyframe_state(h->tb, h->d_kf_stage, frame0, n_frames, h->pnp_stream);
 }
 
@@ -248,9 +245,8 @@ int sd_track_set_keyframe_flags(sd_track* h, int frame0, int n_frames, const uin
 int sd_track_get_keyframe_flags(sd_track* h, int frame0, int n_frames, uint8_t* flags) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(flags, SD_ERR_INVALID_ARG, "NULL argument");
-  SD_HIP_CHECK(hipMemcpyAsync(flags, h->tb.kf_flags + frame0, (size_t)n_frames, hipMemcpyDeviceToHost, h->cur->stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
-  return SD_OK;
+  SD_TRY(download(flags, h->tb.kf_flags, frame0, n_frames, 1, h->cur->stream));
+  return wait_for(h->cur->stream);
 }
 
 int sd_track_need_keyframe(sd_track* h, int n_frames, int rgbd, int frame_id, int min_frames, int max_frames) {
@@ -299,10 +295,10 @@ int sd_track_get_created(sd_track* h, int frame0, int n_frames, int32_t* info4, 
   hipStream_t s = h->cur->stream;
   std::vector<int32_t> list(n * K), id(n * K);
   std::vector<double> X(n * K * 3);
-  SD_HIP_CHECK(hipMemcpyAsync(info4, tb.np_info + o * 4, n * 16, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipMemcpyAsync(list.data(), tb.np_list + o * K, n * K * 4, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipMemcpyAsync(id.data(), tb.np_id + o * K, n * K * 4, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipMemcpyAsync(X.data(), tb.np_Xw + o * K * 3, n * K * 24, hipMemcpyDeviceToHost, s));
+  SD_TRY(download(info4, tb.np_info, o, n, 4, s));
+  SD_TRY(download(list.data(), tb.np_list, o, n, K, s));
+  SD_TRY(download(id.data(), tb.np_id, o, n, K, s));
+  SD_TRY(download(X.data(), tb.np_Xw, o, n, K * 3, s));
   SD_HIP_CHECK(hipStreamSynchronize(s));
   for (size_t f = 0; f < n; f++) SD_REQUIRE(info4[f * 4 + 1] <= cap, SD_ERR_CAPACITY, "cap is smaller than a slot's number of created points");
   for (size_t f = 0; f < n; f++)
@@ -310,7 +306,7 @@ int sd_track_get_created(sd_track* h, int frame0, int n_frames, int32_t* info4, 
       const size_t i = (size_t)list[f * K + r], d = f * (size_t)cap + r;
       if (kp_index) kp_index[d] = (int32_t)i;
       if (ids) ids[d] = id[f * K + i];
-      if (Xw) std::memcpy(Xw + d * 3, &X[(f * K + i) * 3], 24);
+      if (Xw) std::memcpy(Xw + d * 3, &X[(f * K + i) * 3], 3 * sizeof(double));
     }
   return SD_OK;
 }
@@ -320,7 +316,7 @@ int sd_track_set_prior(sd_track* h, int frame0, int n_frames, const double* T_cm
   SD_TRY(check_range(h, frame0, n_frames, RANGE_CHECK));
   SD_REQUIRE(relative == 0 || relative == 1, SD_ERR_INVALID_ARG, "relative must be 0 or 1");
   SD_HIP_CHECK(hipSetDevice(h->device));
-  SD_TRY(h->pose_ring.upload(h->d_prior, T_cm, (size_t)n_frames * 128, h->pnp_stream));
+  SD_TRY(h->pose_ring.upload(h->d_prior, T_cm, (size_t)n_frames * 16, h->pnp_stream));
   hipLaunchKernelGGL(k_set_prior, dim3((n_frames * 16 + 255) / 256), dim3(256), 0, h->pnp_stream, h->d_prior, h->tb, frame0, n_frames, relative);
   SD_HIP_CHECK(hipGetLastError());
   return SD_OK;
@@ -364,14 +360,13 @@ int sd_track_get_motion(sd_track* h, int frame0, int n_frames, double* X6, doubl
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
   const size_t o = frame0, n = n_frames;
-  if (X6) SD_HIP_CHECK(hipMemcpyAsync(X6, tb.mo_X + o * 6, n * 48, hipMemcpyDeviceToHost, s));
-  if (Pdiag6) SD_HIP_CHECK(hipMemcpyAsync(Pdiag6, tb.mo_P + o * 6, n * 48, hipMemcpyDeviceToHost, s));
-  if (started) SD_HIP_CHECK(hipMemcpyAsync(started, tb.mo_started + o, n * 4, hipMemcpyDeviceToHost, s));
-  if (it_time) SD_HIP_CHECK(hipMemcpyAsync(it_time, tb.mo_it + o, n * 8, hipMemcpyDeviceToHost, s));
-  if (E_cm) SD_HIP_CHECK(hipMemcpyAsync(E_cm, tb.mo_E + o * 16, n * 128, hipMemcpyDeviceToHost, s));
-  if (last_pose_cm) SD_HIP_CHECK(hipMemcpyAsync(last_pose_cm, tb.mo_last + o * 16, n * 128, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(download(X6, tb.mo_X, o, n, 6, s));
+  SD_TRY(download(Pdiag6, tb.mo_P, o, n, 6, s));
+  SD_TRY(download(started, tb.mo_started, o, n, 1, s));
+  SD_TRY(download(it_time, tb.mo_it, o, n, 1, s));
+  SD_TRY(download(E_cm, tb.mo_E, o, n, 16, s));
+  SD_TRY(download(last_pose_cm, tb.mo_last, o, n, 16, s));
+  return wait_for(s);
 }
 
 int sd_track_set_motion(sd_track* h, int frame0, int n_frames, const double* X6, const double* Pdiag6, const int32_t* started,
@@ -381,12 +376,11 @@ int sd_track_set_motion(sd_track* h, int frame0, int n_frames, const double* X6,
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
   const size_t o = frame0, n = n_frames;
-  if (X6) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_X + o * 6, X6, n * 48, hipMemcpyHostToDevice, s));
-  if (Pdiag6) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_P + o * 6, Pdiag6, n * 48, hipMemcpyHostToDevice, s));
-  if (started) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_started + o, started, n * 4, hipMemcpyHostToDevice, s));
-  if (it_time) SD_HIP_CHECK(hipMemcpyAsync(tb.mo_it + o, it_time, n * 8, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(upload(tb.mo_X, X6, o, n, 6, s));
+  SD_TRY(upload(tb.mo_P, Pdiag6, o, n, 6, s));
+  SD_TRY(upload(tb.mo_started, started, o, n, 1, s));
+  SD_TRY(upload(tb.mo_it, it_time, o, n, 1, s));
+  return wait_for(s);
 }
 
 // ---- the IMU sensor model (kernels: track_imu.hip)
@@ -417,7 +411,7 @@ int sd_track_set_measurements(sd_track* h, int frame0, int n_frames, const doubl
   SD_REQUIRE(h->sensor_model == SD_SENSOR_IMU, SD_ERR_INVALID_ARG, "the constant-velocity model takes no measurements (sd_track_set_sensor_model)");
   for (size_t i = 0; i < (size_t)n_frames * 6; i++) SD_REQUIRE(std::isfinite(wa6[i]), SD_ERR_INVALID_ARG, "measurements must be finite");
   SD_HIP_CHECK(hipSetDevice(h->device));
-  SD_TRY(h->pose_ring.upload(h->tb.im_meas + (size_t)frame0 * 6, wa6, (size_t)n_frames * 48, h->pnp_stream));
+  SD_TRY(h->pose_ring.upload(h->tb.im_meas + (size_t)frame0 * 6, wa6, (size_t)n_frames * 6, h->pnp_stream));
   for (int f = frame0; f < frame0 + n_frames; f++) h->meas_set[f] = 1;
   return SD_OK;
 }
@@ -428,15 +422,14 @@ int sd_track_get_imu(sd_track* h, int frame0, int n_frames, double* X16, double*
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
   const size_t o = frame0, n = n_frames;
-  if (X16) SD_HIP_CHECK(hipMemcpyAsync(X16, tb.im_X + o * 16, n * 128, hipMemcpyDeviceToHost, s));
-  if (P256) SD_HIP_CHECK(hipMemcpyAsync(P256, tb.im_P + o * 256, n * 2048, hipMemcpyDeviceToHost, s));
-  if (gravity3) SD_HIP_CHECK(hipMemcpyAsync(gravity3, tb.im_g + o * 3, n * 24, hipMemcpyDeviceToHost, s));
-  if (started) SD_HIP_CHECK(hipMemcpyAsync(started, tb.im_started + o, n * 4, hipMemcpyDeviceToHost, s));
-  if (it_time) SD_HIP_CHECK(hipMemcpyAsync(it_time, tb.im_it + o, n * 8, hipMemcpyDeviceToHost, s));
-  if (last_pose_cm) SD_HIP_CHECK(hipMemcpyAsync(last_pose_cm, tb.im_last + o * 16, n * 128, hipMemcpyDeviceToHost, s));
-  if (measurements6) SD_HIP_CHECK(hipMemcpyAsync(measurements6, tb.im_meas + o * 6, n * 48, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(download(X16, tb.im_X, o, n, 16, s));
+  SD_TRY(download(P256, tb.im_P, o, n, 256, s));
+  SD_TRY(download(gravity3, tb.im_g, o, n, 3, s));
+  SD_TRY(download(started, tb.im_started, o, n, 1, s));
+  SD_TRY(download(it_time, tb.im_it, o, n, 1, s));
+  SD_TRY(download(last_pose_cm, tb.im_last, o, n, 16, s));
+  SD_TRY(download(measurements6, tb.im_meas, o, n, 6, s));
+  return wait_for(s);
 }
 
 int sd_track_set_imu(sd_track* h, int frame0, int n_frames, const double* X16, const double* P256, const double* gravity3,
@@ -446,13 +439,12 @@ int sd_track_set_imu(sd_track* h, int frame0, int n_frames, const double* X16, c
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
   const size_t o = frame0, n = n_frames;
-  if (X16) SD_HIP_CHECK(hipMemcpyAsync(tb.im_X + o * 16, X16, n * 128, hipMemcpyHostToDevice, s));
-  if (P256) SD_HIP_CHECK(hipMemcpyAsync(tb.im_P + o * 256, P256, n * 2048, hipMemcpyHostToDevice, s));
-  if (gravity3) SD_HIP_CHECK(hipMemcpyAsync(tb.im_g + o * 3, gravity3, n * 24, hipMemcpyHostToDevice, s));
-  if (started) SD_HIP_CHECK(hipMemcpyAsync(tb.im_started + o, started, n * 4, hipMemcpyHostToDevice, s));
-  if (it_time) SD_HIP_CHECK(hipMemcpyAsync(tb.im_it + o, it_time, n * 8, hipMemcpyHostToDevice, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(upload(tb.im_X, X16, o, n, 16, s));
+  SD_TRY(upload(tb.im_P, P256, o, n, 256, s));
+  SD_TRY(upload(tb.im_g, gravity3, o, n, 3, s));
+  SD_TRY(upload(tb.im_started, started, o, n, 1, s));
+  SD_TRY(upload(tb.im_it, it_time, o, n, 1, s));
+  return wait_for(s);
 }
 
 int sd_track_get_last(sd_track* h, int frame0, int n_frames, int32_t* n_last, uint8_t* valid, double* Xw, uint8_t* desc, int32_t* octave,
@@ -461,16 +453,15 @@ int sd_track_get_last(sd_track* h, int frame0, int n_frames, int32_t* n_last, ui
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
   const size_t M = h->max_points, o = frame0, n = n_frames;
-  if (n_last) SD_HIP_CHECK(hipMemcpyAsync(n_last, tb.n_last + o, n * 4, hipMemcpyDeviceToHost, s));
-  if (valid) SD_HIP_CHECK(hipMemcpyAsync(valid, tb.valid + o * M, n * M, hipMemcpyDeviceToHost, s));
-  if (Xw) SD_HIP_CHECK(hipMemcpyAsync(Xw, tb.Xw + o * M * 3, n * M * 24, hipMemcpyDeviceToHost, s));
-  if (desc) SD_HIP_CHECK(hipMemcpyAsync(desc, tb.mp_desc + o * M * 32, n * M * 32, hipMemcpyDeviceToHost, s));
-  if (octave) SD_HIP_CHECK(hipMemcpyAsync(octave, tb.octave + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
-  if (angle) SD_HIP_CHECK(hipMemcpyAsync(angle, tb.angle + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
-  if (obs) SD_HIP_CHECK(hipMemcpyAsync(obs, tb.obs + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
-  if (ids) SD_HIP_CHECK(hipMemcpyAsync(ids, tb.last_id + o * M, n * M * 4, hipMemcpyDeviceToHost, s));
-  SD_HIP_CHECK(hipStreamSynchronize(s));
-  return SD_OK;
+  SD_TRY(download(n_last, tb.n_last, o, n, 1, s));
+  SD_TRY(download(valid, tb.valid, o, n, M, s));
+  SD_TRY(download(Xw, tb.Xw, o, n, M * 3, s));
+  SD_TRY(download(desc, tb.mp_desc, o, n, M * 32, s));
+  SD_TRY(download(octave, tb.octave, o, n, M, s));
+  SD_TRY(download(angle, tb.angle, o, n, M, s));
+  SD_TRY(download(obs, tb.obs, o, n, M, s));
+  SD_TRY(download(ids, tb.last_id, o, n, M, s));
+  return wait_for(s);
 }
 
 }  // extern "C"

@@ -1037,3 +1037,27 @@ def test_tracker_errors_are_loud(sd):
         trk.set_local(0, [big])                           # more local points than max_points
     with pytest.raises(sd.SdError):
         sd.Tracker(cur, ref, max_points=5000, max_batch=2)   # beyond the matcher's index width
+
+
+def test_stage_timers_past_the_ring(sd, oracle, rig):
+    """More timed calls than the ring of 128 event pairs holds: every stage is timed in its own slot, a stage that has not
+    run reports exactly 0, and switching profiling off and on restarts the three counters."""
+    trk = rig["trk"]
+    s = rig["scenes"][0]
+    trk.set_poses(0, [s["T_ref"]], [s["T_cur"]])
+    trk.set_profiling(True)
+    try:
+        for _ in range(130):
+            trk.match(1)
+        ms = trk.stage_ms()
+        assert np.isfinite(ms[1]) and ms[1] > 0, ms
+        assert ms[0] == 0.0 and ms[2] == 0.0, ms
+        trk.align(1, mode=0)
+        trk.pose_opt(1, source=0)
+        ms = trk.stage_ms()
+        assert np.isfinite(ms).all() and (ms > 0).all(), ms
+        trk.set_profiling(False)
+        trk.set_profiling(True)
+        assert (trk.stage_ms() == 0.0).all()
+    finally:
+        trk.set_profiling(False)
