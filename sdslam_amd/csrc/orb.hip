@@ -600,13 +600,15 @@ extern "C" __device__ __attribute__((const)) int __ockl_wfred_add_i32(int);
 #ifndef FAST_STAGE_DEPTH
 #define FAST_STAGE_DEPTH 12   // tile dwords in flight per thread while staging (256 threads x 12 x 4 B = 12 KB per round trip)
 #endif
+typedef uint32_t fast_u4 __attribute__((ext_vector_type(4)));   // one 16-byte staging unit (global_load_dwordx4 / ds_write_b128)
 
 // 8 waves per SIMD: the kernel needed 65 VGPRs, one over the 64-register step; held to 64 it gains a resident wave per SIMD
 // and the whole extraction 5 % (169 k -> 177 k frames/s ORB-only)
 // Everything the workgroup needs besides its CellGeom arrives as kernel arguments (no dependent cell -> level -> plan loads):
 // img0 / frame_stride / src / edge describe the levels' rows -- the padded pyramid (edge = SD_EDGE), or, for level 0, the
 // caller's frames themselves (edge = 0; 4-byte aligned base and strides): FAST only touches interior pixels (the zones
-// start SD_EDGE - 3 px inside), so level 0 need not wait for the padded copy of the frame.  One launch covers the cells
+// start SD_EDGE - 3 px inside), so level 0 need not wait for the padded copy of the frame.  wide16: base, row pitch and frame
+// stride are all 16-byte aligned (always so for the pyramid), the tile is staged in 16-byte units.  One launch covers the cells
 // cell0 .. cell0 + gridDim.x - 1, of one level or of several consecutive ones (the small levels go together: each of their
 // launches was mostly ramp-up and tail).
 struct FastSrc {   // where the rows of a level start inside a frame's block, and their pitch (by value: one launch may span levels)
@@ -617,7 +619,7 @@ struct FastSrc {   // where the rows of a level start inside a frame's block, an
 __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restrict__ cells, const uint8_t* __restrict__ img0,
                                                     size_t frame_stride, const FastSrc src, int edge, uint32_t* __restrict__ cand,
                                                     uint32_t cand_per_frame, int32_t* __restrict__ cell_count, int ncells_total,
-                                                    int cell0, int th) {
+                                                    int cell0, int th, int wide16) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   __shared__ int wcnt[4];
   unsigned uframe, ucell;
@@ -635,20 +637,25 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
   const int pstride = src.pstride[C.level];
   uint32_t* out = cand + (size_t)frame * cand_per_frame + C.cand_off;
   const int zw = C.zw, zh = C.zh, S = C.strip_rows;
+  // r5: the tile's left edge is aligned down to 16 bytes and its pitch is a multiple of 16, so a row is a whole number of
+  // 16-byte units both in the source and in LDS; the score map has the SAME pitch, so that a pixel's byte offset from the
+  // tile's first zone pixel (the queue entry) addresses its ring (tile0 + entry) and its score (sc0 + entry) alike.
   const int xs = C.zx0 - 3 + edge;   // x of tile column 0 in the source rows (before alignment)
-  const int xa = xs & ~3, sh = xs - xa;
-  const int TPW = (sh + zw + 6 + 3) >> 2;   // tile pitch in 4-byte words
-  const int TP = TPW * 4;
-  const int SP = (zw + 2 + 3) & ~3;         // score-map pitch (bytes)
-  const int RPW = (S + 2 + 3) >> 2;         // score rows per wave (upper bound)
+  const int xa = xs & ~15, sh = xs - xa;
+  const int TPU = (sh + zw + 6 + 15) >> 4;   // tile pitch in 16-byte units
+  const int TP = TPU * 16;
+  const int NSR = min(S + 2, zh);           // zone rows a strip scores at most: its own and one above / below (a whole-cell strip has neither)
+  const int RPW = (NSR + 3) >> 2;           // score rows per wave (upper bound)
   const int QCAP = RPW * zw;                // queue entries per wave (worst case: every pixel)
   uint8_t* tile = smem;
-  uint8_t* sc = smem + (size_t)TP * (S + 2 + 6);
-  uint16_t* queue = (uint16_t*)(sc + (size_t)SP * (S + 2 + 2)) + (size_t)wave * QCAP;
+  uint8_t* sc = smem + (size_t)TP * (NSR + 6);   // score map: rows -1 ... nsr, columns -1 ... TP - 2 of the zone
+  uint16_t* queue = (uint16_t*)(sc + (size_t)TP * (NSR + 2)) + (size_t)wave * QCAP;
   // the wave's queue as a scalar byte offset into the dynamic LDS (phase A stores through SGPR base + lane offset)
-  const uint32_t qbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)((size_t)TP * (S + 2 + 6) + (size_t)SP * (S + 2 + 2) + (size_t)wave * QCAP * 2));
+  const uint32_t qbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)((size_t)TP * (2 * NSR + 8) + (size_t)wave * QCAP * 2));
   const unsigned magic = 0xFFFFFFFFu / (unsigned)zw + 1u;   // q / zw == umulhi(q, magic) for q < 2^16, zw < 2^12
-  const unsigned magic_tpw = 0xFFFFFFFFu / (unsigned)TPW + 1u;   // tile dword index / TPW (indices < 2^16: the tile is < 64 KB)
+  const unsigned magic_tp = 0xFFFFFFFFu / (unsigned)TP + 1u;   // queue entry / TP (entries < 2^16: the tile is < 64 KB)
+  const uint8_t* tile0 = tile + 3 * TP + 3 + sh;   // zone pixel (0, 0) of the strip
+  uint8_t* sc0 = sc + TP + 1;                      // its score
   const unsigned long long lt = lanemask_lt();
   int total = 0;
   FPROF_DECL;
@@ -658,31 +665,60 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
     const int sr0 = max(r0 - 1, 0), sr1 = min(r1 + 1, zh);   // zone rows whose scores are needed
     const int nsr = sr1 - sr0;
     const int npr = nsr + 6;
-    // ---- stage pixels (aligned words) and clear the score map.  The tile's dwords are numbered row-major and dealt to the
-    // 256 threads FAST_STAGE_DEPTH at a time, all loads before the first LDS store: a tile of up to 12 KB is ONE global round
-    // trip (the strip's life is mostly this wait: with 8 rows per wave and batch it was three)
+    // ---- stage pixels and clear the score map.  The tile's 16-byte units are numbered row-major and dealt to the 256 threads
+    // FAST_STAGE_DEPTH / 4 at a time, all loads before the first LDS store: a tile of up to 12 KB is ONE global round trip (the
+    // strip's life is mostly this wait: with 8 rows per wave and batch it was three).  Row and column are computed once per
+    // unit; unit i lands at LDS byte 16 * i (the tile is linear in its units).
+    // Why the last unit of a row never leaves the source row's allocation: a tile row ends at up(xe, 16), xe = zx0 + zw + 3 +
+    // edge the first column the ring does not need, and zx0 + zw <= w - SD_EDGE for every cell the plan evaluates.  Pyramid
+    // (edge = SD_EDGE): xe <= w + 3 <= w + 2 * SD_EDGE <= pstride, and pstride is a multiple of 64, hence up(xe, 16) <= pstride.
+    // Caller frames (edge = 0): xe <= w - 16, hence up(xe, 16) < w <= stride, whatever the stride's alignment (and the last
+    // row staged is SD_EDGE - 3 rows above the frame's last, so even a frame allocated without its last row's padding is safe).
     {
       const uint8_t* g = img + (size_t)(C.zy0 + sr0 - 3 + edge) * pstride + xa;
-      const int ndw = __mul24(TPW, npr);
       int t0 = tid;
       asm volatile("" : "+v"(t0));   // opaque per strip: otherwise the row / column of every slot is hoisted out of the strip loop and spilled
-      for (int i0 = t0; i0 < ndw; i0 += 256 * FAST_STAGE_DEPTH) {
-        uint32_t v[FAST_STAGE_DEPTH];
+      if (wide16) {   // wave-uniform (kernel argument)
+        const int nu = __mul24(TPU, npr);
+        // (2 i + 1) * floor(2^31 / d) >> 32 == i / d for i * d <= 2^30 -- and, unlike the usual magic number, for d == 1 (zones
+        // narrower than 11 pixels have one-unit rows)
+        const unsigned magic_tpu = 0x80000000u / (unsigned)TPU;
+        for (int i0 = t0; i0 < nu; i0 += 256 * (FAST_STAGE_DEPTH / 4)) {
+          fast_u4 v[FAST_STAGE_DEPTH / 4];
 #pragma unroll
-        for (int j = 0; j < FAST_STAGE_DEPTH; j++) {
-          const int i = i0 + 256 * j;
-          const int row = (int)__umulhi((unsigned)i, magic_tpw), wc = i - __mul24(row, TPW);
-          v[j] = i < ndw ? *(const uint32_t*)(g + (uint32_t)(__mul24(row, pstride) + wc * 4)) : 0u;
+          for (int j = 0; j < FAST_STAGE_DEPTH / 4; j++) {
+            const int i = i0 + 256 * j;
+            const int row = (int)__umulhi(2u * (unsigned)i + 1u, magic_tpu), uc = i - __mul24(row, TPU);
+            v[j] = i < nu ? *(const fast_u4*)(g + (uint32_t)(__mul24(row, pstride) + uc * 16)) : fast_u4{0u, 0u, 0u, 0u};
+          }
+#pragma unroll
+          for (int j = 0; j < FAST_STAGE_DEPTH / 4; j++) {
+            const int i = i0 + 256 * j;
+            if (i < nu) ((fast_u4*)tile)[i] = v[j];
+          }
         }
+      } else {   // caller frames that are only 4-byte aligned: the same tile, one dword at a time
+        const int TPW = TPU * 4;
+        const int ndw = __mul24(TPW, npr);
+        const unsigned magic_tpw = 0xFFFFFFFFu / (unsigned)TPW + 1u;   // tile dword index / TPW (indices < 2^16: the tile is < 64 KB)
+        for (int i0 = t0; i0 < ndw; i0 += 256 * FAST_STAGE_DEPTH) {
+          uint32_t v[FAST_STAGE_DEPTH];
 #pragma unroll
-        for (int j = 0; j < FAST_STAGE_DEPTH; j++) {
-          const int i = i0 + 256 * j;
-          if (i < ndw) ((uint32_t*)tile)[i] = v[j];
+          for (int j = 0; j < FAST_STAGE_DEPTH; j++) {
+            const int i = i0 + 256 * j;
+            const int row = (int)__umulhi((unsigned)i, magic_tpw), wc = i - __mul24(row, TPW);
+            v[j] = i < ndw ? *(const uint32_t*)(g + (uint32_t)(__mul24(row, pstride) + wc * 4)) : 0u;
+          }
+#pragma unroll
+          for (int j = 0; j < FAST_STAGE_DEPTH; j++) {
+            const int i = i0 + 256 * j;
+            if (i < ndw) ((uint32_t*)tile)[i] = v[j];
+          }
         }
       }
       FPROF(7);   // kernel / strip start -> this wave's tile words are in LDS
-      const int nsc = ((nsr + 2) * SP) >> 2;
-      for (int i = tid; i < nsc; i += 256) ((uint32_t*)sc)[i] = 0;
+      const int nsc = __mul24(nsr + 2, TPU);
+      for (int i = tid; i < nsc; i += 256) ((fast_u4*)sc)[i] = fast_u4{0u, 0u, 0u, 0u};
     }
     __syncthreads();
     FPROF(0);
@@ -693,11 +729,11 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
     // r3: the wave's band of rows is walked as ONE flat range of pixel indices i = y * zw + x, 64 at a time, instead of row by
     // row: zones are 47...121 pixels wide, so row-wise chunks ran at 57-98 % lane use (74 % on average: a third more chunks, and
     // this phase is bound by LDS-instruction issue as much as by the vector ALU).  Costs one multiply-high and one multiply-add per
-    // chunk (row = i / zw by magic number, LDS address = i + row * (TP - zw) + const); the queue entry IS i.
+    // chunk (row = i / zw by magic number, tile offset = i + row * (TP - zw)); r5: the queue entry is that tile offset, y * TP + x,
+    // monotone in i (raster order is unchanged): phases B and C address ring and score with it and never take it apart.
     {
       const int i_lo = __mul24(y_lo, zw), i_hi = __mul24(y_hi, zw);
       const int pad = TP - zw;
-      const uint8_t* tile0 = tile + 3 * TP + 3 + sh;
 #ifdef FAST_SKIP_A
       for (int i0 = i_hi; i0 < i_hi; i0 += 64) {
 #else
@@ -709,7 +745,8 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
         // max(v - D, Bt - v) > th: 9 full-rate 16-bit instructions and ONE compare.
         const int i = min(i0 + lane, i_hi - 1);
         const int y = (int)__umulhi((unsigned)i, magic);
-        const uint8_t* c = tile0 + (i + __mul24(y, pad));
+        const int ofs = i + __mul24(y, pad);
+        const uint8_t* c = tile0 + ofs;
         const fu16 v = c[0], p0 = c[3 * TP], p4 = c[3], p8 = c[-3 * TP], p12 = c[-3];
         const fu16 D = fmax16(fmin16(p0, p8), fmin16(p4, p12));
         const fu16 Bt = fmin16(fmax16(p0, p8), fmax16(p4, p12));
@@ -718,7 +755,7 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
         if (i_hi - i0 < 64) pass = pass && (i0 + lane < i_hi);   // wave-uniform branch: only the band's last chunk pays this compare
         const unsigned long long m = __builtin_amdgcn_ballot_w64(pass);
         const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        if (pass) *(uint16_t*)(smem + (qbase + 2u * (uint32_t)(qn + rank))) = (uint16_t)i;
+        if (pass) *(uint16_t*)(smem + (qbase + 2u * (uint32_t)(qn + rank))) = (uint16_t)ofs;
         qn += __popcll(m);
       }
     }
@@ -740,14 +777,12 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
         const bool has_b = eb < qn;
         qa = queue[ea];
         qb = has_b ? queue[eb] : qa;
-        const int y_a = (int)__umulhi(qa, magic), x_a = (int)qa - __mul24(y_a, zw);
-        const int y_b = (int)__umulhi(qb, magic), x_b = (int)qb - __mul24(y_b, zw);
         int sa, sb;
-        fast_ring_score2(tile + __mul24(y_a + 3, TP) + x_a + 3 + sh, tile + __mul24(y_b + 3, TP) + x_b + 3 + sh, TP, sa, sb);
+        fast_ring_score2(tile0 + qa, tile0 + qb, TP, sa, sb);
         corner_a = sa >= th;
         corner_b = has_b && sb >= th;
-        if (corner_a && sa > 0) sc[__mul24(y_a + 1, SP) + x_a + 1] = (uint8_t)sa;
-        if (corner_b && sb > 0) sc[__mul24(y_b + 1, SP) + x_b + 1] = (uint8_t)sb;
+        if (corner_a && sa > 0) sc0[qa] = (uint8_t)sa;
+        if (corner_b && sb > 0) sc0[qb] = (uint8_t)sb;
       }
       const unsigned long long ma = __builtin_amdgcn_ballot_w64(corner_a);
       if (corner_a) queue[cn + __popcll(ma & lt)] = (uint16_t)qa;
@@ -769,21 +804,22 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
       unsigned long long bits = 0;
       int cnt = 0;
       const int nj = (qn + 63) >> 6;
+      // rows are contiguous ranges of tile offsets: "the corner's row belongs to this strip" (r0 <= sr0 + y < r1) is one unsigned
+      // compare of the entry against wave-uniform bounds
+      const unsigned own_lo = (unsigned)__mul24(r0 - sr0, TP), own_n = (unsigned)__mul24(r1 - r0, TP);
       for (int j = 0; j < nj; j++) {
         const int e = j * 64 + lane;
         bool keep = false;
         if (e < qn) {
           const unsigned q = queue[e];
-          const int y = (int)__umulhi(q, magic), x = (int)q - __mul24(y, zw);
-          const int yz = sr0 + y;
           // r3: the nine scores are read FIRST and reduced with max3 (strictly greater than all eight neighbours = greater than their
           // maximum).  Written as a short-circuit && chain this was nine dependent LDS round trips per chunk, each behind a branch
           // (ds_read_u8 -> s_waitcnt -> v_cmp -> s_and_saveexec); rows of the halo are inside the score map too, so nothing is conditional.
-          const uint8_t* p = sc + __mul24(y + 1, SP) + x + 1;
+          const uint8_t* p = sc0 + q;
           const int s = p[0];
-          const int n0 = p[-1], n1 = p[1], n2 = p[-SP - 1], n3 = p[-SP], n4 = p[-SP + 1], n5 = p[SP - 1], n6 = p[SP], n7 = p[SP + 1];
+          const int n0 = p[-1], n1 = p[1], n2 = p[-TP - 1], n3 = p[-TP], n4 = p[-TP + 1], n5 = p[TP - 1], n6 = p[TP], n7 = p[TP + 1];
           const int nm = max(max(max(n0, n1), n2), max(max(max(n3, n4), n5), max(n6, n7)));
-          keep = (s > 0) & (s > nm) & (yz >= r0) & (yz < r1);
+          keep = (s > 0) & (s > nm) & (q - own_lo < own_n);
         }
         const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
         cnt += __popcll(m);
@@ -799,8 +835,8 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
         const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
         if (keep) {
           const unsigned q = queue[j * 64 + lane];
-          const int y = (int)__umulhi(q, magic), x = (int)q - __mul24(y, zw);
-          const int s = sc[__mul24(y + 1, SP) + x + 1];
+          const int y = (int)__umulhi(q, magic_tp), x = (int)q - __mul24(y, TP);   // the one place that needs (y, x): the key of a survivor
+          const int s = sc0[q];
           const unsigned pos = (unsigned)(base + __popcll(m & lt));
           if (pos < C.cap)
             out[pos] = ((uint32_t)s << 24) | ((uint32_t)(C.zy0 + sr0 + y) << 12) | (uint32_t)(C.zx0 + x);
@@ -1536,6 +1572,8 @@ static int pipeline_body(sd_orb* h, const uint8_t* d_imgs, int n, int stride, si
   }
   const bool src_aligned = (((uintptr_t)d_imgs | (uintptr_t)stride | (uintptr_t)frame_stride) & 3) == 0;
   // FAST of level 0 reads the frames themselves when they are 4-byte aligned: it starts at once, beside the resize chain
+  // (in 16-byte units when base and strides allow, else dword by dword)
+  const bool src_wide = (((uintptr_t)d_imgs | (uintptr_t)stride | (uintptr_t)frame_stride) & 15) == 0;
   const bool fast0_direct = src_aligned && P.lv[0].ncells > 0 && opt(OPT_FAST0_FROM_FRAMES) != 0;
   const int ring_slot = h->ev_calls % sd_orb::kRing;
   int nfp = 0;   // FAST launches timed so far
@@ -1551,7 +1589,7 @@ static int pipeline_body(sd_orb* h, const uint8_t* d_imgs, int n, int stride, si
     fs0.pstride[0] = stride;
     fast_pair(true);
     hipLaunchKernelGGL(k_fast_cells, dim3(P.lv[0].ncells, n), dim3(256), hp.fast_lds_level[0], h->fast_stream, h->d_cells, d_imgs,
-                       frame_stride, fs0, 0, h->d_cand, P.cand_per_frame, h->d_cell_count, P.ncells, P.lv[0].cell0, P.thFAST);
+                       frame_stride, fs0, 0, h->d_cand, P.cand_per_frame, h->d_cell_count, P.ncells, P.lv[0].cell0, P.thFAST, src_wide ? 1 : 0);
     fast_pair(false);
   }
   FastSrc fsrc;
@@ -1600,7 +1638,7 @@ static int pipeline_body(sd_orb* h, const uint8_t* d_imgs, int n, int stride, si
       fast_pair(true);
       hipLaunchKernelGGL(k_fast_cells, dim3(ncl, n), dim3(256), lds, h->fast_stream, h->d_cells, (const uint8_t*)h->d_pyr,
                          (size_t)P.pyr_frame_bytes, fsrc, SD_EDGE, h->d_cand, P.cand_per_frame, h->d_cell_count, P.ncells, P.lv[first].cell0,
-                         P.thFAST);
+                         P.thFAST, 1);   // (d_pyr, the levels' offsets, their row pitches and the frame stride are multiples of 64)
       fast_pair(false);
     }
   }

@@ -278,12 +278,21 @@ bool plan_geometry(int nfeatures, int nlevels, int thFAST, int w, int h, HostPla
             // 34-KB level would take every small cell of that launch from 6 to 4 workgroups per CU -- 720p: 81.3 k -> 77.7 k)
             bool whole_pass = l < hp.fast_merge_from;   // first candidate: the whole cell under the larger budget
             if (!whole_pass) S = std::min(c.zh, std::max(1, 12288 / c.zw));
+            // r5: the tile's left edge is aligned down to 16 bytes (staged with 16-byte loads and LDS stores) and the score map has
+            // the tile's pitch (a queue entry is the pixel's byte offset in the tile, its score sits a constant further on).  The
+            // STRIP decision is still taken on the r2 sizes the budgets were measured with (4-byte alignment, tight score
+            // pitch): a cell that was one strip stays one strip, and the request is what the wider rows then need (up to 12 + 24
+            // bytes per row more; the kernel's queue entries are 16 bits, hence the tile-offset bound).
             for (;;) {
               size_t tp = up((size_t)c.zw + 6 + 3, 4), sp = up((size_t)c.zw + 2, 4);
               size_t rpw = (size_t)(S + 2 + 3) / 4;
+              const size_t tp16 = up((size_t)c.zw + 6 + 15, 16);   // any pad 0...15: the same cell is staged from the frames (edge 0) or the pyramid
               size_t need = tp * (S + 2 + 6) + sp * (S + 2 + 2) + 2 * 4 * rpw * c.zw + 64;
               const size_t budget = whole_pass ? std::max(whole_kb, lds_kb) : lds_kb;
-              bool fits = need <= budget * 1024 && rpw * c.zw <= 4096 && (size_t)(S + 2) * c.zw < 65536;
+              bool fits = need <= budget * 1024 && rpw * c.zw <= 4096 && (size_t)(std::min(S + 2, c.zh) + 1) * tp16 <= 65536;
+              const size_t nsr = (size_t)std::min(S + 2, c.zh);   // rows a strip scores: a whole-cell strip has no rows above / below
+              need = tp16 * (nsr + 6) + tp16 * (nsr + 2) + 2 * 4 * ((nsr + 3) / 4) * c.zw + 64;
+              fits = fits && need <= std::max(budget * 1024, (size_t)65536);   // (a launch may ask for 64 KB without opting in)
               if (whole_pass && !fits) {
                 whole_pass = false;
                 S = std::min(c.zh, std::max(1, 12288 / c.zw));
