@@ -1,4 +1,5 @@
-// ORB extraction on MI355X (gfx950): hand-written HIP kernels + the sd_orb_* C ABI.
+// ORB extraction on MI355X (gfx950): the hand-written HIP kernels and the pipeline that launches them (sd::orb_launch_pipeline).
+// The sd_orb handle and the sd_orb_* C ABI are in orb_host.hip; orb_internal.h is what the two files share.
 //
 // Replaces SD_SLAM::ORBextractor (reference src/ORBextractor.cc).  Batched-frames-first:
 // every kernel takes the frame index as its outermost grid dimension, so one launch covers
@@ -14,7 +15,7 @@
 //   k_undistort      Frame::UndistortKeyPoints     src/Frame.cc:335-366
 //
 // Streams per handle: main (resize chain, selection, descriptors), fast (FAST of a level as soon as the level is
-// complete), aux (blur); see launch_pipeline / pipeline_body and DESIGN.md section 5.
+// complete), aux (blur); see orb_launch_pipeline / pipeline_body and DESIGN.md section 5.
 // HBM layout (per frame): padded pyramid block (all levels, 19-px border, 64-B aligned rows),
 // blurred block (same geometry), candidate keys (u32: response<<24 | y<<12 | x, per cell, raster
 // order), selected keys per level, output keypoints (28 B) + descriptors (32 B).
@@ -24,20 +25,15 @@
 
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "introselect.h"
 #include "introselect_wave.h"
-#include "orb_plan.h"
-#include "sd_common.h"
+#include "orb_internal.h"
 #include "sd_sincosf.h"
 
 namespace sd {
-
-static thread_local std::string g_err;
-void set_error(const std::string& msg) { g_err = msg; }
 
 // ------------------------------------------------------------------------------------------
 // device helpers
@@ -123,7 +119,10 @@ __device__ __forceinline__ int win_byte(unsigned long long lo, unsigned long lon
   return b < 8 ? (int)((lo >> (8 * b)) & 0xff) : (int)((hi >> (8 * (b - 8))) & 0xff);
 }
 
-#define PYR_ROWS 1   // rows per thread (multi-row unrolling bought nothing and tripped a codegen problem in the byte packing)
+// rows per thread (multi-row unrolling bought nothing and tripped a codegen problem in the byte packing).  The one-iteration
+// loops of k_pyr_level stay: written without them the kernel compiles to other machine code (45 instead of 51 VGPRs, another
+// instruction stream), and it serves the reference's default 5 x 2.0 pyramid as measured.
+#define PYR_ROWS 1
 
 __device__ __forceinline__ uint32_t pyr_px4(const LevelGeom& L, const LevelGeom& S, size_t pyr_frame_bytes, int level, int frame, int px,
                                             int py, const uint8_t* __restrict__ src0, int src_stride, size_t src_frame_stride,
@@ -431,84 +430,15 @@ __global__ __launch_bounds__(256) void k_pyr_split(const LevelGeom L, const Leve
 // The cell (+3 px ring halo) is staged once through LDS in aligned 4-byte words; scores live in
 // a byte map in LDS; ordered emission uses wave ballots over wave-contiguous pixel ranges.
 // ------------------------------------------------------------------------------------------
-// FAST-9/16 on one pixel whose 7x7 neighbourhood is in LDS: ring differences d[k] = v - p[k]
-// (ring offsets (dx,dy) clockwise from (0,3): SURVEY App. A1).
-__device__ __forceinline__ void fast_ring(const uint8_t* __restrict__ c, int tp, int d[16]) {
-  const int v = c[0];
-  d[0] = v - c[3 * tp];
-  d[1] = v - c[3 * tp + 1];
-  d[2] = v - c[2 * tp + 2];
-  d[3] = v - c[tp + 3];
-  d[4] = v - c[3];
-  d[5] = v - c[-tp + 3];
-  d[6] = v - c[-2 * tp + 2];
-  d[7] = v - c[-3 * tp + 1];
-  d[8] = v - c[-3 * tp];
-  d[9] = v - c[-3 * tp - 1];
-  d[10] = v - c[-2 * tp - 2];
-  d[11] = v - c[-tp - 3];
-  d[12] = v - c[-3];
-  d[13] = v - c[tp - 3];
-  d[14] = v - c[2 * tp - 2];
-  d[15] = v - c[3 * tp - 1];
-}
-
-// corner test: >= 9 contiguous ring pixels darker than v - th or brighter than v + th
-__device__ __forceinline__ bool fast_is_corner(const uint8_t* __restrict__ c, int tp, int th) {
-  int d[16];
-  fast_ring(c, tp, d);
-  unsigned dark = 0, bright = 0;   // dark: p < v - th  <=> d > th ; bright: p > v + th <=> d < -th
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    dark |= (unsigned)(d[k] > th) << k;
-    bright |= (unsigned)(d[k] < -th) << k;
-  }
-  unsigned md = dark | (dark << 16), mb = bright | (bright << 16);
-  unsigned rd = md & (md >> 1);
-  rd &= rd >> 2;
-  rd &= rd >> 4;
-  rd &= md >> 8;
-  unsigned rb = mb & (mb >> 1);
-  rb &= rb >> 2;
-  rb &= rb >> 4;
-  rb &= mb >> 8;
-  return ((rd | rb) & 0xffffu) != 0;
-}
-
-// cornerScore<16>: max over the 16 nine-arcs of min(d) / min(-d), minus 1 (>= th for a corner)
-__device__ __forceinline__ int fast_corner_score(const uint8_t* __restrict__ c, int tp) {
-  int d[16];
-  fast_ring(c, tp, d);
-  int m2[16], m4[16], M2[16], M4[16];
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    m2[k] = min(d[k], d[(k + 1) & 15]);
-    M2[k] = max(d[k], d[(k + 1) & 15]);
-  }
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    m4[k] = min(m2[k], m2[(k + 2) & 15]);
-    M4[k] = max(M2[k], M2[(k + 2) & 15]);
-  }
-  int a = -255, b = 255;
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    int m9 = min(min(m4[k], m4[(k + 4) & 15]), d[(k + 8) & 15]);
-    int M9 = max(max(M4[k], M4[(k + 4) & 15]), d[(k + 8) & 15]);
-    a = max(a, m9);
-    b = min(b, M9);
-  }
-  return max(a, -b) - 1;
-}
-
 typedef unsigned short fu16;
 __device__ __forceinline__ fu16 fmin16(fu16 a, fu16 b) { return a < b ? a : b; }
 __device__ __forceinline__ fu16 fmax16(fu16 a, fu16 b) { return a > b ? a : b; }
 
 // Corner test and cornerScore in one: with A = min over the 16 nine-arcs of max(p) and
 // B = max over the arcs of min(p), a 9-arc darker than v - th exists iff v - A > th, a brighter one iff
-// B - v > th, and cornerScore = max(v - A, B - v) - 1 (the same quantity as fast_corner_score: min / max
-// of the differences d = v - p over an arc are v - max(p) / v - min(p)).  Sliding 9-windows on the ring
+// B - v > th, and cornerScore = max(v - A, B - v) - 1 (cv's cornerScore<16>: the max over the 16 nine-arcs of min(d) and of
+// min(-d) of the ring differences d = v - p, minus 1; min / max of d over an arc are v - max(p) / v - min(p)).  The ring is the
+// 16 offsets (dx, dy) clockwise from (0, 3).  Sliding 9-windows on the ring
 // are built from 3-windows: 2 x (16 + 16 + 8) three-input min / max.  The pixel is a corner iff score >= th.
 // r4: TWO pixels at once (ca: low 16-bit half, cb: high half), every min / max a gfx950 v_pk_minimum3_f16 /
 // v_pk_maximum3_f16 (4.16 cycles at 8 waves per SIMD, the rate of v_max3_i32: profiles/r04_valu_microbench_pk3.json), so the
@@ -868,7 +798,6 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
 // ------------------------------------------------------------------------------------------
 #define SEL_WAVES 8         // big-cell buffer = SEL_WAVES x the per-geometry cell capacity (what the single kernel's 8 waves held)
 #define SEL_LIST_CAP 1536   // level list (LDS)
-#define SEL_MAX_CELLS 512
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 
 // ------------------------------------------------------------------------------------------
@@ -1055,7 +984,6 @@ __global__ __launch_bounds__(64) void k_select_final(const OrbPlan* __restrict__
 // (the blurred image is not an output), which frees the stage from waiting for the selection.
 // ------------------------------------------------------------------------------------------
 #define BLUR_RB 32                  // output rows per wave
-#define SD_BLUR_SHIFT 1             // column offset of the blurred levels against the pyramid's layout (see k_blur)
 #ifndef BLUR_PF
 #define BLUR_PF 8                   // input rows in flight per thread (r3, with the 16-lane groups: 8 rows ORB-only 287.8 k, 6 rows 284.4 k, 4 rows 281.1 k)
 #endif
@@ -1429,199 +1357,116 @@ __global__ void k_undistort(const sd_keypoint* __restrict__ kps, sd_keypoint* __
 }  // namespace sd
 
 // ==========================================================================================
-// host side: handle + C ABI
+// host side: the launch pipeline (the handle and the C ABI are in orb_host.hip)
 // ==========================================================================================
 using namespace sd;
 
-#include "orb_internal.h"
-static const char* kStageNames[ST_COUNT] = {"pyramid", "fast_nms", "select", "blur", "orient_desc"};
+namespace {
 
-static int free_geom(sd_orb* h) {
-  void* ptrs[] = {h->d_cells, h->d_tiles, h->d_coef, h->pyr_set[0], h->pyr_set[1], h->d_blur, h->d_cand, h->d_scratch,
-                  h->d_cell_count, h->d_sel, h->d_sel_count, h->d_cell_keep, h->d_cell_off, h->d_lvl_m};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  h->pyr_set[0] = h->pyr_set[1] = nullptr;
-  h->d_cells = nullptr; h->d_tiles = nullptr; h->d_coef = nullptr; h->d_pyr = nullptr; h->d_blur = nullptr;
-  h->d_cand = nullptr; h->d_scratch = nullptr; h->d_cell_count = nullptr; h->d_sel = nullptr; h->d_sel_count = nullptr;
-  h->d_cell_keep = nullptr; h->d_cell_off = nullptr; h->d_lvl_m = nullptr;
-  return SD_OK;
-}
-
-static void select_set(sd_orb* h, int sidx) {
-  h->set = sidx;
-  h->d_pyr = h->pyr_set[sidx];
-  h->d_kps = h->kps_set[sidx];
-  h->d_kps_un = h->kps_un_set[sidx];
-  h->d_desc = h->desc_set[sidx];
-  h->d_nout = h->nout_set[sidx];
-}
-
-static int wait_trackers(sd_orb* h) {   // host-side: nothing may still read any output set
-  for (int i = 0; i < 2; i++)
-    if (h->set_busy[i]) {
-      SD_HIP_CHECK(hipEventSynchronize(h->ev_set_free[i]));
-      h->set_busy[i] = false;
-    }
-  return SD_OK;
-}
-
-static void drop_graphs(sd_orb* h);
-
-// Geometry (re)build.  Everything that can fail -- planning, allocation, upload -- works on a LOCAL plan and the handle is
-// marked "no geometry" first, so a failure (a frame too small to plan, an allocation that does not fit) leaves a handle
-// that rebuilds from scratch on its next call instead of one whose host plan no longer matches its device buffers.
-static int build_geometry(sd_orb* h, const HostPlan& hp) {
-  const size_t B = h->max_batch;
-  const size_t slack = 4096;
-  SD_HIP_CHECK(hipMalloc(&h->d_cells, std::max<size_t>(hp.cells.size(), 1) * sizeof(CellGeom)));
-  SD_HIP_CHECK(hipMalloc(&h->d_tiles, std::max<size_t>(hp.blur_tiles.size(), 1) * sizeof(BlurTile)));
-  SD_HIP_CHECK(hipMalloc(&h->d_coef, std::max<size_t>(hp.coef.size(), 1) * sizeof(int32_t)));
-  for (int i = 0; i < h->nsets; i++) {
-    SD_HIP_CHECK(hipMalloc(&h->pyr_set[i], hp.plan.pyr_frame_bytes * B + slack));
-    SD_HIP_CHECK(hipMemsetAsync(h->pyr_set[i], 0, hp.plan.pyr_frame_bytes * B + slack, h->stream));
-  }
-  select_set(h, 0);
-  SD_HIP_CHECK(hipMalloc(&h->d_blur, hp.plan.pyr_frame_bytes * B + slack));
-  SD_HIP_CHECK(hipMalloc(&h->d_cand, std::max<size_t>(hp.plan.cand_per_frame, 1) * B * 4));
-  SD_HIP_CHECK(hipMalloc(&h->d_scratch, std::max<size_t>(hp.plan.cand_per_frame, 1) * B * 4));
-  SD_HIP_CHECK(hipMalloc(&h->d_cell_count, std::max<size_t>(hp.plan.ncells, 1) * B * 4));
-  SD_HIP_CHECK(hipMalloc(&h->d_sel, std::max<size_t>(hp.plan.nsel, 1) * B * 4));
-  SD_HIP_CHECK(hipMalloc(&h->d_sel_count, (size_t)h->nlevels * B * 4));
-  SD_HIP_CHECK(hipMalloc(&h->d_cell_keep, std::max<size_t>(hp.plan.ncells, 1) * B * 4));
-  SD_HIP_CHECK(hipMalloc(&h->d_cell_off, std::max<size_t>(hp.plan.ncells, 1) * B * 4));
-  SD_HIP_CHECK(hipMalloc(&h->d_lvl_m, (size_t)h->nlevels * B * 4));
-  SD_HIP_CHECK(hipMemsetAsync(h->d_blur, 0, hp.plan.pyr_frame_bytes * B + slack, h->stream));
-  if (!hp.cells.empty())
-    SD_HIP_CHECK(hipMemcpyAsync(h->d_cells, hp.cells.data(), hp.cells.size() * sizeof(CellGeom), hipMemcpyHostToDevice, h->stream));
-  if (!hp.blur_tiles.empty())
-    SD_HIP_CHECK(hipMemcpyAsync(h->d_tiles, hp.blur_tiles.data(), hp.blur_tiles.size() * sizeof(BlurTile), hipMemcpyHostToDevice, h->stream));
-  if (!hp.coef.empty())
-    SD_HIP_CHECK(hipMemcpyAsync(h->d_coef, hp.coef.data(), hp.coef.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-  SD_HIP_CHECK(hipMemcpyAsync(h->d_plan, &hp.plan, sizeof(OrbPlan), hipMemcpyHostToDevice, h->stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return SD_OK;
-}
-
-static int ensure_geometry(sd_orb* h, int w, int hgt) {
-  if (h->have_geom && h->cur_w == w && h->cur_h == hgt) return SD_OK;
-  SD_REQUIRE(w <= h->max_w && hgt <= h->max_h, SD_ERR_CAPACITY, "frame larger than the handle's max_w x max_h");
-  const char* why = "";
-  HostPlan np = h->hp;   // carries the size-independent tables (scale factors, quotas, umax, pattern)
-  if (!plan_geometry(h->nfeatures, h->nlevels, h->thFAST, w, hgt, np, &why)) {
-    set_error(std::string("unsupported geometry: ") + why);
-    return SD_ERR_INVALID_ARG;   // the handle keeps its previous, still consistent geometry
-  }
-  SD_REQUIRE(np.max_cells_per_level <= SEL_MAX_CELLS && (size_t)np.plan.ncells * 16 <= 60 * 1024, SD_ERR_INVALID_ARG,
-             "too many grid cells (k_select_quota keeps four ints per cell in LDS)");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  { int rcw = wait_trackers(h); if (rcw != SD_OK) return rcw; }
-  drop_graphs(h);
-  h->select_recorded = false;
-  h->have_geom = false;
-  h->cur_w = h->cur_h = 0;
-  h->last_frames = 0;
-  free_geom(h);
-  const int rc = build_geometry(h, np);
-  if (rc != SD_OK) {
-    free_geom(h);   // partial allocations; have_geom stays false: the next call rebuilds everything
-    return rc;
-  }
-  h->hp = std::move(np);
-  h->have_geom = true;
-  h->cur_w = w;
-  h->cur_h = hgt;
-  return SD_OK;
-}
-
-// The kernels of one extraction on the handle's three streams (main: pyramid chain, select, descriptors; fast: FAST per
-// level; aux: blur), forked and joined with events only -- also what gets captured into a hipGraph.
-static int pipeline_body(sd_orb* h, const uint8_t* d_imgs, int n, int stride, size_t frame_stride, bool prof, hipEvent_t* ev,
-                         bool frames_ready, bool capturing) {
+// One call of pipeline_body: its arguments, what it chose at the fork, and its profiling state.  The steps are the member
+// functions, in the order pipeline_body calls them; every step queues its records, waits and launches in program order.
+struct Pipeline {
+  sd_orb* const h;
+  const uint8_t* const d_imgs;
+  const int n, stride;
+  const size_t frame_stride;
+  const bool prof;
+  hipEvent_t* const ev;
+  const bool frames_ready, capturing;
   const HostPlan& hp = h->hp;
   const OrbPlan& P = hp.plan;
-  hipStream_t s = h->stream;
-  bool fast_started = false;
-  // The previous call's selection (main stream) read d_cand / d_cell_count: FAST must not overwrite them before it is done.
-  // r3: FAST of level 0 reads the caller's frames and needs nothing else of THIS call, so with frames that are already on the
-  // device (frames_ready: the device-input entry point) it is ordered behind the previous SELECTION only (ev_select_done)
-  // and runs beside the previous batch's descriptor kernel, a gather-latency-bound kernel that leaves the vector ALUs idle.
-  // The upload of these frames is then ordered by sd_orb_stream_fence, which makes the FAST and auxiliary streams wait as
-  // well.  Only on the handle's own stream: on a caller's stream the producer of the frames may be queued on that very
-  // stream, and stream order is the contract.  Otherwise (host frames copied on this stream, a caller's stream, a captured
-  // graph, option off, first call) behind everything queued so far.
-  const bool fast_early = frames_ready && !capturing && h->select_recorded && h->stream == h->own_stream && opt(OPT_FAST0_EARLY) != 0;
-  if (fast_early) SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_select_done, 0));
-  SD_HIP_CHECK(hipEventRecord(h->ev_body_start, s));
-  if (!fast_early) SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_body_start, 0));
-  // r3: with two output sets (a tracker is attached) the pyramid of this call goes into the set the previous call does NOT read,
-  // so the resize chain, too, may run beside the previous call's descriptor kernel -- on the auxiliary stream in front of the
-  // blur, which follows it anyway (a FIFTH stream lands on the hardware queue of the FAST stream and the two serialise: HIP
-  // spreads a process's streams over four hardware queues) -- behind the previous selection, the upload of the frames and the
-  // tracker's last read of that set (launch_pipeline); the FAST launches of levels 1... then follow level 0 without waiting for
-  // the descriptors to end (they were idle for 0.6 ms per step).  OFF by default: bit-exact (tests run it), but the full step with
-  // the PnP solve loses 8 % (172 k vs 194.6 k frames/s, three alternating runs) -- the tracking kernels of the previous batch
-  // then share the machine with two FAST launches instead of one; with TrackWithMotionModel it is even (187 k both).
-  const bool pyr_early = fast_early && h->nsets == 2 && opt(OPT_PYR_EARLY) != 0;
-  hipStream_t ps = pyr_early ? h->aux_stream : s;
-  if (prof && !pyr_early) SD_HIP_CHECK(hipEventRecord(ev[0], s));
-  if (pyr_early) {
-    SD_HIP_CHECK(hipStreamWaitEvent(ps, h->ev_select_done, 0));
-    if (prof) SD_HIP_CHECK(hipEventRecord(ev[0], ps));   // (the pyramid stage is timed on the stream it runs on)
-  }
+  const hipStream_t s = h->stream;
   const bool src_aligned = (((uintptr_t)d_imgs | (uintptr_t)stride | (uintptr_t)frame_stride) & 3) == 0;
   // FAST of level 0 reads the frames themselves when they are 4-byte aligned: it starts at once, beside the resize chain
   // (in 16-byte units when base and strides allow, else dword by dword)
   const bool src_wide = (((uintptr_t)d_imgs | (uintptr_t)stride | (uintptr_t)frame_stride) & 15) == 0;
   const bool fast0_direct = src_aligned && P.lv[0].ncells > 0 && opt(OPT_FAST0_FROM_FRAMES) != 0;
   const int ring_slot = h->ev_calls % sd_orb::kRing;
+  bool fast_early = false, pyr_early = false;
+  hipStream_t ps = nullptr;   // stream of the resize chain: main, or auxiliary (pyr_early)
+  bool fast_started = false;
   int nfp = 0;   // FAST launches timed so far
-  auto fast_pair = [&](bool begin) {
-    if (prof && h->evf_ready && nfp < sd_orb::kFastPairs) (void)hipEventRecord(h->evf[ring_slot][2 * nfp + (begin ? 0 : 1)], h->fast_stream);
-    if (!begin) nfp++;
-  };
-  if (fast0_direct) {
-    if (prof) SD_HIP_CHECK(hipEventRecord(ev[8], h->fast_stream));
+
+  int mark(StageEvent e, hipStream_t stream) {
+    if (prof) SD_HIP_CHECK(hipEventRecord(ev[e], stream));
+    return SD_OK;
+  }
+
+  int fork() {
+    // The previous call's selection (main stream) read d_cand / d_cell_count: FAST must not overwrite them before it is done.
+    // r3: FAST of level 0 reads the caller's frames and needs nothing else of THIS call, so with frames that are already on the
+    // device (frames_ready: the device-input entry point) it is ordered behind the previous SELECTION only (ev_select_done)
+    // and runs beside the previous batch's descriptor kernel, a gather-latency-bound kernel that leaves the vector ALUs idle.
+    // The upload of these frames is then ordered by sd_orb_stream_fence, which makes the FAST and auxiliary streams wait as
+    // well.  Only on the handle's own stream: on a caller's stream the producer of the frames may be queued on that very
+    // stream, and stream order is the contract.  Otherwise (host frames copied on this stream, a caller's stream, a captured
+    // graph, option off, first call) behind everything queued so far.
+    fast_early = frames_ready && !capturing && h->select_recorded && h->stream == h->own_stream && opt(OPT_FAST0_EARLY) != 0;
+    if (fast_early) SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_select_done, 0));
+    SD_HIP_CHECK(hipEventRecord(h->ev_body_start, s));
+    if (!fast_early) SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_body_start, 0));
+    // r3: with two output sets (a tracker is attached) the pyramid of this call goes into the set the previous call does NOT read,
+    // so the resize chain, too, may run beside the previous call's descriptor kernel -- on the auxiliary stream in front of the
+    // blur, which follows it anyway (a FIFTH stream lands on the hardware queue of the FAST stream and the two serialise: HIP
+    // spreads a process's streams over four hardware queues) -- behind the previous selection, the upload of the frames and the
+    // tracker's last read of that set (orb_launch_pipeline); the FAST launches of levels 1... then follow level 0 without waiting for
+    // the descriptors to end (they were idle for 0.6 ms per step).  OFF by default: bit-exact (tests run it), but the full step with
+    // the PnP solve loses 8 % (172 k vs 194.6 k frames/s, three alternating runs) -- the tracking kernels of the previous batch
+    // then share the machine with two FAST launches instead of one; with TrackWithMotionModel it is even (187 k both).
+    pyr_early = fast_early && h->nsets == 2 && opt(OPT_PYR_EARLY) != 0;
+    ps = pyr_early ? h->aux_stream : s;
+    if (pyr_early) SD_HIP_CHECK(hipStreamWaitEvent(ps, h->ev_select_done, 0));
+    return mark(EV_PYR_BEGIN, ps);   // (the pyramid stage is timed on the stream it runs on)
+  }
+
+  // One k_fast_cells launch on the FAST stream: ncl cells from the first cell of level `first`, rows read at src
+  int launch_fast(const uint8_t* src, size_t src_frame_stride, const FastSrc& fs, int edge, int first, int ncl, size_t lds, bool wide) {
+    if (!fast_started) SD_TRY(mark(EV_FAST_BEGIN, h->fast_stream));
     fast_started = true;
+    const bool timed = prof && h->evf_ready && nfp < sd_orb::kFastPairs;
+    if (timed) (void)hipEventRecord(h->evf[ring_slot][2 * nfp], h->fast_stream);
+    hipLaunchKernelGGL(k_fast_cells, dim3(ncl, n), dim3(256), lds, h->fast_stream, h->d_cells, src, src_frame_stride, fs, edge, h->d_cand,
+                       P.cand_per_frame, h->d_cell_count, P.ncells, P.lv[first].cell0, P.thFAST, wide ? 1 : 0);
+    if (timed) (void)hipEventRecord(h->evf[ring_slot][2 * nfp + 1], h->fast_stream);
+    nfp++;
+    return SD_OK;
+  }
+
+  int fast_level0_direct() {
     FastSrc fs0;
     memset(&fs0, 0, sizeof(fs0));
     fs0.pstride[0] = stride;
-    fast_pair(true);
-    hipLaunchKernelGGL(k_fast_cells, dim3(P.lv[0].ncells, n), dim3(256), hp.fast_lds_level[0], h->fast_stream, h->d_cells, d_imgs,
-                       frame_stride, fs0, 0, h->d_cand, P.cand_per_frame, h->d_cell_count, P.ncells, P.lv[0].cell0, P.thFAST, src_wide ? 1 : 0);
-    fast_pair(false);
+    return launch_fast(d_imgs, frame_stride, fs0, 0, 0, P.lv[0].ncells, hp.fast_lds_level[0], src_wide);
   }
-  FastSrc fsrc;
-  memset(&fsrc, 0, sizeof(fsrc));
-  for (int l = 0; l < P.nlevels; l++) {
-    fsrc.off[l] = P.lv[l].off;
-    fsrc.pstride[l] = P.lv[l].pstride;
-  }
-  const int merge_from = hp.fast_merge_from;   // orb_plan.cpp
-  for (int l = 0; l < P.nlevels; l++) {
+
+  int pyramid_level(int l) {
     const LevelGeom& L = P.lv[l];
     const LevelGeom& S = P.lv[l > 0 ? l - 1 : 0];
     const bool split = L.w >= 16 && L.fast_resize != 0 && (l > 0 || src_aligned);
     if (!split) {   // generic single-pass kernel (exact-2x INTER_AREA levels, odd source alignment, tiny levels)
       dim3 grid((L.pstride + 255) / 256, (L.prows + 4 * PYR_ROWS - 1) / (4 * PYR_ROWS), n), block(64, 4, 1);
       hipLaunchKernelGGL(k_pyr_level, grid, block, 0, ps, L, S, (size_t)P.pyr_frame_bytes, l, d_imgs, stride, frame_stride, h->d_pyr);
-    } else {
+      return SD_OK;
+    }
     auto magic = [](unsigned d) { return (unsigned)(0xFFFFFFFFull / d) + 1u; };   // e / d == umulhi(e, magic) for e < 2^31 / d
     const int G = (L.w + 2 * SD_EDGE + 3) / 4;   // 4-pixel groups of a padded row
     const bool mirror = L.h >= 48;   // border rows as second stores of their source rows (single reflections)
     const int Hh = ((mirror ? L.h : L.prows) + PYR_RPT - 1) / PYR_RPT;   // (padded) rows per row-slot of a thread
     const unsigned n_resize = (unsigned)(((size_t)Hh * G + 255) / 256);
-    hipLaunchKernelGGL(k_pyr_split, dim3(n_resize, n), dim3(256), 0, ps, L, S, (size_t)P.pyr_frame_bytes, l, h->d_coef, d_imgs,
-                       stride, frame_stride, h->d_pyr, G, magic((unsigned)G), Hh, mirror ? 1 : 0);
-    }
-    // FAST of this level starts now, on its own stream
+    hipLaunchKernelGGL(k_pyr_split, dim3(n_resize, n), dim3(256), 0, ps, L, S, (size_t)P.pyr_frame_bytes, l, h->d_coef, d_imgs, stride,
+                       frame_stride, h->d_pyr, G, magic((unsigned)G), Hh, mirror ? 1 : 0);
+    return SD_OK;
+  }
+
+  // FAST of level l starts as soon as the level is complete, on its own stream
+  int fast_of_level(int l, const FastSrc& fsrc) {
     // levels >= merge_from share ONE launch after the last level is complete (cells of consecutive levels are contiguous)
+    const int merge_from = hp.fast_merge_from;   // orb_plan.cpp
     const bool merged = l >= merge_from;
-    int ncl = L.ncells;
+    int ncl = P.lv[l].ncells;
     size_t lds = hp.fast_lds_level[l];
     if (merged) {
-      if (l != P.nlevels - 1) continue;
+      if (l != P.nlevels - 1) return SD_OK;
       ncl = 0;
       lds = 0;
       for (int m = merge_from; m < P.nlevels; m++) {
@@ -1629,93 +1474,155 @@ static int pipeline_body(sd_orb* h, const uint8_t* d_imgs, int n, int stride, si
         lds = std::max(lds, hp.fast_lds_level[m]);
       }
     }
-    const int first = merged ? merge_from : l;
-    if (ncl > 0 && !(l == 0 && fast0_direct)) {
-      SD_HIP_CHECK(hipEventRecord(h->ev_level[l], ps));
-      SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_level[l], 0));
-      if (prof && !fast_started) SD_HIP_CHECK(hipEventRecord(ev[8], h->fast_stream));
-      fast_started = true;
-      fast_pair(true);
-      hipLaunchKernelGGL(k_fast_cells, dim3(ncl, n), dim3(256), lds, h->fast_stream, h->d_cells, (const uint8_t*)h->d_pyr,
-                         (size_t)P.pyr_frame_bytes, fsrc, SD_EDGE, h->d_cand, P.cand_per_frame, h->d_cell_count, P.ncells, P.lv[first].cell0,
-                         P.thFAST, 1);   // (d_pyr, the levels' offsets, their row pitches and the frame stride are multiples of 64)
-      fast_pair(false);
-    }
+    if (ncl == 0 || (l == 0 && fast0_direct)) return SD_OK;
+    SD_HIP_CHECK(hipEventRecord(h->ev_level[l], ps));
+    SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_level[l], 0));
+    // (d_pyr, the levels' offsets, their row pitches and the frame stride are multiples of 64)
+    return launch_fast(h->d_pyr, (size_t)P.pyr_frame_bytes, fsrc, SD_EDGE, merged ? merge_from : l, ncl, lds, true);
   }
-  if (prof) SD_HIP_CHECK(hipEventRecord(ev[1], ps));
+
   // blur on the auxiliary stream, beside FAST + selection (d_blur exists once: behind the previous call's descriptors)
-  SD_HIP_CHECK(hipEventRecord(h->ev_pyr_done, ps));
-  SD_HIP_CHECK(hipStreamWaitEvent(h->aux_stream, h->ev_pyr_done, 0));
-  if (pyr_early) SD_HIP_CHECK(hipStreamWaitEvent(h->aux_stream, h->ev_body_start, 0));
-  if (prof) SD_HIP_CHECK(hipEventRecord(ev[3], h->aux_stream));
-  hipLaunchKernelGGL(k_blur, dim3((unsigned)hp.blur_tiles.size(), n), dim3(256), 0, h->aux_stream, h->d_plan, h->d_tiles, h->d_pyr,
-                     h->d_blur, h->d_sel_count);
-  if (prof) SD_HIP_CHECK(hipEventRecord(ev[6], h->aux_stream));
-  SD_HIP_CHECK(hipEventRecord(h->ev_blur_done, h->aux_stream));
-  if (prof) {
-    if (!fast_started) SD_HIP_CHECK(hipEventRecord(ev[8], h->fast_stream));
-    SD_HIP_CHECK(hipEventRecord(ev[2], h->fast_stream));
-    h->evf_n[ring_slot] = h->evf_ready ? nfp : 0;
+  int blur() {
+    SD_HIP_CHECK(hipEventRecord(h->ev_pyr_done, ps));
+    SD_HIP_CHECK(hipStreamWaitEvent(h->aux_stream, h->ev_pyr_done, 0));
+    if (pyr_early) SD_HIP_CHECK(hipStreamWaitEvent(h->aux_stream, h->ev_body_start, 0));
+    SD_TRY(mark(EV_BLUR_BEGIN, h->aux_stream));
+    hipLaunchKernelGGL(k_blur, dim3((unsigned)hp.blur_tiles.size(), n), dim3(256), 0, h->aux_stream, h->d_plan, h->d_tiles, h->d_pyr,
+                       h->d_blur, h->d_sel_count);
+    SD_TRY(mark(EV_BLUR_END, h->aux_stream));
+    SD_HIP_CHECK(hipEventRecord(h->ev_blur_done, h->aux_stream));
+    return SD_OK;
   }
-  // ev_fast_done stands for "pyramid AND FAST complete" (a tracker's ImageAlign waits for it alone, track_handle.h wait_inputs): a
-  // level without grid cells launches no FAST, so the FAST stream has not necessarily waited for that level's resize
-  // (few features: no cells at all on the merged small levels) -- order it behind the whole pyramid explicitly
-  SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_pyr_done, 0));
-  SD_HIP_CHECK(hipEventRecord(h->ev_fast_done, h->fast_stream));
-  SD_HIP_CHECK(hipStreamWaitEvent(s, h->ev_fast_done, 0));
-  if (prof) SD_HIP_CHECK(hipEventRecord(ev[9], s));
-  const int sel_cap = hp.max_cell_pixels > 12000 ? 1024 : 512;
-  if (P.ncells > 0) {
-    hipLaunchKernelGGL(k_select_quota, dim3(n), dim3(64), (size_t)P.ncells * 16, s, h->d_plan, h->d_cells, h->d_cell_count, h->d_cell_keep,
-                       h->d_cell_off, h->d_lvl_m);
-    // small buffer = 2 x sel_cap entries (5 KB at VGA: 32 one-wave workgroups per CU; 4 x was 0.385 ms, 2 x and 1 x 0.275 ms);
-    // big buffer = SEL_WAVES x sel_cap
-    int small_cap = 2 * sel_cap, big_cap = SEL_WAVES * sel_cap;
-    if (const int e = opt(OPT_SELECT_SMALL_CAP)) small_cap = std::max(1, std::min(e, small_cap));   // tests: force the other paths
-    if (const int e = opt(OPT_SELECT_BIG_CAP)) big_cap = std::max(small_cap, std::min(e, big_cap));
-    hipLaunchKernelGGL(k_select_cells, dim3(P.ncells, n), dim3(64), (size_t)small_cap * 4 + 2 * WAVE_SEL_CAP * 2, s, h->d_plan, h->d_cells,
-                       h->d_cand, h->d_cell_count, h->d_cell_keep, h->d_cell_off, h->d_scratch, small_cap);
-    hipLaunchKernelGGL(k_select_bigcells, dim3(P.nlevels, n), dim3(64), (size_t)big_cap * 4 + 2 * WAVE_SEL_CAP * 2, s, h->d_plan, h->d_cells,
-                       h->d_cand, h->d_cell_count, h->d_cell_keep, h->d_cell_off, h->d_scratch, small_cap, big_cap);
+
+  int join_fast() {
+    if (!fast_started) SD_TRY(mark(EV_FAST_BEGIN, h->fast_stream));
+    SD_TRY(mark(EV_FAST_END, h->fast_stream));
+    if (prof) h->evf_n[ring_slot] = h->evf_ready ? nfp : 0;
+    // ev_fast_done stands for "pyramid AND FAST complete" (a tracker's ImageAlign waits for it alone, track_handle.h wait_inputs): a
+    // level without grid cells launches no FAST, so the FAST stream has not necessarily waited for that level's resize
+    // (few features: no cells at all on the merged small levels) -- order it behind the whole pyramid explicitly
+    SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_pyr_done, 0));
+    SD_HIP_CHECK(hipEventRecord(h->ev_fast_done, h->fast_stream));
+    SD_HIP_CHECK(hipStreamWaitEvent(s, h->ev_fast_done, 0));
+    return SD_OK;
   }
-  // (also without any grid cell -- nfeatures so small that every level's levelCols is 0: the per-level counts the descriptor
-  // kernel reads must still be written, as zeros)
-  hipLaunchKernelGGL(k_select_final, dim3(P.nlevels, n), dim3(64), 0, s, h->d_plan, h->d_lvl_m, h->d_scratch, h->d_sel, h->d_sel_count);
-  if (!capturing) {   // d_cand / d_cell_count are free again: the next call's level-0 FAST may start (see the top of this function)
-    SD_HIP_CHECK(hipEventRecord(h->ev_select_done, s));
-    h->select_recorded = true;
+
+  int select() {
+    SD_TRY(mark(EV_SELECT_BEGIN, s));
+    const int sel_cap = hp.max_cell_pixels > 12000 ? 1024 : 512;
+    if (P.ncells > 0) {
+      hipLaunchKernelGGL(k_select_quota, dim3(n), dim3(64), (size_t)P.ncells * 16, s, h->d_plan, h->d_cells, h->d_cell_count, h->d_cell_keep,
+                         h->d_cell_off, h->d_lvl_m);
+      // small buffer = 2 x sel_cap entries (5 KB at VGA: 32 one-wave workgroups per CU; 4 x was 0.385 ms, 2 x and 1 x 0.275 ms);
+      // big buffer = SEL_WAVES x sel_cap
+      int small_cap = 2 * sel_cap, big_cap = SEL_WAVES * sel_cap;
+      if (const int e = opt(OPT_SELECT_SMALL_CAP)) small_cap = std::max(1, std::min(e, small_cap));   // tests: force the other paths
+      if (const int e = opt(OPT_SELECT_BIG_CAP)) big_cap = std::max(small_cap, std::min(e, big_cap));
+      hipLaunchKernelGGL(k_select_cells, dim3(P.ncells, n), dim3(64), (size_t)small_cap * 4 + 2 * WAVE_SEL_CAP * 2, s, h->d_plan, h->d_cells,
+                         h->d_cand, h->d_cell_count, h->d_cell_keep, h->d_cell_off, h->d_scratch, small_cap);
+      hipLaunchKernelGGL(k_select_bigcells, dim3(P.nlevels, n), dim3(64), (size_t)big_cap * 4 + 2 * WAVE_SEL_CAP * 2, s, h->d_plan, h->d_cells,
+                         h->d_cand, h->d_cell_count, h->d_cell_keep, h->d_cell_off, h->d_scratch, small_cap, big_cap);
+    }
+    // (also without any grid cell -- nfeatures so small that every level's levelCols is 0: the per-level counts the descriptor
+    // kernel reads must still be written, as zeros)
+    hipLaunchKernelGGL(k_select_final, dim3(P.nlevels, n), dim3(64), 0, s, h->d_plan, h->d_lvl_m, h->d_scratch, h->d_sel, h->d_sel_count);
+    if (!capturing) {   // d_cand / d_cell_count are free again: the next call's level-0 FAST may start (see fork)
+      SD_HIP_CHECK(hipEventRecord(h->ev_select_done, s));
+      h->select_recorded = true;
+    }
+    return mark(EV_SELECT_END, s);
   }
-  if (prof) SD_HIP_CHECK(hipEventRecord(ev[7], s));
-  SD_HIP_CHECK(hipStreamWaitEvent(s, h->ev_blur_done, 0));
-  if (prof) SD_HIP_CHECK(hipEventRecord(ev[4], s));
-  const int cap = std::max(P.nsel, 1);
-  {
+
+  int describe() {
+    SD_HIP_CHECK(hipStreamWaitEvent(s, h->ev_blur_done, 0));
+    SD_TRY(mark(EV_DESC_BEGIN, s));
+    const int cap = std::max(P.nsel, 1);
     const int bpf = (cap + 4 * DESC_KPW - 1) / (4 * DESC_KPW);   // 4 waves x DESC_KPW keypoints per workgroup
-    hipLaunchKernelGGL(k_orient_desc, dim3((unsigned)(((n + 7) / 8) * 8 * bpf)), dim3(256), 0, s, h->d_plan, h->d_pyr, h->d_blur,
-                       h->d_sel, h->d_sel_count, h->d_kps, h->d_desc, h->d_nout, cap, n, bpf);
+    hipLaunchKernelGGL(k_orient_desc, dim3((unsigned)(((n + 7) / 8) * 8 * bpf)), dim3(256), 0, s, h->d_plan, h->d_pyr, h->d_blur, h->d_sel,
+                       h->d_sel_count, h->d_kps, h->d_desc, h->d_nout, cap, n, bpf);
+    if (h->have_dist) {   // mvKeysUn != mvKeys only when k1 != 0 (src/Frame.cc:336-339)
+      DistParams D;
+      D.fx = h->dist_K[0]; D.fy = h->dist_K[1]; D.cx = h->dist_K[2]; D.cy = h->dist_K[3];
+      for (int i = 0; i < 12; i++) D.k[i] = i < 5 ? (double)h->dist[i] : 0.0;
+      hipLaunchKernelGGL(k_undistort, dim3((cap + 255) / 256, n), dim3(256), 0, s, h->d_kps, h->d_kps_un, h->d_nout, cap, D);
+    }
+    return mark(EV_DESC_END, s);
   }
-  if (h->have_dist) {   // mvKeysUn != mvKeys only when k1 != 0 (src/Frame.cc:336-339)
-    DistParams D;
-    D.fx = h->dist_K[0]; D.fy = h->dist_K[1]; D.cx = h->dist_K[2]; D.cy = h->dist_K[3];
-    for (int i = 0; i < 12; i++) D.k[i] = i < 5 ? (double)h->dist[i] : 0.0;
-    hipLaunchKernelGGL(k_undistort, dim3((cap + 255) / 256, n), dim3(256), 0, s, h->d_kps, h->d_kps_un, h->d_nout, cap, D);
+};
+
+// The kernels of one extraction on the handle's three streams (main: pyramid chain, select, descriptors; fast: FAST per
+// level; aux: blur), forked and joined with events only -- also what gets captured into a hipGraph.
+int pipeline_body(sd_orb* h, const uint8_t* d_imgs, int n, int stride, size_t frame_stride, bool prof, hipEvent_t* ev, bool frames_ready,
+                  bool capturing) {
+  Pipeline p{h, d_imgs, n, stride, frame_stride, prof, ev, frames_ready, capturing};
+  SD_TRY(p.fork());
+  if (p.fast0_direct) SD_TRY(p.fast_level0_direct());
+  FastSrc fsrc;
+  memset(&fsrc, 0, sizeof(fsrc));
+  for (int l = 0; l < p.P.nlevels; l++) {
+    fsrc.off[l] = p.P.lv[l].off;
+    fsrc.pstride[l] = p.P.lv[l].pstride;
   }
-  if (prof) SD_HIP_CHECK(hipEventRecord(ev[5], s));
+  for (int l = 0; l < p.P.nlevels; l++) {
+    SD_TRY(p.pyramid_level(l));
+    SD_TRY(p.fast_of_level(l, fsrc));
+  }
+  SD_TRY(p.mark(EV_PYR_END, p.ps));
+  SD_TRY(p.blur());
+  SD_TRY(p.join_fast());
+  SD_TRY(p.select());
+  SD_TRY(p.describe());
   SD_HIP_CHECK(hipGetLastError());
   return SD_OK;
 }
 
-static void drop_graphs(sd_orb* h) {
+// The cached graph of this call's arguments into ge, captured and instantiated on first use
+int graph_for(sd_orb* h, const uint8_t* d_imgs, int n, int stride, size_t frame_stride, sd_orb::GraphEntry*& ge) {
+  const sd_orb::GraphKey key = graph_key(h, d_imgs, n, stride, frame_stride);
+  for (auto& g : h->graphs)
+    if (g.exec && g.key == key) ge = &g;
+  if (ge) return SD_OK;
+  hipStream_t s = h->stream;
+  hipGraph_t graph = nullptr;
+  SD_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  int rc = pipeline_body(h, d_imgs, n, stride, frame_stride, false, nullptr, false, true);
+  h->select_recorded = false;   // the graph's selection is not an event record a later call could wait for
+  hipError_t e = hipStreamEndCapture(s, &graph);
+  if (rc == SD_OK && e != hipSuccess) {
+    set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+    rc = SD_ERR_HIP;
+  }
+  if (rc == SD_OK) {
+    sd_orb::GraphEntry& slot = h->graphs[h->graph_next++ % 4];
+    if (slot.exec) (void)hipGraphExecDestroy(slot.exec);
+    slot = sd_orb::GraphEntry();
+    e = hipGraphInstantiate(&slot.exec, graph, nullptr, nullptr, 0);
+    if (e != hipSuccess) {
+      set_error(std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+      rc = SD_ERR_HIP;
+    } else {
+      slot.key = key;
+      ge = &slot;
+    }
+  }
+  if (graph) (void)hipGraphDestroy(graph);
+  return rc;
+}
+
+}  // namespace
+
+namespace sd {
+
+void orb_drop_graphs(sd_orb* h) {
   for (auto& g : h->graphs) {
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
     g = sd_orb::GraphEntry();
   }
 }
 
-static int launch_pipeline(sd_orb* h, const uint8_t* d_imgs, int n, int stride, size_t frame_stride, bool frames_ready) {
+int orb_launch_pipeline(sd_orb* h, const uint8_t* d_imgs, int n, int stride, size_t frame_stride, bool frames_ready) {
   hipStream_t s = h->stream;
   const bool prof = h->profiling;
-  hipEvent_t* ev = h->ev[h->ev_calls % sd_orb::kRing];
   // next output set; a tracker may still be reading its previous contents on another stream
   select_set(h, (h->set + 1) % h->nsets);
   if (h->set_busy[h->set]) {
@@ -1726,51 +1633,16 @@ static int launch_pipeline(sd_orb* h, const uint8_t* d_imgs, int n, int stride, 
   // hipGraph replay is opt-in (option "extract.use_graph"): measured on ROCm 7.2 / MI355X the single-frame call takes 0.43 ms through
   // the graph against 0.37 ms with direct launches (tools/exp_pcie.py), so direct launches stay the default
   const bool use_graph = opt(OPT_USE_GRAPH) != 0;
-  int rc = SD_OK;
   if (prof || !use_graph) {
-    rc = pipeline_body(h, d_imgs, n, stride, frame_stride, prof, ev, frames_ready, false);
+    SD_TRY(pipeline_body(h, d_imgs, n, stride, frame_stride, prof, h->ev[h->ev_calls % sd_orb::kRing], frames_ready, false));
   } else {
     sd_orb::GraphEntry* ge = nullptr;
-    float dv[9] = {h->dist_K[0], h->dist_K[1], h->dist_K[2], h->dist_K[3], h->dist[0], h->dist[1], h->dist[2], h->dist[3], h->dist[4]};
-    for (auto& g : h->graphs)
-      if (g.exec && g.imgs == d_imgs && g.n == n && g.stride == stride && g.frame_stride == frame_stride && g.set == h->set &&
-          g.dist == h->have_dist && (!g.dist || memcmp(g.distv, dv, sizeof(dv)) == 0))
-        ge = &g;
-    if (!ge) {
-      hipGraph_t graph = nullptr;
-      SD_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      rc = pipeline_body(h, d_imgs, n, stride, frame_stride, false, ev, false, true);
-      h->select_recorded = false;   // the graph's selection is not an event record a later call could wait for
-      hipError_t e = hipStreamEndCapture(s, &graph);
-      if (rc == SD_OK && e != hipSuccess) {
-        set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        rc = SD_ERR_HIP;
-      }
-      if (rc == SD_OK) {
-        sd_orb::GraphEntry& slot = h->graphs[h->graph_next++ % 4];
-        if (slot.exec) (void)hipGraphExecDestroy(slot.exec);
-        slot = sd_orb::GraphEntry();
-        e = hipGraphInstantiate(&slot.exec, graph, nullptr, nullptr, 0);
-        if (e != hipSuccess) {
-          set_error(std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-          rc = SD_ERR_HIP;
-        } else {
-          slot.imgs = d_imgs; slot.n = n; slot.stride = stride; slot.frame_stride = frame_stride; slot.set = h->set;
-          slot.dist = h->have_dist;
-          memcpy(slot.distv, dv, sizeof(dv));
-          ge = &slot;
-        }
-      }
-      if (graph) (void)hipGraphDestroy(graph);
-    }
-    if (rc == SD_OK) {
-      SD_HIP_CHECK(hipGraphLaunch(ge->exec, s));
-      // a replayed selection records no event either: the next direct call's level-0 FAST must not wait for an older one
-      // (it would overwrite d_cand / d_cell_count under this graph's FAST and selection)
-      h->select_recorded = false;
-    }
+    SD_TRY(graph_for(h, d_imgs, n, stride, frame_stride, ge));
+    SD_HIP_CHECK(hipGraphLaunch(ge->exec, s));
+    // a replayed selection records no event either: the next direct call's level-0 FAST must not wait for an older one
+    // (it would overwrite d_cand / d_cell_count under this graph's FAST and selection)
+    h->select_recorded = false;
   }
-  if (rc != SD_OK) return rc;
   // inside a captured graph ev_pyr_done is a graph node, not an event record a later hipStreamWaitEvent could see
   h->pyr_event_live = prof || !use_graph;
   SD_HIP_CHECK(hipEventRecord(h->ev_extract_done, s));
@@ -1781,30 +1653,6 @@ static int launch_pipeline(sd_orb* h, const uint8_t* d_imgs, int n, int stride, 
   return SD_OK;
 }
 
-
-namespace sd {
-// Second output set for a handle whose frames a tracker consumes on its own stream.
-int orb_enable_double_buffer(sd_orb* h) {
-  if (h->nsets == 2) return SD_OK;
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  const size_t cap = std::max(keypoint_capacity(h), 1), B = h->max_batch;
-  SD_HIP_CHECK(hipMalloc(&h->kps_set[1], cap * B * sizeof(sd_keypoint)));
-  SD_HIP_CHECK(hipMalloc(&h->kps_un_set[1], cap * B * sizeof(sd_keypoint)));
-  SD_HIP_CHECK(hipMalloc(&h->desc_set[1], cap * B * 32));
-  SD_HIP_CHECK(hipMalloc(&h->nout_set[1], B * 4));
-  SD_HIP_CHECK(hipMemset(h->nout_set[1], 0, B * 4));
-  if (h->have_geom) {
-    const size_t bytes = h->hp.plan.pyr_frame_bytes * B + 4096;
-    SD_HIP_CHECK(hipMalloc(&h->pyr_set[1], bytes));
-    SD_HIP_CHECK(hipMemset(h->pyr_set[1], 0, bytes));
-  }
-  h->nsets = 2;
-  return SD_OK;
-}
-}  // namespace sd
-
-namespace sd {
 int read_sel_prof(unsigned long long* out64, int reset) {   // out64[8 * i + 7] = FAST phase i (the other slots: 0)
 #ifdef SD_PNP_PROF
   SD_HIP_CHECK(hipDeviceSynchronize());
@@ -1826,473 +1674,5 @@ int read_sel_prof(unsigned long long* out64, int reset) {   // out64[8 * i + 7] 
   return SD_ERR_INVALID_ARG;
 #endif
 }
+
 }  // namespace sd
-
-extern "C" {
-
-const char* sd_last_error(void) { return g_err.c_str(); }
-const char* sd_version(void) { return "sdslam_hip 0.1 (gfx950)"; }
-
-int sd_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
-
-int sd_orb_create(int nfeatures, float scale_factor, int nlevels, int th_fast, int max_w, int max_h, int max_batch,
-                  int device, sd_orb** out) {
-  SD_REQUIRE(out != nullptr, SD_ERR_INVALID_ARG, "out is NULL");
-  *out = nullptr;
-  SD_REQUIRE(nfeatures > 0 && nlevels >= 1 && nlevels <= SD_MAX_LEVELS && scale_factor > 1.0f, SD_ERR_INVALID_ARG,
-             "bad extractor parameters");
-  SD_REQUIRE(max_w >= 1 && max_h >= 1 && max_w <= SD_MAX_DIM && max_h <= SD_MAX_DIM && max_batch >= 1, SD_ERR_INVALID_ARG,
-             "bad capacity parameters");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("no HIP device visible: the HIP path is the only implementation (no CPU fallback)");
-    return SD_ERR_NO_DEVICE;
-  }
-  SD_REQUIRE(device >= 0 && device < ndev, SD_ERR_INVALID_ARG, "device index out of range");
-  SD_HIP_CHECK(hipSetDevice(device));
-  sd_orb* h = new sd_orb();
-  h->nfeatures = nfeatures;
-  h->scaleFactor = scale_factor;
-  h->nlevels = nlevels;
-  h->thFAST = th_fast;
-  h->max_w = max_w;
-  h->max_h = max_h;
-  h->max_batch = max_batch;
-  h->device = device;
-  plan_tables(nfeatures, scale_factor, nlevels, h->hp);
-  const size_t cap = std::max(keypoint_capacity(h), 1);
-  hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc(&h->d_plan, sizeof(OrbPlan));
-  if (e == hipSuccess) e = hipMalloc(&h->d_img, (size_t)max_w * max_h * max_batch);
-  if (e == hipSuccess) e = hipMalloc(&h->kps_set[0], cap * max_batch * sizeof(sd_keypoint));
-  if (e == hipSuccess) e = hipMalloc(&h->kps_un_set[0], cap * max_batch * sizeof(sd_keypoint));
-  if (e == hipSuccess) e = hipMalloc(&h->desc_set[0], cap * max_batch * 32);
-  if (e == hipSuccess) e = hipMalloc(&h->nout_set[0], (size_t)max_batch * 4);
-  if (e == hipSuccess) e = hipMemset(h->nout_set[0], 0, (size_t)max_batch * 4);
-  for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&h->ev_set_free[i], hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_extract_done, hipEventDisableTiming);
-  if (e == hipSuccess) select_set(h, 0);
-  for (int r = 0; r < sd_orb::kRing && e == hipSuccess; r++)
-    for (int i = 0; i < 10 && e == hipSuccess; i++) e = hipEventCreate(&h->ev[r][i]);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->fast_stream, hipStreamNonBlocking);
-  for (int i = 0; i < SD_MAX_LEVELS && e == hipSuccess; i++) e = hipEventCreateWithFlags(&h->ev_level[i], hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_fast_done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_select_done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_body_start, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_pyr_done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_blur_done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    set_error(std::string("sd_orb_create: ") + hipGetErrorString(e));
-    sd_orb_destroy(h);
-    return SD_ERR_HIP;
-  }
-  h->stream = h->own_stream;
-  *out = h;
-  return SD_OK;
-}
-
-void sd_orb_destroy(sd_orb* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  (void)wait_trackers(h);
-  drop_graphs(h);
-  free_geom(h);
-  void* ptrs[] = {h->d_plan, h->d_img, h->kps_set[0], h->kps_set[1], h->kps_un_set[0], h->kps_un_set[1], h->desc_set[0],
-                  h->desc_set[1], h->nout_set[0], h->nout_set[1]};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (int i = 0; i < 2; i++)
-    if (h->ev_set_free[i]) (void)hipEventDestroy(h->ev_set_free[i]);
-  if (h->ev_extract_done) (void)hipEventDestroy(h->ev_extract_done);
-  for (int r = 0; r < sd_orb::kRing; r++) {
-    for (int i = 0; i < 10; i++)
-      if (h->ev[r][i]) (void)hipEventDestroy(h->ev[r][i]);
-    for (int i = 0; i < 2 * sd_orb::kFastPairs; i++)
-      if (h->evf[r][i]) (void)hipEventDestroy(h->evf[r][i]);
-  }
-  if (h->aux_stream) { (void)hipStreamSynchronize(h->aux_stream); (void)hipStreamDestroy(h->aux_stream); }
-  if (h->fast_stream) { (void)hipStreamSynchronize(h->fast_stream); (void)hipStreamDestroy(h->fast_stream); }
-  for (int i = 0; i < SD_MAX_LEVELS; i++)
-    if (h->ev_level[i]) (void)hipEventDestroy(h->ev_level[i]);
-  if (h->ev_fast_done) (void)hipEventDestroy(h->ev_fast_done);
-  if (h->ev_select_done) (void)hipEventDestroy(h->ev_select_done);
-  if (h->ev_body_start) (void)hipEventDestroy(h->ev_body_start);
-  if (h->ev_pyr_done) (void)hipEventDestroy(h->ev_pyr_done);
-  if (h->ev_blur_done) (void)hipEventDestroy(h->ev_blur_done);
-  for (int i = 0; i < 2; i++)
-    if (h->ev_user_fence[i]) (void)hipEventDestroy(h->ev_user_fence[i]);
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
-}
-
-int sd_orb_levels(const sd_orb* h) { return h ? h->nlevels : 0; }
-
-// Host-only (no GPU needed): geometry the extractor would use for a w x h frame.
-int sd_orb_plan_info(int nfeatures, float scale_factor, int nlevels, int th_fast, int w, int hgt, int32_t* level_info,
-                     int32_t* cell_zones, int cell_cap, int32_t* n_cells, uint64_t* bytes_per_frame) {
-  SD_REQUIRE(level_info && n_cells, SD_ERR_INVALID_ARG, "NULL argument");
-  SD_REQUIRE(nfeatures > 0 && nlevels >= 1 && nlevels <= SD_MAX_LEVELS && scale_factor > 1.0f, SD_ERR_INVALID_ARG,
-             "bad extractor parameters");
-  HostPlan hp;
-  plan_tables(nfeatures, scale_factor, nlevels, hp);
-  const char* why = "";
-  if (!plan_geometry(nfeatures, nlevels, th_fast, w, hgt, hp, &why)) {
-    set_error(std::string("unsupported geometry: ") + why);
-    return SD_ERR_INVALID_ARG;
-  }
-  for (int l = 0; l < nlevels; l++) {
-    const LevelGeom& L = hp.plan.lv[l];
-    int32_t* o = level_info + 8 * l;
-    o[0] = L.w; o[1] = L.h; o[2] = L.quota; o[3] = L.cols; o[4] = L.rows; o[5] = L.cellW; o[6] = L.cellH; o[7] = L.nfeaturesCell;
-  }
-  *n_cells = hp.plan.ncells;
-  if (cell_zones) {
-    SD_REQUIRE(cell_cap >= hp.plan.ncells, SD_ERR_CAPACITY, "cell_cap too small");
-    for (int c = 0; c < hp.plan.ncells; c++) {
-      const CellGeom& C = hp.cells[c];
-      int32_t* o = cell_zones + 6 * c;
-      o[0] = C.level; o[1] = C.zx0; o[2] = C.zy0; o[3] = C.zw; o[4] = C.zh; o[5] = C.evaluated;
-    }
-  }
-  if (bytes_per_frame) *bytes_per_frame = hp.plan.pyr_frame_bytes * 2 + (uint64_t)hp.plan.cand_per_frame * 8;
-  return SD_OK;
-}
-
-int sd_orb_scale_tables(const sd_orb* h, float* sf, float* inv_sf, float* sigma2, float* inv_sigma2) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  for (int i = 0; i < h->nlevels; i++) {
-    if (sf) sf[i] = h->hp.sf[i];
-    if (inv_sf) inv_sf[i] = h->hp.inv_sf[i];
-    if (sigma2) sigma2[i] = h->hp.sigma2[i];
-    if (inv_sigma2) inv_sigma2[i] = h->hp.inv_sigma2[i];
-  }
-  return SD_OK;
-}
-
-int sd_orb_features_per_level(const sd_orb* h, int32_t* quota) {
-  SD_REQUIRE(h && quota, SD_ERR_INVALID_ARG, "NULL argument");
-  for (int i = 0; i < h->nlevels; i++) quota[i] = h->hp.quota[i];
-  return SD_OK;
-}
-
-int sd_orb_extract_batch_device(sd_orb* h, const void* d_imgs, int n_frames, int w, int hgt, int stride,
-                                size_t frame_stride) {
-  SD_REQUIRE(h && d_imgs, SD_ERR_INVALID_ARG, "NULL argument");
-  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
-  SD_REQUIRE(w >= 1 && hgt >= 1 && stride >= w && frame_stride >= (size_t)stride * (hgt - 1) + w, SD_ERR_INVALID_ARG,
-             "bad image shape/stride");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  int rc = ensure_geometry(h, w, hgt);
-  if (rc != SD_OK) return rc;
-  // frames_ready: the caller's frames are complete on the device (or ordered by sd_orb_stream_fence); the host-input entry
-  // points copy them on the extraction stream and call launch_pipeline themselves
-  return launch_pipeline(h, (const uint8_t*)d_imgs, n_frames, stride, frame_stride, !h->staging_input);
-}
-
-int sd_orb_download(sd_orb* h, int frame0, int n_frames, sd_keypoint* kps_out, uint8_t* desc_out, int cap_per_frame,
-                    int32_t* n_out) {
-  SD_REQUIRE(h && n_out, SD_ERR_INVALID_ARG, "NULL argument");
-  SD_REQUIRE(frame0 >= 0 && n_frames >= 1 && frame0 + n_frames <= h->last_frames, SD_ERR_INVALID_ARG,
-             "frame range outside the last batch");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  const int cap = std::max(h->hp.plan.nsel, 1);
-  SD_HIP_CHECK(hipMemcpyAsync(n_out, h->d_nout + frame0, (size_t)n_frames * 4, hipMemcpyDeviceToHost, h->stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  for (int f = 0; f < n_frames; f++)
-    SD_REQUIRE(n_out[f] <= cap_per_frame || (!kps_out && !desc_out), SD_ERR_CAPACITY, "cap_per_frame smaller than keypoint count");
-  if (cap_per_frame == cap && n_frames > 8) {
-    // same row pitch on both sides: two bulk copies instead of 2 x n_frames small ones (entries beyond n_out[f] are
-    // whatever the device rows hold; callers must not read them)
-    if (kps_out)
-      SD_HIP_CHECK(hipMemcpyAsync(kps_out, h->d_kps + (size_t)frame0 * cap, (size_t)n_frames * cap * sizeof(sd_keypoint),
-                                  hipMemcpyDeviceToHost, h->stream));
-    if (desc_out)
-      SD_HIP_CHECK(hipMemcpyAsync(desc_out, h->d_desc + (size_t)frame0 * cap * 32, (size_t)n_frames * cap * 32, hipMemcpyDeviceToHost,
-                                  h->stream));
-    SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return SD_OK;
-  }
-  for (int f = 0; f < n_frames; f++) {
-    int n = n_out[f];
-    if (n <= 0) continue;
-    if (kps_out)
-      SD_HIP_CHECK(hipMemcpyAsync(kps_out + (size_t)f * cap_per_frame, h->d_kps + (size_t)(frame0 + f) * cap,
-                                  (size_t)n * sizeof(sd_keypoint), hipMemcpyDeviceToHost, h->stream));
-    if (desc_out)
-      SD_HIP_CHECK(hipMemcpyAsync(desc_out + (size_t)f * cap_per_frame * 32, h->d_desc + (size_t)(frame0 + f) * cap * 32,
-                                  (size_t)n * 32, hipMemcpyDeviceToHost, h->stream));
-  }
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return SD_OK;
-}
-
-int sd_orb_extract_batch(sd_orb* h, const uint8_t* imgs, int n_frames, int w, int hgt, int stride, size_t frame_stride,
-                         sd_keypoint* kps_out, uint8_t* desc_out, int cap_per_frame, int32_t* n_out) {
-  SD_REQUIRE(h && n_out, SD_ERR_INVALID_ARG, "NULL argument");
-  if (w <= 0 || hgt <= 0 || !imgs) {   // _image.empty(): return silently (src/ORBextractor.cc:622-623)
-    for (int f = 0; f < n_frames; f++) n_out[f] = 0;
-    return SD_OK;
-  }
-  SD_REQUIRE(n_frames >= 1 && n_frames <= h->max_batch, SD_ERR_CAPACITY, "n_frames exceeds max_batch");
-  SD_REQUIRE(w <= h->max_w && hgt <= h->max_h, SD_ERR_CAPACITY, "frame larger than the handle's max_w x max_h");
-  SD_REQUIRE(stride >= w, SD_ERR_INVALID_ARG, "stride < width");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  // pack rows tightly into the staging buffer (one copy when the frames already are tightly packed)
-  if (stride == w && (n_frames == 1 || frame_stride == (size_t)w * hgt)) {
-    SD_HIP_CHECK(hipMemcpyAsync(h->d_img, imgs, (size_t)n_frames * w * hgt, hipMemcpyHostToDevice, h->stream));
-  } else {
-    for (int f = 0; f < n_frames; f++)
-      SD_HIP_CHECK(hipMemcpy2DAsync(h->d_img + (size_t)f * w * hgt, w, imgs + (size_t)f * frame_stride, stride, w,
-                                    (size_t)hgt, hipMemcpyHostToDevice, h->stream));
-  }
-  h->staging_input = true;    // the frames reach d_img by a copy queued on the extraction stream just above
-  int rc = sd_orb_extract_batch_device(h, h->d_img, n_frames, w, hgt, w, (size_t)w * hgt);
-  h->staging_input = false;
-  if (rc != SD_OK) return rc;
-  return sd_orb_download(h, 0, n_frames, kps_out, desc_out, cap_per_frame, n_out);
-}
-
-int sd_orb_extract(sd_orb* h, const uint8_t* img, int w, int hgt, int stride, sd_keypoint* kps_out, uint8_t* desc_out,
-                   int cap, int* n_out) {
-  SD_REQUIRE(n_out, SD_ERR_INVALID_ARG, "n_out is NULL");
-  int32_t n = 0;
-  int rc = sd_orb_extract_batch(h, img, 1, w, hgt, stride, (size_t)stride * (hgt > 0 ? hgt : 0), kps_out, desc_out, cap, &n);
-  *n_out = n;
-  return rc;
-}
-
-int sd_orb_set_distortion(sd_orb* h, float fx, float fy, float cx, float cy, float k1, float k2, float p1, float p2, float k3) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_REQUIRE(fx > 0 && fy > 0, SD_ERR_INVALID_ARG, "bad camera matrix");
-  h->dist_K[0] = fx; h->dist_K[1] = fy; h->dist_K[2] = cx; h->dist_K[3] = cy;
-  h->dist[0] = k1; h->dist[1] = k2; h->dist[2] = p1; h->dist[3] = p2; h->dist[4] = k3;
-  h->have_dist = (k1 != 0.0f);   // mDistCoef.at<float>(0) == 0.0 -> mvKeysUn = mvKeys
-  return SD_OK;
-}
-
-int sd_orb_download_undistorted(sd_orb* h, int frame0, int n_frames, sd_keypoint* kps_un_out, int cap_per_frame) {
-  SD_REQUIRE(h && kps_un_out, SD_ERR_INVALID_ARG, "NULL argument");
-  SD_REQUIRE(frame0 >= 0 && n_frames >= 1 && frame0 + n_frames <= h->last_frames, SD_ERR_INVALID_ARG, "frame range outside the last batch");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  const int cap = std::max(h->hp.plan.nsel, 1);
-  std::vector<int32_t> n(n_frames);
-  SD_HIP_CHECK(hipMemcpyAsync(n.data(), h->d_nout + frame0, (size_t)n_frames * 4, hipMemcpyDeviceToHost, h->stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  const sd_keypoint* src = h->have_dist ? h->d_kps_un : h->d_kps;
-  for (int f = 0; f < n_frames; f++) {
-    SD_REQUIRE(n[f] <= cap_per_frame, SD_ERR_CAPACITY, "cap_per_frame smaller than keypoint count");
-    if (n[f] > 0)
-      SD_HIP_CHECK(hipMemcpyAsync(kps_un_out + (size_t)f * cap_per_frame, src + (size_t)(frame0 + f) * cap, (size_t)n[f] * sizeof(sd_keypoint),
-                                  hipMemcpyDeviceToHost, h->stream));
-  }
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return SD_OK;
-}
-
-int sd_orb_level_info(const sd_orb* h, int level, int* w, int* hgt) {
-  SD_REQUIRE(h && h->have_geom && level >= 0 && level < h->nlevels, SD_ERR_INVALID_ARG, "no geometry / bad level");
-  if (w) *w = h->hp.plan.lv[level].w;
-  if (hgt) *hgt = h->hp.plan.lv[level].h;
-  return SD_OK;
-}
-
-static int copy_level(sd_orb* h, const uint8_t* base, int frame, int level, int padded, uint8_t* out, int out_stride) {
-  SD_REQUIRE(h && out && h->have_geom && level >= 0 && level < h->nlevels && frame >= 0 && frame < h->last_frames,
-             SD_ERR_INVALID_ARG, "bad frame/level");
-  const LevelGeom& L = h->hp.plan.lv[level];
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  const uint8_t* src = base + (size_t)frame * h->hp.plan.pyr_frame_bytes + L.off;
-  int wc = L.w, hc = L.h;
-  if (padded) {
-    wc += 2 * SD_EDGE;
-    hc += 2 * SD_EDGE;
-  } else {
-    src += (size_t)SD_EDGE * L.pstride + SD_EDGE;
-  }
-  SD_REQUIRE(out_stride >= wc, SD_ERR_INVALID_ARG, "out_stride too small");
-  SD_HIP_CHECK(hipMemcpy2DAsync(out, out_stride, src, L.pstride, wc, hc, hipMemcpyDeviceToHost, h->stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return SD_OK;
-}
-
-int sd_orb_level_copy(sd_orb* h, int frame, int level, int padded, uint8_t* out, int out_stride) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  return copy_level(h, h->d_pyr, frame, level, padded, out, out_stride);
-}
-
-int sd_orb_debug_blurred(sd_orb* h, int frame, int level, uint8_t* out, int out_stride) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  return copy_level(h, h->d_blur + SD_BLUR_SHIFT, frame, level, 0, out, out_stride);
-}
-
-int sd_orb_debug_cell_counts(sd_orb* h, int frame, int level, int32_t* out, int cap, int* n_cells) {
-  SD_REQUIRE(h && out && n_cells && h->have_geom && level >= 0 && level < h->nlevels && frame >= 0 && frame < h->last_frames,
-             SD_ERR_INVALID_ARG, "bad frame/level");
-  const LevelGeom& L = h->hp.plan.lv[level];
-  *n_cells = L.ncells;
-  SD_REQUIRE(cap >= L.ncells, SD_ERR_CAPACITY, "cap too small");
-  if (L.ncells == 0) return SD_OK;
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  SD_HIP_CHECK(hipMemcpyAsync(out, h->d_cell_count + (size_t)frame * h->hp.plan.ncells + L.cell0, (size_t)L.ncells * 4,
-                              hipMemcpyDeviceToHost, h->stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return SD_OK;
-}
-
-int sd_orb_debug_level_keys(sd_orb* h, int frame, int level, uint32_t* keys_out, int cap, int* n) {
-  SD_REQUIRE(h && keys_out && n && h->have_geom && level >= 0 && level < h->nlevels && frame >= 0 && frame < h->last_frames,
-             SD_ERR_INVALID_ARG, "bad frame/level");
-  const LevelGeom& L = h->hp.plan.lv[level];
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  int32_t cnt = 0;
-  SD_HIP_CHECK(hipMemcpyAsync(&cnt, h->d_sel_count + (size_t)frame * h->nlevels + level, 4, hipMemcpyDeviceToHost, h->stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  *n = cnt;
-  SD_REQUIRE(cap >= cnt, SD_ERR_CAPACITY, "cap too small");
-  if (cnt > 0) {
-    SD_HIP_CHECK(hipMemcpyAsync(keys_out, h->d_sel + (size_t)frame * h->hp.plan.nsel + L.sel_off, (size_t)cnt * 4,
-                                hipMemcpyDeviceToHost, h->stream));
-    SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  }
-  return SD_OK;
-}
-
-int sd_orb_set_stream(sd_orb* h, void* hip_stream) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
-  return SD_OK;
-}
-
-// Ordering against a caller's HIP stream (an upload stream that fills the frames of the next batch while this one is being
-// processed).  direction 0: `hip_stream` waits for everything queued on the extraction stream so far (the frames of the
-// extractions queued so far have been consumed when it proceeds); 1: the extraction stream and the FAST and auxiliary
-// streams, on which an early level-0 FAST / resize chain of a later extraction reads the frames (pipeline_body), wait for
-// everything queued on `hip_stream` so far.  A wait takes the event's state at the time it is queued, so every fence
-// holds, not only the last one.
-int sd_orb_stream_fence(sd_orb* h, void* hip_stream, int direction) {
-  SD_REQUIRE(h && (direction == 0 || direction == 1), SD_ERR_INVALID_ARG, "bad arguments");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  hipStream_t ext = (hipStream_t)hip_stream;
-  for (int i = 0; i < 2; i++)
-    if (!h->ev_user_fence[i]) SD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_user_fence[i], hipEventDisableTiming));
-  if (direction == 0) {
-    SD_HIP_CHECK(hipEventRecord(h->ev_user_fence[0], h->stream));
-    SD_HIP_CHECK(hipStreamWaitEvent(ext, h->ev_user_fence[0], 0));
-  } else {
-    SD_HIP_CHECK(hipEventRecord(h->ev_user_fence[1], ext));
-    SD_HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_user_fence[1], 0));
-    SD_HIP_CHECK(hipStreamWaitEvent(h->fast_stream, h->ev_user_fence[1], 0));
-    SD_HIP_CHECK(hipStreamWaitEvent(h->aux_stream, h->ev_user_fence[1], 0));
-  }
-  return SD_OK;
-}
-
-int sd_orb_sync(sd_orb* h) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  SD_HIP_CHECK(hipStreamSynchronize(h->aux_stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return SD_OK;
-}
-
-int sd_orb_set_profiling(sd_orb* h, int on) {
-  SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
-  if (on && !h->evf_ready) {
-    SD_HIP_CHECK(hipSetDevice(h->device));
-    for (int r = 0; r < sd_orb::kRing; r++)
-      for (int i = 0; i < 2 * sd_orb::kFastPairs; i++) SD_HIP_CHECK(hipEventCreate(&h->evf[r][i]));
-    h->evf_ready = true;
-  }
-  h->profiling = on != 0;
-  h->ev_calls = 0;
-  return SD_OK;
-}
-
-int sd_orb_num_stages(void) { return ST_COUNT; }
-const char* sd_orb_stage_name(int stage) { return (stage >= 0 && stage < ST_COUNT) ? kStageNames[stage] : ""; }
-
-int sd_orb_stage_ms(sd_orb* h, float* ms_out, int cap) {
-  SD_REQUIRE(h && ms_out && cap >= ST_COUNT, SD_ERR_INVALID_ARG, "bad arguments");
-  SD_REQUIRE(h->profiling && h->ev_calls > 0, SD_ERR_INVALID_ARG, "profiling is off or no call recorded");
-  SD_HIP_CHECK(hipSetDevice(h->device));
-  SD_HIP_CHECK(hipStreamSynchronize(h->stream));
-  const int n = std::min(h->ev_calls, (int)sd_orb::kRing);
-  for (int i = 0; i < ST_COUNT; i++) ms_out[i] = 0.f;
-  static const int kBegin[ST_COUNT] = {0, 8, 9, 3, 4}, kEnd[ST_COUNT] = {1, 2, 7, 6, 5};
-  SD_HIP_CHECK(hipStreamSynchronize(h->aux_stream));
-  SD_HIP_CHECK(hipStreamSynchronize(h->fast_stream));
-  for (int r = 0; r < n; r++) {
-    const int slot = (h->ev_calls - 1 - r) % sd_orb::kRing;
-    for (int i = 0; i < ST_COUNT; i++) {
-      float ms = 0;
-      if (i == ST_FAST && h->evf_n[slot] > 0) {   // sum of the k_fast_cells launches (what a kernel trace of the same run adds up to)
-        for (int k = 0; k < h->evf_n[slot]; k++) {
-          float one = 0;
-          SD_HIP_CHECK(hipEventElapsedTime(&one, h->evf[slot][2 * k], h->evf[slot][2 * k + 1]));
-          ms += one;
-        }
-      } else {
-        SD_HIP_CHECK(hipEventElapsedTime(&ms, h->ev[slot][kBegin[i]], h->ev[slot][kEnd[i]]));
-      }
-      ms_out[i] += ms / n;
-    }
-  }
-  return SD_OK;
-}
-
-int sd_orb_stage_bytes(const sd_orb* h, double* bytes_out, int cap) {
-  SD_REQUIRE(h && bytes_out && cap >= ST_COUNT && h->have_geom, SD_ERR_INVALID_ARG, "bad arguments / no geometry yet");
-  for (int i = 0; i < ST_COUNT; i++) bytes_out[i] = h->hp.stage_bytes[i];
-  return SD_OK;
-}
-
-int sd_dev_alloc(size_t bytes, void** out) {
-  SD_REQUIRE(out, SD_ERR_INVALID_ARG, "out is NULL");
-  SD_HIP_CHECK(hipMalloc(out, bytes));
-  return SD_OK;
-}
-int sd_dev_free(void* p) {
-  SD_HIP_CHECK(hipFree(p));
-  return SD_OK;
-}
-// Page-locked host memory for frames / results: with it the host-buffer entry points copy at the PCIe rate
-// (pageable buffers go through the driver's staging copies, measured 6 GB/s on the test box).
-int sd_host_alloc(size_t bytes, void** out) {
-  SD_REQUIRE(out, SD_ERR_INVALID_ARG, "out is NULL");
-  SD_HIP_CHECK(hipHostMalloc(out, bytes, hipHostMallocDefault));
-  return SD_OK;
-}
-int sd_host_free(void* p) {
-  SD_HIP_CHECK(hipHostFree(p));
-  return SD_OK;
-}
-int sd_dev_upload(void* dst, const void* src, size_t bytes) {
-  SD_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-  return SD_OK;
-}
-int sd_dev_download(void* dst, const void* src, size_t bytes) {
-  SD_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-  return SD_OK;
-}
-
-// ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:1459-1473): 256-bit Hamming distance
-int sd_hamming(const uint8_t* a32, const uint8_t* b32) {
-  int dist = 0;
-  for (int i = 0; i < 4; i++) {
-    uint64_t x, y;
-    memcpy(&x, a32 + 8 * i, 8);
-    memcpy(&y, b32 + 8 * i, 8);
-    dist += __builtin_popcountll(x ^ y);
-  }
-  return dist;
-}
-
-}  // extern "C"

@@ -1,11 +1,25 @@
-// Internal layout of the sd_orb handle (shared by orb.hip and the sd_track sources through track_handle.h; not part of the ABI).
+// Internal layout of the sd_orb handle and what orb.hip (kernels + launch pipeline) and orb_host.hip (handle + C ABI) share; the
+// sd_track sources read the handle through track_handle.h.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <array>
+#include <cstring>
 
 #include "orb_plan.h"
 #include "sd_common.h"
 
 enum { ST_PYR = 0, ST_FAST, ST_SELECT, ST_BLUR, ST_DESC, ST_COUNT };
+// Stage events of one profiled call (sd_orb::ev): pyramid on the stream the resize chain runs on, FAST on the fast stream,
+// blur on the auxiliary stream, selection and descriptors on the main stream.
+enum StageEvent {
+  EV_PYR_BEGIN = 0, EV_PYR_END, EV_FAST_END, EV_BLUR_BEGIN, EV_DESC_BEGIN, EV_DESC_END, EV_BLUR_END, EV_SELECT_END, EV_FAST_BEGIN,
+  EV_SELECT_BEGIN, EV_STAGE_COUNT
+};
+
+// Limits of the kernels that the host layer checks a planned geometry / addresses a buffer against
+#define SEL_MAX_CELLS 512   // grid cells of one level (k_select_quota: one lane per level, four ints per cell in LDS)
+#define SD_BLUR_SHIFT 1     // column offset of the blurred levels against the pyramid's layout (see k_blur)
 
 struct sd_orb {
   int nfeatures, nlevels, thFAST;
@@ -18,14 +32,14 @@ struct sd_orb {
   hipStream_t own_stream = nullptr, stream = nullptr;
   // blur depends only on the pyramid: it runs on aux_stream beside FAST + selection
   hipStream_t aux_stream = nullptr;
-  hipEvent_t ev_pyr_done = nullptr, ev_blur_done = nullptr, ev_blur_start = nullptr;
+  hipEvent_t ev_pyr_done = nullptr, ev_blur_done = nullptr;
   // FAST of level l needs only level l of the pyramid: it runs on fast_stream as soon as that level is complete,
   // beside the (small, dependent) resize launches of the remaining levels
   hipStream_t fast_stream = nullptr;
   hipEvent_t ev_level[SD_MAX_LEVELS] = {};
   hipEvent_t ev_fast_done = nullptr;
   hipEvent_t ev_select_done = nullptr, ev_body_start = nullptr;   // end of a call's selection (d_cand free again) / start of a call on `stream`
-  bool select_recorded = false, staging_input = false;
+  bool select_recorded = false;
   // Output sets.  What a tracker reads (padded pyramid, keypoints, descriptors, counts) exists once
   // or -- after sd::orb_enable_double_buffer, which sd_track_create calls on its `cur` handle -- twice:
   // extraction alternates between the sets, so batch n+1 is extracted on `stream` while the tracker
@@ -68,15 +82,21 @@ struct sd_orb {
   float dist[5] = {0, 0, 0, 0, 0};   // k1, k2, p1, p2, k3
   uint8_t* d_desc = nullptr;
   int32_t* d_nout = nullptr;
-  size_t cap_pyr = 0, cap_cand = 0, cap_cells = 0, cap_tiles = 0, cap_coef = 0;
   // hipGraph cache of the extraction pipeline (multi-stream fork/join captured once per argument set); opt-in with
-  // option "extract.use_graph" -- see launch_pipeline for the measurement that keeps direct launches the default
-  struct GraphEntry {
+  // option "extract.use_graph" -- see orb_launch_pipeline for the measurement that keeps direct launches the default
+  struct GraphKey {   // everything a captured pipeline_body bakes in
     const void* imgs = nullptr;
     int n = 0, stride = 0, set = -1;
     size_t frame_stride = 0;
     bool dist = false;
-    float distv[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    float distv[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // fx, fy, cx, cy, k1, k2, p1, p2, k3; zeros without distortion
+    bool operator==(const GraphKey& o) const {
+      return imgs == o.imgs && n == o.n && stride == o.stride && set == o.set && frame_stride == o.frame_stride && dist == o.dist &&
+             memcmp(distv, o.distv, sizeof(distv)) == 0;
+    }
+  };
+  struct GraphEntry {
+    GraphKey key;
     hipGraphExec_t exec = nullptr;
   };
   GraphEntry graphs[4];
@@ -84,11 +104,9 @@ struct sd_orb {
   bool profiling = false;
   // ring of per-call stage events: the bench reads mean stage times over its whole timed region
   static const int kRing = 128;
-  // per call: [0] start, [1] pyramid end, [8]/[2] FAST start/end (fast stream), [9]/[7] select start/end, [3]/[6] blur start/end
-  // (aux stream), [4]/[5] descriptor start/end
-  hipEvent_t ev[kRing][10] = {};
+  hipEvent_t ev[kRing][EV_STAGE_COUNT] = {};
   // one (start, stop) pair per k_fast_cells launch: the FAST stage is reported as the SUM of its launches' durations (the stream
-  // waits for pyramid levels between them; ev[8] .. ev[2] would count those gaps).  Created when profiling is first switched on.
+  // waits for pyramid levels between them; EV_FAST_BEGIN .. EV_FAST_END would count those gaps).  Created when profiling is first switched on.
   static const int kFastPairs = SD_MAX_LEVELS + 1;
   hipEvent_t evf[kRing][2 * kFastPairs] = {};
   int evf_n[kRing] = {};
@@ -103,6 +121,55 @@ static inline int keypoint_capacity(const sd_orb* h) {
   return n;
 }
 
+static inline void select_set(sd_orb* h, int sidx) {
+  h->set = sidx;
+  h->d_pyr = h->pyr_set[sidx];
+  h->d_kps = h->kps_set[sidx];
+  h->d_kps_un = h->kps_un_set[sidx];
+  h->d_desc = h->desc_set[sidx];
+  h->d_nout = h->nout_set[sidx];
+}
+
+// The cache key of an extraction of n frames at d_imgs into the handle's current output set
+static inline sd_orb::GraphKey graph_key(const sd_orb* h, const void* d_imgs, int n, int stride, size_t frame_stride) {
+  sd_orb::GraphKey k;
+  k.imgs = d_imgs; k.n = n; k.stride = stride; k.set = h->set; k.frame_stride = frame_stride;
+  k.dist = h->have_dist;
+  if (k.dist) {
+    memcpy(k.distv, h->dist_K, sizeof(h->dist_K));
+    memcpy(k.distv + 4, h->dist, sizeof(h->dist));
+  }
+  return k;
+}
+
+// The untimed events that live as long as the handle, in creation order (ev_user_fence is created on first use)
+template <class F>
+static inline void for_each_event(sd_orb* h, F f) {
+  for (hipEvent_t& e : h->ev_set_free) f(e);
+  f(h->ev_extract_done);
+  for (hipEvent_t& e : h->ev_level) f(e);
+  f(h->ev_fast_done);
+  f(h->ev_select_done);
+  f(h->ev_body_start);
+  f(h->ev_pyr_done);
+  f(h->ev_blur_done);
+}
+
+// Device buffers sized by the planned geometry (freed and rebuilt when the frame size changes) / by the handle's capacity
+static inline std::array<void**, 14> geom_buffers(sd_orb* h) {
+  return {(void**)&h->d_cells, (void**)&h->d_tiles, (void**)&h->d_coef, (void**)&h->pyr_set[0], (void**)&h->pyr_set[1],
+          (void**)&h->d_blur, (void**)&h->d_cand, (void**)&h->d_scratch, (void**)&h->d_cell_count, (void**)&h->d_sel,
+          (void**)&h->d_sel_count, (void**)&h->d_cell_keep, (void**)&h->d_cell_off, (void**)&h->d_lvl_m};
+}
+static inline std::array<void**, 10> fixed_buffers(sd_orb* h) {
+  return {(void**)&h->d_plan, (void**)&h->d_img, (void**)&h->kps_set[0], (void**)&h->kps_set[1], (void**)&h->kps_un_set[0],
+          (void**)&h->kps_un_set[1], (void**)&h->desc_set[0], (void**)&h->desc_set[1], (void**)&h->nout_set[0], (void**)&h->nout_set[1]};
+}
+
 namespace sd {
-int orb_enable_double_buffer(sd_orb* h);   // orb.hip; idempotent
+// orb.hip: the kernels of one extraction of n frames at d_imgs into the next output set.  frames_ready: the frames are complete on
+// the device (or ordered by sd_orb_stream_fence), not written by a copy queued on the extraction stream
+int orb_launch_pipeline(sd_orb* h, const uint8_t* d_imgs, int n, int stride, size_t frame_stride, bool frames_ready);
+void orb_drop_graphs(sd_orb* h);           // orb.hip
+int orb_enable_double_buffer(sd_orb* h);   // orb_host.hip; idempotent
 }

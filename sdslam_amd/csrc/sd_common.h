@@ -29,6 +29,8 @@ void set_error(const std::string& msg);
     }                               \
   } while (0)
 
+#define SD_TRY(call) do { const int _rc = (call); if (_rc != SD_OK) return _rc; } while (0)
+
 // Process-wide options (sd_set_option / sd_get_option, sd_options.cpp; documented in include/sdslam_hip.h).
 enum Opt {
   OPT_FAST0_FROM_FRAMES, OPT_USE_GRAPH, OPT_SELECT_SMALL_CAP, OPT_SELECT_BIG_CAP, OPT_FAST_MERGE_FROM, OPT_FAST_LDS_KB,

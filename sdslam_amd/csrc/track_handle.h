@@ -13,8 +13,6 @@
 #include "orb_internal.h"
 #include "track_internal.h"
 
-#define SD_TRY(call) do { const int _rc = (call); if (_rc != SD_OK) return _rc; } while (0)
-
 // Small host arrays on their way into device memory without a host wait: the next of kSlots pinned buffers takes a copy, which
 // goes to the device on the caller's stream, behind whatever that stream has queued.  A buffer is written again once the copy
 // out of it has run (kSlots calls later: only then can the host wait).

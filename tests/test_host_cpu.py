@@ -163,3 +163,15 @@ def test_cpp_frame_overloads_compile_on_reference_shaped_types(sd, tmp_path):
                            "-L", libdir, "-lsdslam_hip", f"-Wl,-rpath,{libdir}"])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "facade frame ok" in out.stdout, (out.returncode, out.stdout, out.stderr)
+
+
+def test_orb_host_helpers_under_sanitizers(tmp_path):
+    """The pure host helpers of orb_internal.h (graph cache key, event and buffer enumerations) in a stand-alone program built
+    with AddressSanitizer and UBSan; only HIP's headers are needed, no HIP call is made."""
+    from sdslam_amd import build
+    exe = str(tmp_path / "orb_host_check")
+    inc = os.path.join(os.path.dirname(os.path.dirname(build.HIPCC)), "include")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", inc, os.path.join(ROOT, "tests", "native", "orb_host_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "orb_host_check OK" in out.stdout, out.stdout + out.stderr
