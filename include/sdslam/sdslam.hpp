@@ -423,6 +423,67 @@ class Tracking {
   }
 };
 
+// Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale) for the batch (src/Sim3Solver.h, src/Sim3Solver.cc): slot f solves KF1 = the
+// batch's current frame f (or the broadcast frame) against KF2 = frame f of the ref extractor, on the match vector
+// ORBmatcher::SearchByPoints left on the device (TrackBatch's SearchByPoints) or on one given to SetMatches.
+class Sim3Solver {
+ public:
+  explicit Sim3Solver(bool bFixScale = false) : fix_(bFixScale) { SetRansacParameters(); }
+  void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+    p_ = probability; minInl_ = minInliers; maxIts_ = maxIterations;
+  }
+  // pMP->GetWorldPos() of both keyframes' map points, [n_frames][n][3], by keypoint index (GetIndexInKeyFrame = identity)
+  static void SetPoints(TrackBatch& batch, int frame0, int n_frames, const double* Xw_cur, const double* Xw_ref, int n) {
+    check(sd_track_set_sim3_points(batch.handle(), frame0, n_frames, Xw_cur, Xw_ref, n));
+  }
+  // vpMatched12 of the caller's (indices of pKF2 keypoints, -1 = NULL) instead of SearchByPoints' result
+  static void SetMatches(TrackBatch& batch, int frame, const int32_t* vpMatched12, int n) {
+    check(sd_track_set_point_matches(batch.handle(), frame, 1, vpMatched12, n));
+  }
+  // Eigen::Matrix4d iterate(int nIterations, bool &bNoMore, vector<bool> &vbInliers, int &nInliers) for slots 0 .. n_frames - 1:
+  // constructs the solvers.  rand_values: 3 raw rand() values per iteration and slot (what SD_SLAM::Random would draw)
+  void iterate(TrackBatch& batch, int n_frames, int nIterations, const int32_t* rand_values, int per_frame) {
+    check(sd_track_set_rand(batch.handle(), 0, n_frames, rand_values, per_frame));
+    check(sd_track_sim3(batch.handle(), n_frames, fix_ ? 1 : 0, p_, minInl_, maxIts_, nIterations));
+  }
+  // the same on a rand() stream the slots already hold
+  void iterate(TrackBatch& batch, int n_frames, int nIterations) {
+    check(sd_track_sim3(batch.handle(), n_frames, fix_ ? 1 : 0, p_, minInl_, maxIts_, nIterations));
+  }
+  // Eigen::Matrix4d find(vector<bool> &vbInliers12, int &nInliers): iterate(mRansacMaxIts)
+  void find(TrackBatch& batch, int n_frames) { iterate(batch, n_frames, maxIts_); }
+  // a further iterate(nIterations) on the same solvers (mnIterations, the best hypothesis and the stream position carry over)
+  void iterateAgain(TrackBatch& batch, int n_frames, int nIterations) { check(sd_track_sim3_iterate(batch.handle(), n_frames, nIterations)); }
+  // T12: Eigen::Matrix4d::data() order (column-major); returns false for the reference's Matrix4d::Zero()
+  bool Result(TrackBatch& batch, int frame, double T12[16], bool& bNoMore, std::vector<uint8_t>& vbInliers, int& nInliers, int kp_cap,
+              int* mnIterations = nullptr) {
+    int32_t info[8];
+    vbInliers.resize(kp_cap);
+    check(sd_track_get_sim3(batch.handle(), frame, 1, T12, nullptr, nullptr, nullptr, vbInliers.data(), kp_cap, info));
+    bNoMore = info[2] != 0;
+    nInliers = info[1];
+    if (mnIterations) *mnIterations = info[3];
+    return info[0] != 0;
+  }
+  // Eigen::Matrix3d GetEstimatedRotation() (column-major), Eigen::Vector3d GetEstimatedTranslation(), float GetEstimatedScale()
+  void GetEstimatedRotation(TrackBatch& batch, int frame, double R12[9]) {
+    check(sd_track_get_sim3(batch.handle(), frame, 1, nullptr, R12, nullptr, nullptr, nullptr, 0, nullptr));
+  }
+  void GetEstimatedTranslation(TrackBatch& batch, int frame, double t12[3]) {
+    check(sd_track_get_sim3(batch.handle(), frame, 1, nullptr, nullptr, t12, nullptr, nullptr, 0, nullptr));
+  }
+  float GetEstimatedScale(TrackBatch& batch, int frame) {
+    double s = 0;
+    check(sd_track_get_sim3(batch.handle(), frame, 1, nullptr, nullptr, nullptr, &s, nullptr, 0, nullptr));
+    return (float)s;
+  }
+
+ private:
+  bool fix_;
+  double p_;
+  int minInl_, maxIts_;
+};
+
 // The candidate search of LoopClosing::DetectLoop (src/LoopClosing.cc:115-149): slot i = kfs[i]; excluded[i] marks the
 // current keyframe itself and its connected keyframes.  Returns the slots with error < 1.5 * best (vpCandidateKFs as a set).
 class LoopClosing {
@@ -436,6 +497,59 @@ class LoopClosing {
                                n_keyframes, &n, best_error, nullptr));
     cand.resize(n);
     return cand;
+  }
+
+  // The RANSAC round-robin of LoopClosing::ComputeSim3 (src/LoopClosing.cc:270-290) over candidate slots 0 .. n - 1 whose
+  // solvers hold their matches, points and rand() streams: SetRansacParameters(0.99, 20, 300) is the caller's (`solver`), then
+  // `while (nCandidates > 0 && !bMatch)` every slot not yet discarded runs iterate(5); a slot that reports bNoMore is discarded
+  // (:279-282), a slot that returns a Sim3 is offered to accept(slot) -- the reference's SearchBySim3 + OptimizeSim3 (:285-308),
+  // which stay with the caller -- and the first accepted slot is returned (bMatch).  A rejected slot stays in the round-robin, as
+  // in the reference; -1 when every slot has been discarded.  discarded (may be NULL): the reference's vbDiscarded on entry
+  // (candidates with too few matches, :257-260) and on return.
+  // The batch iterates slots 0 .. n - 1 together, so a slot rejected or discarded mid-round costs nothing extra and the slots
+  // after it in the round run as they would have; the slots after an ACCEPTED one have run one iterate(5) the reference skips
+  // (it leaves the loop), which no result read afterwards depends on.
+  template <class Accept>
+  static int ComputeSim3Candidates(TrackBatch& batch, int n, Sim3Solver& solver, int kp_cap, std::vector<uint8_t>* discarded, Accept accept,
+                                   std::vector<int>* iterations = nullptr) {
+    std::vector<uint8_t> local((size_t)n, 0);
+    std::vector<uint8_t>& gone = discarded ? *discarded : local;
+    gone.resize((size_t)n, 0);
+    int candidates = 0;
+    for (int i = 0; i < n; i++) candidates += !gone[i];
+    if (iterations) iterations->assign((size_t)n, 0);
+    std::vector<uint8_t> inl;
+    bool first = true;
+    while (candidates > 0) {
+      if (first) solver.iterate(batch, n, 5);
+      else solver.iterateAgain(batch, n, 5);
+      first = false;
+      for (int i = 0; i < n; i++) {
+        if (gone[i]) continue;
+        double T12[16];
+        bool no_more = false;
+        int n_inliers = 0, its = 0;
+        const bool got = solver.Result(batch, i, T12, no_more, inl, n_inliers, kp_cap, &its);
+        if (iterations) (*iterations)[i] = its;
+        if (no_more) {
+          gone[i] = 1;
+          candidates--;
+        }
+        if (got && accept(i)) {
+          // the later slots ran this round too (see above): report the state they are in
+          for (int j = i + 1; iterations && j < n; j++)
+            if (!gone[j]) {
+              solver.Result(batch, j, T12, no_more, inl, n_inliers, kp_cap, &its);
+              (*iterations)[j] = its;
+            }
+          return i;
+        }
+      }
+    }
+    return -1;
+  }
+  static int ComputeSim3Candidates(TrackBatch& batch, int n, Sim3Solver& solver, int kp_cap) {
+    return ComputeSim3Candidates(batch, n, solver, kp_cap, nullptr, [](int) { return true; });
   }
 };
 

@@ -312,6 +312,42 @@ int sd_track_set_point_flags(sd_track* h, int frame0, int n_frames, const uint8_
 int sd_track_search_by_points(sd_track* h, int n_frames, float nnratio, int check_ori);
 int sd_track_get_point_matches(sd_track* h, int frame0, int n_frames, int32_t* matches12, int cap, int32_t* n_matches);
 
+/* Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, const vector<MapPoint*>& vpMatched12, bool bFixScale)
+ *   src/Sim3Solver.h, src/Sim3Solver.cc:36-393 (caller: LoopClosing::ComputeSim3, src/LoopClosing.cc:255-283, right after
+ *   SearchByPoints: SetRansacParameters(0.99, 20, 300), then iterate(5) round-robin over the candidates)
+ * for the whole batch, one solver per slot: KF1 = the slot's cur frame (or the broadcast frame) with pose Tcur, KF2 = frame f
+ * of the ref extractor with pose Tref (sd_track_set_poses).  vpMatched12 is the matches12 buffer: what sd_track_search_by_points
+ * left there (no host copy), or any vector given to sd_track_set_point_matches (cap entries per slot, the rest NULL; entries
+ * in [-1, keypoint capacity)), as sd_track_set_matches does for PnPsolver.  A correspondence needs both map points valid:
+ * has_mp_cur[i1] and has_mp_ref[matches12[i1]] of sd_track_set_point_flags, i.e. != NULL && !isBad(), the constructor's test
+ * (:65-69).  GetIndexInKeyFrame is taken as the identity: indexKF1 = i1, indexKF2 = matches12[i1] (:71-72); an index beyond
+ * the keypoints the extraction produced is no correspondence.  K, the keypoint octaves and mvLevelSigma2 are the tracker's and
+ * the extractors' own.
+ * sd_track_set_sim3_points: pMP->GetWorldPos() of the two keyframes' map points, [n_frames][cap][3] doubles each, indexed by
+ *   that keyframe's keypoint index (:90-96).
+ * sd_track_sim3 = constructor (:36-110) + SetRansacParameters(probability, min_inliers, max_iterations) (:112-135) +
+ *   iterate(n_iterations) (:137-198; n_iterations = max_iterations is find(), :200-203) for slots 0 .. n_frames - 1.
+ *   probability in (0, 1), min_inliers >= 3, max_iterations >= 1, n_iterations >= 1.
+ * sd_track_sim3_iterate = a further iterate(n_iterations): mnIterations, mnBestInliers, mvbBestInliers, mBestT12, the best
+ *   R / t / scale and the position in the rand() stream persist on the device.  The lifetime rule is sd_track_pnp_iterate's:
+ *   a new extraction on `cur` or `ref`, sd_track_search_by_points, sd_track_set_point_matches / _set_sim3_points /
+ *   _set_point_flags / _set_poses / _set_rand, or another broadcast setting end the solvers' life, and the next
+ *   sd_track_sim3_iterate fails with SD_ERR_INVALID_ARG until sd_track_sim3 constructs new ones.
+ * Both are queued on the tracking stream: no host wait, no allocation.  Draws use the stream of sd_track_set_rand, 3 values
+ * per iteration (Random(0, size - 1) with size N, N - 1, N - 2; src/extra/utils.cc:23-26); a call that could run past the
+ * supplied values fails with SD_ERR_INVALID_ARG before anything is launched.
+ * sd_track_get_sim3 (synchronises; NULL outputs are skipped): T12_cm = the matrix iterate() returned, 16 doubles
+ *   column-major, all zero when none was returned; R12_cm (9, column-major) / t12 (3) / scale (1; a float value) =
+ *   GetEstimatedRotation / Translation / Scale (:344-354), the best so far whether returned or not (zeros before the first
+ *   iteration); inliers[i1] = vbInliers over KF1's keypoints (mN1 = the keypoint capacity; cap >= it);
+ *   info8 = {returned (0/1), nInliers, bNoMore, mnIterations, N, mRansacMaxIts, mnBestInliers, 0}. */
+int sd_track_set_sim3_points(sd_track* h, int frame0, int n_frames, const double* Xw_cur, const double* Xw_ref, int cap);
+int sd_track_set_point_matches(sd_track* h, int frame0, int n_frames, const int32_t* matches12, int cap);
+int sd_track_sim3(sd_track* h, int n_frames, int fix_scale, double probability, int min_inliers, int max_iterations, int n_iterations);
+int sd_track_sim3_iterate(sd_track* h, int n_frames, int n_iterations);
+int sd_track_get_sim3(sd_track* h, int frame0, int n_frames, double* T12_cm, double* R12_cm, double* t12, double* scale,
+                      uint8_t* inliers, int cap, int32_t* info8);
+
 int sd_track_align(sd_track* h, int n_frames, int mode);
 int sd_track_match(sd_track* h, int n_frames, float th, int mono, int check_ori);
 /* sd_track_pnp = PnPsolver(CurrentFrame, CurrentFrame.mvpMapPoints) + SetRansacParameters(...) + iterate(n_iterations)

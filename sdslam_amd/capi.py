@@ -633,6 +633,42 @@ class Tracker:
         _check(self.L.sd_track_get_point_matches(self.h, frame0, n, _p(m), self.cap, _p(nm)))
         return m, nm
 
+    # --- Sim3Solver on the SearchByPoints pairing (src/Sim3Solver.cc; caller LoopClosing::ComputeSim3) ---
+    def set_sim3_points(self, frame0, Xw_cur, Xw_ref):
+        """GetWorldPos() of the two keyframes' map points, [n, cap', 3] each, by that keyframe's keypoint index."""
+        a, b = np.ascontiguousarray(Xw_cur, np.float64), np.ascontiguousarray(Xw_ref, np.float64)
+        assert a.ndim == 3 and a.shape == b.shape and a.shape[2] == 3
+        self.L.sd_track_set_sim3_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        _check(self.L.sd_track_set_sim3_points(self.h, frame0, a.shape[0], _p(a), _p(b), a.shape[1]))
+
+    def set_point_matches(self, frame0, matches12):
+        """vpMatched12 of the slots from the caller: [n, cap'] indices of pKF keypoints, -1 = NULL."""
+        m = np.ascontiguousarray(matches12, np.int32)
+        assert m.ndim == 2
+        self.L.sd_track_set_point_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        _check(self.L.sd_track_set_point_matches(self.h, frame0, m.shape[0], _p(m), m.shape[1]))
+
+    def sim3(self, n_frames, fix_scale=False, probability=0.99, min_inliers=20, max_iterations=300, n_iterations=None):
+        """Sim3Solver ctor + SetRansacParameters + iterate(n_iterations) (None: find())."""
+        n_iterations = max_iterations if n_iterations is None else n_iterations
+        self.L.sd_track_sim3.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int]
+        _check(self.L.sd_track_sim3(self.h, n_frames, int(fix_scale), probability, min_inliers, max_iterations, n_iterations))
+
+    def sim3_iterate(self, n_frames, n_iterations):
+        """A further Sim3Solver::iterate(n_iterations) on the solvers the last sim3() call constructed."""
+        self.L.sd_track_sim3_iterate.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(self.L.sd_track_sim3_iterate(self.h, n_frames, int(n_iterations)))
+
+    def get_sim3(self, frame0, n):
+        T, R, t, s = np.zeros((n, 16)), np.zeros((n, 9)), np.zeros((n, 3)), np.zeros(n)
+        inl = np.zeros((n, self.cap), np.uint8)
+        info = np.zeros((n, 8), np.int32)
+        self.L.sd_track_get_sim3.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+        _check(self.L.sd_track_get_sim3(self.h, frame0, n, _p(T), _p(R), _p(t), _p(s), _p(inl), self.cap, _p(info)))
+        return dict(T12=np.stack([_from_cm(x) for x in T]), R=R.reshape(n, 3, 3).transpose(0, 2, 1), t=t, scale=s,
+                    inliers=inl.astype(bool), info=info, returned=info[:, 0].astype(bool), n_inliers=info[:, 1],
+                    no_more=info[:, 2].astype(bool), iterations=info[:, 3], N=info[:, 4], max_its=info[:, 5], best_inliers=info[:, 6])
+
     def features_in_area(self, frame, x, y, r, min_level=-1, max_level=-1, want_grid=False):
         """Frame::GetFeaturesInArea on the device grid of current frame `frame` (debug read-out)."""
         idx = np.zeros(self.cap, np.int32)

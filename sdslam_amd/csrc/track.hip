@@ -189,6 +189,21 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &tb.sp_valid2, B * K));
   A(dalloc(h, &tb.sp_match, B * K));
   A(dalloc(h, &tb.sp_n, B));
+  A(dalloc(h, &tb.s3_Xw1, B * K * 3));
+  A(dalloc(h, &tb.s3_Xw2, B * K * 3));
+  A(dalloc(h, &tb.s3_X, B * K * 6));
+  A(dalloc(h, &tb.s3_F, B * K * 6));
+  A(dalloc(h, &tb.s3_idx, B * K));
+  A(dalloc(h, &tb.s3_state, B * 8));
+  A(dalloc(h, &tb.s3_best_mask, B * 32));
+  A(dalloc(h, &tb.s3_bestT, B * 16));
+  A(dalloc(h, &tb.s3_R, B * 9));
+  A(dalloc(h, &tb.s3_t, B * 3));
+  A(dalloc(h, &tb.s3_s, B));
+  A(dalloc(h, &tb.s3_T, B * 16));
+  A(dalloc(h, &tb.s3_inliers, B * K));
+  A(dalloc(h, &tb.s3_info, B * 8));
+  A(dalloc(h, &h->d_sim3_max_its, K + 1));
   A(dalloc(h, &tb.lm_cand, B * M));
   A(dalloc(h, &tb.lm_Xw, B * M * 3));
   A(dalloc(h, &tb.lm_normal, B * M * 3));
@@ -250,6 +265,7 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
       for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipEventCreate(&h->ev[r][i]);
     if (e == hipSuccess) e = h->pose_ring.create(B * 16 * sizeof(double));
     if (e == hipSuccess) e = h->small_ring.create(B * 8 * sizeof(int32_t));
+    if (e == hipSuccess) e = h->sim3_ring.create((K + 1) * sizeof(int32_t));
     if (e == hipSuccess) {
       // Priority of the tracking stream.  Round 1 (extraction kernels at 6-7 waves per SIMD): lowest was best (122.3 k vs
       // 119.2 k frames/s at highest) -- the few, long-running, latency-bound tracking workgroups filled what the extraction
@@ -293,6 +309,7 @@ void sd_track_destroy(sd_track* h) {
   if (h->ev_fence) (void)hipEventDestroy(h->ev_fence);
   h->pose_ring.destroy();
   h->small_ring.destroy();
+  h->sim3_ring.destroy();
   for (int r = 0; r < sd_track::kRing; r++)
     for (int i = 0; i < 6; i++)
       if (h->ev[r][i]) (void)hipEventDestroy(h->ev[r][i]);
@@ -341,6 +358,7 @@ int sd_track_set_last(sd_track* h, int frame0, int n_frames, const int32_t* n_la
 int sd_track_set_poses(sd_track* h, int frame0, int n_frames, const double* Tref_cm, const double* Tcur_cm) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(Tref_cm && Tcur_cm, SD_ERR_INVALID_ARG, "NULL argument");
+  sim3_end(h);           // the Sim3 solvers' keyframe poses are being replaced
   hipStream_t s = h->cur->stream;
   SD_TRY(upload(h->tb.Tref, Tref_cm, frame0, n_frames, 16, s));
   SD_TRY(upload(h->tb.Tprior, Tcur_cm, frame0, n_frames, 16, s));
@@ -352,6 +370,7 @@ int sd_track_set_rand(sd_track* h, int frame0, int n_frames, const int32_t* rand
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(rand_values && per_frame >= 1 && per_frame <= h->rand_per_frame, SD_ERR_INVALID_ARG, "bad rand stream");
   h->have_pnp = false;   // a resumed iterate() continues at a position of the OLD stream
+  sim3_end(h);
   SD_TRY(upload_rows(h->tb.rand_stream, h->rand_per_frame, rand_values, per_frame, frame0, n_frames, h->cur->stream));
   SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
   for (int f = 0; f < n_frames; f++) h->rand_len[(size_t)frame0 + f] = per_frame;
@@ -724,6 +743,7 @@ int sd_track_get_stereo(sd_track* h, int frame0, int n_frames, float* uright, fl
 int sd_track_set_point_flags(sd_track* h, int frame0, int n_frames, const uint8_t* has_mp_cur, const uint8_t* has_mp_ref, int cap) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(has_mp_cur && has_mp_ref && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad flag arrays (cap must be 1..keypoint capacity)");
+  sim3_end(h);           // the Sim3 solvers' validity test is being replaced
   hipStream_t s = h->cur->stream;
   const size_t K = h->kp_cap, o = (size_t)frame0 * K;
   SD_HIP_CHECK(hipMemsetAsync(h->tb.sp_valid1 + o, 0, (size_t)n_frames * K, s));
@@ -737,6 +757,7 @@ int sd_track_search_by_points(sd_track* h, int n_frames, float nnratio, int chec
   SD_TRY(check_ready(h, n_frames));
   SD_TRY(require_ref_frames(h, n_frames, false));
   SD_REQUIRE(keypoint_capacity(h->ref) == h->kp_cap, SD_ERR_INVALID_ARG, "cur / ref extractors must share the keypoint capacity");
+  sim3_end(h);           // matches12 is rewritten: Sim3 solvers built on the old vector cannot be continued
   return run_stage(h, true, false, STAGE_MATCH, [&](hipStream_t s) {   // timed in the matcher's slot
     return launch_search_points(h->cur, h->ref, h->tb, n_frames, nnratio, check_ori, s);
   });

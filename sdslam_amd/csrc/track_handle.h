@@ -74,6 +74,13 @@ struct sd_track {
   unsigned long long pnp_serial = 0;   // ... on the keypoints of THIS extraction of `cur` (the reference's solver owns copies of its inputs)
   sd::PnpParams pnp_params{};
   int pnp_frames = 0, pnp_iter_upper = 0;   // slots / upper bound of mnIterations of those solvers
+  // Sim3Solver (track_sim3.hip): sd_track_sim3 constructs, sd_track_sim3_iterate continues while the stamp holds (sim3_end)
+  RunStamp sim3;                   // mode = the broadcast setting the solvers were built under
+  unsigned long long sim3_ref_serial = 0;   // ... and on THIS extraction of `ref`
+  sd::Sim3Params sim3_params{};
+  int sim3_max_its = 0, sim3_iter_upper = 0;   // maxIterations argument / upper bound of mnIterations of those solvers
+  UploadRing sim3_ring;            // [kp_cap + 1] int32: the mRansacMaxIts table of a sd_track_sim3 call
+  int32_t* d_sim3_max_its = nullptr;
   sd::TrackBuffers tb{};
   sd::TrackCam cam{};
   bool have_cam = false;
@@ -116,6 +123,9 @@ inline void RunStamp::set(const sd_track* h, int n_frames, int mode_, int source
 inline bool RunStamp::covers(const sd_track* h, int n_frames) const {
   return cur == h->cur && serial == h->cur->extract_serial && n_frames <= n;
 }
+
+// Something a Sim3Solver was constructed from is being replaced: sd_track_sim3_iterate refuses until sd_track_sim3 runs again
+static inline void sim3_end(sd_track* h) { h->sim3 = RunStamp{}; }
 
 // "<the call `source` names> has not run on these slots since the last extraction"; 2: sd_track_stereo_init
 static inline const char* not_run_msg(int source) {

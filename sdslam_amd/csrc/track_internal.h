@@ -123,6 +123,25 @@ struct TrackBuffers {
   double* im_it;         // [B]     it_time_
   double* im_last;       // [B][16] Sensor::last_pose_, column-major
   double* im_meas;       // [B][6]  Tracking::measurements_ (SetMeasurements): gyro xyz, accelerometer xyz
+  // Sim3Solver (track_sim3.hip) on the SearchByPoints pairing: KF1 = the cur slot (pose Tcur), KF2 = the ref slot (pose Tref),
+  // matches = sp_match, validity = sp_valid1 / sp_valid2
+  double* s3_Xw1;        // [B][kp_cap][3] GetWorldPos() of KF1's map points, by KF1 keypoint index (sd_track_set_sim3_points)
+  double* s3_Xw2;        // [B][kp_cap][3] the same for KF2
+  // the constructor's gather, in mvnIndices1 order (structure of arrays, stride kp_cap)
+  double* s3_X;          // [B][6][kp_cap] mvX3Dc1 xyz | mvX3Dc2 xyz
+  float* s3_F;           // [B][6][kp_cap] mvP1im1 uv | mvP2im2 uv (float values, see FromCameraToImage) | mvnMaxError1 | mvnMaxError2
+  uint16_t* s3_idx;      // [B][kp_cap] mvnIndices1
+  // Sim3Solver members that persist between iterate() calls
+  int32_t* s3_state;     // [B][8]: mnIterations, mnBestInliers, N, mRansacMaxIts, mRansacMinInliers, mbFixScale, 0, 0
+  unsigned long long* s3_best_mask;   // [B][32] mvbBestInliers as bits over the gathered correspondences
+  double* s3_bestT;      // [B][16] mBestT12, column-major
+  double* s3_R;          // [B][9]  mBestRotation, column-major
+  double* s3_t;          // [B][3]  mBestTranslation
+  double* s3_s;          // [B]     mBestScale (a float value)
+  // iterate() outputs
+  double* s3_T;          // [B][16] the returned matrix, column-major (zeros: none)
+  uint8_t* s3_inliers;   // [B][kp_cap] vbInliers, over KF1 keypoints
+  int32_t* s3_info;      // [B][8]: returned, nInliers, bNoMore, mnIterations, N, mRansacMaxIts, mnBestInliers, 0
 };
 
 // Entry (r, c) of the 4x4 product A * B, both column-major: k = 0..3 in order, every product and sum rounded on its own (no
@@ -220,6 +239,16 @@ int read_sel_prof(unsigned long long* out64, int reset);
 int read_align_prof(unsigned long long* out16, int reset);
 int launch_pnp(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_sigma2, const PnpParams& pp,
                int n_frames, hipStream_t s);
+
+struct Sim3Params {
+  int fix_scale, min_inliers;
+  int n_iterations;     // argument of iterate()
+  int rand_per_frame;   // entries of rand_stream per slot
+  int resume;           // 0: construct (gather, SetRansacParameters) and iterate; 1: a further iterate() on the saved state
+};
+// d_max_its[N], N = 0..kp_cap: mRansacMaxIts for N correspondences (host libm, see sd_track_sim3); read only when !resume
+int launch_sim3(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const TrackCam& cam, const float* d_sigma2,
+                const int32_t* d_max_its, const Sim3Params& sp, int n_frames, hipStream_t s);
 
 int run_epnp_debug(int n, const double* Xw, const double* uv, double fx, double fy, double cx, double cy, double* R9, double* t3,
                    double* err);
