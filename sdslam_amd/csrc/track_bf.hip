@@ -23,18 +23,14 @@
 
 #include "orb_internal.h"
 #include "track_internal.h"
+#include "track_match_dev.h"
 
 namespace sd {
 
 #define BF_THREADS 256
-#define BF_K 4          // smallest keys kept per currentKF point
 #define BF_PT 2         // currentKF points per lane in phase 1
-#define BF_TILE 512     // pKF descriptors per LDS tile (16 KB)
 #define BF_TH_LOW 50
-#define BF_HISTO 30
 #define BF_INF 0xFFFFFFFFu
-
-extern "C" __device__ __attribute__((const)) unsigned int __ockl_wfred_min_u32(unsigned int);
 
 __device__ __forceinline__ int bf_dist(const uint32_t (&a)[8], const uint32_t (&b)[8]) {
   int d = 0;
@@ -54,22 +50,22 @@ __device__ __forceinline__ void bf_insert(uint32_t (&k)[BF_K], uint32_t key) {
   }
 }
 
-// Dynamic LDS: u32 s_tile[BF_TILE * 8] | u32 s_list[cap * BF_K] | u16 s_i1[cap] | i16 s_match[cap] | u32 s_v2[cap/32] |
-//              u32 s_m2[cap/32] | int s_hist[32] | int s_n1v
+// Dynamic LDS: LdsSearchPoints (track_match_lds.h)
 __global__ __launch_bounds__(BF_THREADS) void k_search_points(const sd_keypoint* __restrict__ kps1_all, const uint8_t* __restrict__ desc1_all,
                                                               const int32_t* __restrict__ n1_all, const sd_keypoint* __restrict__ kps2_all,
                                                               const uint8_t* __restrict__ desc2_all, const int32_t* __restrict__ n2_all,
                                                               TrackBuffers tb, float nnratio, int check_ori, int capw /* cap rounded up to 64 */,
                                                               int klist /* keys of a point's list phase 2 may use: BF_K (tests: fewer) */) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint32_t* s_tile = (uint32_t*)smem;
-  uint32_t* s_list = s_tile + BF_TILE * 8;
-  uint16_t* s_i1 = (uint16_t*)(s_list + (size_t)capw * BF_K);
-  int16_t* s_match = (int16_t*)(s_i1 + capw);
-  uint32_t* s_v2 = (uint32_t*)(s_match + capw);
-  uint32_t* s_m2 = s_v2 + (capw >> 5);
-  int* s_hist = (int*)(s_m2 + (capw >> 5));
-  int* s_n1v = s_hist + 32;
+  const LdsSearchPoints L(capw);
+  uint32_t* s_tile = lds_at<uint32_t>(smem, L.tile);
+  uint32_t* s_list = lds_at<uint32_t>(smem, L.list);
+  uint16_t* s_i1 = lds_at<uint16_t>(smem, L.i1);
+  int16_t* s_match = lds_at<int16_t>(smem, L.match);
+  uint32_t* s_v2 = lds_at<uint32_t>(smem, L.v2);
+  uint32_t* s_m2 = lds_at<uint32_t>(smem, L.m2);
+  int* s_hist = lds_at<int>(smem, L.hist);
+  int* s_n1v = lds_at<int>(smem, L.n1v);
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
   const int cap = tb.kp_cap;
@@ -186,9 +182,9 @@ __global__ __launch_bounds__(BF_THREADS) void k_search_points(const sd_keypoint*
           if (kk < m0) { m1 = m0; m0 = kk; }
           else if (kk < m1) m1 = kk;
         }
-        k1 = __ockl_wfred_min_u32(m0);
+        k1 = wave_min_u32(m0);
         if (m0 == k1) m0 = m1;                               // keys are unique: exactly one lane gives up its first
-        k2 = __ockl_wfred_min_u32(m0);
+        k2 = wave_min_u32(m0);
       } else {
         k1 = BF_INF;                                         // bestDist1 >= TH_LOW whatever lies beyond the list: no match
       }
@@ -206,39 +202,16 @@ __global__ __launch_bounds__(BF_THREADS) void k_search_points(const sd_keypoint*
   }
   // ---- rotation consistency (src/ORBmatcher.cc:1269-1296), after the loop: the bins never influence a match decision
   if (check_ori) {
-    const float factor = 1.0f / BF_HISTO;
     for (int e = lane; e < n1v; e += 64) {
       const int i1 = s_i1[e], j = s_match[i1];
       if (j < 0) continue;
-      float rot = kps1[i1].angle - kps2[j].angle;
-      if (rot < 0.0) rot += 360.0f;
-      int bin = (int)roundf(rot * factor);
-      if (bin == BF_HISTO) bin = 0;
+      const int bin = rot_bin(kps1[i1].angle, kps2[j].angle);
       atomicAdd(&s_hist[bin], 1);
       s_list[e] = (uint32_t)bin;   // phase 1's lists are dead
     }
     __threadfence_block();
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    int max1 = 0, max2 = 0, max3 = 0;
-    for (int b = 0; b < BF_HISTO; b++) {
-      const int sh = s_hist[b];
-      if (sh > max1) {
-        max3 = max2; max2 = max1; max1 = sh;
-        ind3 = ind2; ind2 = ind1; ind1 = b;
-      } else if (sh > max2) {
-        max3 = max2; max2 = sh;
-        ind3 = ind2; ind2 = b;
-      } else if (sh > max3) {
-        max3 = sh;
-        ind3 = b;
-      }
-    }
-    if (max2 < 0.1f * (float)max1) {
-      ind2 = -1;
-      ind3 = -1;
-    } else if (max3 < 0.1f * (float)max1) {
-      ind3 = -1;
-    }
+    int ind1, ind2, ind3;
+    three_maxima(s_hist, ind1, ind2, ind3);
     int dropped = 0;
     for (int e0 = 0; e0 < n1v; e0 += 64) {
       const int e = e0 + lane;
@@ -269,8 +242,7 @@ int launch_search_points(const sd_orb* cur, const sd_orb* ref, const TrackBuffer
   // option "track.bf_list_k" = 1..3 (tests): phase 2 sees only the first keys of every list, so the whole-wave recomputation -- rare on real
   // data -- runs for most points
   const int klist = std::min(BF_K, std::max(1, opt(OPT_BF_LIST_K)));
-  const size_t lds = (size_t)BF_TILE * 32 + (size_t)capw * BF_K * 4 + (size_t)capw * 2 * 2 + (size_t)(capw >> 5) * 4 * 2 + 8 + 33 * 4 + 16;
-  hipLaunchKernelGGL(k_search_points, dim3(n_frames), dim3(BF_THREADS), lds, s, (cur->have_dist ? cur->d_kps_un : cur->d_kps), cur->d_desc,
+  hipLaunchKernelGGL(k_search_points, dim3(n_frames), dim3(BF_THREADS), LdsSearchPoints(capw).bytes, s, (cur->have_dist ? cur->d_kps_un : cur->d_kps), cur->d_desc,
                      cur->d_nout, (ref->have_dist ? ref->d_kps_un : ref->d_kps), ref->d_desc, ref->d_nout, tb, nnratio, check_ori, capw, klist);
   SD_HIP_CHECK(hipGetLastError());
   return SD_OK;

@@ -25,18 +25,13 @@
 
 #include "orb_internal.h"
 #include "track_internal.h"
+#include "track_match_dev.h"
 
 namespace sd {
 
 #define MT_MAXKP 2048      // keypoints per frame supported by the 11-bit index fields
 #define MT_WAVES 8
-#ifndef MT_LIST_CAP
-#define MT_LIST_CAP 4096   // candidate keys per frame kept in LDS (more: per-point slow path)
-#endif
-#define GRID_COLS 64
-#define GRID_ROWS 48
 #define TH_HIGH 100
-#define HISTO_LENGTH 30
 
 struct MatchGeom {   // what every per-point evaluation needs (uniform over the workgroup)
   double R[3][3], t[3];
@@ -44,20 +39,6 @@ struct MatchGeom {   // what every per-point evaluation needs (uniform over the 
   bool bForward, bBackward;
 };
 
-// Candidate keys of last-frame point i: projection, window (GetFeaturesInArea), level / distance / uRight
-// gates, Hamming distance.  Everything here is independent of earlier assignments.  All 64 lanes call.
-//   mode 0: returns the number of candidates (wave-uniform)
-//   mode 1: writes key = dist << 22 | order-in-vIndices2 << 11 | keypoint index to list[0 .. count)
-//   mode 2: returns this lane's minimum key over the candidates not claimed by a point with observations
-// *seq_total = entries of the searched cells (keys carry 11 bits of order).
-// Candidates of one search window: GetFeaturesInArea(u, v, radius, minLevel, maxLevel) (src/Frame.cc:271-321) in
-// the reference's order, then the stereo gate |ur - mvuRight[idx]| <= radius for keypoints with a right
-// coordinate (src/ORBmatcher.cc:76-80, 1020-1025) and, in MODE 2, the "already holds a map point with
-// Observations() > 0" gate.  All 64 lanes call.
-//   mode 0: returns the number of candidates (wave-uniform)
-//   mode 1: writes key = dist << 22 | order-in-vIndices << 11 | keypoint index to list[0 .. count)
-//   mode 2: returns this lane's minimum key over the unclaimed candidates
-// *seq_total = entries of the searched cells (keys carry 11 bits of order).
 struct MatchLds {
   const uint32_t* s_key;      // sorted (cell << 11 | index)
   const uint16_t* s_cstart;   // first sorted position of every cell
@@ -66,16 +47,26 @@ struct MatchLds {
   const uint32_t* s_kclaim;   // bit idx: keypoint idx already held such a point before the call (may be null)
 };
 
-// GL = lanes that work on one point: 64 (the whole wave; `lane`, `lt` as usual, gm = ~0) or 32 (a wave handles two points,
-// one per half: `lane` = lane within the half, `lt` = the lower lanes OF THE HALF and `gm` = the half's lanes, both as
-// bit masks of the 64-bit wave ballot).  The halves diverge freely; a ballot only ever carries the active lanes.
-// Minimum over the wave, every lane gets it: the device library's DPP reduction instead of six LDS-crossbar shuffles
-// (the serial phase-2 chain of the matchers does one per point: single-frame search 1.25 -> 0.97 ms; A/B on one box at
-// 1024 frames: 129.6 k vs 129.2 k frames/s).
-extern "C" __device__ __attribute__((const)) unsigned int __ockl_wfred_min_u32(unsigned int);
+// GL lanes of a wave work on one point.  64: the whole wave (`lane`, `lt` as usual, gm = ~0).  Fewer: one point per group, `glane` =
+// lane within the group, `glt` = the lower lanes OF THE GROUP and `gm` = the group's lanes, both as bit masks of the 64-bit wave
+// ballot.  The groups diverge freely; a ballot only ever carries the active lanes.
+template <int GL>
+struct SubWave {
+  int group, glane;
+  unsigned long long gm, glt;
+  __device__ __forceinline__ explicit SubWave(int lane)
+      : group(lane / GL), glane(lane % GL), gm(((1ull << GL) - 1ull) << (GL * group)), glt(((1ull << glane) - 1ull) << (GL * group)) {}
+};
 __device__ __forceinline__ void sdsel_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return __ockl_wfred_min_u32(v); }
 
+// Candidates of one search window: GetFeaturesInArea(u, v, radius, minLevel, maxLevel) (src/Frame.cc:271-321) in
+// the reference's order, then the stereo gate |ur - mvuRight[idx]| <= radius for keypoints with a right
+// coordinate (src/ORBmatcher.cc:76-80, 1020-1025) and, in MODE 2, the "already holds a map point with
+// Observations() > 0" gate.  All lanes of the group call.
+//   mode 0: returns the number of candidates (uniform over the group)
+//   mode 1: writes key = dist << 22 | order-in-vIndices << 11 | keypoint index to list[0 .. count)
+//   mode 2: returns this lane's minimum key over the unclaimed candidates
+// *seq_total = entries of the searched cells (keys carry 11 bits of order).
 template <int MODE, int GL = 64>
 __device__ __forceinline__ uint32_t match_window(float u, float v, float radius, int minLevel, int maxLevel, float ur,
                                                  const uint8_t* __restrict__ dmp /* 32-byte map point descriptor */,
@@ -171,25 +162,29 @@ __device__ __forceinline__ uint32_t grid_key(const sd_keypoint& kp, const TrackC
   if (posX < 0 || posX >= GRID_COLS || posY < 0 || posY >= GRID_ROWS) return 0xFFFFFFFFu;
   return ((uint32_t)(posX * GRID_ROWS + posY) << 11) | (uint32_t)i;
 }
-// Frame::AssignFeaturesToGrid (src/Frame.cc:179-192): bitonic sort of the KP2 keys in LDS (mGrid[x][y] in ascending
-// keypoint index = one contiguous, ordered run per cell) and the first sorted position of every cell.  All NT threads
-// call, after a barrier that makes s_key complete; ends with s_cstart written but NOT yet synchronised.
-__device__ __forceinline__ void grid_sort_and_starts(uint32_t* s_key, uint16_t* s_cstart, int KP2, int tid, int NT) {
-  for (int k = 2; k <= KP2; k <<= 1)
+// Ascending bitonic sort of v[0 .. n) in LDS, n a power of two.  All NT threads call, after a barrier that makes v complete;
+// ends with a barrier.
+__device__ __forceinline__ void bitonic_sort_lds(uint32_t* v, int n, int tid, int NT) {
+  for (int k = 2; k <= n; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < KP2; i += NT) {
-        int ixj = i ^ j;
+      for (int i = tid; i < n; i += NT) {
+        const int ixj = i ^ j;
         if (ixj > i) {
-          uint32_t a = s_key[i], b = s_key[ixj];
-          bool up = (i & k) == 0;
-          if ((a > b) == up) {
-            s_key[i] = b;
-            s_key[ixj] = a;
+          const uint32_t a = v[i], b = v[ixj];
+          if ((a > b) == ((i & k) == 0)) {
+            v[i] = b;
+            v[ixj] = a;
           }
         }
       }
       __syncthreads();
     }
+}
+// Frame::AssignFeaturesToGrid (src/Frame.cc:179-192): sort of the KP2 keys in LDS (mGrid[x][y] in ascending keypoint index =
+// one contiguous, ordered run per cell) and the first sorted position of every cell.  All NT threads call, after a barrier
+// that makes s_key complete; ends with s_cstart written but NOT yet synchronised.
+__device__ __forceinline__ void grid_sort_and_starts(uint32_t* s_key, uint16_t* s_cstart, int KP2, int tid, int NT) {
+  bitonic_sort_lds(s_key, KP2, tid, NT);
   for (int c = tid; c <= GRID_COLS * GRID_ROWS; c += NT) {
     const uint32_t target = (uint32_t)c << 11;
     int lo = 0, hi = KP2;
@@ -199,6 +194,54 @@ __device__ __forceinline__ void grid_sort_and_starts(uint32_t* s_key, uint16_t* 
       else hi = mid;
     }
     s_cstart[c] = (uint16_t)lo;
+  }
+}
+
+// Flags pred(i), i in [0, n_bits), packed into the 32-bit words dst[0 .. (n_bits + 31) / 32): one flag per thread and round,
+// a wave's 64 flags are one ballot = two words.  All NT threads call (NT a multiple of 64; tid = lane for a single wave).
+template <typename Pred>
+__device__ __forceinline__ void pack_flags(Pred pred, int n_bits, uint32_t* dst, int tid, int NT) {
+  const int lane = tid & 63, wave = tid >> 6, n_words = (n_bits + 31) >> 5;
+  for (int i0 = 0; i0 < ((n_bits + 63) & ~63); i0 += NT) {
+    const unsigned long long b = __ballot(pred(i0 + tid));
+    const int w = (i0 >> 5) + 2 * wave;
+    if (lane == 0 && w < n_words) {
+      dst[w] = (uint32_t)b;
+      if (w + 1 < n_words) dst[w + 1] = (uint32_t)(b >> 32);
+    }
+  }
+}
+
+// Phase 1 of k_match / k_match_local for one point and its group of GL lanes: count_fn(&seq) counts the candidates, one atomic
+// reserves that many slots of the LDS list, write_fn(list, &seq) writes the keys.  Returns the point's word: 0 (nothing to do) |
+// offset << 16 | count | 0xFFFFFFFF (list full, or >= 2048 grid entries in the window: keys carry 11 bits of order -- phase 2 evaluates it).
+template <int GL, typename CountFn, typename WriteFn>
+__device__ __forceinline__ uint32_t collect_candidates(CountFn count_fn, WriteFn write_fn, int* s_nlist, uint32_t* s_list,
+                                                       const SubWave<GL>& g) {
+  int seq = 0;
+  const int cnt = (int)count_fn(&seq);
+  if (cnt <= 0) return 0u;
+  int off = 0;
+  if (g.glane == 0) off = atomicAdd(s_nlist, cnt);
+  off = __shfl(off, GL * g.group);
+  if (off + cnt > MT_LIST_CAP || seq >= 2048 || cnt > 0xffff) return 0xFFFFFFFFu;
+  write_fn(s_list + off, &seq);
+  return ((uint32_t)off << 16) | (uint32_t)cnt;
+}
+
+// Phase 2's walk over the points in order, one wave: word_of(base + lane) fetches the per-point words 64 at a time and only the
+// points with a non-zero word are visited, body(i, word) with both wave-uniform (most slots of the arrays hold no valid point:
+// one LDS round trip per slot was a tenth of the kernel for a single frame).
+template <typename WordOf, typename Body>
+__device__ __forceinline__ void for_each_marked_point(int n, int lane, WordOf word_of, Body body) {
+  for (int base = 0; base < n; base += 64) {
+    const uint32_t pcv = word_of(base + lane);
+    unsigned long long todo = __ballot(pcv != 0);
+    while (todo) {
+      const int jsel = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      body(base + jsel, (uint32_t)__builtin_amdgcn_readlane((int)pcv, jsel));
+    }
   }
 }
 
@@ -232,11 +275,26 @@ __device__ __forceinline__ uint32_t match_point(int i, const sd_keypoint* __rest
                                 list, lane, lt, seq_total, -1, gm);
 }
 
-// Dynamic LDS layout (KP2 = power of two >= keypoint capacity, MP = max_points):
-//   u32 s_key[KP2] | u32 s_list[MT_LIST_CAP] | u32 s_pt[MP] | f32 s_kang[KP2] | u32 s_obs[(MP+31)/32] | u32 s_valid[(MP+31)/32] |
-//   i16 s_match[KP2] | u16 s_ev[max(KP2, MP)] | u16 s_cstart[64*48+2] | int s_hist[30] | int s_nlist
-// (s_ev records one entry per ASSIGNMENT -- rotHist[bin].push_back -- and a keypoint may be assigned again by a later
-// point, so up to n_last <= MP entries: it is sized by the larger of the two capacities)
+// pose / direction flags of a search: column-major Tcw, bForward / bBackward from tlc = Rlw * (-Rcw^T tcw) + tlw
+__device__ __forceinline__ void match_geom(MatchGeom& G, const double* Tc, const double* Tl, const TrackCam& cam, float th, int mono) {
+  G.th = th;
+  G.invW = (float)GRID_COLS / (float)(cam.max_x - cam.min_x);
+  G.invH = (float)GRID_ROWS / (float)(cam.max_y - cam.min_y);
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) G.R[r][c] = Tc[c * 4 + r];
+    G.t[r] = Tc[12 + r];
+  }
+  G.bForward = G.bBackward = false;
+  if (!mono) {
+    double twc[3], tlc2;
+    for (int i = 0; i < 3; i++) twc[i] = (-G.R[0][i]) * G.t[0] + (-G.R[1][i]) * G.t[1] + (-G.R[2][i]) * G.t[2];
+    tlc2 = (Tl[0 * 4 + 2] * twc[0] + Tl[1 * 4 + 2] * twc[1] + Tl[2 * 4 + 2] * twc[2]) + Tl[12 + 2];
+    G.bForward = tlc2 > cam.mb;
+    G.bBackward = -tlc2 > cam.mb;
+  }
+}
+
+// Dynamic LDS: LdsMatch (track_match_lds.h)
 __global__ __launch_bounds__(64 * MT_WAVES) void k_match(const sd_keypoint* __restrict__ kps_all, const uint8_t* __restrict__ desc_all,
                                                           const int32_t* __restrict__ nkp_all, TrackBuffers tb, TrackCam cam,
                                                           const float* __restrict__ sf, float th, int mono, int check_ori, int KP2,
@@ -246,17 +304,18 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match(const sd_keypoint* __re
   // TrackWithMotionModel runs only for the frames whose first search found < retry_below matches (whole-workgroup exit)
   if (retry_below > 0 && tb.n_matches[blockIdx.x] >= retry_below) return;
   const int MP = tb.max_points;
-  uint32_t* s_key = (uint32_t*)smem;
-  uint32_t* s_list = s_key + KP2;
-  uint32_t* s_pt = s_list + MT_LIST_CAP;
-  float* s_kang = (float*)(s_pt + MP);
-  uint32_t* s_obs = (uint32_t*)(s_kang + KP2);
-  uint32_t* s_valid = s_obs + ((MP + 31) >> 5);
-  int16_t* s_match = (int16_t*)(s_valid + ((MP + 31) >> 5));
-  uint16_t* s_ev = (uint16_t*)(s_match + KP2);
-  uint16_t* s_cstart = s_ev + (KP2 > MP ? KP2 : MP);
-  int* s_hist = (int*)(((uintptr_t)(s_cstart + GRID_COLS * GRID_ROWS + 2) + 3) & ~(uintptr_t)3);
-  int* s_nlist = s_hist + HISTO_LENGTH;
+  const LdsMatch L(KP2, MP);
+  uint32_t* s_key = lds_at<uint32_t>(smem, L.key);
+  uint32_t* s_list = lds_at<uint32_t>(smem, L.list);
+  uint32_t* s_pt = lds_at<uint32_t>(smem, L.pt);
+  float* s_kang = lds_at<float>(smem, L.kang);
+  uint32_t* s_obs = lds_at<uint32_t>(smem, L.obs);
+  uint32_t* s_valid = lds_at<uint32_t>(smem, L.valid);
+  int16_t* s_match = lds_at<int16_t>(smem, L.match);
+  uint16_t* s_ev = lds_at<uint16_t>(smem, L.ev);
+  uint16_t* s_cstart = lds_at<uint16_t>(smem, L.cstart);
+  int* s_hist = lds_at<int>(smem, L.hist);
+  int* s_nlist = lds_at<int>(smem, L.nlist);
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NT = 64 * MT_WAVES;
   const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
   const int cap = tb.kp_cap;
@@ -264,10 +323,8 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match(const sd_keypoint* __re
   const sd_keypoint* kps = kps_all + (size_t)fc * cap;
   const uint8_t* desc = desc_all + (size_t)fc * cap * 32;
   const int N = min(nkp_all[fc], min(cap, KP2));
-  MatchGeom G;
-  G.th = th;
-  G.invW = (float)GRID_COLS / (float)(cam.max_x - cam.min_x);   // mfGridElementWidthInv
-  G.invH = (float)GRID_ROWS / (float)(cam.max_y - cam.min_y);
+  const float invW = (float)GRID_COLS / (float)(cam.max_x - cam.min_x);   // mfGridElementWidthInv
+  const float invH = (float)GRID_ROWS / (float)(cam.max_y - cam.min_y);
   const int M = MP;
   const uint8_t* valid = tb.valid + (size_t)f * M;
   const double* Xw = tb.Xw + (size_t)f * M * 3;
@@ -285,82 +342,44 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match(const sd_keypoint* __re
     if (i < N) {
       const sd_keypoint kp = kps[i];
       ang = kp.angle;
-      key = grid_key(kp, cam, G.invW, G.invH, i);
+      key = grid_key(kp, cam, invW, invH, i);
     }
     s_key[i] = key;
     s_kang[i] = ang;
     s_match[i] = -1;   // CurrentFrame.mvpMapPoints filled with NULL (src/Tracking.cc:676)
   }
-  // Observations() > 0 and validity flags of the last frame's points as bit masks: one element per thread, wave ballots
-  for (int m0 = 0; m0 < ((MP + 63) & ~63); m0 += NT) {
-    const int m = m0 + tid;
-    const unsigned long long bo = __ballot(m < n_last && l_obs[m] > 0), bv = __ballot(m < n_last && valid[m] != 0);
-    const int w = (m0 >> 5) + 2 * wave;
-    if (lane == 0 && w < ((MP + 31) >> 5)) {
-      s_obs[w] = (uint32_t)bo;
-      s_valid[w] = (uint32_t)bv;
-      if (w + 1 < ((MP + 31) >> 5)) {
-        s_obs[w + 1] = (uint32_t)(bo >> 32);
-        s_valid[w + 1] = (uint32_t)(bv >> 32);
-      }
-    }
-  }
+  // Observations() > 0 and validity flags of the last frame's points as bit masks
+  pack_flags([&](int m) { return m < n_last && l_obs[m] > 0; }, MP, s_obs, tid, NT);
+  pack_flags([&](int m) { return m < n_last && valid[m] != 0; }, MP, s_valid, tid, NT);
   if (tid < HISTO_LENGTH) s_hist[tid] = 0;
   if (tid == 0) *s_nlist = 0;
   __syncthreads();
   grid_sort_and_starts(s_key, s_cstart, KP2, tid, NT);
-  {
-    // column-major; the retry searches from the predicted pose, which becomes the frame's pose (SetPose(predicted_pose))
-    const double* Tc = (retry_below > 0 ? tb.Tprior : tb.Tcur) + (size_t)f * 16;
-    if (retry_below > 0 && tid < 16) tb.Tcur[(size_t)f * 16 + tid] = Tc[tid];
-    if (retry_below > 0 && tid == 0) tb.tw_info[(size_t)f * 4 + 3] = 1;
-    for (int r = 0; r < 3; r++) {
-      for (int c = 0; c < 3; c++) G.R[r][c] = Tc[c * 4 + r];
-      G.t[r] = Tc[12 + r];
-    }
-    // bForward / bBackward: tlc = Rlw * (-Rcw^T tcw) + tlw compared with the baseline mb
-    G.bForward = G.bBackward = false;
-    if (!mono) {
-      const double* Tl = tb.Tref + (size_t)f * 16;
-      double twc[3], tlc2;
-      for (int i = 0; i < 3; i++) twc[i] = (-G.R[0][i]) * G.t[0] + (-G.R[1][i]) * G.t[1] + (-G.R[2][i]) * G.t[2];
-      tlc2 = (Tl[0 * 4 + 2] * twc[0] + Tl[1 * 4 + 2] * twc[1] + Tl[2 * 4 + 2] * twc[2]) + Tl[12 + 2];
-      G.bForward = tlc2 > cam.mb;
-      G.bBackward = -tlc2 > cam.mb;
-    }
-  }
+  // the retry searches from the predicted pose, which becomes the frame's pose (SetPose(predicted_pose))
+  const double* Tc = (retry_below > 0 ? tb.Tprior : tb.Tcur) + (size_t)f * 16;
+  if (retry_below > 0 && tid < 16) tb.Tcur[(size_t)f * 16 + tid] = Tc[tid];
+  if (retry_below > 0 && tid == 0) tb.tw_info[(size_t)f * 4 + 3] = 1;
+  MatchGeom G;
+  match_geom(G, Tc, tb.Tref + (size_t)f * 16, cam, th, mono);
   __syncthreads();
 
   const MatchLds SL = {s_key, s_cstart, s_match, s_obs, nullptr};
-  // ---- phase 1 (all waves, one wave per last-frame point): candidate keys into the LDS list.
-  // s_pt[i] = 0 (nothing to do) | offset << 16 | count | 0xFFFFFFFF (list full: evaluate in phase 2)
+  // ---- phase 1 (all waves): candidate keys into the LDS list, s_pt[i] = the point's word (collect_candidates).
   // Two points per wave, one per 32-lane half: a point's window rarely holds more than 32 candidates, and a wave is one
   // dependent chain of loads per point (map point -> keypoints of the window -> their descriptors), so two chains in flight
   // per wave nearly halve the phase.
   {
-    const int half = lane >> 5, glane = lane & 31;
-    const unsigned long long gm = 0xFFFFFFFFull << (32 * half);
-    const unsigned long long glt = ((1ull << glane) - 1ull) << (32 * half);
+    const SubWave<32> g(lane);
     for (int i0 = 0; i0 < n_last; i0 += 2 * MT_WAVES) {
-      const int i = i0 + 2 * wave + half;
+      const int i = i0 + 2 * wave + g.group;
       if (i < n_last) {
         uint32_t pc = 0;
-        if ((s_valid[i >> 5] >> (i & 31)) & 1u) {
-          int seq = 0;
-          const int cnt = (int)match_point<0, 32>(i, kps, desc, Xw, mp_desc, l_oct, uright, SL, G, cam, sf, nullptr, glane, glt, &seq, gm);
-          if (cnt > 0) {
-            int off = 0;
-            if (glane == 0) off = atomicAdd(s_nlist, cnt);
-            off = __shfl(off, 32 * half);
-            if (off + cnt > MT_LIST_CAP || seq >= 2048 || cnt > 0xffff) {
-              pc = 0xFFFFFFFFu;
-            } else {
-              match_point<1, 32>(i, kps, desc, Xw, mp_desc, l_oct, uright, SL, G, cam, sf, s_list + off, glane, glt, &seq, gm);
-              pc = ((uint32_t)off << 16) | (uint32_t)cnt;
-            }
-          }
-        }
-        if (glane == 0) s_pt[i] = pc;
+        if ((s_valid[i >> 5] >> (i & 31)) & 1u)
+          pc = collect_candidates<32>(
+              [&](int* seq) { return match_point<0, 32>(i, kps, desc, Xw, mp_desc, l_oct, uright, SL, G, cam, sf, nullptr, g.glane, g.glt, seq, g.gm); },
+              [&](uint32_t* list, int* seq) { match_point<1, 32>(i, kps, desc, Xw, mp_desc, l_oct, uright, SL, G, cam, sf, list, g.glane, g.glt, seq, g.gm); },
+              s_nlist, s_list, g);
+        if (g.glane == 0) s_pt[i] = pc;
       }
     }
   }
@@ -370,74 +389,43 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match(const sd_keypoint* __re
   // ---- phase 2 (points in order): minimum over the candidates not claimed by a point with observations
   // (first strict minimum = smallest key), assignment (later points overwrite), rotation histogram
   int nmatches = 0, nev = 0;
-  const float factor = 1.0f / HISTO_LENGTH;
-  // s_pt is read 64 entries at a time and only the points with something to do are visited (most slots of the arrays
-  // hold no valid point: one LDS round trip per slot was a tenth of the kernel for a single frame)
-  for (int base = 0; base < n_last; base += 64) {
-   const uint32_t pcv = (base + lane < n_last) ? s_pt[base + lane] : 0u;
-   unsigned long long todo = __ballot(pcv != 0);
-   while (todo) {
-    const int jsel = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const int i = base + jsel;
-    const uint32_t pc = (uint32_t)__builtin_amdgcn_readlane((int)pcv, jsel);
-    uint32_t best = 0x7FFFFFFFu;
-    if (pc != 0xFFFFFFFFu) {
-      const int off = pc >> 16, cnt = pc & 0xffff;
-      for (int j = lane; j < cnt; j += 64) {
-        const uint32_t key = s_list[off + j];
-        const int m = s_match[key & 2047];
-        const bool claimed = (m >= 0) && ((s_obs[m >> 5] >> (m & 31)) & 1u);
-        if (!claimed) best = min(best, key);
-      }
-    } else {
-      int seq = 0;
-      best = match_point<2>(i, kps, desc, Xw, mp_desc, l_oct, uright, SL, G, cam, sf, nullptr, lane, lt, &seq);
-    }
-    best = wave_min_u32(best);
-    if (best == 0x7FFFFFFFu) continue;
-    const int bestDist = best >> 22;
-    const int bestIdx2 = best & 2047;
-    if (bestDist <= TH_HIGH) {
-      if (lane == 0) s_match[bestIdx2] = (int16_t)i;
-      nmatches++;
-      if (check_ori) {
-        float rot = l_ang[i] - s_kang[bestIdx2];
-        if (rot < 0.0) rot += 360.0f;
-        int bin = (int)roundf(rot * factor);
-        if (bin == HISTO_LENGTH) bin = 0;
-        if (lane == 0) {
-          s_ev[nev] = (uint16_t)((bin << 11) | bestIdx2);
-          s_hist[bin]++;
+  for_each_marked_point(
+      n_last, lane, [&](int m) { return m < n_last ? s_pt[m] : 0u; },
+      [&](int i, uint32_t pc) {
+        uint32_t best = 0x7FFFFFFFu;
+        if (pc != 0xFFFFFFFFu) {
+          const int off = pc >> 16, cnt = pc & 0xffff;
+          for (int j = lane; j < cnt; j += 64) {
+            const uint32_t key = s_list[off + j];
+            const int m = s_match[key & 2047];
+            const bool claimed = (m >= 0) && ((s_obs[m >> 5] >> (m & 31)) & 1u);
+            if (!claimed) best = min(best, key);
+          }
+        } else {
+          int seq = 0;
+          best = match_point<2>(i, kps, desc, Xw, mp_desc, l_oct, uright, SL, G, cam, sf, nullptr, lane, lt, &seq);
         }
-        nev++;
-      }
-    }
-     }
-  }
+        best = wave_min_u32(best);
+        if (best == 0x7FFFFFFFu) return;
+        const int bestDist = best >> 22;
+        const int bestIdx2 = best & 2047;
+        if (bestDist <= TH_HIGH) {
+          if (lane == 0) s_match[bestIdx2] = (int16_t)i;
+          nmatches++;
+          if (check_ori) {
+            const int bin = rot_bin(l_ang[i], s_kang[bestIdx2]);
+            if (lane == 0) {
+              s_ev[nev] = (uint16_t)((bin << 11) | bestIdx2);
+              s_hist[bin]++;
+            }
+            nev++;
+          }
+        }
+      });
   // ---- rotation consistency: keep the three dominant 30-degree bins (10 % rule)
   if (check_ori) {
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    int max1 = 0, max2 = 0, max3 = 0;
-    for (int b = 0; b < HISTO_LENGTH; b++) {
-      const int sh = s_hist[b];
-      if (sh > max1) {
-        max3 = max2; max2 = max1; max1 = sh;
-        ind3 = ind2; ind2 = ind1; ind1 = b;
-      } else if (sh > max2) {
-        max3 = max2; max2 = sh;
-        ind3 = ind2; ind2 = b;
-      } else if (sh > max3) {
-        max3 = sh;
-        ind3 = b;
-      }
-    }
-    if (max2 < 0.1f * (float)max1) {
-      ind2 = -1;
-      ind3 = -1;
-    } else if (max3 < 0.1f * (float)max1) {
-      ind3 = -1;
-    }
+    int ind1, ind2, ind3;
+    three_maxima(s_hist, ind1, ind2, ind3);
     for (int e = 0; e < nev; e++) {   // uniform loop; lane 0 applies
       const unsigned ev = s_ev[e];
       const int bin = ev >> 11;
@@ -475,35 +463,17 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match(const sd_keypoint* __re
 #define MT_HBM_CSTART (GRID_COLS * GRID_ROWS + 4)
 extern "C" __device__ __attribute__((const)) int __ockl_wfred_add_i32(int);
 
-// pose / direction flags of a search (k_match's preamble): column-major Tcw, bForward / bBackward from tlc = Rlw * (-Rcw^T tcw) + tlw
-__device__ __forceinline__ void match_geom(MatchGeom& G, const double* Tc, const double* Tl, const TrackCam& cam, float th, int mono) {
-  G.th = th;
-  G.invW = (float)GRID_COLS / (float)(cam.max_x - cam.min_x);
-  G.invH = (float)GRID_ROWS / (float)(cam.max_y - cam.min_y);
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) G.R[r][c] = Tc[c * 4 + r];
-    G.t[r] = Tc[12 + r];
-  }
-  G.bForward = G.bBackward = false;
-  if (!mono) {
-    double twc[3], tlc2;
-    for (int i = 0; i < 3; i++) twc[i] = (-G.R[0][i]) * G.t[0] + (-G.R[1][i]) * G.t[1] + (-G.R[2][i]) * G.t[2];
-    tlc2 = (Tl[0 * 4 + 2] * twc[0] + Tl[1 * 4 + 2] * twc[1] + Tl[2 * 4 + 2] * twc[2]) + Tl[12 + 2];
-    G.bForward = tlc2 > cam.mb;
-    G.bBackward = -tlc2 > cam.mb;
-  }
-}
-
 __device__ __forceinline__ void match_cand_frame(const int f, uint8_t* smem, const sd_keypoint* __restrict__ kps_all,
                                                  const uint8_t* __restrict__ desc_all, const int32_t* __restrict__ nkp_all, const TrackBuffers& tb,
-                                                 const TrackCam& cam, const float* __restrict__ sf, float th, int mono, int KP2, int retry_below) {
+                                                 const TrackCam& cam, const float* __restrict__ sf, float th, int mono, int KP2) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NT = 64 * MT_WAVES;
   const int MP = tb.max_points;
-  uint32_t* s_key = (uint32_t*)smem;
-  uint32_t* s_off = s_key + KP2;                                  // exclusive prefix of the counts (may exceed the list)
-  uint16_t* s_cnt = (uint16_t*)(s_off + MP);                      // 0xFFFF: window too large for the 11-bit order field
-  uint32_t* s_valid = (uint32_t*)(s_cnt + MP + (MP & 1));
-  uint16_t* s_cstart = (uint16_t*)(s_valid + ((MP + 31) >> 5));
+  const LdsMatchCand L(KP2, MP);
+  uint32_t* s_key = lds_at<uint32_t>(smem, L.key);
+  uint32_t* s_off = lds_at<uint32_t>(smem, L.off);
+  uint16_t* s_cnt = lds_at<uint16_t>(smem, L.cnt);
+  uint32_t* s_valid = lds_at<uint32_t>(smem, L.valid);
+  uint16_t* s_cstart = lds_at<uint16_t>(smem, L.cstart);
   const int cap = tb.kp_cap;
   const int fc = tb.cur_bcast >= 0 ? tb.cur_bcast : f;
   const sd_keypoint* kps = kps_all + (size_t)fc * cap;
@@ -521,25 +491,11 @@ __device__ __forceinline__ void match_cand_frame(const int f, uint8_t* smem, con
   const float invW = (float)GRID_COLS / (float)(cam.max_x - cam.min_x), invH = (float)GRID_ROWS / (float)(cam.max_y - cam.min_y);
 
   for (int i = tid; i < KP2; i += NT) s_key[i] = i < N ? grid_key(kps[i], cam, invW, invH, i) : 0xFFFFFFFFu;
-  for (int m0 = 0; m0 < ((MP + 63) & ~63); m0 += NT) {
-    const int m = m0 + tid;
-    const unsigned long long bv = __ballot(m < n_last && valid[m] != 0);
-    const int w = (m0 >> 5) + 2 * wave;
-    if (lane == 0 && w < ((MP + 31) >> 5)) {
-      s_valid[w] = (uint32_t)bv;
-      if (w + 1 < ((MP + 31) >> 5)) s_valid[w + 1] = (uint32_t)(bv >> 32);
-    }
-  }
+  pack_flags([&](int m) { return m < n_last && valid[m] != 0; }, MP, s_valid, tid, NT);
   __syncthreads();
   grid_sort_and_starts(s_key, s_cstart, KP2, tid, NT);
-  MatchGeom G;
-  {
-    // column-major; the retry searches from the predicted pose, which becomes the frame's pose (SetPose(predicted_pose))
-    const double* Tc = (retry_below > 0 ? tb.Tprior : tb.Tcur) + (size_t)f * 16;
-    if (retry_below > 0 && tid < 16) tb.Tcur[(size_t)f * 16 + tid] = Tc[tid];
-    if (retry_below > 0 && tid == 0) tb.tw_info[(size_t)f * 4 + 3] = 1;
-    match_geom(G, Tc, tb.Tref + (size_t)f * 16, cam, th, mono);
-  }
+  MatchGeom G;   // (the retry of a frame is done by k_match_assign_retry alone: this kernel always starts from Tcur)
+  match_geom(G, tb.Tcur + (size_t)f * 16, tb.Tref + (size_t)f * 16, cam, th, mono);
   __syncthreads();
   {   // the grid for the assignment kernel's slow path
     uint32_t* g_key = tb.mt_key + (size_t)f * MT_MAXKP;
@@ -551,20 +507,18 @@ __device__ __forceinline__ void match_cand_frame(const int f, uint8_t* smem, con
   // r3: FOUR points per wave, one per 16-lane quarter (k_match: two).  A point's window is walked one grid-cell column at a time and a
   // column's run holds 0...3 keypoints of the ~1000 spread over 64 x 48 cells: with 32 lanes per point nine tenths of them idled.
   constexpr int CGL = 8, CPW = 64 / CGL;
-  const int half = lane / CGL, glane = lane % CGL;
-  const unsigned long long gm = ((1ull << CGL) - 1ull) << (CGL * half);
-  const unsigned long long glt = ((1ull << glane) - 1ull) << (CGL * half);
+  const SubWave<CGL> g(lane);
   // ---- pass A: candidates per point
   for (int i0 = 0; i0 < n_last; i0 += CPW * MT_WAVES) {
-    const int i = i0 + CPW * wave + half;
+    const int i = i0 + CPW * wave + g.group;
     if (i < n_last) {
       int cnt = 0;
       if ((s_valid[i >> 5] >> (i & 31)) & 1u) {
         int seq = 0;
-        cnt = (int)match_point<0, CGL>(i, kps, desc, Xw, mp_desc, l_oct, uright, SL, G, cam, sf, nullptr, glane, glt, &seq, gm);
+        cnt = (int)match_point<0, CGL>(i, kps, desc, Xw, mp_desc, l_oct, uright, SL, G, cam, sf, nullptr, g.glane, g.glt, &seq, g.gm);
         if (cnt > 0 && seq >= 2048) cnt = 0xFFFF;   // (cnt itself is at most the keypoint count, < 0xFFFF)
       }
-      if (glane == 0) s_cnt[i] = (uint16_t)cnt;
+      if (g.glane == 0) s_cnt[i] = (uint16_t)cnt;
     }
   }
   __syncthreads();
@@ -588,7 +542,7 @@ __device__ __forceinline__ void match_cand_frame(const int f, uint8_t* smem, con
   __syncthreads();
   // ---- pass B: the keys, straight into the frame's HBM list
   for (int i0 = 0; i0 < n_last; i0 += CPW * MT_WAVES) {
-    const int i = i0 + CPW * wave + half;
+    const int i = i0 + CPW * wave + g.group;
     if (i < n_last) {
       const int cnt = s_cnt[i];
       const uint32_t off = s_off[i];
@@ -597,10 +551,10 @@ __device__ __forceinline__ void match_cand_frame(const int f, uint8_t* smem, con
         pc = 0xFFFFFFFFu;   // evaluated by the assignment loop itself
       } else if (cnt > 0) {
         int seq = 0;
-        match_point<1, CGL>(i, kps, desc, Xw, mp_desc, l_oct, uright, SL, G, cam, sf, g_list + off, glane, glt, &seq, gm);
+        match_point<1, CGL>(i, kps, desc, Xw, mp_desc, l_oct, uright, SL, G, cam, sf, g_list + off, g.glane, g.glt, &seq, g.gm);
         pc = (off << 16) | (uint32_t)cnt;
       }
-      if (glane == 0) g_pt[i] = pc;
+      if (g.glane == 0) g_pt[i] = pc;
     }
   }
 }
@@ -617,7 +571,7 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match_cand(const sd_keypoint*
                                                                const float* __restrict__ sf, float th, int mono, int KP2, int note_below) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   if (note_below > 0 && blockIdx.x == 0 && threadIdx.x == 0) tb.retry_list[0] = 0;   // the assignment kernel behind this launch fills it
-  match_cand_frame(blockIdx.x, smem, kps_all, desc_all, nkp_all, tb, cam, sf, th, mono, KP2, 0);
+  match_cand_frame(blockIdx.x, smem, kps_all, desc_all, nkp_all, tb, cam, sf, th, mono, KP2);
 }
 // RETRY: TrackWithMotionModel's second search of a frame (from the predicted pose, with the doubled window) done by THIS wave alone:
 // every valid point goes through the per-point path that walks its window on the grid copy the first pass left in HBM (the keypoints,
@@ -629,10 +583,11 @@ __device__ __forceinline__ void match_assign_frame(const int f, uint8_t* smem, c
                                                    int check_ori, int KP2, int retry_below, int note_below) {
   const int lane = threadIdx.x;
   const int MP = tb.max_points, cap = tb.kp_cap;
-  uint32_t* s_ev = (uint32_t*)smem;                      // one entry per ASSIGNMENT (rotHist[bin].push_back): <= n_last
-  uint32_t* s_obs = s_ev + MP;
-  int* s_hist = (int*)(s_obs + ((MP + 31) >> 5));
-  int16_t* s_match = (int16_t*)(s_hist + HISTO_LENGTH + 2);   // -1 | point index | 0x4000 where that point has observations
+  const LdsMatchAssign L(KP2, MP);
+  uint32_t* s_ev = lds_at<uint32_t>(smem, L.ev);
+  uint32_t* s_obs = lds_at<uint32_t>(smem, L.obs);
+  int* s_hist = lds_at<int>(smem, L.hist);
+  int16_t* s_match = lds_at<int16_t>(smem, L.match);
   const int fc = tb.cur_bcast >= 0 ? tb.cur_bcast : f;
   const sd_keypoint* kps = kps_all + (size_t)fc * cap;
   const float* l_ang = tb.angle + (size_t)f * MP;
@@ -723,38 +678,15 @@ __device__ __forceinline__ void match_assign_frame(const int f, uint8_t* smem, c
   sdsel_fence();
   // ---- rotation consistency (src/ORBmatcher.cc:1041-1072): bins of all recorded assignments, three dominant bins stay
   if (check_ori) {
-    const float factor = 1.0f / HISTO_LENGTH;
     for (int e = lane; e < nev; e += 64) {
       const uint32_t ev = s_ev[e];
-      float rot = l_ang[ev >> 11] - kps[ev & 2047].angle;
-      if (rot < 0.0) rot += 360.0f;
-      int bin = (int)roundf(rot * factor);
-      if (bin == HISTO_LENGTH) bin = 0;
+      const int bin = rot_bin(l_ang[ev >> 11], kps[ev & 2047].angle);
       atomicAdd(&s_hist[bin], 1);
       s_ev[e] = ev | ((uint32_t)bin << 22);
     }
     sdsel_fence();
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    int max1 = 0, max2 = 0, max3 = 0;
-    for (int b = 0; b < HISTO_LENGTH; b++) {
-      const int sh = s_hist[b];
-      if (sh > max1) {
-        max3 = max2; max2 = max1; max1 = sh;
-        ind3 = ind2; ind2 = ind1; ind1 = b;
-      } else if (sh > max2) {
-        max3 = max2; max2 = sh;
-        ind3 = ind2; ind2 = b;
-      } else if (sh > max3) {
-        max3 = sh;
-        ind3 = b;
-      }
-    }
-    if (max2 < 0.1f * (float)max1) {
-      ind2 = -1;
-      ind3 = -1;
-    } else if (max3 < 0.1f * (float)max1) {
-      ind3 = -1;
-    }
+    int ind1, ind2, ind3;
+    three_maxima(s_hist, ind1, ind2, ind3);
     int bad = 0;
     for (int e = lane; e < nev; e += 64) {
       const uint32_t ev = s_ev[e];
@@ -810,33 +742,21 @@ __global__ __launch_bounds__(64) void k_match_assign_retry(const sd_keypoint* __
 // vIndices order.
 // k_seen_ids: per frame, the ids (tb.last_id) of the points in tb.tw_seen, ascending, -1 (none) last as 0xFFFFFFFF, into
 // tb.tw_seen_ids -- k_match_local's seen-point exclusion binary-searches them.  A kernel of its own: the sort's loop nest
-// inside k_match_local raised that kernel from 57 to 75 VGPRs.  KP2 (a power of two >= kp_cap) u32 of LDS.
+// inside k_match_local raised that kernel from 57 to 75 VGPRs.  Dynamic LDS: LdsSeenIds.
 __global__ __launch_bounds__(256) void k_seen_ids(TrackBuffers tb, int KP2) {
-  extern __shared__ uint32_t s_ids[];
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint32_t* s_ids = lds_at<uint32_t>(smem, LdsSeenIds(KP2).ids);
   const int f = blockIdx.x, tid = threadIdx.x, NT = blockDim.x, cap = tb.kp_cap;
   for (int i = tid; i < KP2; i += NT) {
     const int v = i < cap ? tb.tw_seen[(size_t)f * cap + i] : -1;
     s_ids[i] = (uint32_t)(v >= 0 ? tb.last_id[(size_t)f * tb.max_points + v] : -1);
   }
   __syncthreads();
-  for (int k = 2; k <= KP2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < KP2; i += NT) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const uint32_t a = s_ids[i], b = s_ids[ixj];
-          if ((a > b) == ((i & k) == 0)) {
-            s_ids[i] = b;
-            s_ids[ixj] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_sort_lds(s_ids, KP2, tid, NT);
   for (int i = tid; i < cap; i += NT) tb.tw_seen_ids[(size_t)f * cap + i] = s_ids[i];
 }
 
-// Dynamic LDS: the k_match layout + u32 s_kclaim[KP2/32] + u8 s_koct[KP2].  The seen-point exclusion borrows s_list for KP2 ids.
+// Dynamic LDS: LdsMatchLocal.  The seen-point exclusion borrows s_list for KP2 ids.
 static_assert(MT_LIST_CAP >= MT_MAXKP, "k_match_local keeps the sorted seen ids in s_list");
 __global__ __launch_bounds__(64 * MT_WAVES) void k_match_local(const sd_keypoint* __restrict__ kps_all, const uint8_t* __restrict__ desc_all,
                                                                 const int32_t* __restrict__ nkp_all, TrackBuffers tb, TrackCam cam,
@@ -845,15 +765,16 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match_local(const sd_keypoint
                                                                 int claim_from_matches, int frustum_given, int exclude_seen) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int MP = tb.max_points;
-  uint32_t* s_key = (uint32_t*)smem;
-  uint32_t* s_list = s_key + KP2;
-  uint32_t* s_pt = s_list + MT_LIST_CAP;
-  uint32_t* s_obs = s_pt + MP;
-  uint32_t* s_kclaim = s_obs + ((MP + 31) >> 5);
-  int16_t* s_match = (int16_t*)(s_kclaim + (KP2 >> 5));
-  uint16_t* s_cstart = (uint16_t*)(s_match + KP2);
-  uint8_t* s_koct = (uint8_t*)(s_cstart + GRID_COLS * GRID_ROWS + 2);
-  int* s_nlist = (int*)(((uintptr_t)(s_koct + KP2) + 3) & ~(uintptr_t)3);
+  const LdsMatchLocal L(KP2, MP);
+  uint32_t* s_key = lds_at<uint32_t>(smem, L.key);
+  uint32_t* s_list = lds_at<uint32_t>(smem, L.list);
+  uint32_t* s_pt = lds_at<uint32_t>(smem, L.pt);
+  uint32_t* s_obs = lds_at<uint32_t>(smem, L.obs);
+  uint32_t* s_kclaim = lds_at<uint32_t>(smem, L.kclaim);
+  int16_t* s_match = lds_at<int16_t>(smem, L.match);
+  uint16_t* s_cstart = lds_at<uint16_t>(smem, L.cstart);
+  uint8_t* s_koct = lds_at<uint8_t>(smem, L.koct);
+  int* s_nlist = lds_at<int>(smem, L.nlist);
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NT = 64 * MT_WAVES;
   const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
   const int cap = tb.kp_cap, M = MP;
@@ -892,33 +813,14 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match_local(const sd_keypoint
     s_koct[i] = (uint8_t)oct;
     s_match[i] = -1;
   }
-  for (int i0 = 0; i0 < KP2; i0 += NT) {   // claim flags / Observations() > 0 flags as bit masks (wave ballots)
-    const int i = i0 + tid;
-    bool claimed = false;
-    if (i < N) {
-      if (claim_from_matches) {   // F.mvpMapPoints[idx] && F.mvpMapPoints[idx]->Observations() > 0 (src/ORBmatcher.cc:81-83)
-        const int m = tb.cur_match[(size_t)f * cap + i];
-        claimed = m >= 0 && tb.obs[(size_t)f * MP + m] > 0;
-      } else {
-        claimed = kclaim[i] != 0;
-      }
-    }
-    const unsigned long long bc = __ballot(claimed);
-    const int w = (i0 >> 5) + 2 * wave;
-    if (lane == 0 && w < (KP2 >> 5)) {
-      s_kclaim[w] = (uint32_t)bc;
-      if (w + 1 < (KP2 >> 5)) s_kclaim[w + 1] = (uint32_t)(bc >> 32);
-    }
-  }
-  for (int m0 = 0; m0 < ((MP + 63) & ~63); m0 += NT) {
-    const int m = m0 + tid;
-    const unsigned long long bo = __ballot(m < n_loc && l_obs[m] > 0);
-    const int w = (m0 >> 5) + 2 * wave;
-    if (lane == 0 && w < ((MP + 31) >> 5)) {
-      s_obs[w] = (uint32_t)bo;
-      if (w + 1 < ((MP + 31) >> 5)) s_obs[w + 1] = (uint32_t)(bo >> 32);
-    }
-  }
+  // claim flags / Observations() > 0 flags as bit masks
+  pack_flags([&](int i) {
+    if (i >= N) return false;
+    if (!claim_from_matches) return kclaim[i] != 0;
+    const int m = tb.cur_match[(size_t)f * cap + i];   // F.mvpMapPoints[idx] && ...->Observations() > 0 (src/ORBmatcher.cc:81-83)
+    return m >= 0 && tb.obs[(size_t)f * MP + m] > 0;
+  }, KP2, s_kclaim, tid, NT);
+  pack_flags([&](int m) { return m < n_loc && l_obs[m] > 0; }, MP, s_obs, tid, NT);
   // seen-point exclusion (exclude_seen): the sorted ids of the last-frame points TrackWithMotionModel's final search matched,
   // before its outlier discard (k_seen_ids) -- pMP->mnLastFrameSeen == mCurrentFrame.mnId (src/Tracking.cc:703, :900-918).
   // They go into s_list, which phase 1 fills only after the isInFrustum pass.
@@ -1004,11 +906,9 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match_local(const sd_keypoint
   // 0...3 keypoints)
   {
     constexpr int CGL = 8, CPW = 64 / CGL;
-    const int half = lane / CGL, glane = lane % CGL;
-    const unsigned long long gm = ((1ull << CGL) - 1ull) << (CGL * half);
-    const unsigned long long glt = ((1ull << glane) - 1ull) << (CGL * half);
+    const SubWave<CGL> g(lane);
     for (int i0 = 0; i0 < n_loc; i0 += CPW * MT_WAVES) {
-      const int i = i0 + CPW * wave + half;
+      const int i = i0 + CPW * wave + g.group;
       if (i < n_loc) {
         uint32_t pc = 0;
         if (o_inview[i]) {
@@ -1016,23 +916,18 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match_local(const sd_keypoint
           if (bFactor) r *= th;
           const int lvl = o_level[i];
           const float radius = r * sf[lvl];
-          int seq = 0;
-          const int cnt = (int)match_window<0, CGL>(o_proj[(size_t)i * 3], o_proj[(size_t)i * 3 + 1], radius, lvl - 1, lvl, o_proj[(size_t)i * 3 + 2],
-                                                   mp_desc + (size_t)i * 32, kps, desc, uright, SL, cam, invW, invH, nullptr, glane, glt, &seq, -1, gm);
-          if (cnt > 0) {
-            int off = 0;
-            if (glane == 0) off = atomicAdd(s_nlist, cnt);
-            off = __shfl(off, CGL * half);
-            if (off + cnt > MT_LIST_CAP || seq >= 2048 || cnt > 0xffff) {
-              pc = 0xFFFFFFFFu;
-            } else {
-              match_window<1, CGL>(o_proj[(size_t)i * 3], o_proj[(size_t)i * 3 + 1], radius, lvl - 1, lvl, o_proj[(size_t)i * 3 + 2],
-                                  mp_desc + (size_t)i * 32, kps, desc, uright, SL, cam, invW, invH, s_list + off, glane, glt, &seq, -1, gm);
-              pc = ((uint32_t)off << 16) | (uint32_t)cnt;
-            }
-          }
+          pc = collect_candidates<CGL>(
+              [&](int* seq) {
+                return match_window<0, CGL>(o_proj[(size_t)i * 3], o_proj[(size_t)i * 3 + 1], radius, lvl - 1, lvl, o_proj[(size_t)i * 3 + 2],
+                                            mp_desc + (size_t)i * 32, kps, desc, uright, SL, cam, invW, invH, nullptr, g.glane, g.glt, seq, -1, g.gm);
+              },
+              [&](uint32_t* list, int* seq) {
+                match_window<1, CGL>(o_proj[(size_t)i * 3], o_proj[(size_t)i * 3 + 1], radius, lvl - 1, lvl, o_proj[(size_t)i * 3 + 2],
+                                     mp_desc + (size_t)i * 32, kps, desc, uright, SL, cam, invW, invH, list, g.glane, g.glt, seq, -1, g.gm);
+              },
+              s_nlist, s_list, g);
         }
-        if (glane == 0) s_pt[i] = pc;
+        if (g.glane == 0) s_pt[i] = pc;
       }
     }
   }
@@ -1040,61 +935,53 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match_local(const sd_keypoint
   if (tid >= 64) return;
   // ---- phase 2: best / second best over the unclaimed candidates, ratio test, assignment
   int nmatches = 0;
-  // s_pt is read 64 entries at a time and only the points with something to do are visited (most slots of the arrays
-  // hold no valid point: one LDS round trip per slot was a tenth of the kernel for a single frame)
-  for (int base = 0; base < n_loc; base += 64) {
-   const uint32_t pcv = (base + lane < n_loc) ? s_pt[base + lane] : 0u;
-   unsigned long long todo = __ballot(pcv != 0);
-   while (todo) {
-    const int jsel = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const int i = base + jsel;
-    const uint32_t pc = (uint32_t)__builtin_amdgcn_readlane((int)pcv, jsel);
-    uint32_t gb, gs;   // the two smallest unclaimed keys of the point (wave-uniform)
-    if (pc != 0xFFFFFFFFu) {
-      uint32_t best = 0x7FFFFFFFu, second = 0x7FFFFFFFu;
-      const int off = pc >> 16, cnt = pc & 0xffff;
-      for (int j = lane; j < cnt; j += 64) {
-        const uint32_t key = s_list[off + j];
-        const int idx = key & 2047;
-        const int m = s_match[idx];
-        const bool claimed = m >= 0 ? (((s_obs[m >> 5] >> (m & 31)) & 1u) != 0) : (((s_kclaim[idx >> 5] >> (idx & 31)) & 1u) != 0);
-        if (!claimed) {
-          if (key < best) { second = best; best = key; }
-          else if (key < second) second = key;
+  for_each_marked_point(
+      n_loc, lane, [&](int m) { return m < n_loc ? s_pt[m] : 0u; },
+      [&](int i, uint32_t pc) {
+        uint32_t gb, gs;   // the two smallest unclaimed keys of the point (wave-uniform)
+        if (pc != 0xFFFFFFFFu) {
+          uint32_t best = 0x7FFFFFFFu, second = 0x7FFFFFFFu;
+          const int off = pc >> 16, cnt = pc & 0xffff;
+          for (int j = lane; j < cnt; j += 64) {
+            const uint32_t key = s_list[off + j];
+            const int idx = key & 2047;
+            const int m = s_match[idx];
+            const bool claimed = m >= 0 ? (((s_obs[m >> 5] >> (m & 31)) & 1u) != 0) : (((s_kclaim[idx >> 5] >> (idx & 31)) & 1u) != 0);
+            if (!claimed) {
+              if (key < best) { second = best; best = key; }
+              else if (key < second) second = key;
+            }
+          }
+          gb = best;
+          gb = wave_min_u32(gb);
+          gs = (best == gb) ? second : best;   // the lane that holds the best offers its runner-up, the others their best
+          gs = wave_min_u32(gs);
+        } else {   // candidate list did not fit in LDS: enumerate the window again (best, then the best above it)
+          float r = o_cos[i] > 0.998 ? 2.5f : 4.0f;
+          if (bFactor) r *= th;
+          const int lvl = o_level[i];
+          int seq = 0;
+          gb = match_window<2>(o_proj[(size_t)i * 3], o_proj[(size_t)i * 3 + 1], r * sf[lvl], lvl - 1, lvl, o_proj[(size_t)i * 3 + 2],
+                               mp_desc + (size_t)i * 32, kps, desc, uright, SL, cam, invW, invH, nullptr, lane, lt, &seq);
+          gb = wave_min_u32(gb);
+          gs = 0x7FFFFFFFu;
+          if (gb != 0x7FFFFFFFu) {
+            gs = match_window<2>(o_proj[(size_t)i * 3], o_proj[(size_t)i * 3 + 1], r * sf[lvl], lvl - 1, lvl, o_proj[(size_t)i * 3 + 2],
+                                 mp_desc + (size_t)i * 32, kps, desc, uright, SL, cam, invW, invH, nullptr, lane, lt, &seq, (long long)gb);
+            gs = wave_min_u32(gs);
+          }
         }
-      }
-      gb = best;
-      gb = wave_min_u32(gb);
-      gs = (best == gb) ? second : best;   // the lane that holds the best offers its runner-up, the others their best
-      gs = wave_min_u32(gs);
-    } else {   // candidate list did not fit in LDS: enumerate the window again (best, then the best above it)
-      float r = o_cos[i] > 0.998 ? 2.5f : 4.0f;
-      if (bFactor) r *= th;
-      const int lvl = o_level[i];
-      int seq = 0;
-      gb = match_window<2>(o_proj[(size_t)i * 3], o_proj[(size_t)i * 3 + 1], r * sf[lvl], lvl - 1, lvl, o_proj[(size_t)i * 3 + 2],
-                           mp_desc + (size_t)i * 32, kps, desc, uright, SL, cam, invW, invH, nullptr, lane, lt, &seq);
-      gb = wave_min_u32(gb);
-      gs = 0x7FFFFFFFu;
-      if (gb != 0x7FFFFFFFu) {
-        gs = match_window<2>(o_proj[(size_t)i * 3], o_proj[(size_t)i * 3 + 1], r * sf[lvl], lvl - 1, lvl, o_proj[(size_t)i * 3 + 2],
-                             mp_desc + (size_t)i * 32, kps, desc, uright, SL, cam, invW, invH, nullptr, lane, lt, &seq, (long long)gb);
-        gs = wave_min_u32(gs);
-      }
-    }
-    if (gb == 0x7FFFFFFFu) continue;
-    const int bestDist = gb >> 22, bestIdx = gb & 2047;
-    const int bestDist2 = gs == 0x7FFFFFFFu ? 256 : (int)(gs >> 22);
-    const int bestLevel = s_koct[bestIdx];
-    const int bestLevel2 = gs == 0x7FFFFFFFu ? -1 : (int)s_koct[gs & 2047];
-    if (bestDist <= TH_HIGH) {
-      if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) continue;
-      if (lane == 0) s_match[bestIdx] = (int16_t)i;
-      nmatches++;
-    }
-     }
-  }
+        if (gb == 0x7FFFFFFFu) return;
+        const int bestDist = gb >> 22, bestIdx = gb & 2047;
+        const int bestDist2 = gs == 0x7FFFFFFFu ? 256 : (int)(gs >> 22);
+        const int bestLevel = s_koct[bestIdx];
+        const int bestLevel2 = gs == 0x7FFFFFFFu ? -1 : (int)s_koct[gs & 2047];
+        if (bestDist <= TH_HIGH) {
+          if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) return;
+          if (lane == 0) s_match[bestIdx] = (int16_t)i;
+          nmatches++;
+        }
+      });
   int32_t* out = tb.lm_match + (size_t)f * cap;
   for (int i = lane; i < cap; i += 64) out[i] = i < KP2 ? (int32_t)s_match[i] : -1;
   if (lane == 0) tb.lm_nmatch[f] = nmatches;
@@ -1167,9 +1054,10 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_features_in_area(const sd_key
                                                                      int maxLevel, int32_t* __restrict__ out, int out_cap,
                                                                      int32_t* __restrict__ n_out, int32_t* __restrict__ grid_cells) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint32_t* s_key = (uint32_t*)smem;
-  uint32_t* s_list = s_key + KP2;
-  uint16_t* s_cstart = (uint16_t*)(s_list + KP2);
+  const LdsFeaturesInArea L(KP2);
+  uint32_t* s_key = lds_at<uint32_t>(smem, L.key);
+  uint32_t* s_list = lds_at<uint32_t>(smem, L.list);
+  uint16_t* s_cstart = lds_at<uint16_t>(smem, L.cstart);
   const int tid = threadIdx.x, lane = tid & 63, NT = 64 * MT_WAVES;
   const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
   const int N = min(nkp[0], min(cap, KP2));
@@ -1194,14 +1082,20 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_features_in_area(const sd_key
   if (lane == 0) *n_out = cnt;
 }
 
+// KP2 = the power of two >= the keypoint capacity that the LDS sorts run on
+static int matcher_kp2(const TrackBuffers& tb, int* KP2) {
+  *KP2 = 64;
+  while (*KP2 < tb.kp_cap) *KP2 <<= 1;
+  SD_REQUIRE(*KP2 <= MT_MAXKP && tb.max_points <= 2048, SD_ERR_CAPACITY, "matcher supports at most 2048 keypoints / map points per frame");
+  return SD_OK;
+}
+
 int launch_features_in_area(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, int frame, float x, float y, float r,
                             int min_level, int max_level, int32_t* d_out, int out_cap, int32_t* d_n, int32_t* d_grid, hipStream_t s) {
-  int KP2 = 64;
-  while (KP2 < tb.kp_cap) KP2 <<= 1;
-  SD_REQUIRE(KP2 <= MT_MAXKP, SD_ERR_CAPACITY, "matcher supports at most 2048 keypoints per frame");
-  const size_t lds = (size_t)KP2 * 8 + (GRID_COLS * GRID_ROWS + 2) * 2;
+  int KP2;
+  SD_TRY(matcher_kp2(tb, &KP2));
   const sd_keypoint* kps = (cur->have_dist ? cur->d_kps_un : cur->d_kps) + (size_t)frame * tb.kp_cap;
-  hipLaunchKernelGGL(k_features_in_area, dim3(1), dim3(64 * MT_WAVES), lds, s, kps, cur->d_desc + (size_t)frame * tb.kp_cap * 32,
+  hipLaunchKernelGGL(k_features_in_area, dim3(1), dim3(64 * MT_WAVES), LdsFeaturesInArea(KP2).bytes, s, kps, cur->d_desc + (size_t)frame * tb.kp_cap * 32,
                      cur->d_nout + frame, tb.uright + (size_t)frame * tb.kp_cap, cam, tb.kp_cap, KP2, x, y, r, min_level, max_level, d_out,
                      out_cap, d_n, d_grid);
   SD_HIP_CHECK(hipGetLastError());
@@ -1211,18 +1105,15 @@ int launch_features_in_area(const sd_orb* cur, const TrackBuffers& tb, const Tra
 int launch_match_local(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_sf, const float* d_scale_thr,
                        int nlevels, int n_frames, float th, float nnratio, float cos_limit, hipStream_t s, int claim_from_matches,
                        int frustum_given, int exclude_seen) {
-  int KP2 = 64;
-  while (KP2 < tb.kp_cap) KP2 <<= 1;
-  SD_REQUIRE(KP2 <= MT_MAXKP && tb.max_points <= 2048, SD_ERR_CAPACITY, "matcher supports at most 2048 keypoints / map points per frame");
+  int KP2;
+  SD_TRY(matcher_kp2(tb, &KP2));
   const int MP = tb.max_points;
   exclude_seen = exclude_seen && !frustum_given;
   if (exclude_seen) {
-    hipLaunchKernelGGL(k_seen_ids, dim3(n_frames), dim3(256), (size_t)KP2 * 4, s, tb, KP2);
+    hipLaunchKernelGGL(k_seen_ids, dim3(n_frames), dim3(256), LdsSeenIds(KP2).bytes, s, tb, KP2);
     SD_HIP_CHECK(hipGetLastError());
   }
-  const size_t lds = (size_t)KP2 * 4 + MT_LIST_CAP * 4 + (size_t)MP * 4 + (size_t)((MP + 31) >> 5) * 4 + (size_t)(KP2 >> 5) * 4 + (size_t)KP2 * 2 +
-                     (GRID_COLS * GRID_ROWS + 2) * 2 + (size_t)KP2 + 4 + 8;
-  hipLaunchKernelGGL(k_match_local, dim3(n_frames), dim3(64 * MT_WAVES), lds, s, (cur->have_dist ? cur->d_kps_un : cur->d_kps), cur->d_desc,
+  hipLaunchKernelGGL(k_match_local, dim3(n_frames), dim3(64 * MT_WAVES), LdsMatchLocal(KP2, MP).bytes, s, (cur->have_dist ? cur->d_kps_un : cur->d_kps), cur->d_desc,
                      cur->d_nout, tb, cam, d_sf, d_scale_thr, nlevels, th, nnratio, cos_limit, KP2, claim_from_matches, frustum_given,
                      exclude_seen ? 1 : 0);
   SD_HIP_CHECK(hipGetLastError());
@@ -1231,17 +1122,12 @@ int launch_match_local(const sd_orb* cur, const TrackBuffers& tb, const TrackCam
 
 int launch_match(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_sf, int n_frames, float th,
                  int mono, int check_ori, hipStream_t s, int retry_below, int note_below) {
-  int KP2 = 64;
-  while (KP2 < tb.kp_cap) KP2 <<= 1;
-  SD_REQUIRE(KP2 <= MT_MAXKP && tb.max_points <= 2048, SD_ERR_CAPACITY, "matcher supports at most 2048 keypoints / map points per frame");
+  int KP2;
+  SD_TRY(matcher_kp2(tb, &KP2));
   const int MP = tb.max_points;
   const sd_keypoint* kps = cur->have_dist ? cur->d_kps_un : cur->d_kps;
-  const size_t lds = (size_t)KP2 * 4 + MT_LIST_CAP * 4 + (size_t)MP * 4 + (size_t)KP2 * 4 + (size_t)((MP + 31) >> 5) * 8 + (size_t)KP2 * 2 +
-                     (size_t)std::max(KP2, MP) * 2 + (GRID_COLS * GRID_ROWS + 2) * 2 + 4 + (HISTO_LENGTH + 1) * 4;
   if (opt(OPT_MATCH_SPLIT)) {   // candidates -> HBM list -> one-wave assignment
-    const size_t lds_c = (size_t)KP2 * 4 + (size_t)MP * 4 + (size_t)(MP + (MP & 1)) * 2 + (size_t)((MP + 31) >> 5) * 4 +
-                         (GRID_COLS * GRID_ROWS + 2) * 2 + 8;
-    const size_t lds_a = (size_t)MP * 4 + (size_t)((MP + 31) >> 5) * 4 + (HISTO_LENGTH + 2) * 4 + (size_t)KP2 * 2;
+    const size_t lds_c = LdsMatchCand(KP2, MP).bytes, lds_a = LdsMatchAssign(KP2, MP).bytes;
     // first pass: one workgroup per frame (note_below > 0: frames with fewer matches are listed for a retry pass);
     // retry pass (retry_below > 0): a small grid walks that list
     if (retry_below > 0) {   // one wave per listed frame does the whole second search (match_assign_frame<true>)
@@ -1254,7 +1140,7 @@ int launch_match(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam,
                          KP2, note_below);
     }
   } else {
-    hipLaunchKernelGGL(k_match, dim3(n_frames), dim3(64 * MT_WAVES), lds, s, kps, cur->d_desc, cur->d_nout, tb, cam, d_sf, th, mono, check_ori,
+    hipLaunchKernelGGL(k_match, dim3(n_frames), dim3(64 * MT_WAVES), LdsMatch(KP2, MP).bytes, s, kps, cur->d_desc, cur->d_nout, tb, cam, d_sf, th, mono, check_ori,
                        KP2, retry_below);
   }
   SD_HIP_CHECK(hipGetLastError());

@@ -175,3 +175,14 @@ def test_orb_host_helpers_under_sanitizers(tmp_path):
                            "-I", inc, os.path.join(ROOT, "tests", "native", "orb_host_check.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "orb_host_check OK" in out.stdout, out.stdout + out.stderr
+
+
+def test_match_lds_layouts_under_sanitizers(tmp_path):
+    """Every dynamic-LDS layout of the matchers (track_match_lds.h), for every capacity a launcher can pass: arrays aligned, disjoint,
+    inside the total, and the total equal to the launchers' former byte formulas.  Stand-alone program, AddressSanitizer and UBSan."""
+    exe = str(tmp_path / "match_lds_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "sdslam_amd", "csrc"), os.path.join(ROOT, "tests", "native", "match_lds_check.cpp"),
+                           "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "match_lds_check OK" in out.stdout, out.stdout + out.stderr

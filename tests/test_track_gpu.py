@@ -57,8 +57,9 @@ def rig(sd, oracle, request):
 
 @pytest.fixture(params=[1, 0], ids=["split", "single"])
 def match_mode(sd, request):
-    """Both forms of SearchByProjection(Frame, Frame): candidate kernel + one-wave assignment kernel (the default; a frame whose
-    candidates do not fit its HBM list is handed to the single kernel) and the single 39-KB kernel alone."""
+    """Both forms of SearchByProjection(Frame, Frame): candidate kernel + one-wave assignment kernel (the default; a point whose
+    candidates do not fit the frame's HBM list is evaluated by the assignment kernel itself, on the grid copy in HBM) and the
+    single 39-KB kernel alone."""
     with sd.options({"track.match_split": request.param}):
         yield request.param
 
