@@ -8,7 +8,8 @@
 // INTEGRATION.md for the type-alias header that maps cv::Mat / Eigen arguments onto these.
 //
 //   ORBextractor   reference src/ORBextractor.h:38-70
-//   ORBmatcher     reference src/ORBmatcher.h:40-52  (DescriptorDistance, SearchByProjection(Frame,Frame))
+//   ORBmatcher     reference src/ORBmatcher.h:40-65  (DescriptorDistance, SearchByProjection(Frame,Frame), SearchByPoints,
+//                                                      SearchForTriangulation)
 //   ImageAlign     reference src/ImageAlign.h:32-44  (ComputePose, GetError)
 //   PnPsolver      reference src/PnPsolver.h:67-76   (SetRansacParameters, iterate)
 // ImageAlign / ORBmatcher / PnPsolver operate on a TrackBatch (frames resident on the GPU).
@@ -16,6 +17,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../sdslam_hip.h"
@@ -348,6 +350,72 @@ class ORBmatcher {
     int32_t n = 0;
     check(sd_track_get_matches(batch.handle(), frame, 1, mvpMapPoints.data(), kp_cap, &n));
     return n;
+  }
+  // int SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, const Eigen::Matrix3d& F12, vector<pair<size_t, size_t>>&)
+  //                                            src/ORBmatcher.h:65, src/ORBmatcher.cc:359-475, LocalMapping::CreateNewMapPoints
+  // Frame 0 of the batch's cur extractor holds pKF1's image, frame 0 of its ref extractor pKF2's.  KeyFrameT needs N,
+  // GetMapPointMatches(), mvuRight and GetPose(); F12 is anything indexable as F12(r, c).  kp_cap: the keypoint capacity.
+  template <class KeyFrameT, class Matrix3T>
+  int SearchForTriangulation(TrackBatch& batch, KeyFrameT* pKF1, KeyFrameT* pKF2, const Matrix3T& F12,
+                             std::vector<std::pair<size_t, size_t> >& vMatchedPairs, int kp_cap) {
+    UploadTriangulationSlot(batch, 0, pKF1, pKF2, kp_cap);
+    double F[9];
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) F[r * 3 + c] = F12(r, c);
+    check(sd_track_set_f12(batch.handle(), 0, 1, F));
+    check(sd_track_search_for_triangulation(batch.handle(), 1, 1, mbCheckOrientation ? 1 : 0));
+    return TriangulationResult(batch, 0, vMatchedPairs, kp_cap);
+  }
+  // The loop of CreateNewMapPoints over the neighbours in one call: pKF1 (frame 0 of the cur extractor, broadcast) against
+  // vpNeighKFs[i] (frame i of the ref extractor), F12 = LocalMapping::ComputeF12 on the device.  vMatchedPairs[i] is what the
+  // reference returns for neighbour i on pKF1's map points as they are NOW; with orientation checking off, dropping the pairs
+  // whose idx1 an earlier neighbour turned into a point gives the reference's sequential result (sdslam_hip.h).
+  template <class KeyFrameT>
+  void SearchForTriangulation(TrackBatch& batch, KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpNeighKFs,
+                              std::vector<std::vector<std::pair<size_t, size_t> > >& vMatchedPairs, int kp_cap) {
+    const int n = (int)vpNeighKFs.size();
+    vMatchedPairs.assign(n, {});
+    if (n == 0) return;
+    for (int i = 0; i < n; i++) UploadTriangulationSlot(batch, i, pKF1, vpNeighKFs[i], kp_cap);
+    batch.SetCurrentBroadcast(0);
+    const int rc = sd_track_search_for_triangulation(batch.handle(), n, 0, mbCheckOrientation ? 1 : 0);
+    if (rc == SD_OK)
+      for (int i = 0; i < n; i++) TriangulationResult(batch, i, vMatchedPairs[i], kp_cap);
+    batch.SetCurrentBroadcast(-1);
+    check(rc);
+  }
+  int TriangulationResult(TrackBatch& batch, int frame, std::vector<std::pair<size_t, size_t> >& vMatchedPairs, int kp_cap) {
+    std::vector<int32_t> m12(kp_cap);
+    int32_t n = 0;
+    check(sd_track_get_triangulation_matches(batch.handle(), frame, 1, m12.data(), kp_cap, &n, nullptr, nullptr));
+    vMatchedPairs.clear();
+    vMatchedPairs.reserve(n);
+    for (int i = 0; i < kp_cap; i++)
+      if (m12[i] >= 0) vMatchedPairs.push_back(std::make_pair((size_t)i, (size_t)m12[i]));
+    return n;
+  }
+  // Slot `slot` of a SearchForTriangulation call: "holds a map point" flags (bad points count, :385-403), mvuRight and poses.
+  // pKF1's mvuRight goes to row 0 of the cur extractor's frames, the row every slot reads under the broadcast.
+  template <class KeyFrameT>
+  void UploadTriangulationSlot(TrackBatch& batch, int slot, KeyFrameT* pKF1, KeyFrameT* pKF2, int kp_cap) {
+    const auto vpMapPoints1 = pKF1->GetMapPointMatches();
+    const auto vpMapPoints2 = pKF2->GetMapPointMatches();
+    std::vector<uint8_t> has1(kp_cap, 0), has2(kp_cap, 0);
+    std::vector<float> ur1(kp_cap, -1.f), ur2(kp_cap, -1.f);
+    for (int i = 0; i < pKF1->N && i < kp_cap; i++) {
+      has1[i] = vpMapPoints1[i] != nullptr;
+      ur1[i] = pKF1->mvuRight[i];
+    }
+    for (int i = 0; i < pKF2->N && i < kp_cap; i++) {
+      has2[i] = vpMapPoints2[i] != nullptr;
+      ur2[i] = pKF2->mvuRight[i];
+    }
+    check(sd_track_set_point_flags(batch.handle(), slot, 1, has1.data(), has2.data(), kp_cap));
+    if (slot == 0) check(sd_track_set_uright(batch.handle(), 0, 1, ur1.data(), kp_cap));
+    check(sd_track_set_uright_ref(batch.handle(), slot, 1, ur2.data(), kp_cap));
+    const auto T1 = pKF1->GetPose();
+    const auto T2 = pKF2->GetPose();
+    batch.SetPoses(slot, T2.data(), T1.data());
   }
 
  protected:

@@ -348,6 +348,44 @@ int sd_track_sim3_iterate(sd_track* h, int n_frames, int n_iterations);
 int sd_track_get_sim3(sd_track* h, int frame0, int n_frames, double* T12_cm, double* R12_cm, double* t12, double* scale,
                       uint8_t* inliers, int cap, int32_t* info8);
 
+/* ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, const Eigen::Matrix3d& F12, vMatchedPairs)
+ *   src/ORBmatcher.cc:359-475 with CheckDistEpipolarLine (:128-144), and LocalMapping::ComputeF12 (src/LocalMapping.cc:494-511);
+ *   caller LocalMapping::CreateNewMapPoints, once per neighbour keyframe
+ * for the whole batch on the SearchByPoints pairing: KF1 = the slot's cur frame (or the broadcast frame) with pose Tcur and
+ * mvuRight row sd_track_set_uright (in broadcast mode the broadcast frame's row), KF2 = frame f of the ref extractor with pose
+ * Tref and mvuRight row sd_track_set_uright_ref.  Poses are per slot: in broadcast mode every slot's Tcur holds KF1's pose.  Keypoints are the undistorted ones, K, mvScaleFactors and mvLevelSigma2 the
+ * tracker's and the extractors' own.
+ * Map-point flags are the buffers of sd_track_set_point_flags, read as "the keypoint holds a map point": for this call pass
+ *   GetMapPointMatches()[i] != NULL -- bad points count, as in the reference (:385-389, :399-403).
+ * sd_track_set_uright_ref: mvuRight of the ref extractor's frames, [n_frames][cap], rows shorter than the keypoint capacity
+ *   leave the rest; -1 everywhere for a new handle, as the cur rows are.  Ordered on the tracking stream; returns once the rows are read.
+ * sd_track_set_f12: the caller's own F12 for use_set_f12 = 1, 9 doubles row-major per slot.  Queued on the tracking stream.
+ * sd_track_search_for_triangulation: use_set_f12 = 0 computes F12 from Tcur / Tref on the device, which is ComputeF12 (in
+ *   double; operation order: sdslam_amd/csrc/track_tri.hip); the epipole is always computed from the poses.  check_ori =
+ *   mbCheckOrientation (CreateNewMapPoints: off).  With check_ori = 0 the rows are independent, so one broadcast call over all
+ *   neighbours followed by an in-order walk that skips the idx1 already turned into points equals the reference's sequential loop.
+ *   Queued on the tracking stream: no host wait, no allocation.  The result lives in a buffer of its own: matches12 of
+ *   sd_track_search_by_points and live Sim3 solvers are untouched.
+ * sd_track_get_triangulation_matches (synchronises; NULL outputs are skipped): matches12[idx1] = the KF2 keypoint index of
+ *   vMatchedPairs or -1 ([n_frames][cap], cap >= keypoint capacity), *n_matches = the return value, F12_rm9 = the F12 used,
+ *   epipole2 = (ex, ey).  A result ends with a new extraction on `cur` or `ref`, sd_track_set_point_flags / _set_poses /
+ *   _set_uright / _set_uright_ref / _set_f12 or another broadcast setting: the getter then fails with SD_ERR_INVALID_ARG until
+ *   the search has run again.
+ * Errors: SD_ERR_INVALID_ARG for use_set_f12 = 1 on a slot sd_track_set_f12 has not covered, missing extractions or camera;
+ *   SD_ERR_CAPACITY for n_frames > max_batch or a keypoint capacity above 2048.
+ * sd_debug_search_for_triangulation: one keyframe pair from host arrays through the same kernel, synchronous, with buffers of
+ *   its own (no extractor, no tracker): n1 / n2 <= 2048 keypoints, has_mp / uright per keypoint, tables of nlevels entries;
+ *   matches12 has n1 entries. */
+int sd_track_set_uright_ref(sd_track* h, int frame0, int n_frames, const float* uright, int cap);
+int sd_track_set_f12(sd_track* h, int frame0, int n_frames, const double* F12_rm9);
+int sd_track_search_for_triangulation(sd_track* h, int n_frames, int use_set_f12, int check_ori);
+int sd_track_get_triangulation_matches(sd_track* h, int frame0, int n_frames, int32_t* matches12, int cap, int32_t* n_matches,
+                                       double* F12_rm9, float* epipole2);
+int sd_debug_search_for_triangulation(int n1, int n2, const sd_keypoint* kps1, const uint8_t* desc1, const uint8_t* has_mp1,
+                                      const float* uright1, const sd_keypoint* kps2, const uint8_t* desc2, const uint8_t* has_mp2,
+                                      const float* uright2, const double* F12_rm9, const float* epipole2, const float* scale_factors,
+                                      const float* level_sigma2, int nlevels, int check_ori, int32_t* matches12, int32_t* n_matches);
+
 int sd_track_align(sd_track* h, int n_frames, int mode);
 int sd_track_match(sd_track* h, int n_frames, float th, int mono, int check_ori);
 /* sd_track_pnp = PnPsolver(CurrentFrame, CurrentFrame.mvpMapPoints) + SetRansacParameters(...) + iterate(n_iterations)

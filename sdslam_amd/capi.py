@@ -633,6 +633,34 @@ class Tracker:
         _check(self.L.sd_track_get_point_matches(self.h, frame0, n, _p(m), self.cap, _p(nm)))
         return m, nm
 
+    # --- ORBmatcher::SearchForTriangulation + LocalMapping::ComputeF12 on the SearchByPoints pairing (track_tri.hip) ---
+    def set_uright_ref(self, frame0, uright):
+        """mvuRight of the ref extractor's frames, [n, cap'] (-1: mono)."""
+        u = np.ascontiguousarray(uright, np.float32)
+        assert u.ndim == 2
+        self.L.sd_track_set_uright_ref.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        _check(self.L.sd_track_set_uright_ref(self.h, frame0, u.shape[0], _p(u), u.shape[1]))
+
+    def set_f12(self, frame0, F12):
+        """The caller's own F12 per slot, [n, 3, 3], for search_for_triangulation(use_set_f12=True)."""
+        F = np.ascontiguousarray(F12, np.float64).reshape(-1, 9)
+        self.L.sd_track_set_f12.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _check(self.L.sd_track_set_f12(self.h, frame0, F.shape[0], _p(F)))
+
+    def search_for_triangulation(self, n_frames, use_set_f12=False, check_ori=False):
+        """SearchForTriangulation(KF1 = cur slot, KF2 = ref slot, F12) with the flags of set_point_flags read as "holds a map
+        point"; F12 = ComputeF12 of the slot's poses unless use_set_f12."""
+        self.L.sd_track_search_for_triangulation.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        _check(self.L.sd_track_search_for_triangulation(self.h, n_frames, int(use_set_f12), int(check_ori)))
+
+    def get_triangulation_matches(self, frame0, n):
+        m = np.zeros((n, self.cap), np.int32)
+        nm = np.zeros(n, np.int32)
+        F, e = np.zeros((n, 9)), np.zeros((n, 2), np.float32)
+        self.L.sd_track_get_triangulation_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        _check(self.L.sd_track_get_triangulation_matches(self.h, frame0, n, _p(m), self.cap, _p(nm), _p(F), _p(e)))
+        return dict(matches12=m, n_matches=nm, F12=F.reshape(n, 3, 3), epipole=e)
+
     # --- Sim3Solver on the SearchByPoints pairing (src/Sim3Solver.cc; caller LoopClosing::ComputeSim3) ---
     def set_sim3_points(self, frame0, Xw_cur, Xw_ref):
         """GetWorldPos() of the two keyframes' map points, [n, cap', 3] each, by that keyframe's keypoint index."""
@@ -890,3 +918,23 @@ def debug_epnp(Xw, uv, K):
     _check(L.sd_debug_epnp(len(Xw), _p(Xw), _p(uv), float(K[0]), float(K[1]), float(K[2]), float(K[3]), _p(R), _p(t),
                            C.byref(e)))
     return R.reshape(3, 3), t, e.value
+
+
+def debug_search_for_triangulation(kps1, desc1, has_mp1, uright1, kps2, desc2, has_mp2, uright2, F12, epipole, scale_factors,
+                                   level_sigma2, check_ori=False):
+    """One keyframe pair from host arrays through k_search_triangulation (diagnostics): (nmatches, matches12[n1])."""
+    L = lib()
+    L.sd_debug_search_for_triangulation.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    k1, k2 = np.ascontiguousarray(kps1, KP_DTYPE), np.ascontiguousarray(kps2, KP_DTYPE)
+    n1, n2 = len(k1), len(k2)
+    d1, d2 = np.ascontiguousarray(desc1, np.uint8).reshape(n1, 32), np.ascontiguousarray(desc2, np.uint8).reshape(n2, 32)
+    h1, h2 = np.ascontiguousarray(has_mp1, np.uint8), np.ascontiguousarray(has_mp2, np.uint8)
+    u1, u2 = np.ascontiguousarray(uright1, np.float32), np.ascontiguousarray(uright2, np.float32)
+    assert len(h1) == len(u1) == n1 and len(h2) == len(u2) == n2
+    F, e = np.ascontiguousarray(F12, np.float64).reshape(9), np.ascontiguousarray(epipole, np.float32).reshape(2)
+    sf, s2 = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(level_sigma2, np.float32)
+    assert len(sf) == len(s2)
+    m, n = np.full(max(n1, 1), -1, np.int32), np.zeros(1, np.int32)
+    _check(L.sd_debug_search_for_triangulation(n1, n2, _p(k1), _p(d1), _p(h1), _p(u1), _p(k2), _p(d2), _p(h2), _p(u2), _p(F), _p(e),
+                                               _p(sf), _p(s2), len(sf), int(check_ori), _p(m), _p(n)))
+    return int(n[0]), m[:n1]

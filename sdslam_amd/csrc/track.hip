@@ -108,6 +108,7 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   h->rand_per_frame = 4 * pnp_max_iterations;
   h->rand_len.assign((size_t)max_batch, 0);
   h->meas_set.assign((size_t)max_batch, 0);
+  h->f12_set.assign((size_t)max_batch, 0);
   const size_t B = max_batch, M = max_points, K = nsel;
   TrackBuffers& tb = h->tb;
   tb.max_points = max_points;
@@ -189,6 +190,12 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &tb.sp_valid2, B * K));
   A(dalloc(h, &tb.sp_match, B * K));
   A(dalloc(h, &tb.sp_n, B));
+  A(dalloc<FILL_MINUS_ONE>(h, &tb.uright_ref, B * K));
+  A(dalloc(h, &tb.tri_F12_set, B * 9));
+  A(dalloc(h, &tb.tri_F12, B * 9));
+  A(dalloc(h, &tb.tri_epi, B * 2));
+  A(dalloc<FILL_FF>(h, &tb.tri_match, B * K));
+  A(dalloc(h, &tb.tri_n, B));
   A(dalloc(h, &tb.s3_Xw1, B * K * 3));
   A(dalloc(h, &tb.s3_Xw2, B * K * 3));
   A(dalloc(h, &tb.s3_X, B * K * 6));
@@ -359,6 +366,7 @@ int sd_track_set_poses(sd_track* h, int frame0, int n_frames, const double* Tref
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(Tref_cm && Tcur_cm, SD_ERR_INVALID_ARG, "NULL argument");
   sim3_end(h);           // the Sim3 solvers' keyframe poses are being replaced
+  tri_end(h);            // ... and the poses F12 and the epipole were computed from
   hipStream_t s = h->cur->stream;
   SD_TRY(upload(h->tb.Tref, Tref_cm, frame0, n_frames, 16, s));
   SD_TRY(upload(h->tb.Tprior, Tcur_cm, frame0, n_frames, 16, s));
@@ -681,6 +689,7 @@ int sd_track_get_pose_opt(sd_track* h, int frame0, int n_frames, double* Tcw_cm,
 int sd_track_set_uright(sd_track* h, int frame0, int n_frames, const float* uright, int cap) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(uright && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad uright array");
+  tri_end(h);            // KF1's stereo bits are being replaced
   SD_TRY(upload_rows(h->tb.uright, h->kp_cap, uright, cap, frame0, n_frames, h->cur->stream));
   return wait_for(h->cur->stream);
 }
@@ -744,6 +753,7 @@ int sd_track_set_point_flags(sd_track* h, int frame0, int n_frames, const uint8_
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(has_mp_cur && has_mp_ref && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad flag arrays (cap must be 1..keypoint capacity)");
   sim3_end(h);           // the Sim3 solvers' validity test is being replaced
+  tri_end(h);            // ... and the map-point flags of a SearchForTriangulation result
   hipStream_t s = h->cur->stream;
   const size_t K = h->kp_cap, o = (size_t)frame0 * K;
   SD_HIP_CHECK(hipMemsetAsync(h->tb.sp_valid1 + o, 0, (size_t)n_frames * K, s));

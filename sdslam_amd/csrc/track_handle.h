@@ -81,6 +81,10 @@ struct sd_track {
   int sim3_max_its = 0, sim3_iter_upper = 0;   // maxIterations argument / upper bound of mnIterations of those solvers
   UploadRing sim3_ring;            // [kp_cap + 1] int32: the mRansacMaxIts table of a sd_track_sim3 call
   int32_t* d_sim3_max_its = nullptr;
+  // SearchForTriangulation (track_tri.hip): the result sd_track_get_triangulation_matches returns while the stamp holds (tri_end)
+  RunStamp tri;                    // mode = the broadcast setting the search ran under
+  unsigned long long tri_ref_serial = 0;   // ... and on THIS extraction of `ref`
+  std::vector<uint8_t> f12_set;    // [max_batch] sd_track_set_f12 has covered the slot
   sd::TrackBuffers tb{};
   sd::TrackCam cam{};
   bool have_cam = false;
@@ -126,6 +130,8 @@ inline bool RunStamp::covers(const sd_track* h, int n_frames) const {
 
 // Something a Sim3Solver was constructed from is being replaced: sd_track_sim3_iterate refuses until sd_track_sim3 runs again
 static inline void sim3_end(sd_track* h) { h->sim3 = RunStamp{}; }
+// Something a SearchForTriangulation result was computed from is being replaced: the getter refuses until the search runs again
+static inline void tri_end(sd_track* h) { h->tri = RunStamp{}; }
 
 // "<the call `source` names> has not run on these slots since the last extraction"; 2: sd_track_stereo_init
 static inline const char* not_run_msg(int source) {

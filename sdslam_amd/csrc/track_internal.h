@@ -66,6 +66,13 @@ struct TrackBuffers {
   uint8_t* sp_valid2;    // [B][kp_cap] the same for pKF (the `ref` extractor's frame)
   int32_t* sp_match;     // [B][kp_cap] pKF keypoint index assigned to the currentKF keypoint, or -1
   int32_t* sp_n;         // [B]
+  // ORBmatcher::SearchForTriangulation (track_tri.hip) on the same pairing and the same flags, read as "holds a map point"
+  float* uright_ref;     // [B][kp_cap]  mvuRight of the ref extractor's frames (-1: none)
+  double* tri_F12_set;   // [B][9] the caller's F12, row-major (sd_track_set_f12)
+  double* tri_F12;       // [B][9] the F12 the last search used: ComputeF12 or the caller's
+  float* tri_epi;        // [B][2] the epipole in KF2
+  int32_t* tri_match;    // [B][kp_cap] KF2 keypoint index matched to the KF1 keypoint, or -1
+  int32_t* tri_n;        // [B]
   // local map (TrackLocalMap's search); capacity M like the last-frame arrays
   uint8_t* lm_cand;      // [B][M]   point reaches isInFrustum (not bad, not already seen in this frame)
   double* lm_Xw;         // [B][M][3]
@@ -211,6 +218,9 @@ int launch_features_in_area(const sd_orb* cur, const TrackBuffers& tb, const Tra
                             int min_level, int max_level, int32_t* d_out, int out_cap, int32_t* d_n, int32_t* d_grid, hipStream_t s);
 int launch_search_points(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, int n_frames, float nnratio, int check_ori,
                          hipStream_t s);
+// ComputeF12 (use_set_f12: tri_F12_set instead) and the epipole of every slot, then SearchForTriangulation (track_tri.hip)
+int launch_tri(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const TrackCam& cam, const float* d_sf, const float* d_sigma2,
+               int n_frames, int use_set_f12, int check_ori, hipStream_t s);
 int launch_stereo_from_depth(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_depth, int w, int h,
                              int stride_elems, size_t frame_stride_elems, int n_frames, hipStream_t s);
 // the same on a depth map of uint16_t (u16 != 0, always converted) or float elements; convert: d = (float)raw * scale

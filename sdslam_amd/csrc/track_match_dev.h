@@ -1,4 +1,4 @@
-// Device helpers the matchers of track_match.hip and track_bf.hip share.
+// Device helpers the matchers of track_match.hip, track_bf.hip and track_tri.hip share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// Dynamic-LDS layouts of the matcher kernels (track_match.hip, track_bf.hip): one struct per kernel, built from the launch's
+// Dynamic-LDS layouts of the matcher kernels (track_match.hip, track_bf.hip, track_tri.hip): one struct per kernel, built from the launch's
 // capacities.  The kernel carves its pointers from the struct (lds_at, track_match_dev.h) and the launcher passes .bytes, so the two cannot
 // disagree.  Plain C++ (no HIP): tests/native/match_lds_check.cpp sweeps every capacity on the host.
 #pragma once
@@ -109,6 +109,22 @@ struct LdsSearchPoints : LdsLayout {   // k_search_points; capw = keypoint capac
     match = take<int16_t>(capw);
     v2 = take<uint32_t>(capw >> 5);                // bit j: pKF point j has a map point
     m2 = take<uint32_t>(capw >> 5);                // bit j: pKF point j is given away (vbMatched2)
+    hist = take<int32_t>(32);
+    n1v = take<int32_t>(1);
+  }
+};
+
+struct LdsQuad { uint32_t w[4]; };   // 16 bytes: what take<> aligns to for arrays read as uint4 / float4
+
+struct LdsSearchTri : LdsLayout {   // k_search_triangulation; capw = keypoint capacity rounded up to 64
+  uint32_t tile = 0, aux = 0, i1 = 0, match = 0, elig = 0, erej = 0, hist = 0, n1v = 0;
+  constexpr explicit LdsSearchTri(int capw) {
+    tile = take<LdsQuad>(BF_TILE * 2);             // one tile of KF2 descriptors
+    aux = take<LdsQuad>(BF_TILE);                  // ... and per keypoint x, y, 3.84 * mvLevelSigma2[octave] rounded up, 0
+    i1 = take<uint16_t>(capw);                     // KF1 rows without a map point, ascending
+    match = take<int16_t>(capw);
+    elig = take<uint32_t>(capw >> 5);              // bit j: KF2 keypoint j exists and holds no map point
+    erej = take<uint32_t>(capw >> 5);              // bit j: ... is mono and inside the epipole's radius (rejects mono rows)
     hist = take<int32_t>(32);
     n1v = take<int32_t>(1);
   }

@@ -1,0 +1,443 @@
+// ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, F12, vMatchedPairs) and LocalMapping::ComputeF12 on
+// MI355X (reference src/ORBmatcher.cc:359-475, :128-144; src/LocalMapping.cc:494-511; caller LocalMapping::CreateNewMapPoints):
+// the epipolar brute-force matcher that finds the pairs a new keyframe triangulates against each of its neighbours.
+//
+// Slot f pairs frame f (or the broadcast frame) of the `cur` extractor -- KF1, pose Tcur -- with frame f of the `ref`
+// extractor -- KF2, pose Tref -- as k_search_points does.  Two kernels:
+//
+//   k_tri_geometry, one lane per slot, double throughout, every product and sum rounded on its own (the library is built
+//   with -ffp-contract=off).  With R1w, t1w from Tcur and R2w, t2w from Tref, every 3 x 3 product entry is
+//   (x0 * y0 + x1 * y1) + x2 * y2, k = 0..2 in order, and matrix chains go left to right:
+//     R12 = R1w * R2w^T;   t12[r] = (((-R12[r][0]) * t2w[0] + (-R12[r][1]) * t2w[1]) + (-R12[r][2]) * t2w[2]) + t1w[r]
+//     inverse of a 3 x 3 M by cofactors: C[i][j] = M[i+1][j+1] * M[i+2][j+2] - M[i+1][j+2] * M[i+2][j+1] (indices mod 3),
+//       det = (M[0][0] * C[0][0] + M[0][1] * C[0][1]) + M[0][2] * C[0][2], inv[i][j] = C[j][i] * (1.0 / det)
+//     F12 = ((inv(K^T) * [t12]x) * R12) * inv(K),  K = the tracker's camera (both keyframes share it)
+//   and the epipole (:362-368): Cw = -(R1w^T * t1w), C2 = R2w * Cw + t2w, invz = (float)(1.0 / C2z),
+//     ex = (float)((fx * C2x) * invz + cx), ey likewise.
+//
+//   k_search_triangulation, one workgroup per slot.  This variant of the matcher never sets vbMatched2, so every idx1 row is
+//   independent: one lane owns TRI_PT rows (descriptor, epipolar line a, b, c, den and the stereo bit in registers), KF2 goes
+//   through LDS in tiles of BF_TILE keypoints (descriptor + x, y, gate threshold) read as broadcasts, and the loop runs over
+//   the set bits of the tile's eligibility mask (idx2 < N2, no map point) on the scalar unit.  Every gate of the reference is
+//   a pure filter and `dist > bestDist -> continue` keeps the smallest distance, the LARGEST idx2 among equals, so a row's
+//   result is min over the passing candidates of dist << 11 | (2047 - idx2).
+//   What depends on the KF2 keypoint alone is evaluated once per keypoint instead of once per pair, in the reference's
+//   arithmetic: the epipole gate (ex - x2)^2 + (ey - y2)^2 < 100 * mvScaleFactors[octave2] becomes a second bit mask (set:
+//   keypoint is mono and inside the radius; it rejects the pair when the row is mono too), and the threshold of
+//   (double)dsqr < 3.84 * (double)mvLevelSigma2[octave2] becomes the float thr = 3.84 * sigma2 rounded UP: for a float dsqr,
+//   dsqr < thr holds exactly when (double)dsqr < the double product does.  den == 0 makes dsqr inf or NaN, which fails the
+//   comparison as the reference's explicit test does; the row is also dropped explicitly at the end.
+//   Gate order: the epipolar test first, for the wave's 128 rows; the tile's descriptor is read and the popcounts run only
+//   when one of them passes.  The gate passes so few candidates that this beats computing both and selecting, although a wave
+//   skips only when all of its rows reject (measured: DESIGN.md section 6, SearchForTriangulation).
+//   Rotation check (:434-463): the bin arithmetic is that of SearchByPoints (:1269-1278, rot_bin) and the cut is the same
+//   ComputeThreeMaxima, so both helpers of track_match_dev.h are used as they are; the bins never feed back into the scan.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "track_handle.h"
+#include "track_match_dev.h"
+
+namespace sd {
+
+#define TRI_THREADS 256
+#define TRI_PT 2          // KF1 rows per lane
+#define TRI_TH_LOW 50
+#define TRI_NONE 0xFFFFFFFFu
+
+// What the matcher reads and writes besides the two keyframes' keypoints: rows of `cap` entries per slot
+struct TriBuffers {
+  const uint8_t* has1;   // [B][cap] KF1 keypoint holds a map point (slot row)
+  const uint8_t* has2;   // [B][cap] the same for KF2
+  const float* ur1;      // [.][cap] KF1 mvuRight (row of the cur FRAME)
+  const float* ur2;      // [B][cap] KF2 mvuRight
+  const double* F12;     // [B][9] row-major
+  const float* epi;      // [B][2]
+  const float* sf;       // [nlevels] mvScaleFactors
+  const float* sigma2;   // [nlevels] mvLevelSigma2
+  int32_t* match;        // [B][cap] KF2 index or -1
+  int32_t* n;            // [B]
+};
+
+// (x0 * y0 + x1 * y1) + x2 * y2
+__device__ __forceinline__ double dot3(double x0, double x1, double x2, double y0, double y1, double y2) {
+  return __dadd_rn(__dadd_rn(__dmul_rn(x0, y0), __dmul_rn(x1, y1)), __dmul_rn(x2, y2));
+}
+// out = A * B, row-major 3 x 3
+__device__ __forceinline__ void mul33(const double* A, const double* B, double* out) {
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) out[r * 3 + c] = dot3(A[r * 3], A[r * 3 + 1], A[r * 3 + 2], B[c], B[3 + c], B[6 + c]);
+}
+__device__ __forceinline__ void inv33(const double* M, double* out) {
+  double C[9];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+      C[i * 3 + j] = __dsub_rn(__dmul_rn(M[i1 * 3 + j1], M[i2 * 3 + j2]), __dmul_rn(M[i1 * 3 + j2], M[i2 * 3 + j1]));
+    }
+  const double invdet = __ddiv_rn(1.0, dot3(M[0], M[1], M[2], C[0], C[1], C[2]));
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) out[i * 3 + j] = __dmul_rn(C[j * 3 + i], invdet);
+}
+
+__global__ __launch_bounds__(64) void k_tri_geometry(const double* __restrict__ Tcur, const double* __restrict__ Tref, TrackCam cam,
+                                                     const double* __restrict__ F12_set /* NULL: ComputeF12 */, double* __restrict__ F12_out,
+                                                     float* __restrict__ epi_out, int n_frames) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_frames) return;
+  const double *T1 = Tcur + (size_t)f * 16, *T2 = Tref + (size_t)f * 16;   // column-major: R[r][c] = T[c * 4 + r]
+  double R1[9], R2[9], t1[3], t2[3];
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) {
+      R1[r * 3 + c] = T1[c * 4 + r];
+      R2[r * 3 + c] = T2[c * 4 + r];
+    }
+    t1[r] = T1[12 + r];
+    t2[r] = T2[12 + r];
+  }
+  double* F = F12_out + (size_t)f * 9;
+  if (F12_set) {
+    for (int i = 0; i < 9; i++) F[i] = F12_set[(size_t)f * 9 + i];
+  } else {
+    double R12[9], t12[3];
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) R12[r * 3 + c] = dot3(R1[r * 3], R1[r * 3 + 1], R1[r * 3 + 2], R2[c * 3], R2[c * 3 + 1], R2[c * 3 + 2]);
+    for (int r = 0; r < 3; r++) t12[r] = __dadd_rn(dot3(-R12[r * 3], -R12[r * 3 + 1], -R12[r * 3 + 2], t2[0], t2[1], t2[2]), t1[r]);
+    const double tx[9] = {0.0, -t12[2], t12[1], t12[2], 0.0, -t12[0], -t12[1], t12[0], 0.0};
+    const double K[9] = {cam.fx, 0.0, cam.cx, 0.0, cam.fy, cam.cy, 0.0, 0.0, 1.0};
+    const double Kt[9] = {cam.fx, 0.0, 0.0, 0.0, cam.fy, 0.0, cam.cx, cam.cy, 1.0};
+    double Kti[9], Ki[9], A[9], Bm[9];
+    inv33(Kt, Kti);
+    inv33(K, Ki);
+    mul33(Kti, tx, A);
+    mul33(A, R12, Bm);
+    mul33(Bm, Ki, F);
+  }
+  double Cw[3], C2[3];
+  for (int r = 0; r < 3; r++) Cw[r] = -dot3(R1[r], R1[3 + r], R1[6 + r], t1[0], t1[1], t1[2]);
+  for (int r = 0; r < 3; r++) C2[r] = __dadd_rn(dot3(R2[r * 3], R2[r * 3 + 1], R2[r * 3 + 2], Cw[0], Cw[1], Cw[2]), t2[r]);
+  const float invz = (float)__ddiv_rn(1.0, C2[2]);
+  epi_out[(size_t)f * 2] = (float)__dadd_rn(__dmul_rn(__dmul_rn(cam.fx, C2[0]), (double)invz), cam.cx);
+  epi_out[(size_t)f * 2 + 1] = (float)__dadd_rn(__dmul_rn(__dmul_rn(cam.fy, C2[1]), (double)invz), cam.cy);
+}
+
+__device__ __forceinline__ int tri_dist(const uint32_t (&a)[8], const uint32_t (&b)[8]) {
+  int d = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) d += __popc(a[k] ^ b[k]);
+  return d;
+}
+
+// Dynamic LDS: LdsSearchTri (track_match_lds.h)
+__global__ __launch_bounds__(TRI_THREADS) void k_search_triangulation(const sd_keypoint* __restrict__ kps1_all, const uint8_t* __restrict__ desc1_all,
+                                                                      const int32_t* __restrict__ n1_all, const sd_keypoint* __restrict__ kps2_all,
+                                                                      const uint8_t* __restrict__ desc2_all, const int32_t* __restrict__ n2_all,
+                                                                      TriBuffers tb, int cur_bcast, int cap, int capw /* cap rounded up to 64 */,
+                                                                      int nlevels, int check_ori) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const LdsSearchTri L(capw);
+  uint32_t* s_tile = lds_at<uint32_t>(smem, L.tile);
+  float4* s_aux = lds_at<float4>(smem, L.aux);
+  uint16_t* s_i1 = lds_at<uint16_t>(smem, L.i1);
+  int16_t* s_match = lds_at<int16_t>(smem, L.match);
+  uint32_t* s_elig = lds_at<uint32_t>(smem, L.elig);
+  uint32_t* s_erej = lds_at<uint32_t>(smem, L.erej);
+  int* s_hist = lds_at<int>(smem, L.hist);
+  int* s_n1v = lds_at<int>(smem, L.n1v);
+  const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  const int fc = cur_bcast >= 0 ? cur_bcast : f;
+  const sd_keypoint* kps1 = kps1_all + (size_t)fc * cap;
+  const sd_keypoint* kps2 = kps2_all + (size_t)f * cap;
+  const uint32_t* desc1 = (const uint32_t*)(desc1_all + (size_t)fc * cap * 32);
+  const uint32_t* desc2 = (const uint32_t*)(desc2_all + (size_t)f * cap * 32);
+  const int N1 = min(max(n1_all[fc], 0), cap), N2 = min(max(n2_all[f], 0), cap);
+  const uint8_t* has1 = tb.has1 + (size_t)f * cap;
+  const uint8_t* has2 = tb.has2 + (size_t)f * cap;
+  const float* ur1 = tb.ur1 + (size_t)fc * cap;
+  const float* ur2 = tb.ur2 + (size_t)f * cap;
+  const double* F = tb.F12 + (size_t)f * 9;
+  const float ex = tb.epi[(size_t)f * 2], ey = tb.epi[(size_t)f * 2 + 1];
+
+  // ---- KF2 as bits: eligible (idx2 < N2, no map point); mono and inside the epipole's radius (:418-423)
+  for (int i0 = 0; i0 < capw; i0 += TRI_THREADS) {
+    const int i = i0 + tid;
+    const bool el = i < N2 && has2[i] == 0;
+    bool rj = false;
+    if (el && !(ur2[i] >= 0)) {
+      const sd_keypoint kp = kps2[i];
+      const float distex = ex - kp.x, distey = ey - kp.y;
+      rj = distex * distex + distey * distey < 100.0f * tb.sf[min(max(kp.octave, 0), nlevels - 1)];
+    }
+    const unsigned long long be = __ballot(el), br = __ballot(rj);
+    if (lane == 0 && i < capw) {
+      s_elig[i >> 5] = (uint32_t)be;
+      s_elig[(i >> 5) + 1] = (uint32_t)(be >> 32);
+      s_erej[i >> 5] = (uint32_t)br;
+      s_erej[(i >> 5) + 1] = (uint32_t)(br >> 32);
+    }
+  }
+  for (int i = tid; i < capw; i += TRI_THREADS) s_match[i] = -1;
+  if (tid < 32) s_hist[tid] = 0;
+  // ---- the KF1 rows without a map point, ascending
+  if (wave == 0) {
+    int n = 0;
+    for (int i0 = 0; i0 < capw; i0 += 64) {
+      const int i = i0 + lane;
+      const bool ok = i < N1 && has1[i] == 0;
+      const unsigned long long b = __ballot(ok);
+      if (ok) s_i1[n + __popcll(b & lt)] = (uint16_t)i;
+      n += __popcll(b);
+    }
+    if (lane == 0) *s_n1v = n;
+  }
+  __syncthreads();
+  const int n1v = *s_n1v;
+  const int ntiles = (N2 + BF_TILE - 1) / BF_TILE;
+
+  for (int e0 = 0; e0 < n1v; e0 += TRI_THREADS * TRI_PT) {
+    uint32_t d1[TRI_PT][8], best[TRI_PT];
+    float la[TRI_PT], lb[TRI_PT], lc[TRI_PT], den[TRI_PT];
+    bool mono1[TRI_PT];
+    int ent[TRI_PT];
+#pragma unroll
+    for (int p = 0; p < TRI_PT; p++) {
+      ent[p] = e0 + p * TRI_THREADS + tid;
+      const int i1 = ent[p] < n1v ? s_i1[ent[p]] : s_i1[0];   // n1v >= 1 here: entry 0 exists
+      const uint4 a = ((const uint4*)(desc1 + (size_t)i1 * 8))[0], b = ((const uint4*)(desc1 + (size_t)i1 * 8))[1];
+      d1[p][0] = a.x; d1[p][1] = a.y; d1[p][2] = a.z; d1[p][3] = a.w;
+      d1[p][4] = b.x; d1[p][5] = b.y; d1[p][6] = b.z; d1[p][7] = b.w;
+      // l = x1' F12 = [a b c] (:130-132): double, left to right, rounded to float once
+      const double x1 = (double)kps1[i1].x, y1 = (double)kps1[i1].y;
+      la[p] = (float)__dadd_rn(__dadd_rn(__dmul_rn(x1, F[0]), __dmul_rn(y1, F[3])), F[6]);
+      lb[p] = (float)__dadd_rn(__dadd_rn(__dmul_rn(x1, F[1]), __dmul_rn(y1, F[4])), F[7]);
+      lc[p] = (float)__dadd_rn(__dadd_rn(__dmul_rn(x1, F[2]), __dmul_rn(y1, F[5])), F[8]);
+      den[p] = __fadd_rn(__fmul_rn(la[p], la[p]), __fmul_rn(lb[p], lb[p]));
+      mono1[p] = !(ur1[i1] >= 0);
+      best[p] = TRI_NONE;
+    }
+    for (int t = 0; t < ntiles; t++) {
+      __syncthreads();   // previous tile fully consumed
+      const int j0 = t * BF_TILE, jn = min(BF_TILE, N2 - j0);
+      for (int w = tid; w < jn * 2; w += TRI_THREADS) ((uint4*)s_tile)[w] = ((const uint4*)(desc2 + (size_t)j0 * 8))[w];
+      for (int j = tid; j < jn; j += TRI_THREADS) {
+        const sd_keypoint kp = kps2[j0 + j];
+        const double thr = __dmul_rn(3.84, (double)tb.sigma2[min(max(kp.octave, 0), nlevels - 1)]);
+        s_aux[j] = make_float4(kp.x, kp.y, __double2float_ru(thr), 0.f);
+      }
+      __syncthreads();
+      for (int wd = 0; wd < (jn + 31) >> 5; wd++) {
+        uint32_t mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_elig[(j0 >> 5) + wd]);   // wave-uniform: scalar loop
+        const uint32_t rej = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_erej[(j0 >> 5) + wd]);
+        while (mask) {
+          const int bit = __ffs((int)mask) - 1;
+          mask &= mask - 1;
+          const int jl = wd * 32 + bit;
+          const float4 q = s_aux[jl];                                                                       // LDS broadcasts
+          const bool mono_rej = (rej >> bit) & 1u;
+          bool pass[TRI_PT];
+#pragma unroll
+          for (int p = 0; p < TRI_PT; p++) {
+            // CheckDistEpipolarLine (:134-143), all float
+            const float num = __fadd_rn(__fadd_rn(__fmul_rn(la[p], q.x), __fmul_rn(lb[p], q.y)), lc[p]);
+            const float dsqr = __fdiv_rn(__fmul_rn(num, num), den[p]);
+            pass[p] = dsqr < q.z && !(mono_rej && mono1[p]);
+          }
+          bool any = false;
+#pragma unroll
+          for (int p = 0; p < TRI_PT; p++) any |= pass[p];
+          if (!__ballot(any)) continue;   // wave-uniform: no row of this wave takes the candidate
+          const uint4 a = ((const uint4*)(s_tile + jl * 8))[0], b = ((const uint4*)(s_tile + jl * 8))[1];
+          const uint32_t d2[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+          const uint32_t low = (uint32_t)(2047 - (j0 + jl));
+#pragma unroll
+          for (int p = 0; p < TRI_PT; p++) {
+            const int dist = tri_dist(d1[p], d2);
+            const uint32_t key = ((uint32_t)dist << 11) | low;
+            if (pass[p] && dist <= TRI_TH_LOW) best[p] = min(best[p], key);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < TRI_PT; p++)
+      if (ent[p] < n1v && best[p] != TRI_NONE && den[p] != 0.f) s_match[s_i1[ent[p]]] = (int16_t)(2047 - (int)(best[p] & 2047u));
+  }
+  __syncthreads();
+  if (tid >= 64) return;   // one wavefront counts and runs the rotation check
+
+  int nmatches = 0;
+  for (int e0 = 0; e0 < n1v; e0 += 64) {
+    const int e = e0 + lane;
+    const int i1 = e < n1v ? s_i1[e] : 0;
+    const int j = e < n1v ? s_match[i1] : -1;
+    nmatches += __popcll(__ballot(j >= 0));
+    if (check_ori && j >= 0) atomicAdd(&s_hist[rot_bin(kps1[i1].angle, kps2[j].angle)], 1);
+  }
+  if (check_ori) {
+    __threadfence_block();
+    int ind1, ind2, ind3;
+    three_maxima(s_hist, ind1, ind2, ind3);
+    for (int e0 = 0; e0 < n1v; e0 += 64) {
+      const int e = e0 + lane;
+      bool drop = false;
+      if (e < n1v) {
+        const int i1 = s_i1[e], j = s_match[i1];
+        if (j >= 0) {
+          const int bin = rot_bin(kps1[i1].angle, kps2[j].angle);
+          drop = bin != ind1 && bin != ind2 && bin != ind3;
+          if (drop) s_match[i1] = -1;
+        }
+      }
+      nmatches -= __popcll(__ballot(drop));
+    }
+  }
+  int32_t* out = tb.match + (size_t)f * cap;
+  for (int i = lane; i < cap; i += 64) out[i] = (int32_t)s_match[i];
+  if (lane == 0) tb.n[f] = nmatches;
+}
+
+static int launch_search_triangulation(const sd_keypoint* kps1, const uint8_t* desc1, const int32_t* n1, const sd_keypoint* kps2,
+                                       const uint8_t* desc2, const int32_t* n2, const TriBuffers& tb, int cur_bcast, int cap, int nlevels,
+                                       int n_frames, int check_ori, hipStream_t s) {
+  const int capw = (cap + 63) & ~63;
+  SD_REQUIRE(capw <= 2048, SD_ERR_CAPACITY, "SearchForTriangulation supports at most 2048 keypoints per keyframe");
+  hipLaunchKernelGGL(k_search_triangulation, dim3(n_frames), dim3(TRI_THREADS), LdsSearchTri(capw).bytes, s, kps1, desc1, n1, kps2, desc2, n2,
+                     tb, cur_bcast, cap, capw, nlevels, check_ori != 0);
+  SD_HIP_CHECK(hipGetLastError());
+  return SD_OK;
+}
+
+int launch_tri(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& b, const TrackCam& cam, const float* d_sf, const float* d_sigma2,
+               int n_frames, int use_set_f12, int check_ori, hipStream_t s) {
+  hipLaunchKernelGGL(k_tri_geometry, dim3((n_frames + 63) / 64), dim3(64), 0, s, b.Tcur, b.Tref, cam,
+                     use_set_f12 ? (const double*)b.tri_F12_set : (const double*)nullptr, b.tri_F12, b.tri_epi, n_frames);
+  SD_HIP_CHECK(hipGetLastError());
+  const TriBuffers tb = {b.sp_valid1, b.sp_valid2, b.uright, b.uright_ref, b.tri_F12, b.tri_epi, d_sf, d_sigma2, b.tri_match, b.tri_n};
+  return launch_search_triangulation(cur->have_dist ? cur->d_kps_un : cur->d_kps, cur->d_desc, cur->d_nout,
+                                     ref->have_dist ? ref->d_kps_un : ref->d_kps, ref->d_desc, ref->d_nout, tb, b.cur_bcast, b.kp_cap,
+                                     cur->nlevels, n_frames, check_ori, s);
+}
+
+}  // namespace sd
+
+using namespace sd;
+
+// One device allocation of the debug entry, carved in 16-byte steps
+namespace {
+struct Blob {
+  uint8_t* base = nullptr;
+  size_t bytes = 0;
+  size_t reserve(size_t n) {
+    const size_t off = bytes;
+    bytes += (n + 15) & ~(size_t)15;
+    return off;
+  }
+};
+}  // namespace
+
+extern "C" {
+
+int sd_track_set_uright_ref(sd_track* h, int frame0, int n_frames, const float* uright, int cap) {
+  QUEUE_RANGE(h, frame0, n_frames);
+  SD_REQUIRE(uright && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad uright array");
+  tri_end(h);
+  SD_TRY(upload_rows(h->tb.uright_ref, h->kp_cap, uright, cap, frame0, n_frames, h->pnp_stream));
+  return wait_for(h->pnp_stream);   // the rows are the caller's pageable memory: back once they are read
+}
+
+int sd_track_set_f12(sd_track* h, int frame0, int n_frames, const double* F12_rm9) {
+  QUEUE_RANGE(h, frame0, n_frames);
+  SD_REQUIRE(F12_rm9, SD_ERR_INVALID_ARG, "NULL argument");
+  tri_end(h);
+  SD_TRY(h->pose_ring.upload(h->tb.tri_F12_set + (size_t)frame0 * 9, F12_rm9, (size_t)n_frames * 9, h->pnp_stream));
+  std::fill(h->f12_set.begin() + frame0, h->f12_set.begin() + frame0 + n_frames, (uint8_t)1);
+  return SD_OK;
+}
+
+int sd_track_search_for_triangulation(sd_track* h, int n_frames, int use_set_f12, int check_ori) {
+  SD_TRY(check_ready(h, n_frames));
+  SD_TRY(require_ref_frames(h, n_frames, false));
+  SD_REQUIRE(keypoint_capacity(h->ref) == h->kp_cap, SD_ERR_INVALID_ARG, "cur / ref extractors must share the keypoint capacity");
+  if (use_set_f12)
+    for (int f = 0; f < n_frames; f++)
+      SD_REQUIRE(h->f12_set[f], SD_ERR_INVALID_ARG, "use_set_f12 = 1, but sd_track_set_f12 has not covered these slots");
+  tri_end(h);
+  SD_TRY(run_stage(h, true, false, STAGE_MATCH, [&](hipStream_t s) {   // timed in the matcher's slot
+    return launch_tri(h->cur, h->ref, h->tb, h->cam, h->d_sf, h->d_sigma2, n_frames, use_set_f12, check_ori, s);
+  }));
+  h->tri.set(h, n_frames, h->tb.cur_bcast);
+  h->tri_ref_serial = h->ref->extract_serial;
+  return SD_OK;
+}
+
+int sd_track_get_triangulation_matches(sd_track* h, int frame0, int n_frames, int32_t* matches12, int cap, int32_t* n_matches,
+                                       double* F12_rm9, float* epipole2) {
+  TRACK_RANGE(h, frame0, n_frames);
+  SD_REQUIRE(h->tri.covers(h, frame0 + n_frames) && h->tri_ref_serial == h->ref->extract_serial && h->tri.mode == h->tb.cur_bcast,
+             SD_ERR_INVALID_ARG,
+             "sd_track_search_for_triangulation has not run on these slots (or their keyframes, flags, mvuRight, poses, F12 or the "
+             "broadcast setting were replaced since)");
+  SD_REQUIRE(!matches12 || cap >= h->kp_cap, SD_ERR_CAPACITY, "cap smaller than the keypoint capacity");
+  hipStream_t s = h->cur->stream;
+  SD_TRY(download_rows(matches12, cap, h->tb.tri_match, frame0, n_frames, h->kp_cap, s));
+  SD_TRY(download(n_matches, h->tb.tri_n, frame0, n_frames, 1, s));
+  SD_TRY(download(F12_rm9, h->tb.tri_F12, frame0, n_frames, 9, s));
+  SD_TRY(download(epipole2, h->tb.tri_epi, frame0, n_frames, 2, s));
+  return wait_for(s);
+}
+
+int sd_debug_search_for_triangulation(int n1, int n2, const sd_keypoint* kps1, const uint8_t* desc1, const uint8_t* has_mp1,
+                                      const float* uright1, const sd_keypoint* kps2, const uint8_t* desc2, const uint8_t* has_mp2,
+                                      const float* uright2, const double* F12_rm9, const float* epipole2, const float* scale_factors,
+                                      const float* level_sigma2, int nlevels, int check_ori, int32_t* matches12, int32_t* n_matches) {
+  SD_REQUIRE(n1 >= 0 && n2 >= 0 && n1 <= 2048 && n2 <= 2048, SD_ERR_CAPACITY, "at most 2048 keypoints per keyframe");
+  SD_REQUIRE((n1 == 0 || (kps1 && desc1 && has_mp1 && uright1 && matches12)) && (n2 == 0 || (kps2 && desc2 && has_mp2 && uright2)),
+             SD_ERR_INVALID_ARG, "NULL keyframe array");
+  SD_REQUIRE(F12_rm9 && epipole2 && scale_factors && level_sigma2 && nlevels >= 1 && nlevels <= SD_MAX_LEVELS && n_matches,
+             SD_ERR_INVALID_ARG, "bad arguments");
+  const size_t cap = (size_t)std::max(std::max(n1, n2), 1);
+  Blob b;
+  const size_t o_k1 = b.reserve(cap * sizeof(sd_keypoint)), o_k2 = b.reserve(cap * sizeof(sd_keypoint));
+  const size_t o_d1 = b.reserve(cap * 32), o_d2 = b.reserve(cap * 32);
+  const size_t o_h1 = b.reserve(cap), o_h2 = b.reserve(cap);
+  const size_t o_u1 = b.reserve(cap * 4), o_u2 = b.reserve(cap * 4);
+  const size_t o_F = b.reserve(9 * 8), o_e = b.reserve(2 * 4), o_sf = b.reserve((size_t)nlevels * 4), o_s2 = b.reserve((size_t)nlevels * 4);
+  const size_t o_n = b.reserve(3 * 4), o_m = b.reserve(cap * 4);
+  std::vector<uint8_t> host(b.bytes, 0);
+  auto put = [&](size_t off, const void* src, size_t n) { if (n) std::memcpy(host.data() + off, src, n); };
+  put(o_k1, kps1, (size_t)n1 * sizeof(sd_keypoint)); put(o_k2, kps2, (size_t)n2 * sizeof(sd_keypoint));
+  put(o_d1, desc1, (size_t)n1 * 32); put(o_d2, desc2, (size_t)n2 * 32);
+  put(o_h1, has_mp1, (size_t)n1); put(o_h2, has_mp2, (size_t)n2);
+  put(o_u1, uright1, (size_t)n1 * 4); put(o_u2, uright2, (size_t)n2 * 4);
+  put(o_F, F12_rm9, 72); put(o_e, epipole2, 8);
+  put(o_sf, scale_factors, (size_t)nlevels * 4); put(o_s2, level_sigma2, (size_t)nlevels * 4);
+  const int32_t counts[3] = {n1, n2, 0};
+  put(o_n, counts, sizeof(counts));
+  SD_HIP_CHECK(hipMalloc(&b.base, b.bytes));
+  uint8_t* d = b.base;
+  hipError_t e = hipMemcpy(d, host.data(), b.bytes, hipMemcpyHostToDevice);
+  int rc = SD_OK;
+  if (e == hipSuccess) {
+    const TriBuffers tb = {d + o_h1, d + o_h2, (const float*)(d + o_u1), (const float*)(d + o_u2), (const double*)(d + o_F),
+                           (const float*)(d + o_e), (const float*)(d + o_sf), (const float*)(d + o_s2), (int32_t*)(d + o_m),
+                           (int32_t*)(d + o_n) + 2};
+    rc = launch_search_triangulation((const sd_keypoint*)(d + o_k1), d + o_d1, (const int32_t*)(d + o_n), (const sd_keypoint*)(d + o_k2),
+                                     d + o_d2, (const int32_t*)(d + o_n) + 1, tb, -1, (int)cap, nlevels, 1, check_ori, 0);
+    if (rc == SD_OK) e = hipMemcpy(host.data(), d, b.bytes, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(b.base);
+  if (e != hipSuccess) {
+    set_error(std::string("sd_debug_search_for_triangulation: ") + hipGetErrorString(e));
+    return SD_ERR_HIP;
+  }
+  SD_TRY(rc);
+  if (n1) std::memcpy(matches12, host.data() + o_m, (size_t)n1 * 4);
+  std::memcpy(n_matches, host.data() + o_n + 8, 4);
+  return SD_OK;
+}
+
+}  // extern "C"
