@@ -29,11 +29,145 @@ def lib_path() -> str:
     return os.environ.get("SD_LIB") or os.path.join(_HERE, "libsdslam_hip.so")
 
 
+# name -> (restype, [argtypes]), in the order of include/sdslam_hip.h: the one place a C signature is written down.  lib()
+# applies every row at load; tests/test_capi_signatures_cpu.py holds the rows to the header.
+_I, _F, _D, _Z, _P, _S = C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_void_p, C.c_char_p
+_PP, _PI = C.POINTER(C.c_void_p), C.POINTER(C.c_int)        # a handle / an int the call returns through byref()
+
+_SIGNATURES = {
+    # status, version, process-wide options
+    "sd_last_error": (_S, []),
+    "sd_device_count": (_I, []),
+    "sd_version": (_S, []),
+    "sd_set_option": (_I, [_S, _I]),
+    "sd_get_option": (_I, [_S, _PI]),
+    "sd_option_count": (_I, []),
+    "sd_option_name": (_S, [_I]),
+    # ORB extractor
+    "sd_orb_create": (_I, [_I, _F, _I, _I, _I, _I, _I, _I, _PP]),
+    "sd_orb_destroy": (None, [_P]),
+    "sd_orb_levels": (_I, [_P]),
+    "sd_orb_scale_tables": (_I, [_P, _P, _P, _P, _P]),
+    "sd_orb_features_per_level": (_I, [_P, _P]),
+    "sd_orb_plan_info": (_I, [_I, _F, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "sd_orb_extract": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P]),
+    "sd_orb_extract_batch": (_I, [_P, _P, _I, _I, _I, _I, _Z, _P, _P, _I, _P]),
+    "sd_orb_extract_batch_device": (_I, [_P, _P, _I, _I, _I, _I, _Z]),
+    "sd_orb_download": (_I, [_P, _I, _I, _P, _P, _I, _P]),
+    "sd_orb_set_distortion": (_I, [_P, _F, _F, _F, _F, _F, _F, _F, _F, _F]),
+    "sd_orb_download_undistorted": (_I, [_P, _I, _I, _P, _I]),
+    "sd_orb_level_info": (_I, [_P, _I, _P, _P]),
+    "sd_orb_level_copy": (_I, [_P, _I, _I, _I, _P, _I]),
+    "sd_orb_debug_blurred": (_I, [_P, _I, _I, _P, _I]),
+    "sd_orb_debug_cell_counts": (_I, [_P, _I, _I, _P, _I, _P]),
+    "sd_orb_debug_level_keys": (_I, [_P, _I, _I, _P, _I, _P]),
+    "sd_orb_set_stream": (_I, [_P, _P]),
+    "sd_orb_stream_fence": (_I, [_P, _P, _I]),
+    "sd_orb_sync": (_I, [_P]),
+    "sd_orb_set_profiling": (_I, [_P, _I]),
+    "sd_orb_num_stages": (_I, []),
+    "sd_orb_stage_name": (_S, [_I]),
+    "sd_orb_stage_ms": (_I, [_P, _P, _I]),
+    "sd_orb_stage_bytes": (_I, [_P, _P, _I]),
+    # device / pinned memory helpers
+    "sd_dev_alloc": (_I, [_Z, _PP]),
+    "sd_host_alloc": (_I, [_Z, _PP]),
+    "sd_host_free": (_I, [_P]),
+    "sd_dev_free": (_I, [_P]),
+    "sd_dev_upload": (_I, [_P, _P, _Z]),
+    "sd_dev_download": (_I, [_P, _P, _Z]),
+    # batched tracking context
+    "sd_track_create": (_I, [_P, _P, _I, _I, _I, _PP]),
+    "sd_track_destroy": (None, [_P]),
+    "sd_track_set_camera": (_I, [_P, _F, _F, _F, _F, _F, _F, _F, _F, _F]),
+    "sd_track_set_last": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "sd_track_set_poses": (_I, [_P, _I, _I, _P, _P]),
+    "sd_track_set_rand": (_I, [_P, _I, _I, _P, _I]),
+    "sd_track_set_uright": (_I, [_P, _I, _I, _P, _I]),
+    "sd_track_stereo_from_depth": (_I, [_P, _I, _P, _I, _I, _I, _Z]),
+    "sd_track_get_stereo": (_I, [_P, _I, _I, _P, _P, _I]),
+    "sd_track_stereo_from_depth_device": (_I, [_P, _I, _P, _I, _I, _I, _I, _Z, _F]),
+    "sd_track_set_local": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sd_track_match_local": (_I, [_P, _I, _F, _F, _F]),
+    "sd_track_get_local": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "sd_track_pose_opt": (_I, [_P, _I, _I]),
+    "sd_track_get_pose_opt": (_I, [_P, _I, _I, _P, _P, _I, _P]),
+    "sd_track_set_current_broadcast": (_I, [_P, _I]),
+    "sd_track_relocalize": (_I, [_P, _I, _I, _F, _I, _I, _I, _P, _P]),
+    "sd_track_detect_loop": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "sd_track_with_motion_model": (_I, [_P, _I, _I, _F, _I, _I, _I]),
+    "sd_track_get_tracked": (_I, [_P, _I, _I, _P]),
+    "sd_track_local_map": (_I, [_P, _I, _F, _F, _F, _I]),
+    "sd_track_get_local_map": (_I, [_P, _I, _I, _P, _I, _P]),
+    "sd_track_set_point_flags": (_I, [_P, _I, _I, _P, _P, _I]),
+    "sd_track_search_by_points": (_I, [_P, _I, _F, _I]),
+    "sd_track_get_point_matches": (_I, [_P, _I, _I, _P, _I, _P]),
+    "sd_track_set_sim3_points": (_I, [_P, _I, _I, _P, _P, _I]),
+    "sd_track_set_point_matches": (_I, [_P, _I, _I, _P, _I]),
+    "sd_track_sim3": (_I, [_P, _I, _I, _D, _I, _I, _I]),
+    "sd_track_sim3_iterate": (_I, [_P, _I, _I]),
+    "sd_track_get_sim3": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "sd_track_set_uright_ref": (_I, [_P, _I, _I, _P, _I]),
+    "sd_track_set_f12": (_I, [_P, _I, _I, _P]),
+    "sd_track_search_for_triangulation": (_I, [_P, _I, _I, _I]),
+    "sd_track_get_triangulation_matches": (_I, [_P, _I, _I, _P, _I, _P, _P, _P]),
+    "sd_debug_search_for_triangulation": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "sd_track_align": (_I, [_P, _I, _I]),
+    "sd_track_match": (_I, [_P, _I, _F, _I, _I]),
+    "sd_track_pnp": (_I, [_P, _I, _D, _I, _I, _I, _F, _F, _I]),
+    "sd_track_pnp_iterate": (_I, [_P, _I, _I]),
+    "sd_track_set_matches": (_I, [_P, _I, _I, _P, _I]),
+    "sd_track_get_align": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
+    "sd_track_get_matches": (_I, [_P, _I, _I, _P, _I, _P]),
+    "sd_track_get_pnp": (_I, [_P, _I, _I, _P, _P, _I, _P]),
+    "sd_debug_pnp_prof": (_I, [_P, _I]),          # the three *_prof: called by tools/prof_pnp.py and tools/prof_select.py
+    "sd_debug_align_prof": (_I, [_P, _I]),
+    "sd_debug_sel_prof": (_I, [_P, _I]),
+    "sd_debug_epnp": (_I, [_I, _P, _P, _D, _D, _D, _D, _P, _P, _P]),
+    "sd_track_debug_features_in_area": (_I, [_P, _I, _F, _F, _F, _I, _I, _P, _I, _P, _P]),
+    "sd_track_pack_records": (_I, [_P, _I, _I, _P]),
+    # sequential tracking, motion and IMU models
+    "sd_track_set_map_ids": (_I, [_P, _I, _I, _I, _P, _I]),
+    "sd_track_advance": (_I, [_P, _I, _I]),
+    "sd_track_set_prior": (_I, [_P, _I, _I, _P, _I]),
+    "sd_track_get_last": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sd_track_get_extractors": (_I, [_P, _PP, _PP]),
+    "sd_track_close_points": (_I, [_P, _I, _I, _F]),
+    "sd_track_get_close_points": (_I, [_P, _I, _I, _P]),
+    "sd_track_motion_predict": (_I, [_P, _I, _D]),
+    "sd_track_motion_update": (_I, [_P, _I, _I]),
+    "sd_track_motion_restart": (_I, [_P, _I, _I]),
+    "sd_track_get_motion": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "sd_track_set_motion": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "sd_track_set_sensor_model": (_I, [_P, _I]),
+    "sd_track_get_sensor_model": (_I, [_P, _PI]),
+    "sd_track_set_measurements": (_I, [_P, _I, _I, _P]),
+    "sd_track_get_imu": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "sd_track_set_imu": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
+    "sd_track_stream_fence": (_I, [_P, _P, _I]),
+    "sd_track_set_profiling": (_I, [_P, _I]),
+    "sd_track_stage_ms": (_I, [_P, _P, _I]),
+    # RGB-D map point creation and the keyframe decision
+    "sd_track_set_next_map_id": (_I, [_P, _I, _I, _P]),
+    "sd_track_stereo_init": (_I, [_P, _I, _I]),
+    "sd_track_set_keyframe_state": (_I, [_P, _I, _I, _P]),
+    "sd_track_need_keyframe": (_I, [_P, _I, _I, _I, _I, _I]),
+    "sd_track_set_keyframe_flags": (_I, [_P, _I, _I, _P]),
+    "sd_track_get_keyframe_flags": (_I, [_P, _I, _I, _P]),
+    "sd_track_create_keyframe_points": (_I, [_P, _I, _I, _F, _I, _I]),
+    "sd_track_get_created": (_I, [_P, _I, _I, _P, _P, _P, _P, _I]),
+    "sd_hamming": (_I, [_P, _P]),
+}
+
+# Header prototypes left without a row, with the reason: nothing in Python calls them.
+_UNBOUND = ("sd_track_set_local_view", "sd_track_match_local_view",      # the caller's own isInFrustum results: C++ facade only
+            "sd_track_debug_read")                                       # raw read of a tracker's device buffers: no caller in the tree
+
 _lib = None
 
 
 def lib():
-    """Load libsdslam_hip.so.  Fails loudly if it has not been built (no fallback)."""
+    """Load libsdslam_hip.so and declare every _SIGNATURES row on it.  Fails loudly if it is not built or lacks a row's name (no fallback)."""
     global _lib
     if _lib is None:
         p = lib_path()
@@ -41,44 +175,10 @@ def lib():
             raise SdError(-1, f"{p} is missing: build it with `python -m sdslam_amd.build` "
                               "(hipcc, gfx950). There is no CPU fallback.")
         L = C.CDLL(p)
-        L.sd_last_error.restype = C.c_char_p
-        L.sd_version.restype = C.c_char_p
-        L.sd_orb_stage_name.restype = C.c_char_p
-        L.sd_orb_create.argtypes = [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                    C.POINTER(C.c_void_p)]
-        L.sd_orb_destroy.argtypes = [C.c_void_p]
-        L.sd_orb_plan_info.argtypes = [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.sd_orb_extract_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t,
-                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.sd_orb_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                  C.c_size_t]
-        L.sd_orb_download.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.sd_orb_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                     C.c_int, C.c_void_p]
-        L.sd_orb_level_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.sd_orb_level_copy.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
-        L.sd_orb_debug_blurred.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
-        L.sd_orb_debug_cell_counts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        L.sd_orb_debug_level_keys.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        L.sd_orb_scale_tables.argtypes = [C.c_void_p] + [C.c_void_p] * 4
-        L.sd_orb_features_per_level.argtypes = [C.c_void_p, C.c_void_p]
-        L.sd_orb_set_stream.argtypes = [C.c_void_p, C.c_void_p]
-        L.sd_orb_sync.argtypes = [C.c_void_p]
-        L.sd_orb_set_profiling.argtypes = [C.c_void_p, C.c_int]
-        L.sd_orb_stage_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.sd_orb_stage_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.sd_orb_stage_name.argtypes = [C.c_int]
-        L.sd_orb_levels.argtypes = [C.c_void_p]
-        L.sd_dev_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
-        L.sd_dev_free.argtypes = [C.c_void_p]
-        L.sd_dev_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        L.sd_dev_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        L.sd_hamming.argtypes = [C.c_void_p, C.c_void_p]
-        L.sd_set_option.argtypes = [C.c_char_p, C.c_int]
-        L.sd_get_option.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
-        L.sd_option_name.restype = C.c_char_p
-        L.sd_option_name.argtypes = [C.c_int]
+        for name, (restype, argtypes) in _SIGNATURES.items():
+            fn = getattr(L, name)           # AttributeError "undefined symbol" for a name the library lacks
+            fn.restype = restype
+            fn.argtypes = argtypes
         _lib = L
     return _lib
 
@@ -154,7 +254,6 @@ def pinned_array(shape, dtype=np.uint8):
     n = int(np.prod(shape)) * np.dtype(dtype).itemsize
     L = lib()
     p = C.c_void_p()
-    L.sd_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
     _check(L.sd_host_alloc(n, C.byref(p)))
     buf = (C.c_uint8 * n).from_address(p.value)
     arr = np.frombuffer(buf, dtype=dtype).reshape(shape)
@@ -165,7 +264,6 @@ def pinned_array(shape, dtype=np.uint8):
 
         def __del__(self):
             try:
-                L.sd_host_free.argtypes = [C.c_void_p]
                 L.sd_host_free(self.ptr)
             except Exception:
                 pass
@@ -280,12 +378,10 @@ class ORBextractor:
 
     def set_distortion(self, fx, fy, cx, cy, k1, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
         """Frame::UndistortKeyPoints parameters (mK as CV_32F, mDistCoef); k1 == 0 disables."""
-        self.L.sd_orb_set_distortion.argtypes = [C.c_void_p] + [C.c_float] * 9
         _check(self.L.sd_orb_set_distortion(self.h, fx, fy, cx, cy, k1, k2, p1, p2, k3))
 
     def download_undistorted(self, frame0=0, n_frames=1):
         kps = np.zeros((n_frames, self.cap), KP_DTYPE)
-        self.L.sd_orb_download_undistorted.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         _check(self.L.sd_orb_download_undistorted(self.h, frame0, n_frames, _p(kps), self.cap))
         return kps
 
@@ -327,7 +423,6 @@ class ORBextractor:
 
     def stream_fence(self, stream_ptr, direction):
         """sd_orb_stream_fence: 0 = the caller's stream waits for the extractions queued so far, 1 = later extractions wait for it."""
-        self.L.sd_orb_stream_fence.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _check(self.L.sd_orb_stream_fence(self.h, C.c_void_p(stream_ptr), direction))
 
     def sync(self):
@@ -352,6 +447,16 @@ class ORBextractor:
         return b
 
 
+def _padded(items, shape, dtype, fill=0):
+    """Per-frame arrays of differing length -> (one [n, M, ...] array of `shape`, row i = items[i] then `fill`; the lengths, int32)."""
+    a, lens = np.full(shape, fill, dtype), np.zeros(shape[0], np.int32)
+    for i, v in enumerate(items):
+        v = np.asarray(v, dtype)
+        a[i, :len(v)] = v
+        lens[i] = len(v)
+    return a, lens
+
+
 def _cm(T):
     """4x4 (row-major math) -> 16 doubles column-major (Eigen::Matrix4d::data())."""
     return np.ascontiguousarray(np.asarray(T, np.float64).T).ravel()
@@ -370,25 +475,10 @@ class Tracker:
 
     def __init__(self, cur: ORBextractor, ref: ORBextractor, max_points=1000, max_batch=1, pnp_max_iterations=300):
         self.L = lib()
-        L = self.L
-        L.sd_track_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.sd_track_destroy.argtypes = [C.c_void_p]
-        L.sd_track_set_camera.argtypes = [C.c_void_p] + [C.c_float] * 9
-        L.sd_track_set_last.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
-        L.sd_track_set_poses.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.sd_track_set_rand.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
-        L.sd_track_align.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.sd_track_match.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int]
-        L.sd_track_pnp.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int]
-        L.sd_track_get_align.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
-        L.sd_track_get_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        L.sd_track_get_pnp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.sd_track_set_profiling.argtypes = [C.c_void_p, C.c_int]
-        L.sd_track_stage_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         self.cur, self.ref = cur, ref
         self.M, self.B, self.cap = max_points, max_batch, cur.cap
         self.h = C.c_void_p()
-        _check(L.sd_track_create(cur.h, ref.h, max_points, max_batch, pnp_max_iterations, C.byref(self.h)))
+        _check(self.L.sd_track_create(cur.h, ref.h, max_points, max_batch, pnp_max_iterations, C.byref(self.h)))
 
     def close(self):
         if self.h:
@@ -401,27 +491,25 @@ class Tracker:
         except Exception:
             pass
 
+    def _set_rows(self, fn, frame0, dtype, *rows, pitch=True):
+        """A row setter fn(h, frame0, n, rows..., [cap']): `rows` are [n, cap'] arrays of one shape, cap' is passed with `pitch`."""
+        a = [np.ascontiguousarray(r, dtype) for r in rows]
+        assert a[0].ndim == 2 and all(r.shape == a[0].shape for r in a)
+        _check(fn(self.h, frame0, a[0].shape[0], *[_p(r) for r in a], *([a[0].shape[1]] if pitch else [])))
+
     def set_camera(self, fx, fy, cx, cy, bf=0.0, bounds=(0.0, 640.0, 0.0, 480.0)):
         _check(self.L.sd_track_set_camera(self.h, fx, fy, cx, cy, bf, *[float(b) for b in bounds]))
 
     def set_last(self, frame0, cases):
         """cases: list of dict(valid, Xw, desc, octave, angle, obs) (one per frame)."""
         n, M = len(cases), self.M
-        n_last = np.zeros(n, np.int32)
-        valid = np.zeros((n, M), np.uint8)
-        Xw = np.zeros((n, M, 3), np.float64)
-        desc = np.zeros((n, M, 32), np.uint8)
-        octave = np.zeros((n, M), np.int32)
-        angle = np.zeros((n, M), np.float32)
-        obs = np.zeros((n, M), np.int32)
-        for i, c in enumerate(cases):
-            k = len(c["valid"])
-            assert k <= M
-            n_last[i] = k
-            valid[i, :k], Xw[i, :k], desc[i, :k] = c["valid"], c["Xw"], c["desc"]
-            octave[i, :k], angle[i, :k], obs[i, :k] = c["octave"], c["angle"], c["obs"]
-        _check(self.L.sd_track_set_last(self.h, frame0, n, _p(n_last), _p(valid), _p(Xw), _p(desc), _p(octave), _p(angle),
-                                        _p(obs)))
+        assert all(len(c["valid"]) <= M for c in cases)
+        cols = [_padded([c[k] for c in cases], (n, M) + tail, dt) for k, tail, dt in (
+            ("valid", (), np.uint8), ("Xw", (3,), np.float64), ("desc", (32,), np.uint8), ("octave", (), np.int32),
+            ("angle", (), np.float32), ("obs", (), np.int32))]
+        n_last = cols[0][1]
+        assert all((k == n_last).all() for _, k in cols)          # a frame's arrays have one length
+        _check(self.L.sd_track_set_last(self.h, frame0, n, _p(n_last), *[_p(a) for a, _ in cols]))
 
     def set_poses(self, frame0, T_ref_list, T_cur_list):
         n = len(T_ref_list)
@@ -430,19 +518,14 @@ class Tracker:
         _check(self.L.sd_track_set_poses(self.h, frame0, n, _p(a), _p(b)))
 
     def set_rand(self, frame0, rand_values):
-        r = np.ascontiguousarray(rand_values, np.int32)
-        assert r.ndim == 2
-        _check(self.L.sd_track_set_rand(self.h, frame0, r.shape[0], _p(r), r.shape[1]))
+        self._set_rows(self.L.sd_track_set_rand, frame0, np.int32, rand_values)
 
     def set_uright(self, frame0, uright):
-        u = np.ascontiguousarray(uright, np.float32)
-        self.L.sd_track_set_uright.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
-        _check(self.L.sd_track_set_uright(self.h, frame0, u.shape[0], _p(u), u.shape[1]))
+        self._set_rows(self.L.sd_track_set_uright, frame0, np.float32, uright)
 
     def stereo_from_depth(self, depth):
         """Frame::ComputeStereoFromRGBD for the current frames; depth: [n, H, W] float32."""
         d = np.ascontiguousarray(depth, np.float32)
-        self.L.sd_track_stereo_from_depth.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t]
         _check(self.L.sd_track_stereo_from_depth(self.h, d.shape[0], _p(d), d.shape[2], d.shape[1], d.shape[2], d.shape[1] * d.shape[2]))
 
     DEPTH_F32, DEPTH_U16 = 0, 1
@@ -454,42 +537,24 @@ class Tracker:
         stride = stride or W
         frame_stride = frame_stride or stride * H
         n = self.B if n_frames is None else n_frames
-        self.L.sd_track_stereo_from_depth_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t,
-                                                             C.c_float]
         _check(self.L.sd_track_stereo_from_depth_device(self.h, n, d_ptr, int(dtype), W, H, stride, frame_stride, float(depth_map_factor)))
 
     def get_stereo(self, frame0, n):
         u = np.zeros((n, self.cap), np.float32)
         d = np.zeros((n, self.cap), np.float32)
-        self.L.sd_track_get_stereo.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         _check(self.L.sd_track_get_stereo(self.h, frame0, n, _p(u), _p(d), self.cap))
         return u, d
 
     def set_local(self, frame0, pts_list, kp_claimed=None):
         """pts_list: per frame dict(cand, Xw, normal, min_dist, max_dist, mf_max_dist, desc, obs) (TrackLocalMap's points)."""
         n, M = len(pts_list), self.M
-        nl = np.array([len(p["cand"]) for p in pts_list], np.int32)
-
-        def pad(key, shape, dt):
-            a = np.zeros((n,) + shape, dt)
-            for i, p in enumerate(pts_list):
-                v = np.asarray(p[key], dt)
-                a[i, :len(v)] = v
-            return a
-        cand, Xw, nr = pad("cand", (M,), np.uint8), pad("Xw", (M, 3), np.float64), pad("normal", (M, 3), np.float64)
-        mn, mx, mf = pad("min_dist", (M,), np.float32), pad("max_dist", (M,), np.float32), pad("mf_max_dist", (M,), np.float32)
-        md, ob = pad("desc", (M, 32), np.uint8), pad("obs", (M,), np.int32)
-        kc = None
-        if kp_claimed is not None:
-            kc = np.zeros((n, self.cap), np.uint8)
-            for i, k in enumerate(kp_claimed):
-                kc[i, :len(k)] = k
-        self.L.sd_track_set_local.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10
-        _check(self.L.sd_track_set_local(self.h, frame0, n, _p(nl), _p(cand), _p(Xw), _p(nr), _p(mn), _p(mx), _p(mf), _p(md), _p(ob),
-                                         _p(kc) if kc is not None else None))
+        cols = [_padded([p[k] for p in pts_list], (n, M) + tail, dt) for k, tail, dt in (
+            ("cand", (), np.uint8), ("Xw", (3,), np.float64), ("normal", (3,), np.float64), ("min_dist", (), np.float32),
+            ("max_dist", (), np.float32), ("mf_max_dist", (), np.float32), ("desc", (32,), np.uint8), ("obs", (), np.int32))]
+        kc = None if kp_claimed is None else _padded(kp_claimed, (n, self.cap), np.uint8)[0]
+        _check(self.L.sd_track_set_local(self.h, frame0, n, _p(cols[0][1]), *[_p(a) for a, _ in cols], _p(kc)))
 
     def match_local(self, n_frames, th=1.0, nnratio=0.8, cos_limit=0.5):
-        self.L.sd_track_match_local.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]
         _check(self.L.sd_track_match_local(self.h, n_frames, float(th), float(nnratio), float(cos_limit)))
 
     def get_local(self, frame0, n):
@@ -500,19 +565,16 @@ class Tracker:
         pr = np.zeros((n, M, 3), np.float32)
         lv = np.zeros((n, M), np.int32)
         cs = np.zeros((n, M), np.float32)
-        self.L.sd_track_get_local.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
         _check(self.L.sd_track_get_local(self.h, frame0, n, _p(lm), self.cap, _p(nm), _p(iv), _p(pr), _p(lv), _p(cs)))
         return dict(match=lm, n=nm, in_view=iv.astype(bool), proj=pr, level=lv, cos=cs)
 
     def pose_opt(self, n_frames, source=0):
-        self.L.sd_track_pose_opt.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(self.L.sd_track_pose_opt(self.h, n_frames, int(source)))
 
     def get_pose_opt(self, frame0, n):
         T = np.zeros((n, 16))
         out = np.zeros((n, self.cap), np.uint8)
         info = np.zeros((n, 8), np.int32)
-        self.L.sd_track_get_pose_opt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _check(self.L.sd_track_get_pose_opt(self.h, frame0, n, _p(T), _p(out), self.cap, _p(info)))
         return dict(T=[_from_cm(t) for t in T], outlier=out.astype(bool), n_initial=info[:, 0], n_bad=info[:, 1], rounds=info[:, 2],
                     iterations=info[:, 3], lm_trials=info[:, 4], n_inliers=info[:, 5])
@@ -520,37 +582,31 @@ class Tracker:
     def track_with_motion_model(self, n_frames, th=15.0, mono=True, align_mode=0, min_matches=20, min_inliers=10):
         """Tracking::TrackWithMotionModel (src/Tracking.cc:654-718) for the batch; align_mode 1 = against the reference
         keyframe (TrackReferenceKeyFrame), -1 = align_image_ off."""
-        self.L.sd_track_with_motion_model.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int]
         _check(self.L.sd_track_with_motion_model(self.h, n_frames, int(align_mode), th, int(mono), min_matches, min_inliers))
 
     def get_tracked(self, frame0, n):
         info = np.zeros((n, 4), np.int32)
-        self.L.sd_track_get_tracked.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _check(self.L.sd_track_get_tracked(self.h, frame0, n, _p(info)))
         return dict(status=info[:, 0], nmatches=info[:, 1], nmatches_map=info[:, 2], retried=info[:, 3])
 
     def track_local_map(self, n_frames, th=1.0, nnratio=0.8, cos_limit=0.5, min_inliers=30):
         """Tracking::TrackLocalMap (src/Tracking.cc:720-751) on top of the frame-to-frame matches and the current pose."""
-        self.L.sd_track_local_map.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int]
         _check(self.L.sd_track_local_map(self.h, n_frames, th, nnratio, cos_limit, min_inliers))
 
     def get_local_map(self, frame0, n):
         mm = np.zeros((n, self.cap), np.int32)
         info = np.zeros((n, 4), np.int32)
-        self.L.sd_track_get_local_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         _check(self.L.sd_track_get_local_map(self.h, frame0, n, _p(mm), self.cap, _p(info)))
         return dict(match=mm, status=info[:, 0], n_points=info[:, 1], n_inliers=info[:, 2], n_local=info[:, 3])
 
     def set_current_broadcast(self, cur_frame):
         """One current frame against many keyframes (-1: slot f <-> current frame f)."""
-        self.L.sd_track_set_current_broadcast.argtypes = [C.c_void_p, C.c_int]
         _check(self.L.sd_track_set_current_broadcast(self.h, int(cur_frame)))
 
     def relocalize(self, n_keyframes, cur_frame=0, th=15.0, mono=True, min_matches=20, min_good=10):
         """Tracking::Relocalization (src/Tracking.cc:1064-1097), one batch slot per keyframe attempt."""
         win = C.c_int32(-1)
         st = np.zeros((n_keyframes, 3), np.int32)
-        self.L.sd_track_relocalize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _check(self.L.sd_track_relocalize(self.h, n_keyframes, cur_frame, th, int(mono), min_matches, min_good, C.byref(win), _p(st)))
         return int(win.value), st
 
@@ -561,8 +617,6 @@ class Tracker:
         n = C.c_int32(0)
         best = C.c_double(0)
         err = np.zeros(n_keyframes)
-        self.L.sd_track_detect_loop.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                                C.c_void_p]
         _check(self.L.sd_track_detect_loop(self.h, n_keyframes, cur_frame, None if ex is None else _p(ex), _p(cand), n_keyframes,
                                            C.byref(n), C.byref(best), _p(err)))
         return dict(candidates=cand[:n.value].copy(), best_error=best.value, errors=err)
@@ -581,15 +635,11 @@ class Tracker:
 
     def pnp_iterate(self, n_frames, n_iterations):
         """A further PnPsolver::iterate(n_iterations) on the solvers the last pnp() call constructed."""
-        self.L.sd_track_pnp_iterate.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(self.L.sd_track_pnp_iterate(self.h, n_frames, int(n_iterations)))
 
     def set_matches(self, frame0, cur_match):
         """CurrentFrame.mvpMapPoints of the slots from the caller: [n, cap'] indices into the last-frame arrays, -1 = NULL."""
-        m = np.ascontiguousarray(cur_match, np.int32)
-        assert m.ndim == 2
-        self.L.sd_track_set_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
-        _check(self.L.sd_track_set_matches(self.h, frame0, m.shape[0], _p(m), m.shape[1]))
+        self._set_rows(self.L.sd_track_set_matches, frame0, np.int32, cur_match)
 
     def get_align(self, frame0, n):
         T = np.zeros((n, 16))
@@ -616,48 +666,37 @@ class Tracker:
                     max_its=info[:, 6], refined=info[:, 7].astype(bool))
 
     def set_point_flags(self, frame0, has_mp_cur, has_mp_ref):
-        a, b = np.ascontiguousarray(has_mp_cur, np.uint8), np.ascontiguousarray(has_mp_ref, np.uint8)
-        assert a.ndim == 2 and a.shape == b.shape
-        self.L.sd_track_set_point_flags.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-        _check(self.L.sd_track_set_point_flags(self.h, frame0, a.shape[0], _p(a), _p(b), a.shape[1]))
+        self._set_rows(self.L.sd_track_set_point_flags, frame0, np.uint8, has_mp_cur, has_mp_ref)
 
     def search_by_points(self, n_frames, nnratio=0.75, check_ori=True):
         """ORBmatcher::SearchByPoints(currentKF, pKF, matches): brute-force Hamming between two keyframes' map points."""
-        self.L.sd_track_search_by_points.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int]
         _check(self.L.sd_track_search_by_points(self.h, n_frames, float(nnratio), int(check_ori)))
 
     def get_point_matches(self, frame0, n):
         m = np.zeros((n, self.cap), np.int32)
         nm = np.zeros(n, np.int32)
-        self.L.sd_track_get_point_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         _check(self.L.sd_track_get_point_matches(self.h, frame0, n, _p(m), self.cap, _p(nm)))
         return m, nm
 
     # --- ORBmatcher::SearchForTriangulation + LocalMapping::ComputeF12 on the SearchByPoints pairing (track_tri.hip) ---
     def set_uright_ref(self, frame0, uright):
         """mvuRight of the ref extractor's frames, [n, cap'] (-1: mono)."""
-        u = np.ascontiguousarray(uright, np.float32)
-        assert u.ndim == 2
-        self.L.sd_track_set_uright_ref.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
-        _check(self.L.sd_track_set_uright_ref(self.h, frame0, u.shape[0], _p(u), u.shape[1]))
+        self._set_rows(self.L.sd_track_set_uright_ref, frame0, np.float32, uright)
 
     def set_f12(self, frame0, F12):
         """The caller's own F12 per slot, [n, 3, 3], for search_for_triangulation(use_set_f12=True)."""
         F = np.ascontiguousarray(F12, np.float64).reshape(-1, 9)
-        self.L.sd_track_set_f12.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _check(self.L.sd_track_set_f12(self.h, frame0, F.shape[0], _p(F)))
 
     def search_for_triangulation(self, n_frames, use_set_f12=False, check_ori=False):
         """SearchForTriangulation(KF1 = cur slot, KF2 = ref slot, F12) with the flags of set_point_flags read as "holds a map
         point"; F12 = ComputeF12 of the slot's poses unless use_set_f12."""
-        self.L.sd_track_search_for_triangulation.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         _check(self.L.sd_track_search_for_triangulation(self.h, n_frames, int(use_set_f12), int(check_ori)))
 
     def get_triangulation_matches(self, frame0, n):
         m = np.zeros((n, self.cap), np.int32)
         nm = np.zeros(n, np.int32)
         F, e = np.zeros((n, 9)), np.zeros((n, 2), np.float32)
-        self.L.sd_track_get_triangulation_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
         _check(self.L.sd_track_get_triangulation_matches(self.h, frame0, n, _p(m), self.cap, _p(nm), _p(F), _p(e)))
         return dict(matches12=m, n_matches=nm, F12=F.reshape(n, 3, 3), epipole=e)
 
@@ -666,32 +705,25 @@ class Tracker:
         """GetWorldPos() of the two keyframes' map points, [n, cap', 3] each, by that keyframe's keypoint index."""
         a, b = np.ascontiguousarray(Xw_cur, np.float64), np.ascontiguousarray(Xw_ref, np.float64)
         assert a.ndim == 3 and a.shape == b.shape and a.shape[2] == 3
-        self.L.sd_track_set_sim3_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         _check(self.L.sd_track_set_sim3_points(self.h, frame0, a.shape[0], _p(a), _p(b), a.shape[1]))
 
     def set_point_matches(self, frame0, matches12):
         """vpMatched12 of the slots from the caller: [n, cap'] indices of pKF keypoints, -1 = NULL."""
-        m = np.ascontiguousarray(matches12, np.int32)
-        assert m.ndim == 2
-        self.L.sd_track_set_point_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
-        _check(self.L.sd_track_set_point_matches(self.h, frame0, m.shape[0], _p(m), m.shape[1]))
+        self._set_rows(self.L.sd_track_set_point_matches, frame0, np.int32, matches12)
 
     def sim3(self, n_frames, fix_scale=False, probability=0.99, min_inliers=20, max_iterations=300, n_iterations=None):
         """Sim3Solver ctor + SetRansacParameters + iterate(n_iterations) (None: find())."""
         n_iterations = max_iterations if n_iterations is None else n_iterations
-        self.L.sd_track_sim3.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int]
         _check(self.L.sd_track_sim3(self.h, n_frames, int(fix_scale), probability, min_inliers, max_iterations, n_iterations))
 
     def sim3_iterate(self, n_frames, n_iterations):
         """A further Sim3Solver::iterate(n_iterations) on the solvers the last sim3() call constructed."""
-        self.L.sd_track_sim3_iterate.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(self.L.sd_track_sim3_iterate(self.h, n_frames, int(n_iterations)))
 
     def get_sim3(self, frame0, n):
         T, R, t, s = np.zeros((n, 16)), np.zeros((n, 9)), np.zeros((n, 3)), np.zeros(n)
         inl = np.zeros((n, self.cap), np.uint8)
         info = np.zeros((n, 8), np.int32)
-        self.L.sd_track_get_sim3.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
         _check(self.L.sd_track_get_sim3(self.h, frame0, n, _p(T), _p(R), _p(t), _p(s), _p(inl), self.cap, _p(info)))
         return dict(T12=np.stack([_from_cm(x) for x in T]), R=R.reshape(n, 3, 3).transpose(0, 2, 1), t=t, scale=s,
                     inliers=inl.astype(bool), info=info, returned=info[:, 0].astype(bool), n_inliers=info[:, 1],
@@ -702,44 +734,34 @@ class Tracker:
         idx = np.zeros(self.cap, np.int32)
         n = C.c_int32(0)
         grid = np.zeros((64, 48), np.int32) if want_grid else None
-        self.L.sd_track_debug_features_in_area.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
-                                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _check(self.L.sd_track_debug_features_in_area(self.h, frame, x, y, r, min_level, max_level, _p(idx), self.cap, C.byref(n),
                                                       _p(grid) if want_grid else None))
         return (idx[:n.value].copy(), grid) if want_grid else idx[:n.value].copy()
 
     def pack_records(self, n_frames, source, d_ptr):
         """Queue the packing of the batch's result records (n_frames x 20 f64) into device memory at `d_ptr`."""
-        self.L.sd_track_pack_records.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _check(self.L.sd_track_pack_records(self.h, n_frames, int(source), C.c_void_p(d_ptr)))
 
     def stream_fence(self, stream_ptr, direction):
         """direction 0: the caller's stream waits for the tracking stream; 1: the tracking stream waits for the caller's."""
-        self.L.sd_track_stream_fence.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _check(self.L.sd_track_stream_fence(self.h, C.c_void_p(stream_ptr) if stream_ptr else None, int(direction)))
 
     # --- sequential tracking: the last-frame hand-off on the device (src/Tracking.cc:250-292) ---
     def set_map_ids(self, frame0, ids_list, which=0):
         """The caller's identity of each map point, one array per slot (-1 = none); which 0: last-frame points, 1: local map."""
         n, M = len(ids_list), self.M
-        ids = np.full((n, M), -1, np.int32)
-        for i, v in enumerate(ids_list):
-            v = np.asarray(v, np.int32)
-            assert len(v) <= M
-            ids[i, :len(v)] = v
-        self.L.sd_track_set_map_ids.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        assert all(len(v) <= M for v in ids_list)
+        ids, _ = _padded(ids_list, (n, M), np.int32, fill=-1)
         _check(self.L.sd_track_set_map_ids(self.h, frame0, n, int(which), _p(ids), M))
 
     def advance(self, n_frames, source=1):
         """mLastFrame = Frame(mCurrentFrame) for every slot on the device; source 0: after track_with_motion_model, 1: after
         track_local_map, 2: after stereo_init.  The extractors swap roles: extract the next frame into `self.cur`."""
-        self.L.sd_track_advance.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(self.L.sd_track_advance(self.h, n_frames, int(source)))
         self._follow_extractors()
 
     def _follow_extractors(self):
         cur, ref = C.c_void_p(), C.c_void_p()
-        self.L.sd_track_get_extractors.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         _check(self.L.sd_track_get_extractors(self.h, C.byref(cur), C.byref(ref)))
         if cur.value != self.cur.h.value:
             self.cur, self.ref = self.ref, self.cur
@@ -748,30 +770,25 @@ class Tracker:
     def set_prior(self, frame0, T_list, relative=False):
         """Tprior = Tcur = T (relative False) or T @ Tref computed on the device (ConstantVelocity::GetPose); Tref stays."""
         a = np.ascontiguousarray(np.stack([_cm(T) for T in T_list]))
-        self.L.sd_track_set_prior.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         _check(self.L.sd_track_set_prior(self.h, frame0, len(T_list), _p(a), int(bool(relative))))
 
     # --- motion model on the device: EKF + ConstantVelocity per slot (src/sensors/EKF.cc, ConstantVelocity.cc) ---
     def motion_predict(self, n_frames, dt):
         """Queue EKF::Predict for slots < n_frames: Tprior = Tcur = Exp(X) @ Tref; dt is the time since the last update."""
-        self.L.sd_track_motion_predict.argtypes = [C.c_void_p, C.c_int, C.c_double]
         _check(self.L.sd_track_motion_predict(self.h, n_frames, float(dt)))
 
     def motion_update(self, n_frames, source=1):
         """Queue EKF::Update with the frames' final poses for the slots the call named by `source` tracked (0
         track_with_motion_model, 1 track_local_map, -1 every slot), EKF::Restart for the others.  Before advance()."""
-        self.L.sd_track_motion_update.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(self.L.sd_track_motion_update(self.h, n_frames, int(source)))
 
     def motion_restart(self, frame0, n_frames):
-        self.L.sd_track_motion_restart.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(self.L.sd_track_motion_restart(self.h, frame0, n_frames))
 
     def get_motion(self, frame0, n):
         """dict(X [n][6], P [n][6] diagonal, started [n], it_time [n], E and last_pose as n 4x4 matrices); synchronises."""
         X, P, st, it = np.zeros((n, 6)), np.zeros((n, 6)), np.zeros(n, np.int32), np.zeros(n)
         E, Lp = np.zeros((n, 16)), np.zeros((n, 16))
-        self.L.sd_track_get_motion.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
         _check(self.L.sd_track_get_motion(self.h, frame0, n, _p(X), _p(P), _p(st), _p(it), _p(E), _p(Lp)))
         return dict(X=X, P=P, started=st, it_time=it, E=[_from_cm(e) for e in E], last_pose=[_from_cm(t) for t in Lp])
 
@@ -781,7 +798,6 @@ class Tracker:
                                                                               (it_time, np.float64))]
         n = {len(v) for v in a if v is not None}
         assert len(n) == 1
-        self.L.sd_track_set_motion.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
         _check(self.L.sd_track_set_motion(self.h, frame0, n.pop(), *[None if v is None else _p(v) for v in a]))
 
     # --- IMU sensor model: the 16-state EKF of Monocular-IMU tracking (src/sensors/IMU.cc), chosen per tracker ---
@@ -789,19 +805,16 @@ class Tracker:
 
     def set_sensor_model(self, model):
         """The filter motion_predict / motion_update / motion_restart run; every slot's filter of that model restarts."""
-        self.L.sd_track_set_sensor_model.argtypes = [C.c_void_p, C.c_int]
         _check(self.L.sd_track_set_sensor_model(self.h, int(model)))
 
     def get_sensor_model(self):
         m = C.c_int(-1)
-        self.L.sd_track_get_sensor_model.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         _check(self.L.sd_track_get_sensor_model(self.h, C.byref(m)))
         return m.value
 
     def set_measurements(self, frame0, wa):
         """Tracking::SetMeasurements for slots frame0 ..: [n][6] (gyro xyz, accelerometer xyz); queued, persists until replaced."""
         a = np.ascontiguousarray(wa, np.float64).reshape(-1, 6)
-        self.L.sd_track_set_measurements.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _check(self.L.sd_track_set_measurements(self.h, frame0, len(a), _p(a)))
 
     def get_imu(self, frame0, n):
@@ -809,7 +822,6 @@ class Tracker:
         [n][6]); synchronises."""
         X, P, g, st, it = np.zeros((n, 16)), np.zeros((n, 16, 16)), np.zeros((n, 3)), np.zeros(n, np.int32), np.zeros(n)
         Lp, me = np.zeros((n, 16)), np.zeros((n, 6))
-        self.L.sd_track_get_imu.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
         _check(self.L.sd_track_get_imu(self.h, frame0, n, _p(X), _p(P), _p(g), _p(st), _p(it), _p(Lp), _p(me)))
         return dict(X=X, P=P, gravity=g, started=st, it_time=it, last_pose=[_from_cm(t) for t in Lp], measurements=me)
 
@@ -819,7 +831,6 @@ class Tracker:
                                                                               (started, np.int32), (it_time, np.float64))]
         n = {len(v) for v in a if v is not None}
         assert len(n) == 1
-        self.L.sd_track_set_imu.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
         _check(self.L.sd_track_set_imu(self.h, frame0, n.pop(), *[None if v is None else _p(v) for v in a]))
 
     def get_last(self, frame0, n):
@@ -828,7 +839,6 @@ class Tracker:
         out = dict(n_last=np.zeros(n, np.int32), valid=np.zeros((n, M), np.uint8), Xw=np.zeros((n, M, 3)), desc=np.zeros((n, M, 32), np.uint8),
                    octave=np.zeros((n, M), np.int32), angle=np.zeros((n, M), np.float32), obs=np.zeros((n, M), np.int32),
                    ids=np.zeros((n, M), np.int32))
-        self.L.sd_track_get_last.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
         _check(self.L.sd_track_get_last(self.h, frame0, n, *[_p(out[k]) for k in ("n_last", "valid", "Xw", "desc", "octave", "angle", "obs",
                                                                                  "ids")]))
         return out
@@ -836,13 +846,11 @@ class Tracker:
     def close_points(self, n_frames, source, th_depth):
         """Queue Tracking::NeedNewKeyFrame's RGB-D counts (src/Tracking.cc:776-789) for slots < n_frames: keypoints with
         0 < mvDepth < th_depth (mThDepth = mbf * ThDepth / fx) whose map point advance(source) would keep, and the others."""
-        self.L.sd_track_close_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float]
         _check(self.L.sd_track_close_points(self.h, n_frames, int(source), float(th_depth)))
 
     def get_close_points(self, frame0, n):
         """dict(tracked=nTrackedClose, non_tracked=nNonTrackedClose), one entry per slot."""
         out = np.zeros((n, 2), np.int32)
-        self.L.sd_track_get_close_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _check(self.L.sd_track_get_close_points(self.h, frame0, n, _p(out)))
         return dict(tracked=out[:, 0].copy(), non_tracked=out[:, 1].copy())
 
@@ -852,40 +860,32 @@ class Tracker:
     def set_next_map_id(self, frame0, next_ids):
         """MapPoint::nNextId of every slot's map: the id the next created point receives."""
         a = np.ascontiguousarray(next_ids, np.int32)
-        self.L.sd_track_set_next_map_id.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _check(self.L.sd_track_set_next_map_id(self.h, frame0, len(a), _p(a)))
 
     def stereo_init(self, n_frames, min_keypoints=500):
         """Queue Tracking::StereoInitialization for slots < n_frames: identity pose, one map point per keypoint with depth."""
-        self.L.sd_track_stereo_init.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(self.L.sd_track_stereo_init(self.h, n_frames, int(min_keypoints)))
 
     def set_keyframe_state(self, frame0, state8):
         """NeedNewKeyFrame's caller state, [n][8] int32: nKFs, nRefMatches, last_kf_id, last_reloc_id, flags, 3 reserved."""
-        a = np.ascontiguousarray(state8, np.int32)
-        assert a.ndim == 2 and a.shape[1] == 8
-        self.L.sd_track_set_keyframe_state.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        _check(self.L.sd_track_set_keyframe_state(self.h, frame0, a.shape[0], _p(a)))
+        assert np.shape(state8)[1:] == (8,)
+        self._set_rows(self.L.sd_track_set_keyframe_state, frame0, np.int32, state8, pitch=False)
 
     def need_keyframe(self, n_frames, rgbd, frame_id, min_frames, max_frames):
         """Queue Tracking::NeedNewKeyFrame for slots < n_frames; the result is the slots' keyframe flags."""
-        self.L.sd_track_need_keyframe.argtypes = [C.c_void_p] + [C.c_int] * 5
         _check(self.L.sd_track_need_keyframe(self.h, n_frames, int(bool(rgbd)), int(frame_id), int(min_frames), int(max_frames)))
 
     def set_keyframe_flags(self, frame0, flags):
         a = np.ascontiguousarray(flags, np.uint8)
-        self.L.sd_track_set_keyframe_flags.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _check(self.L.sd_track_set_keyframe_flags(self.h, frame0, len(a), _p(a)))
 
     def get_keyframe_flags(self, frame0, n):
         out = np.zeros(n, np.uint8)
-        self.L.sd_track_get_keyframe_flags.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _check(self.L.sd_track_get_keyframe_flags(self.h, frame0, n, _p(out)))
         return out
 
     def create_keyframe_points(self, n_frames, source, th_depth, use_flags=False, frame_id=0):
         """Queue the RGB-D part of Tracking::CreateNewKeyFrame for slots < n_frames (use_flags: only where flag bit 0 is set)."""
-        self.L.sd_track_create_keyframe_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int]
         _check(self.L.sd_track_create_keyframe_points(self.h, n_frames, int(source), float(th_depth), int(bool(use_flags)), int(frame_id)))
 
     def get_created(self, frame0, n, cap=None):
@@ -894,7 +894,6 @@ class Tracker:
         cap = self.cap if cap is None else cap
         info = np.zeros((n, 4), np.int32)
         idx, ids, Xw = np.full((n, cap), -1, np.int32), np.full((n, cap), -1, np.int32), np.zeros((n, cap, 3))
-        self.L.sd_track_get_created.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int]
         _check(self.L.sd_track_get_created(self.h, frame0, n, _p(info), _p(idx), _p(Xw), _p(ids), cap))
         return dict(mode=info[:, 0].copy(), created=info[:, 1].copy(), P=info[:, 2].copy(), candidates=info[:, 3].copy(), kp_index=idx,
                     Xw=Xw, ids=ids)
@@ -911,7 +910,6 @@ class Tracker:
 def debug_epnp(Xw, uv, K):
     """Device EPnP on explicit correspondences (diagnostics)."""
     L = lib()
-    L.sd_debug_epnp.argtypes = [C.c_int, C.c_void_p, C.c_void_p] + [C.c_double] * 4 + [C.c_void_p] * 3
     Xw = np.ascontiguousarray(Xw, np.float64)
     uv = np.ascontiguousarray(uv, np.float64)
     R, t, e = np.zeros(9), np.zeros(3), C.c_double()
@@ -924,7 +922,6 @@ def debug_search_for_triangulation(kps1, desc1, has_mp1, uright1, kps2, desc2, h
                                    level_sigma2, check_ori=False):
     """One keyframe pair from host arrays through k_search_triangulation (diagnostics): (nmatches, matches12[n1])."""
     L = lib()
-    L.sd_debug_search_for_triangulation.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     k1, k2 = np.ascontiguousarray(kps1, KP_DTYPE), np.ascontiguousarray(kps2, KP_DTYPE)
     n1, n2 = len(k1), len(k2)
     d1, d2 = np.ascontiguousarray(desc1, np.uint8).reshape(n1, 32), np.ascontiguousarray(desc2, np.uint8).reshape(n2, 32)

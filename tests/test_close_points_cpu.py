@@ -31,13 +31,9 @@ def test_close_points_declared_exported_and_bound(sd):
 
 def test_close_points_refuse_a_null_handle(sd):
     L = sd.lib()
-    L.sd_track_close_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float]
-    L.sd_track_get_close_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     out = (C.c_int32 * 2)(-5, -5)
     assert L.sd_track_close_points(None, 1, 1, 1.0) == 1
     assert L.sd_track_get_close_points(None, 0, 1, out) == 1
     assert list(out) == [-5, -5]
-    L.sd_track_stereo_from_depth_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t,
-                                                    C.c_float]
     assert L.sd_track_stereo_from_depth_device(None, 1, 4096, 1, 640, 480, 640, 640 * 480, 5000.0) == 1
     assert b"handle is NULL" in L.sd_last_error()

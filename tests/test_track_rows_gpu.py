@@ -1,7 +1,6 @@
 """GPU: what sd_track_create leaves in the per-slot buffers, and the row copies between a caller's pitch `cap` and the
 device's pitch (the keypoint capacity K) in every getter and setter that takes a `cap`.  No extraction: none of these calls
 needs frames."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -23,17 +22,6 @@ def rows():
     ref = sd.ORBextractor(100, 1.2, 8, 20, 64, 48, B)
     trk = sd.Tracker(cur, ref, max_points=M, max_batch=B, pnp_max_iterations=4)
     L = capi.lib()
-    P, I = C.c_void_p, C.c_int
-    L.sd_track_get_matches.argtypes = [P, I, I, P, I, P]
-    L.sd_track_get_local.argtypes = [P, I, I, P, I] + [P] * 5
-    L.sd_track_get_local_map.argtypes = [P, I, I, P, I, P]
-    L.sd_track_get_point_matches.argtypes = [P, I, I, P, I, P]
-    L.sd_track_get_pose_opt.argtypes = [P, I, I, P, P, I, P]
-    L.sd_track_get_pnp.argtypes = [P, I, I, P, P, I, P]
-    L.sd_track_get_stereo.argtypes = [P, I, I, P, P, I]
-    L.sd_track_get_align.argtypes = [P, I, I] + [P] * 5
-    L.sd_track_set_matches.argtypes = [P, I, I, P, I]
-    L.sd_track_set_uright.argtypes = [P, I, I, P, I]
     yield dict(trk=trk, L=L, K=trk.cap)
     trk.close()
     cur.close()

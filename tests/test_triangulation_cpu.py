@@ -2,7 +2,6 @@
 out by hand, the proof that every case of tests/triangulation_cases.py reaches the gate it claims (the reference's own
 per-gate rejection counts) and keeps a match, the seeds of the extraction test of tests/test_triangulation_gpu.py (the oracle's
 keypoints are the device's), the new entry points' link / NULL-handle behaviour and the C++ facade."""
-import ctypes as C
 import os
 import re
 import subprocess
@@ -177,15 +176,10 @@ def test_library_exports_the_new_entry_points(sd):
     for name in NEW_CALLS:
         assert getattr(L, name) is not None
         assert re.search(r"\bint %s\(" % name, hdr), name
-    L.sd_track_search_for_triangulation.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     assert L.sd_track_search_for_triangulation(None, 1, 0, 0) == 1
-    L.sd_track_set_f12.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     assert L.sd_track_set_f12(None, 0, 1, None) == 1
-    L.sd_track_set_uright_ref.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     assert L.sd_track_set_uright_ref(None, 0, 1, None, 1) == 1
-    L.sd_track_get_triangulation_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
     assert L.sd_track_get_triangulation_matches(None, 0, 1, None, 0, None, None, None) == 1
-    L.sd_debug_search_for_triangulation.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     assert L.sd_debug_search_for_triangulation(4096, 1, *([None] * 12), 8, 0, None, None) == 3
     assert L.sd_debug_search_for_triangulation(1, 1, *([None] * 12), 8, 0, None, None) == 1
 
