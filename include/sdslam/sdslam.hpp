@@ -9,12 +9,13 @@
 //
 //   ORBextractor   reference src/ORBextractor.h:38-70
 //   ORBmatcher     reference src/ORBmatcher.h:40-65  (DescriptorDistance, SearchByProjection(Frame,Frame), SearchByPoints,
-//                                                      SearchForTriangulation)
+//                                                      SearchForTriangulation, Fuse)
 //   ImageAlign     reference src/ImageAlign.h:32-44  (ComputePose, GetError)
 //   PnPsolver      reference src/PnPsolver.h:67-76   (SetRansacParameters, iterate)
 // ImageAlign / ORBmatcher / PnPsolver operate on a TrackBatch (frames resident on the GPU).
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -288,6 +289,7 @@ class TrackBatch {
     return c == cur_->handle() ? *cur_ : *ref_;
   }
   sd_track* handle() { return h_; }
+  int max_points() const { return max_points_; }
 
  private:
   sd_track* h_ = nullptr;
@@ -416,6 +418,126 @@ class ORBmatcher {
     const auto T1 = pKF1->GetPose();
     const auto T2 = pKF2->GetPose();
     batch.SetPoses(slot, T2.data(), T1.data());
+  }
+
+  // int Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th = 3.0)     src/ORBmatcher.cc:477-615
+  // Frame i of the batch's ref extractor holds vpTargetKFs[i]'s image (i = 0 for the single-keyframe overloads).  The device
+  // searches (sd_track_fuse), the caller's objects are fused here.  KeyFrameT needs N, mvuRight, GetPose(), GetMapPoint(idx),
+  // AddMapPoint(pMP, idx) (and GetMapPoints() for the Sim3 overload); MapPointT needs isBad(), IsInKeyFrame(pKF), Observations(),
+  // Replace(pMP), AddObservation(pKF, idx), GetWorldPos() / GetNormal() indexable as v(i), GetMinDistanceInvariance(),
+  // GetMaxDistanceInvariance(), GetMaxDistance() (= mfMaxDistance, which PredictScale reads) and GetDescriptor() -> 32 bytes.
+  template <class KeyFrameT, class MapPointT>
+  int Fuse(TrackBatch& batch, KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, float th = 3.0f) {
+    std::vector<int> nFused;
+    Fuse(batch, std::vector<KeyFrameT*>(1, pKF), vpMapPoints, th, nFused);
+    return nFused[0];
+  }
+  // The first loop of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:456-461) in one device call: vpMapPoints against every
+  // target keyframe (shared point row, kf_side 1), then the keyframes in order and, inside each, the points in order.
+  template <class KeyFrameT, class MapPointT>
+  void Fuse(TrackBatch& batch, const std::vector<KeyFrameT*>& vpTargetKFs, const std::vector<MapPointT*>& vpMapPoints, float th,
+            std::vector<int>& nFused) {
+    const int n = (int)vpTargetKFs.size(), M = batch.max_points();
+    nFused.assign(n, 0);
+    if (n == 0) return;
+    for (int k = 0; k < n; k++) {
+      KeyFrameT* pKF = vpTargetKFs[k];
+      UploadFusePoints(batch, k, vpMapPoints, k == 0, [&](MapPointT* pMP) { return pMP->IsInKeyFrame(pKF); });
+      UploadFuseKeyFrame(batch, k, pKF);
+    }
+    check(sd_track_fuse(batch.handle(), n, 1, 0, th, 0));
+    std::vector<int32_t> best((size_t)n * M);
+    check(sd_track_get_fuse(batch.handle(), 0, n, best.data(), nullptr, M, nullptr));
+    // Equal to the sequential loop: best_idx depends on nothing the walk changes, and for a point that is not bad isBad() and
+    // IsInKeyFrame() only ever go from false to true during the walk, so the uploaded cand is a superset of the live test.
+    for (int k = 0; k < n; k++) {
+      KeyFrameT* pKF = vpTargetKFs[k];
+      for (size_t i = 0; i < vpMapPoints.size() && i < (size_t)M; i++) {
+        MapPointT* pMP = vpMapPoints[i];
+        if (!pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
+        const int bestIdx = best[(size_t)k * M + i];
+        if (bestIdx < 0) continue;
+        MapPointT* pMPinKF = pKF->GetMapPoint(bestIdx);   // :597-611
+        if (pMPinKF) {
+          if (!pMPinKF->isBad()) {
+            if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
+            else pMPinKF->Replace(pMP);
+          }
+        } else {
+          pMP->AddObservation(pKF, bestIdx);
+          pKF->AddMapPoint(pMP, bestIdx);
+        }
+        nFused[k]++;
+      }
+    }
+  }
+  // int Fuse(KeyFrame* pKF, const Eigen::Matrix4d& Scw, const vector<MapPoint*>& vpPoints, float th, vector<MapPoint*>& vpReplacePoint)
+  //                                                                     src/ORBmatcher.cc:617-732, LoopClosing::SearchAndFuse
+  // Scw is anything indexable as Scw(r, c); vpReplacePoint has vpPoints.size() entries, as in the reference.
+  template <class KeyFrameT, class Matrix4T, class MapPointT>
+  int Fuse(TrackBatch& batch, KeyFrameT* pKF, const Matrix4T& Scw, const std::vector<MapPointT*>& vpPoints, float th,
+           std::vector<MapPointT*>& vpReplacePoint) {
+    const int M = batch.max_points();
+    const auto spAlreadyFound = pKF->GetMapPoints();
+    UploadFusePoints(batch, 0, vpPoints, true, [&](MapPointT* pMP) { return spAlreadyFound.count(pMP) != 0; });
+    UploadFuseKeyFrame(batch, 0, pKF);
+    double S[16];
+    for (int r = 0; r < 4; r++)
+      for (int c = 0; c < 4; c++) S[c * 4 + r] = Scw(r, c);
+    check(sd_track_set_fuse_scw(batch.handle(), 0, 1, S));
+    check(sd_track_fuse(batch.handle(), 1, 1, -1, th, 1));
+    std::vector<int32_t> best(M);
+    check(sd_track_get_fuse(batch.handle(), 0, 1, best.data(), nullptr, M, nullptr));
+    int nFused = 0;
+    for (size_t i = 0; i < vpPoints.size() && i < (size_t)M; i++) {   // :718-728; nothing here makes a point bad or adds to the set
+      MapPointT* pMP = vpPoints[i];
+      if (!pMP || pMP->isBad() || spAlreadyFound.count(pMP) || best[i] < 0) continue;
+      MapPointT* pMPinKF = pKF->GetMapPoint(best[i]);
+      if (pMPinKF) {
+        if (!pMPinKF->isBad()) vpReplacePoint[i] = pMPinKF;
+      } else {
+        pMP->AddObservation(pKF, best[i]);
+        pKF->AddMapPoint(pMP, best[i]);
+      }
+      nFused++;
+    }
+    return nFused;
+  }
+  // Point row `slot` of a Fuse call: cand = pMP && !isBad() && !in_kf(pMP); the other fields only where `full` (the shared row).
+  template <class MapPointT, class InKF>
+  void UploadFusePoints(TrackBatch& batch, int slot, const std::vector<MapPointT*>& pts, bool full, InKF in_kf) {
+    const size_t M = batch.max_points();
+    if (pts.size() > M) throw Error(SD_ERR_CAPACITY, "Fuse: more points than the batch's max_points (split the list)");
+    const int32_t n = (int32_t)pts.size();
+    std::vector<uint8_t> cand(M, 0), desc(M * 32, 0);
+    std::vector<double> Xw(M * 3, 0.0), normal(M * 3, 0.0);
+    std::vector<float> dmin(M, 0.f), dmax(M, 0.f), mfmax(M, 0.f);
+    std::vector<int32_t> obs(M, 0);
+    for (size_t i = 0; i < pts.size(); i++) {
+      MapPointT* p = pts[i];
+      if (!p) continue;
+      cand[i] = !p->isBad() && !in_kf(p);
+      if (!full) continue;
+      const auto X = p->GetWorldPos();
+      const auto Nn = p->GetNormal();
+      for (int k = 0; k < 3; k++) {
+        Xw[i * 3 + k] = X(k);
+        normal[i * 3 + k] = Nn(k);
+      }
+      dmin[i] = p->GetMinDistanceInvariance();
+      dmax[i] = p->GetMaxDistanceInvariance();
+      mfmax[i] = p->GetMaxDistance();
+      std::memcpy(&desc[i * 32], p->GetDescriptor(), 32);
+    }
+    check(sd_track_set_local(batch.handle(), slot, 1, &n, cand.data(), Xw.data(), normal.data(), dmin.data(), dmax.data(), mfmax.data(),
+                             desc.data(), obs.data(), nullptr));
+  }
+  // Keyframe of slot `slot` (frame `slot` of the ref extractor): mvuRight and the pose, as Tref
+  template <class KeyFrameT>
+  void UploadFuseKeyFrame(TrackBatch& batch, int slot, KeyFrameT* pKF) {
+    if (pKF->N > 0) check(sd_track_set_uright_ref(batch.handle(), slot, 1, pKF->mvuRight.data(), pKF->N));
+    const auto T = pKF->GetPose();
+    batch.SetPoses(slot, T.data(), T.data());
   }
 
  protected:

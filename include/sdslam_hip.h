@@ -386,6 +386,54 @@ int sd_debug_search_for_triangulation(int n1, int n2, const sd_keypoint* kps1, c
                                       const float* uright2, const double* F12_rm9, const float* epipole2, const float* scale_factors,
                                       const float* level_sigma2, int nlevels, int check_ori, int32_t* matches12, int32_t* n_matches);
 
+/* ORBmatcher::Fuse, both overloads: the search (src/ORBmatcher.cc:493-594 with a keyframe pose, :639-715 with a Sim3 Scw;
+ *   KeyFrame::GetFeaturesInArea / IsInImage src/KeyFrame.cc:529-570; MapPoint::PredictScale src/MapPoint.cc:355-369; callers
+ *   LocalMapping::SearchInNeighbors src/LocalMapping.cc:422-492 and LoopClosing::SearchAndFuse src/LoopClosing.cc:535-560)
+ * for the whole batch: slot f projects a list of map points into one keyframe and returns, per point i, best_idx[i] = the keypoint
+ * the reference reaches :597 / :718 with (bestDist <= TH_LOW = 50), else -1, and best_dist[i] = bestDist (256: no candidate).
+ * The search reads nothing the reference's fusing changes (no observations, no mvpMapPoints), so all keyframes of a
+ * SearchInNeighbors or SearchAndFuse go in one call; Replace / AddObservation / AddMapPoint stay with the caller, who walks the
+ * results in the reference's order (ORBmatcher::Fuse of include/sdslam/sdslam.hpp does).
+ * Points: the local-map buffers of sd_track_set_local, same fields and layout (obs and kp_claimed are not read); here
+ *   cand[f][i] = pMP != NULL && !isBad() && !IsInKeyFrame(KF of slot f) at upload time.  sd_track_set_local is shared with
+ *   TrackLocalMap's search: like relocalisation and loop detection, Fuse is meant for a tracker handle of its own.
+ * kf_side 0: KF = the slot's cur frame (or the broadcast frame), pose Tcur of the slot, mvuRight row sd_track_set_uright.  Under
+ *   sd_track_set_current_broadcast this is the second Fuse of SearchInNeighbors (all candidates against the current keyframe),
+ *   split over as many slots as the list needs.
+ * kf_side 1: KF = frame f of the ref extractor, pose Tref, mvuRight row sd_track_set_uright_ref: over n target keyframes the
+ *   first loop of SearchInNeighbors.
+ * point_row -1: slot f reads point row f.  r >= 0: every slot reads n_local, Xw, normal, the distances and desc of row r and only
+ *   cand of its own row -- one upload of the current keyframe's points for all neighbours.
+ * sim3 0: the keyframe-pose overload, with its chi-square gate (7.8 for keypoints with mvuRight >= 0, 5.99 otherwise).
+ * sim3 1: the Scw overload: the slot's Scw (sd_track_set_fuse_scw, 16 doubles column-major, queued on the tracking stream) is
+ *   decomposed on the device as :625-629 does (operation order: sdslam_amd/csrc/track_fuse.hip); no chi-square gate.
+ * th: the search radius factor (3.0 in SearchInNeighbors, 4 in SearchAndFuse).  Keypoints are the undistorted ones; K, the image
+ *   bounds, mvScaleFactors and mvInvLevelSigma2 are the tracker's and the extractor's own (sd_track_create requires both extractors
+ *   to share nlevels and scaleFactor, so PredictScale is the same on either side).
+ * sd_track_fuse is queued on the tracking stream: no host wait, no allocation.  The result lives in buffers of its own: the results
+ *   of sd_track_match_local, sd_track_search_by_points and sd_track_search_for_triangulation are untouched.
+ * sd_track_get_fuse (synchronises; NULL outputs are skipped): best_idx / best_dist [n_frames][cap], cap >= max_points, entries
+ *   beyond n_local read -1 / 256; n_found[f] = points with best_idx >= 0 (= nFused when the walk skips none).  A result ends with
+ *   a new extraction on the side in use, sd_track_set_local / _set_local_view / _set_poses / _set_uright / _set_uright_ref /
+ *   _set_fuse_scw / _set_camera or another broadcast setting: the getter then fails with SD_ERR_INVALID_ARG until the search
+ *   has run again.
+ * Errors: SD_ERR_INVALID_ARG for a NULL handle, th <= 0 or not finite, point_row outside [-1, max_batch), kf_side / sim3 outside
+ *   {0, 1}, sim3 = 1 on a slot sd_track_set_fuse_scw has not covered, a missing extraction or camera; SD_ERR_CAPACITY for
+ *   n_frames > max_batch.
+ * sd_debug_fuse: one keyframe and one point list from host arrays through the same kernel, synchronous, with buffers of its own
+ *   (no extractor, no tracker).  n_kp <= kp_cap <= 2048 keypoints, n_pts <= max_points <= 2048 points (the capacities shape the
+ *   launch as a tracker's would); T_cm16 = Tcw or Scw, column-major; cam9 = fx, fy, cx, cy, bf, mnMinX, mnMaxX, mnMinY, mnMaxY;
+ *   tables of nlevels entries, scale_factor = mfScaleFactor (for PredictScale).  best_idx / best_dist have max_points entries;
+ *   pose15 (may be NULL) = Rcw row-major | tcw | Ow as projected with (also sd_track_debug_read, which = 2, bytes <= 120). */
+int sd_track_set_fuse_scw(sd_track* h, int frame0, int n_frames, const double* Scw_cm16);
+int sd_track_fuse(sd_track* h, int n_frames, int kf_side, int point_row, float th, int sim3);
+int sd_track_get_fuse(sd_track* h, int frame0, int n_frames, int32_t* best_idx, int32_t* best_dist, int cap, int32_t* n_found);
+int sd_debug_fuse(int n_kp, const sd_keypoint* kps, const uint8_t* desc, const float* uright, int n_pts, const uint8_t* cand,
+                  const double* Xw, const double* normal, const float* min_dist, const float* max_dist, const float* mf_max_dist,
+                  const uint8_t* pt_desc, const double* T_cm16, int sim3, const float* cam9, const float* scale_factors,
+                  const float* inv_level_sigma2, int nlevels, float scale_factor, float th, int kp_cap, int max_points,
+                  int32_t* best_idx, int32_t* best_dist, int32_t* n_found, double* pose15);
+
 int sd_track_align(sd_track* h, int n_frames, int mode);
 int sd_track_match(sd_track* h, int n_frames, float th, int mono, int check_ori);
 /* sd_track_pnp = PnPsolver(CurrentFrame, CurrentFrame.mvpMapPoints) + SetRansacParameters(...) + iterate(n_iterations)

@@ -112,6 +112,10 @@ _SIGNATURES = {
     "sd_track_search_for_triangulation": (_I, [_P, _I, _I, _I]),
     "sd_track_get_triangulation_matches": (_I, [_P, _I, _I, _P, _I, _P, _P, _P]),
     "sd_debug_search_for_triangulation": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "sd_track_set_fuse_scw": (_I, [_P, _I, _I, _P]),
+    "sd_track_fuse": (_I, [_P, _I, _I, _I, _F, _I]),
+    "sd_track_get_fuse": (_I, [_P, _I, _I, _P, _P, _I, _P]),
+    "sd_debug_fuse": (_I, [_I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _F, _F, _I, _I, _P, _P, _P, _P]),
     "sd_track_align": (_I, [_P, _I, _I]),
     "sd_track_match": (_I, [_P, _I, _F, _I, _I]),
     "sd_track_pnp": (_I, [_P, _I, _D, _I, _I, _I, _F, _F, _I]),
@@ -124,6 +128,7 @@ _SIGNATURES = {
     "sd_debug_align_prof": (_I, [_P, _I]),
     "sd_debug_sel_prof": (_I, [_P, _I]),
     "sd_debug_epnp": (_I, [_I, _P, _P, _D, _D, _D, _D, _P, _P, _P]),
+    "sd_track_debug_read": (_I, [_P, _I, _I, _P, _Z]),
     "sd_track_debug_features_in_area": (_I, [_P, _I, _F, _F, _F, _I, _I, _P, _I, _P, _P]),
     "sd_track_pack_records": (_I, [_P, _I, _I, _P]),
     # sequential tracking, motion and IMU models
@@ -160,8 +165,7 @@ _SIGNATURES = {
 }
 
 # Header prototypes left without a row, with the reason: nothing in Python calls them.
-_UNBOUND = ("sd_track_set_local_view", "sd_track_match_local_view",      # the caller's own isInFrustum results: C++ facade only
-            "sd_track_debug_read")                                       # raw read of a tracker's device buffers: no caller in the tree
+_UNBOUND = ("sd_track_set_local_view", "sd_track_match_local_view")      # the caller's own isInFrustum results: C++ facade only
 
 _lib = None
 
@@ -700,6 +704,29 @@ class Tracker:
         _check(self.L.sd_track_get_triangulation_matches(self.h, frame0, n, _p(m), self.cap, _p(nm), _p(F), _p(e)))
         return dict(matches12=m, n_matches=nm, F12=F.reshape(n, 3, 3), epipole=e)
 
+    # --- ORBmatcher::Fuse, both overloads (src/ORBmatcher.cc:477-732); the points are set_local's rows ---
+    def set_fuse_scw(self, frame0, Scw):
+        """The Sim3 Scw per slot, [n, 4, 4], for fuse(sim3=True)."""
+        S = np.ascontiguousarray(np.asarray(Scw, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1, 16)
+        _check(self.L.sd_track_set_fuse_scw(self.h, frame0, S.shape[0], _p(S)))
+
+    def fuse(self, n_frames, kf_side=0, point_row=-1, th=3.0, sim3=False):
+        """The Fuse search of every slot: kf_side 0 = the cur frame (or the broadcast frame) at Tcur, 1 = the ref frame at Tref;
+        point_row r >= 0: every slot reads the points of row r and the cand flags of its own row."""
+        _check(self.L.sd_track_fuse(self.h, n_frames, int(kf_side), int(point_row), float(th), int(sim3)))
+
+    def get_fuse(self, frame0, n):
+        bi, bd = np.zeros((n, self.M), np.int32), np.zeros((n, self.M), np.int32)
+        nf = np.zeros(n, np.int32)
+        _check(self.L.sd_track_get_fuse(self.h, frame0, n, _p(bi), _p(bd), self.M, _p(nf)))
+        return dict(best_idx=bi, best_dist=bd, n_found=nf)
+
+    def fuse_pose(self, frame):
+        """What the last fuse() projected slot `frame` with: (Rcw [3, 3], tcw [3], Ow [3])."""
+        p = np.zeros(15)
+        _check(self.L.sd_track_debug_read(self.h, 2, frame, _p(p), p.nbytes))
+        return p[:9].reshape(3, 3), p[9:12], p[12:]
+
     # --- Sim3Solver on the SearchByPoints pairing (src/Sim3Solver.cc; caller LoopClosing::ComputeSim3) ---
     def set_sim3_points(self, frame0, Xw_cur, Xw_ref):
         """GetWorldPos() of the two keyframes' map points, [n, cap', 3] each, by that keyframe's keypoint index."""
@@ -935,3 +962,29 @@ def debug_search_for_triangulation(kps1, desc1, has_mp1, uright1, kps2, desc2, h
     _check(L.sd_debug_search_for_triangulation(n1, n2, _p(k1), _p(d1), _p(h1), _p(u1), _p(k2), _p(d2), _p(h2), _p(u2), _p(F), _p(e),
                                                _p(sf), _p(s2), len(sf), int(check_ori), _p(m), _p(n)))
     return int(n[0]), m[:n1]
+
+
+def debug_fuse(kps, desc, uright, pts, T, cam9, scale_factors, inv_level_sigma2, scale_factor, th=3.0, sim3=False, kp_cap=None,
+               max_points=None):
+    """One keyframe and one point list from host arrays through k_fuse (diagnostics).  pts: dict(cand, Xw, normal, min_dist,
+    max_dist, mf_max_dist, desc); T: Tcw or Scw [4, 4].  Returns dict(best_idx, best_dist [n_pts], n_found, pose = (Rcw, tcw, Ow))."""
+    L = lib()
+    k = np.ascontiguousarray(kps, KP_DTYPE)
+    nk = len(k)
+    d, u = np.ascontiguousarray(desc, np.uint8).reshape(nk, 32), np.ascontiguousarray(uright, np.float32)
+    c = np.ascontiguousarray(pts["cand"], np.uint8)
+    n = len(c)
+    X, N = np.ascontiguousarray(pts["Xw"], np.float64).reshape(n, 3), np.ascontiguousarray(pts["normal"], np.float64).reshape(n, 3)
+    mn, mx, mf = (np.ascontiguousarray(pts[key], np.float32) for key in ("min_dist", "max_dist", "mf_max_dist"))
+    pd = np.ascontiguousarray(pts["desc"], np.uint8).reshape(n, 32)
+    Tc = np.ascontiguousarray(np.asarray(T, np.float64).reshape(4, 4).T)
+    cam = np.ascontiguousarray(cam9, np.float32)
+    sf, is2 = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(inv_level_sigma2, np.float32)
+    K, M = int(kp_cap or max(nk, 1)), int(max_points or max(n, 1))
+    bi, bd = np.zeros(M, np.int32), np.zeros(M, np.int32)
+    nf, pose = np.zeros(1, np.int32), np.zeros(15)
+    assert len(cam) == 9 and len(u) == nk and len(sf) == len(is2)
+    _check(L.sd_debug_fuse(nk, _p(k), _p(d), _p(u), n, _p(c), _p(X), _p(N), _p(mn), _p(mx), _p(mf), _p(pd), _p(Tc), int(sim3), _p(cam),
+                           _p(sf), _p(is2), len(sf), float(scale_factor), float(th), K, M, _p(bi), _p(bd), _p(nf), _p(pose)))
+    return dict(best_idx=bi[:n], best_dist=bd[:n], n_found=int(nf[0]), pose=(pose[:9].reshape(3, 3), pose[9:12], pose[12:]),
+                rest_idx=bi[n:], rest_dist=bd[n:])

@@ -109,6 +109,7 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   h->rand_len.assign((size_t)max_batch, 0);
   h->meas_set.assign((size_t)max_batch, 0);
   h->f12_set.assign((size_t)max_batch, 0);
+  h->scw_set.assign((size_t)max_batch, 0);
   const size_t B = max_batch, M = max_points, K = nsel;
   TrackBuffers& tb = h->tb;
   tb.max_points = max_points;
@@ -196,6 +197,11 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &tb.tri_epi, B * 2));
   A(dalloc<FILL_FF>(h, &tb.tri_match, B * K));
   A(dalloc(h, &tb.tri_n, B));
+  A(dalloc(h, &h->fu.Scw, B * 16));
+  A(dalloc(h, &h->fu.pose, B * 15));
+  A(dalloc<FILL_FF>(h, &h->fu.idx, B * M));
+  A(dalloc(h, &h->fu.dist, B * M));
+  A(dalloc(h, &h->fu.n, B));
   A(dalloc(h, &tb.s3_Xw1, B * K * 3));
   A(dalloc(h, &tb.s3_Xw2, B * K * 3));
   A(dalloc(h, &tb.s3_X, B * K * 6));
@@ -248,24 +254,8 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
     table(h->d_sigma2, cur->hp.sigma2.data());
     table(h->d_inv_sigma2, cur->hp.inv_sigma2.data());
     if (e == hipSuccess) {
-      // MapPoint::PredictScale (src/MapPoint.cc:371-385): nScale = ceil(log(ratio) / mfLogScaleFactor), float overloads,
-      // mfLogScaleFactor = log(mfScaleFactor) (src/Frame.cc:80).  thr[n] = smallest float ratio that reaches level n,
-      // by bisection over the float bit patterns with THIS host's libm (the function is monotone).
-      float thr[SD_MAX_LEVELS];
-      const float Lsf = logf(cur->scaleFactor);
-      thr[0] = 0.f;
-      for (int n = 1; n < SD_MAX_LEVELS; n++) {
-        uint32_t lo = 1, hi = 0x7f800000u;   // hi = +inf: never reached
-        while (lo < hi) {
-          const uint32_t mid = lo + (hi - lo) / 2;
-          float r;
-          memcpy(&r, &mid, 4);
-          const int ns = (int)ceilf(logf(r) / Lsf);
-          if (ns >= n) hi = mid;
-          else lo = mid + 1;
-        }
-        memcpy(&thr[n], &lo, 4);
-      }
+      float thr[SD_MAX_LEVELS];   // MapPoint::PredictScale breakpoints (track_handle.h)
+      predict_scale_thresholds(cur->scaleFactor, thr);
       e = hipMemcpy(h->d_scale_thr, thr, sizeof(thr), hipMemcpyHostToDevice);
     }
     for (int r = 0; r < sd_track::kRing && e == hipSuccess; r++)
@@ -334,6 +324,7 @@ int sd_track_set_camera(sd_track* h, float fx, float fy, float cx, float cy, flo
   c.bf = bf;
   c.mb = bf / fx;
   h->have_cam = true;
+  fuse_end(h);           // a Fuse result was projected with the old K and image bounds
   return SD_OK;
 }
 
@@ -367,6 +358,7 @@ int sd_track_set_poses(sd_track* h, int frame0, int n_frames, const double* Tref
   SD_REQUIRE(Tref_cm && Tcur_cm, SD_ERR_INVALID_ARG, "NULL argument");
   sim3_end(h);           // the Sim3 solvers' keyframe poses are being replaced
   tri_end(h);            // ... and the poses F12 and the epipole were computed from
+  fuse_end(h);           // ... and the keyframe pose of a Fuse result
   hipStream_t s = h->cur->stream;
   SD_TRY(upload(h->tb.Tref, Tref_cm, frame0, n_frames, 16, s));
   SD_TRY(upload(h->tb.Tprior, Tcur_cm, frame0, n_frames, 16, s));
@@ -421,6 +413,7 @@ int sd_track_set_local(sd_track* h, int frame0, int n_frames, const int32_t* n_l
   SD_REQUIRE(n_local && cand && Xw && normal && min_dist && max_dist && mf_max_dist && desc && obs, SD_ERR_INVALID_ARG, "NULL argument");
   const size_t M = h->max_points, K = h->kp_cap, o = (size_t)frame0, n = (size_t)n_frames;
   for (int f = 0; f < n_frames; f++) SD_REQUIRE(n_local[f] >= 0 && n_local[f] <= h->max_points, SD_ERR_CAPACITY, "n_local exceeds max_points");
+  fuse_end(h);           // sd_track_fuse reads these rows too
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
   SD_TRY(upload(tb.lm_n, n_local, o, n, 1, s));
@@ -452,6 +445,7 @@ int sd_track_set_local_view(sd_track* h, int frame0, int n_frames, const int32_t
       SD_REQUIRE(!in_view[(size_t)f * M + i] || (level[(size_t)f * M + i] >= 0 && level[(size_t)f * M + i] < h->cur->nlevels), SD_ERR_INVALID_ARG,
                  "mnTrackScaleLevel of an in-view point outside [0, nlevels)");
   }
+  fuse_end(h);           // lm_n and lm_desc are rows sd_track_fuse reads
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
   SD_TRY(upload(tb.lm_n, n_local, o, n, 1, s));
@@ -690,6 +684,7 @@ int sd_track_set_uright(sd_track* h, int frame0, int n_frames, const float* urig
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(uright && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad uright array");
   tri_end(h);            // KF1's stereo bits are being replaced
+  fuse_end(h);           // ... and the mvuRight row of a Fuse result's chi-square gate
   SD_TRY(upload_rows(h->tb.uright, h->kp_cap, uright, cap, frame0, n_frames, h->cur->stream));
   return wait_for(h->cur->stream);
 }
@@ -923,14 +918,17 @@ int sd_debug_epnp(int n, const double* Xw, const double* uv, double fx, double f
   return run_epnp_debug(n, Xw, uv, fx, fy, cx, cy, R9, t3, reproj_err);
 }
 
-// diagnostics: raw copy of an internal per-frame buffer (0: pnp correspondences f32[kp_cap*6], 1: pnp keypoint indices u16[kp_cap])
+// diagnostics: raw copy of an internal per-frame buffer (0: pnp correspondences f32[kp_cap*6], 1: pnp keypoint indices u16[kp_cap],
+// 2: what the last sd_track_fuse projected the slot with, f64[15] = Rcw row-major | tcw | Ow)
 int sd_track_debug_read(sd_track* h, int which, int frame, void* out, size_t bytes) {
   SD_REQUIRE(h && out && frame >= 0 && frame < h->max_batch, SD_ERR_INVALID_ARG, "bad arguments");
+  SD_REQUIRE(which != 2 || bytes <= 15 * sizeof(double), SD_ERR_CAPACITY, "the Fuse pose of a slot is 15 doubles");
   SD_HIP_CHECK(hipSetDevice(h->device));
   SD_HIP_CHECK(hipStreamSynchronize(h->pnp_stream));
   SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
-  const void* src = which == 0 ? (const void*)(h->tb.pnp_pts + (size_t)frame * h->kp_cap * 6)
-                               : (const void*)(h->tb.pnp_kpidx + (size_t)frame * h->kp_cap);
+  const void* src = which == 0   ? (const void*)(h->tb.pnp_pts + (size_t)frame * h->kp_cap * 6)
+                    : which == 2 ? (const void*)(h->fu.pose + (size_t)frame * 15)
+                                 : (const void*)(h->tb.pnp_kpidx + (size_t)frame * h->kp_cap);
   SD_HIP_CHECK(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
   return SD_OK;
 }

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -85,6 +86,13 @@ struct sd_track {
   RunStamp tri;                    // mode = the broadcast setting the search ran under
   unsigned long long tri_ref_serial = 0;   // ... and on THIS extraction of `ref`
   std::vector<uint8_t> f12_set;    // [max_batch] sd_track_set_f12 has covered the slot
+  // ORBmatcher::Fuse (track_fuse.hip): the result sd_track_get_fuse returns while the stamp holds (fuse_end)
+  struct FuseStamp {
+    int n = 0, kf_side = 0, bcast = -1;   // slots < n hold a result of this side, searched under this broadcast setting ...
+    unsigned long long serial = 0;        // ... on THIS extraction of the side's extractor
+  } fuse;
+  std::vector<uint8_t> scw_set;    // [max_batch] sd_track_set_fuse_scw has covered the slot
+  sd::FuseBuffers fu{};
   sd::TrackBuffers tb{};
   sd::TrackCam cam{};
   bool have_cam = false;
@@ -132,6 +140,28 @@ inline bool RunStamp::covers(const sd_track* h, int n_frames) const {
 static inline void sim3_end(sd_track* h) { h->sim3 = RunStamp{}; }
 // Something a SearchForTriangulation result was computed from is being replaced: the getter refuses until the search runs again
 static inline void tri_end(sd_track* h) { h->tri = RunStamp{}; }
+// Something a Fuse result was computed from is being replaced: sd_track_get_fuse refuses until sd_track_fuse runs again
+static inline void fuse_end(sd_track* h) { h->fuse = sd_track::FuseStamp{}; }
+
+// MapPoint::PredictScale (src/MapPoint.cc:355-385): nScale = ceil(log(ratio) / mfLogScaleFactor), float overloads,
+// mfLogScaleFactor = log(mfScaleFactor) (src/Frame.cc:80).  thr[n] = smallest float ratio that reaches level n,
+// by bisection over the float bit patterns with THIS host's libm (the function is monotone).
+static inline void predict_scale_thresholds(float scale_factor, float (&thr)[SD_MAX_LEVELS]) {
+  const float Lsf = logf(scale_factor);
+  thr[0] = 0.f;
+  for (int n = 1; n < SD_MAX_LEVELS; n++) {
+    uint32_t lo = 1, hi = 0x7f800000u;   // hi = +inf: never reached
+    while (lo < hi) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      float r;
+      memcpy(&r, &mid, 4);
+      const int ns = (int)ceilf(logf(r) / Lsf);
+      if (ns >= n) hi = mid;
+      else lo = mid + 1;
+    }
+    memcpy(&thr[n], &lo, 4);
+  }
+}
 
 // "<the call `source` names> has not run on these slots since the last extraction"; 2: sd_track_stereo_init
 static inline const char* not_run_msg(int source) {

@@ -221,6 +221,19 @@ int launch_search_points(const sd_orb* cur, const sd_orb* ref, const TrackBuffer
 // ComputeF12 (use_set_f12: tri_F12_set instead) and the epipole of every slot, then SearchForTriangulation (track_tri.hip)
 int launch_tri(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const TrackCam& cam, const float* d_sf, const float* d_sigma2,
                int n_frames, int use_set_f12, int check_ori, hipStream_t s);
+// ORBmatcher::Fuse (track_fuse.hip): what the search owns besides the local-map point rows (lm_*) it reads.  Kept out of
+// TrackBuffers, which travels by value with every other kernel.
+struct FuseBuffers {
+  double* Scw;           // [B][16] the caller's Scw, column-major (sd_track_set_fuse_scw)
+  double* pose;          // [B][15] what the last search projected with: Rcw row-major | tcw | Ow
+  int32_t* idx;          // [B][M]  best_idx
+  int32_t* dist;         // [B][M]  best_dist
+  int32_t* n;            // [B]     points with best_idx >= 0
+};
+// kf_side 0: KF = the slot's cur frame (or the broadcast frame), Tcur, tb.uright; 1: frame f of `ref`, Tref, tb.uright_ref
+int launch_fuse(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const FuseBuffers& fb, const TrackCam& cam, const float* d_sf,
+                const float* d_inv_sigma2, const float* d_scale_thr, int n_frames, int kf_side, int point_row, float th, int sim3,
+                hipStream_t s);
 int launch_stereo_from_depth(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_depth, int w, int h,
                              int stride_elems, size_t frame_stride_elems, int n_frames, hipStream_t s);
 // the same on a depth map of uint16_t (u16 != 0, always converted) or float elements; convert: d = (float)raw * scale

@@ -47,16 +47,6 @@ struct MatchLds {
   const uint32_t* s_kclaim;   // bit idx: keypoint idx already held such a point before the call (may be null)
 };
 
-// GL lanes of a wave work on one point.  64: the whole wave (`lane`, `lt` as usual, gm = ~0).  Fewer: one point per group, `glane` =
-// lane within the group, `glt` = the lower lanes OF THE GROUP and `gm` = the group's lanes, both as bit masks of the 64-bit wave
-// ballot.  The groups diverge freely; a ballot only ever carries the active lanes.
-template <int GL>
-struct SubWave {
-  int group, glane;
-  unsigned long long gm, glt;
-  __device__ __forceinline__ explicit SubWave(int lane)
-      : group(lane / GL), glane(lane % GL), gm(((1ull << GL) - 1ull) << (GL * group)), glt(((1ull << glane) - 1ull) << (GL * group)) {}
-};
 __device__ __forceinline__ void sdsel_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 
 // Candidates of one search window: GetFeaturesInArea(u, v, radius, minLevel, maxLevel) (src/Frame.cc:271-321) in
@@ -151,50 +141,6 @@ __device__ __forceinline__ uint32_t match_window(float u, float v, float radius,
   }
   *seq_total = seq0;
   return MODE == 2 ? best : (uint32_t)w;
-}
-
-// ---- Frame bucket grid (shared by k_match, k_match_local and the debug read-out k_features_in_area) ----
-// Frame::PosInGrid (src/Frame.cc:323-332, round()) as a sort key: cell << 11 | keypoint index, cell = posX * 48 + posY;
-// 0xFFFFFFFF for a keypoint outside the grid (AssignFeaturesToGrid skips it).
-__device__ __forceinline__ uint32_t grid_key(const sd_keypoint& kp, const TrackCam& cam, float invW, float invH, int i) {
-  const int posX = (int)roundf((kp.x - cam.min_x) * invW);
-  const int posY = (int)roundf((kp.y - cam.min_y) * invH);
-  if (posX < 0 || posX >= GRID_COLS || posY < 0 || posY >= GRID_ROWS) return 0xFFFFFFFFu;
-  return ((uint32_t)(posX * GRID_ROWS + posY) << 11) | (uint32_t)i;
-}
-// Ascending bitonic sort of v[0 .. n) in LDS, n a power of two.  All NT threads call, after a barrier that makes v complete;
-// ends with a barrier.
-__device__ __forceinline__ void bitonic_sort_lds(uint32_t* v, int n, int tid, int NT) {
-  for (int k = 2; k <= n; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < n; i += NT) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const uint32_t a = v[i], b = v[ixj];
-          if ((a > b) == ((i & k) == 0)) {
-            v[i] = b;
-            v[ixj] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-}
-// Frame::AssignFeaturesToGrid (src/Frame.cc:179-192): sort of the KP2 keys in LDS (mGrid[x][y] in ascending keypoint index =
-// one contiguous, ordered run per cell) and the first sorted position of every cell.  All NT threads call, after a barrier
-// that makes s_key complete; ends with s_cstart written but NOT yet synchronised.
-__device__ __forceinline__ void grid_sort_and_starts(uint32_t* s_key, uint16_t* s_cstart, int KP2, int tid, int NT) {
-  bitonic_sort_lds(s_key, KP2, tid, NT);
-  for (int c = tid; c <= GRID_COLS * GRID_ROWS; c += NT) {
-    const uint32_t target = (uint32_t)c << 11;
-    int lo = 0, hi = KP2;
-    while (lo < hi) {
-      int mid = (lo + hi) >> 1;
-      if (s_key[mid] < target) lo = mid + 1;
-      else hi = mid;
-    }
-    s_cstart[c] = (uint16_t)lo;
-  }
 }
 
 // Flags pred(i), i in [0, n_bits), packed into the 32-bit words dst[0 .. (n_bits + 31) / 32): one flag per thread and round,

@@ -130,4 +130,14 @@ struct LdsSearchTri : LdsLayout {   // k_search_triangulation; capw = keypoint c
   }
 };
 
+struct LdsFuse : LdsLayout {   // k_fuse (track_fuse.hip)
+  uint32_t key = 0, cstart = 0, pose = 0, nfound = 0;
+  constexpr explicit LdsFuse(int KP2) {
+    key = take<uint32_t>(KP2);                     // sorted (cell << 11 | index) of the keyframe's keypoints
+    cstart = take<uint16_t>(GRID_CSTART);
+    pose = take<double>(16);                       // Rcw row-major, tcw, Ow (15 used)
+    nfound = take<int32_t>(1);
+  }
+};
+
 }  // namespace sd

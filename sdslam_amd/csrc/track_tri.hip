@@ -345,6 +345,7 @@ int sd_track_set_uright_ref(sd_track* h, int frame0, int n_frames, const float* 
   QUEUE_RANGE(h, frame0, n_frames);
   SD_REQUIRE(uright && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad uright array");
   tri_end(h);
+  fuse_end(h);
   SD_TRY(upload_rows(h->tb.uright_ref, h->kp_cap, uright, cap, frame0, n_frames, h->pnp_stream));
   return wait_for(h->pnp_stream);   // the rows are the caller's pageable memory: back once they are read
 }
