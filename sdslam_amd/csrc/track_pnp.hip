@@ -22,14 +22,11 @@
 #include "orb_internal.h"
 #include "sd_hypot.h"
 #include "track_internal.h"
+#include "track_pnp_lds.h"   // PNP_CHUNK and the LDS address maps
 
 namespace sd {
 
 #define PNP_MAXN 2048   // = the tracker's keypoint capacity limit (sd_track_create)
-#ifndef PNP_CHUNK
-#define PNP_CHUNK 8    // RANSAC hypotheses evaluated side by side (typical runs accept within the first few);
-                       // 3 lanes per hypothesis (one per EPnP beta variant)
-#endif
 #define PNP_WORDS (PNP_MAXN / 64)
 #define PNP_MAXSET 64   // largest RANSAC minimal set (mRansacMinSet) the general path draws
 
@@ -37,6 +34,8 @@ namespace sd {
 // PNP_CHUNK lanes that solve hypotheses side by side hit distinct banks.  The big per-lane EPnP
 // work arrays (12x12 Gram / singular-vector matrix, L_6x10) live here instead of in private
 // (scratch) memory: with 9 KB of scratch per lane the kernel was bound by scratch traffic.
+// L and the parked alphas are plain lane-interleaved arrays (LArr); the 12 x 12 matrix, which up to six lanes per hypothesis
+// share during the Jacobi sweeps, has the padded and rotated rows of pnp_lds::mat_index (LMat).
 // Optional stage timers (build with -DSD_PNP_PROF; read through sd_debug_pnp_prof): shader-clock
 // cycles of lane 0 per stage, summed over frames.  Slots 0-8: EPnP stages of the RANSAC minimal
 // sets, 16-24: of the refit, 10-15: k_pnp phases.
@@ -72,6 +71,14 @@ struct LArr {
   __device__ __forceinline__ ldsd& operator[](int i) const { return p[i * PNP_CHUNK]; }
   __device__ __forceinline__ LArr operator+(int off) const { return LArr{p + off * PNP_CHUNK}; }
 };
+// The 12 x 12 matrix + W of hypothesis h in the work area `p` (pnp_lds::mat_index: padded rows, rotated by row, so that the
+// lanes that share the Jacobi sweeps never meet on an LDS bank).  row(i)[k] = element (i, k), w(i) = W[i].
+struct LMat {
+  ldsd* p;
+  int h;
+  __device__ __forceinline__ LArr row(int i) const { return LArr{p + pnp_lds::mat_index(i, 0, h)}; }
+  __device__ __forceinline__ ldsd& w(int i) const { return p[pnp_lds::mat_index(i, pnp_lds::kMatW, h)]; }
+};
 
 // ---- one-sided Jacobi SVD (OpenCV 3.2 JacobiSVDImpl_<double>), n <= 12 --------------------
 // The 12 x 12 case (EPnP's M^T M) keeps the matrix and the squared norms W in lane-interleaved LDS
@@ -81,75 +88,78 @@ struct LArr {
 // a global-memory round trip, which dominated the first version of this kernel.
 // Tail of JacobiSVDImpl_ for the 12 x 12 case (final norms, descending selection sort of the rows,
 // normalisation / zero-singular-value fill-in), matrix and W in (lane-interleaved) LDS.
-template <typename Ptr>
-__device__ PNP_FN void jacobi_finish12(Ptr At, Ptr W) {
+__device__ PNP_FN void jacobi_finish12(LMat A) {
   const double minval = DBL_MIN, eps = DBL_EPSILON * 10;
   constexpr int m = 12, n = 12;
   int i, j, k, iter;
   double s, sd;
   for (i = 0; i < n; i++) {
+    const LArr Ai = A.row(i);
     sd = 0;
 #pragma unroll
     for (k = 0; k < m; k++) {
-      double t = At[i * m + k];
+      double t = Ai[k];
       sd += t * t;
     }
-    W[i] = sqrt(sd);
+    A.w(i) = sqrt(sd);
   }
   for (i = 0; i < n - 1; i++) {
     j = i;
-    double wj = W[i];
+    double wj = A.w(i);
     for (k = i + 1; k < n; k++) {
-      const double wk = W[k];
+      const double wk = A.w(k);
       if (wj < wk) {
         j = k;
         wj = wk;
       }
     }
     if (i != j) {
-      double tw = W[i]; W[i] = W[j]; W[j] = tw;
+      const LArr Ai = A.row(i), Aj = A.row(j);
+      double tw = A.w(i); A.w(i) = A.w(j); A.w(j) = tw;
 #pragma unroll
-      for (k = 0; k < m; k++) { double t = At[i * m + k]; At[i * m + k] = At[j * m + k]; At[j * m + k] = t; }
+      for (k = 0; k < m; k++) { double t = Ai[k]; Ai[k] = Aj[k]; Aj[k] = t; }
     }
   }
   unsigned long long rng = 0x12345678ull;
   for (i = 0; i < n; i++) {
-    sd = W[i];
+    const LArr Ai = A.row(i);
+    sd = A.w(i);
     for (int ii = 0; ii < 100 && sd <= minval; ii++) {
       const double val0 = 1. / m;
       for (k = 0; k < m; k++) {
         rng = (unsigned long long)(unsigned)rng * 4164903690U + (unsigned)(rng >> 32);
         double val = ((unsigned)rng & 256) != 0 ? val0 : -val0;
-        At[i * m + k] = val;
+        Ai[k] = val;
       }
       for (iter = 0; iter < 2; iter++) {
         for (j = 0; j < i; j++) {
+          const LArr Aj = A.row(j);
           sd = 0;
 #pragma unroll
-          for (k = 0; k < m; k++) sd += At[i * m + k] * At[j * m + k];
+          for (k = 0; k < m; k++) sd += Ai[k] * Aj[k];
           double asum = 0;
 #pragma unroll
           for (k = 0; k < m; k++) {
-            double t = At[i * m + k] - sd * At[j * m + k];
-            At[i * m + k] = t;
+            double t = Ai[k] - sd * Aj[k];
+            Ai[k] = t;
             asum += fabs(t);
           }
           asum = asum > eps * 100 ? 1 / asum : 0;
 #pragma unroll
-          for (k = 0; k < m; k++) At[i * m + k] *= asum;
+          for (k = 0; k < m; k++) Ai[k] *= asum;
         }
       }
       sd = 0;
 #pragma unroll
       for (k = 0; k < m; k++) {
-        double t = At[i * m + k];
+        double t = Ai[k];
         sd += t * t;
       }
       sd = sqrt(sd);
     }
     s = sd > minval ? 1 / sd : 0.;
 #pragma unroll
-    for (k = 0; k < m; k++) At[i * m + k] *= s;
+    for (k = 0; k < m; k++) Ai[k] *= s;
   }
 }
 
@@ -306,10 +316,9 @@ __device__ __forceinline__ void jacobi_svd_small(double (&At)[N][M], double (&Wo
 // JacobiSVDImpl_'s final row swaps).
 // One (i, j) step of JacobiSVDImpl_'s rotation sweeps (for (i) for (j > i) in cyclic order, up to 30 sweeps, stop after a
 // sweep without rotation); rows are copied to registers, everything else stays in LDS.  Returns true when the rows were rotated.
-template <typename Ptr>
-__device__ __forceinline__ bool jacobi_pair12(Ptr A, Ptr W, int i, int j) {
+__device__ __forceinline__ bool jacobi_pair12(LMat A, int i, int j) {
   const double eps = DBL_EPSILON * 10;
-  const Ptr Ai = A + i * 12, Aj = A + j * 12;
+  const LArr Ai = A.row(i), Aj = A.row(j);
   double ai[12], aj[12];
 #pragma unroll
   for (int k = 0; k < 12; k++) {
@@ -319,7 +328,7 @@ __device__ __forceinline__ bool jacobi_pair12(Ptr A, Ptr W, int i, int j) {
   double p = 0;
 #pragma unroll
   for (int k = 0; k < 12; k++) p += ai[k] * aj[k];
-  const double a = W[i], b = W[j];
+  const double a = Ai[pnp_lds::kMatW], b = Aj[pnp_lds::kMatW];
   if (fabs(p) <= eps * sqrt(a * b)) return false;
   p *= 2;
   double c, s;
@@ -342,8 +351,8 @@ __device__ __forceinline__ bool jacobi_pair12(Ptr A, Ptr W, int i, int j) {
     na += t0 * t0;
     nb += t1 * t1;
   }
-  W[i] = na;
-  W[j] = nb;
+  Ai[pnp_lds::kMatW] = na;
+  Aj[pnp_lds::kMatW] = nb;
   return true;
 }
 
@@ -354,17 +363,17 @@ __device__ __forceinline__ bool jacobi_pair12(Ptr A, Ptr W, int i, int j) {
 // order, so the result has the same bits; only independent pairs change places.  Called by ALL 64 lanes of the (single-wave) workgroup: lane
 // g < 6 of a matrix takes the g-th pair of the step; `act` = this lane's matrix exists.  A matrix whose sweep rotated
 // nothing is finished (the sequential loop's `break`).
-template <typename Ptr>
-__device__ PNP_FN void jacobi_sweeps12_coop(Ptr A, Ptr W, int g, bool act, unsigned long long group_mask) {
+__device__ PNP_FN void jacobi_sweeps12_coop(LMat A, int g, bool act, unsigned long long group_mask) {
   if (act && g < 6)
     for (int i = g; i < 12; i += 6) {
+      const LArr Ai = A.row(i);
       double sd = 0;
 #pragma unroll
       for (int k = 0; k < 12; k++) {
-        const double t = A[i * 12 + k];
+        const double t = Ai[k];
         sd += t * t;
       }
-      W[i] = sd;
+      A.w(i) = sd;
     }
   __syncthreads();
   bool live = act;
@@ -372,7 +381,7 @@ __device__ PNP_FN void jacobi_sweeps12_coop(Ptr A, Ptr W, int g, bool act, unsig
     bool changed = false;
     for (int st = 1; st <= 21; st++) {
       const int i = max(0, st - 11) + g, j = st - i;
-      if (live && g < 6 && i < j) changed |= jacobi_pair12(A, W, i, j);
+      if (live && g < 6 && i < j) changed |= jacobi_pair12(A, i, j);
       __syncthreads();   // one wave: orders this step's LDS writes before the next step's reads
     }
     const unsigned long long any = __ballot(changed);
@@ -680,12 +689,12 @@ __device__ __forceinline__ void epnp_alphas(const double* pi, const double cws[4
 __device__ const int8_t kPairA[6] = {0, 0, 0, 1, 1, 2}, kPairB[6] = {1, 2, 3, 2, 3, 3};
 __device__ const int8_t kColU[10] = {0, 0, 1, 0, 1, 2, 0, 1, 2, 3}, kColV[10] = {0, 1, 1, 2, 2, 2, 3, 3, 3, 3};
 template <typename Ptr>
-__device__ void epnp_L_rho(Ptr ut, const double cws[4][3], Ptr L, double rho[6], bool write_L) {
+__device__ void epnp_L_rho(LMat ut, const double cws[4][3], Ptr L, double rho[6], bool write_L) {
   if (write_L) {
     for (int p = 0; p < 6; p++) {
       double d[4][3];   // the pair's difference vector in each of the four null-space vectors
       for (int v = 0; v < 4; v++) {
-        const Ptr nv = ut + 12 * (11 - v);
+        const LArr nv = ut.row(11 - v);
         for (int k = 0; k < 3; k++) d[v][k] = nv[3 * kPairA[p] + k] - nv[3 * kPairB[p] + k];
       }
       Ptr row = L + 10 * p;
@@ -774,11 +783,10 @@ __device__ PNP_FN void epnp_betas(int variant, Ptr L, const Rho6 rho_v, Betas4& 
 }
 
 // compute_ccs
-template <typename Ptr>
-__device__ __forceinline__ void epnp_ccs(Ptr ut, const double* betas, double ccs[4][3]) {
+__device__ __forceinline__ void epnp_ccs(LMat ut, const double* betas, double ccs[4][3]) {
   for (int i = 0; i < 4; i++) ccs[i][0] = ccs[i][1] = ccs[i][2] = 0.0f;
   for (int i = 0; i < 4; i++) {
-    const Ptr v = ut + 12 * (11 - i);
+    const LArr v = ut.row(11 - i);
     for (int j = 0; j < 4; j++)
       for (int k = 0; k < 3; k++) ccs[j][k] += betas[i] * v[3 * j + k];
   }
@@ -820,12 +828,14 @@ __device__ __forceinline__ double epnp_reproj_term(const double Rv[3][3], const 
 // and writes L into the hypothesis' LDS view, then each lane follows its own
 // find_betas variant / Gauss-Newton / R,t / reprojection error.  Returns that variant's error.
 // r3: inlined into its one caller; the four correspondences are fetched by `gather(k, pw, u)` where they lie (twice: they are not
-// kept across the find_betas call), and the barycentric coordinates wait in the lane's slot of the (by then idle) M-row scratch
+// kept across the find_betas call), and the barycentric coordinates wait in the hypothesis' slot of the (by then idle) M-row scratch
 // area while epnp_betas runs -- that call uses the whole register file, and what is alive across it would otherwise go to scratch.
+// L lies in the same idle area (pnp_lds::kL).
 template <typename Ptr, typename G>
 __device__ __forceinline__ double epnp_minimal(bool active, int variant, G&& gather, const EpnpCam cam, double (&Rv)[3][3],
-                                               double (&tv)[3], Ptr ut, Ptr L, ldsd* Mrows /* PNP_CHUNK x 4 x 24 */,
+                                               double (&tv)[3], LMat ut, Ptr L, ldsd* scr /* s_scr: pnp_lds::kMrows .. kL */,
                                                int nhyp /* hypotheses in flight: lanes h < nhyp are active */) {
+  ldsd* const Mrows = scr;   // PNP_CHUNK x 4 x 24
   constexpr int n = 4;
   double cws[4][3], alphas[16], rho[6];
   double pws[12], us[8];
@@ -885,9 +895,9 @@ __device__ __forceinline__ double epnp_minimal(bool active, int variant, G&& gat
       acc += rows[i * 24 + a] * rows[i * 24 + b];
       acc += rows[i * 24 + 12 + a] * rows[i * 24 + 12 + b];
     }
-    ldsd* uh = ut.p - (threadIdx.x % PNP_CHUNK) + h;   // hypothesis h's lane-interleaved view of the work area
-    uh[(a * 12 + b) * PNP_CHUNK] = acc;
-    uh[(b * 12 + a) * PNP_CHUNK] = acc;
+    const LMat uh{ut.p, h};   // hypothesis h's view of the work area
+    uh.row(a)[b] = acc;
+    uh.row(b)[a] = acc;
   }
   __syncthreads();
   PROF(2);
@@ -897,18 +907,21 @@ __device__ __forceinline__ double epnp_minimal(bool active, int variant, G&& gat
     const int lane = threadIdx.x, h = lane % PNP_CHUNK, g = lane / PNP_CHUNK;
     __syncthreads();
     const bool act_h = __shfl((int)active, h) != 0;   // lane h is the variant-1 lane of hypothesis h
-    jacobi_sweeps12_coop(ut, ut + 144, g, act_h, 0x0000010101010101ull << h);
-    if (active && variant == 1) jacobi_finish12(ut, ut + 144);
+    jacobi_sweeps12_coop(ut, g, act_h, 0x0000010101010101ull << h);
+    if (active && variant == 1) jacobi_finish12(ut);
     PROF(3);
   }
+  // The M rows were consumed above: their doubles now take L and the barycentric coordinates.  The three variant lanes of a
+  // hypothesis computed the same alphas from the same inputs in lock-step (same bits), so the variant-1 lane parks them once,
+  // lane-interleaved like L.
   epnp_L_rho(ut, cws, L, rho, active && variant == 1);
-  PROF(4);
-  __syncthreads();   // ut / L of every hypothesis visible to its variant lanes
-  double err = 0;
-  ldsd* park = Mrows + (threadIdx.x & 63) * 16;   // 3 * PNP_CHUNK lanes x 16 doubles <= PNP_CHUNK x 4 x 24 (the M rows were consumed above)
-  static_assert(3 * 16 <= 4 * 24, "alpha parking area");
-  if (active) {
+  const LArr park{scr + pnp_lds::kPark + threadIdx.x % PNP_CHUNK};
+  if (active && variant == 1)
     for (int i = 0; i < 16; i++) park[i] = alphas[i];
+  PROF(4);
+  __syncthreads();   // ut / L / alphas of every hypothesis visible to its variant lanes
+  double err = 0;
+  if (active) {
     double betas[4], ccs[4][3], pcs[12];
     {
       Rho6 rv;
@@ -995,17 +1008,21 @@ __device__ __forceinline__ void ordered_sums(int n, ldsd* terms, ldsd* out, F&& 
 // terms) is lane-parallel, every reduction is an ordered_sums (bit-identical to the sequential
 // loops of the reference).  M^T M: one lane per non-zero upper-triangle entry (62 of 78; the other
 // 16 pair an x- with a y-column of M and stay +0), inputs staged through LDS.  The 12 x 12 SVD
-// runs on lane 0, the three beta variants on lanes 0..2.  ut / L: lane 0's LDS views.
-// lds: terms[64 * 9], red[64], mtm[144].  Writes {R (row-major), t} to Rt_out[12] (LDS).
+// runs on lanes 0..5 (sweeps) and lane 0 (tail), the three beta variants on lanes 0..2.  ut: hypothesis 0's matrix.
+// scr: terms[64 * 9], mtm[144], red[64] and L as pnp_lds lays them out.  Writes {R (row-major), t} to Rt_out[12] (LDS).
 // r3: pws / us are read where they lie -- TIn = float: the compacted copy of the gathered f32 correspondences (PnPsolver narrows
 // its 3-D points to Point3f and takes kp.pt, src/PnPsolver.cc:92-93; (double) of the same float is the same double) -- and the
 // barycentric coordinates (alphas) and camera-frame points (pcs) are RECOMPUTED from them wherever the reference reads its
 // alphas[] / pcs[] arrays (same expressions on the same inputs: same bits).  Round 2 kept all four as double arrays in HBM:
 // 96 bytes written and re-read several times per inlier, a third of the kernel's 19 x algorithmic traffic.
-template <typename Ptr, typename TIn>
-__device__ PNP_FN void epnp_refit_wave(int n, const TIn* pws, const TIn* us, const EpnpCam cam, ldsd* Rt_out, Ptr ut, Ptr L,
-                                               ldsd* terms, ldsd* red, ldsd* mtm) {
+template <typename TIn>
+__device__ PNP_FN void epnp_refit_wave(int n, const TIn* pws, const TIn* us, const EpnpCam cam, ldsd* Rt_out, LMat ut, ldsd* scr) {
   const int lane = threadIdx.x & 63;
+  // s_scr as pnp_lds lays it out.  L is alive from epnp_L_rho to epnp_betas only: no M^T M staging or ordered sum in between.
+  ldsd* const terms = scr + pnp_lds::kTerms;
+  ldsd* const mtm = scr + pnp_lds::kMtm;
+  ldsd* const red = scr + pnp_lds::kRed;
+  const LArr L{scr + pnp_lds::kRefitL};   // hypothesis 0's view
   double cws[4][3], ci[9];
   auto PW = [&](int i, double* p) {
     p[0] = (double)pws[3 * i];
@@ -1094,10 +1111,10 @@ __device__ PNP_FN void epnp_refit_wave(int n, const TIn* pws, const TIn* us, con
   __syncthreads();
   PROF(18);
   double rho[6];
-  for (int i = lane; i < 144; i += 64) ut[i] = mtm[i];
+  for (int i = lane; i < 144; i += 64) ut.row(i / 12)[i % 12] = mtm[i];
   __syncthreads();
-  jacobi_sweeps12_coop(ut, ut + 144, lane, true, 0x3full);   // six lanes on the one matrix
-  if (lane == 0) jacobi_finish12(ut, ut + 144);
+  jacobi_sweeps12_coop(ut, lane, true, 0x3full);   // six lanes on the one matrix
+  if (lane == 0) jacobi_finish12(ut);
   PROF(19);
   epnp_L_rho(ut, cws, L, rho, lane == 0);
   __syncthreads();
@@ -1218,7 +1235,7 @@ __global__ __launch_bounds__(64, 2) __attribute__((disable_tail_calls)) void k_p
                                             TrackBuffers tb, TrackCam tcam, const float* __restrict__ sigma2, PnpParams pp,
                                             int n_frames) {
   // gathered correspondences live in HBM (read-mostly, L2-resident): {u, v, X, Y, Z, maxErr} f32
-  __shared__ double s_work[PNP_CHUNK * (156 + 60)];   // per-hypothesis EPnP matrices, lane-interleaved
+  __shared__ double s_work[pnp_lds::kWorkDoubles];   // per-hypothesis 12 x 12 matrix + W (pnp_lds::mat_index)
   __shared__ double s_Rt[PNP_CHUNK][12];
   __shared__ unsigned long long s_mask[PNP_CHUNK][PNP_WORDS];
   __shared__ unsigned long long s_best[PNP_WORDS], s_ref[PNP_WORDS];
@@ -1228,12 +1245,9 @@ __global__ __launch_bounds__(64, 2) __attribute__((disable_tail_calls)) void k_p
   // One scratch area for two call-local uses (one wave per workgroup, the calls are sequential): the rows of M of the chunk's
   // minimal sets inside epnp_minimal, and the ordered-sum terms / MtM / reduction slots inside epnp_refit_wave.  Keeping them
   // apart cost 6 KB of the 30 KB this kernel holds per frame -- four frames per CU, beside k_fast_cells workgroups of 24-39 KB.
-  constexpr int kScrMrows = PNP_CHUNK * 4 * 24, kScrRefit = 64 * 9 + 144 + 64;
-  __shared__ double s_scr[kScrMrows > kScrRefit ? kScrMrows : kScrRefit];
-  double* const s_Mrows = s_scr;
-  double* const s_terms = s_scr;
-  double* const s_mtm = s_scr + 64 * 9;
-  double* const s_red = s_scr + 64 * 9 + 144;
+  // L (6 x 10 per hypothesis) lives here too, in doubles that are dead by the time it is written (layout: track_pnp_lds.h);
+  // beside the matrices it cost another 3.75 KB.
+  __shared__ double s_scr[pnp_lds::kScrDoubles];
   __shared__ int s_modp[PNP_MAXSET], s_modv[PNP_MAXSET], s_draw[PNP_MAXSET];   // general minimal sets (mRansacMinSet != 4)
   const int lane = threadIdx.x;
   // one wave per frame.  (r2 walked the frames with a persistent loop for a capped-grid experiment, "track.pnp_grid_cap": the
@@ -1255,8 +1269,9 @@ __global__ __launch_bounds__(64, 2) __attribute__((disable_tail_calls)) void k_p
   float* g_p = tb.pnp_pts + (size_t)f * cap * 6;
   uint16_t* g_idx = tb.pnp_kpidx + (size_t)f * cap;
   const int hyp = lane % PNP_CHUNK, variant = lane / PNP_CHUNK + 1;   // lanes >= 3 * PNP_CHUNK: no hypothesis
-  const LArr w_ut{LDS_PTR(s_work) + hyp}, w_L{LDS_PTR(s_work) + 156 * PNP_CHUNK + hyp};
-  const LArr r_ut{LDS_PTR(s_work)}, r_L{LDS_PTR(s_work) + 156 * PNP_CHUNK};             // the refit uses hypothesis 0's storage
+  const LMat w_ut{LDS_PTR(s_work), hyp};
+  const LArr w_L{LDS_PTR(s_scr) + pnp_lds::kL + hyp};
+  const LMat r_ut{LDS_PTR(s_work), 0};   // the refit uses hypothesis 0's storage
 
   PROF_DECL;
   for (int i = lane; i < cap; i += 64) inl_out[i] = 0;
@@ -1377,7 +1392,7 @@ __global__ __launch_bounds__(64, 2) __attribute__((disable_tail_calls)) void k_p
             u[0] = q[0];
             u[1] = q[1];
           },
-          cam, R, t, w_ut, w_L, LDS_PTR(s_Mrows), nact);
+          cam, R, t, w_ut, w_L, LDS_PTR(s_scr), nact);
       // N = 1; if (e2 < e1) N = 2; if (e3 < e[N]) N = 3   (src/PnPsolver.cc:385-389)
       const double e1 = __shfl(err, hyp), e2 = __shfl(err, hyp + PNP_CHUNK), e3 = __shfl(err, hyp + 2 * PNP_CHUNK);
       int win = 1;
@@ -1423,8 +1438,7 @@ __global__ __launch_bounds__(64, 2) __attribute__((disable_tail_calls)) void k_p
         us[2 * lane + 1] = q[1];
       }
       __syncthreads();
-      epnp_refit_wave(mset, (const float*)pws, (const float*)us, cam, LDS_PTR(s_Rt[0]), r_ut, r_L, LDS_PTR(s_terms), LDS_PTR(s_red),
-                      LDS_PTR(s_mtm));
+      epnp_refit_wave(mset, (const float*)pws, (const float*)us, cam, LDS_PTR(s_Rt[0]), r_ut, LDS_PTR(s_scr));
     }
     __syncthreads();
     PROF(12);
@@ -1490,8 +1504,7 @@ __global__ __launch_bounds__(64, 2) __attribute__((disable_tail_calls)) void k_p
           }
         }
         __syncthreads();
-        epnp_refit_wave(best, (const float*)pws, (const float*)us, cam, LDS_PTR(s_RtRef), r_ut, r_L, LDS_PTR(s_terms), LDS_PTR(s_red),
-                        LDS_PTR(s_mtm));   // best == popcount(s_best)
+        epnp_refit_wave(best, (const float*)pws, (const float*)us, cam, LDS_PTR(s_RtRef), r_ut, LDS_PTR(s_scr));   // best == popcount(s_best)
         __syncthreads();
         int rcnt = 0;
         for (int w = 0; w < nwords; w++) {
@@ -1562,24 +1575,22 @@ __global__ __launch_bounds__(64, 2) __attribute__((disable_tail_calls)) void k_p
 
 // diagnostics: EPnP alone on explicit correspondences (one lane)
 __global__ __launch_bounds__(64, 2) __attribute__((disable_tail_calls)) void k_epnp_debug(int n, const double* pws, const double* us, EpnpCam cam, double* out13) {
-  __shared__ double s_work[PNP_CHUNK * (156 + 60)];
-  __shared__ double s_mtm[144], s_terms[64 * 9], s_red[64], s_Rt[12];
-  __shared__ double s_Mrows[PNP_CHUNK * 4 * 24];
+  __shared__ double s_work[pnp_lds::kWorkDoubles], s_scr[pnp_lds::kScrDoubles], s_Rt[12];   // as in k_pnp
   const int lane = threadIdx.x;
-  const LArr ut{LDS_PTR(s_work)}, L{LDS_PTR(s_work) + 156 * PNP_CHUNK};
   double e;
   if (n == 4) {   // the RANSAC minimal-set solver: lanes 0, PNP_CHUNK, 2 * PNP_CHUNK run the three variants
     double R[3][3], t[3];
     const int hyp = lane % PNP_CHUNK, variant = lane / PNP_CHUNK + 1;
     const bool active = hyp == 0 && variant <= 3;
-    const LArr h_ut{LDS_PTR(s_work) + hyp}, h_L{LDS_PTR(s_work) + 156 * PNP_CHUNK + hyp};   // per-hypothesis views, as in k_pnp
+    const LMat h_ut{LDS_PTR(s_work), hyp};   // per-hypothesis views, as in k_pnp
+    const LArr h_L{LDS_PTR(s_scr) + pnp_lds::kL + hyp};
     const double err = epnp_minimal(
         active, variant,
         [&](int k, double* pw, double* u) {
           for (int j = 0; j < 3; j++) pw[j] = pws[3 * k + j];
           for (int j = 0; j < 2; j++) u[j] = us[2 * k + j];
         },
-        cam, R, t, h_ut, h_L, LDS_PTR(s_Mrows), 1);
+        cam, R, t, h_ut, h_L, LDS_PTR(s_scr), 1);
     const double e1 = __shfl(err, 0), e2 = __shfl(err, PNP_CHUNK), e3 = __shfl(err, 2 * PNP_CHUNK);
     int win = 1;
     e = e1;
@@ -1591,8 +1602,8 @@ __global__ __launch_bounds__(64, 2) __attribute__((disable_tail_calls)) void k_e
     }
     __syncthreads();
   } else {
-    epnp_refit_wave(n, pws, us, cam, LDS_PTR(s_Rt), ut, L, LDS_PTR(s_terms), LDS_PTR(s_red), LDS_PTR(s_mtm));
-    e = s_red[63];
+    epnp_refit_wave(n, pws, us, cam, LDS_PTR(s_Rt), LMat{LDS_PTR(s_work), 0}, LDS_PTR(s_scr));
+    e = s_scr[pnp_lds::kRed + 63];
   }
   if (lane == 0) {
     for (int i = 0; i < 12; i++) out13[i] = s_Rt[i];
