@@ -386,6 +386,85 @@ class ORBmatcher {
     batch.SetCurrentBroadcast(-1);
     check(rc);
   }
+  // void LocalMapping::CreateNewMapPoints()                                                  src/LocalMapping.cc:187-420
+  // pKF1 = mpCurrentKeyFrame (frame 0 of the cur extractor, broadcast), vpNeighKFs = GetBestCovisibilityKeyFrames(nn) (frame i
+  // of the ref extractor).  The device searches every neighbour, triangulates every match with the reference's tests and
+  // numbers the new points in the reference's creation order (sd_track_triangulate); the caller's objects are made here, in
+  // that order (WalkNewPoints).  nNextId = MapPoint::nNextId; make_point(Xw[3], pKF1, id) is `new MapPoint(x3D, pKF1, mpMap)`
+  // (+ mpMap->AddMapPoint, which stays the caller's); recent = mlpRecentAddedMapPoints.  Returns nnew.  The matcher must have
+  // been made with checkOri = false, as the reference's `ORBmatcher matcher(0.6, false)` is.  CheckNewKeyFrames' early return
+  // between neighbours is not taken: all neighbours are done in one call.
+  // KeyFrameT needs, besides what SearchForTriangulation needs, mvDepth, ComputeSceneMedianDepth(q) and AddMapPoint(pMP, idx);
+  // MapPointT needs AddObservation(pKF, idx), SetDescriptor(const uint8_t*), SetNormalVector(const double*),
+  // SetMaxDistance(float) and SetMinDistance(float): what ComputeDistinctiveDescriptors and UpdateNormalAndDepth would compute.
+  template <class KeyFrameT, class MakePoint, class RecentList>
+  int CreateNewMapPoints(TrackBatch& batch, KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpNeighKFs, bool monocular, int32_t nNextId,
+                         MakePoint make_point, RecentList& recent, int kp_cap) {
+    const int n = (int)vpNeighKFs.size();
+    if (n == 0) return 0;
+    std::vector<float> z(kp_cap, -1.f), median(n, -1.f);
+    for (int i = 0; i < pKF1->N && i < kp_cap; i++) z[i] = pKF1->mvDepth[i];
+    check(sd_track_set_tri_depth(batch.handle(), 0, 0, 1, z.data(), kp_cap));
+    for (int k = 0; k < n; k++) {
+      KeyFrameT* pKF2 = vpNeighKFs[k];
+      UploadTriangulationSlot(batch, k, pKF1, pKF2, kp_cap);
+      std::fill(z.begin(), z.end(), -1.f);
+      for (int i = 0; i < pKF2->N && i < kp_cap; i++) z[i] = pKF2->mvDepth[i];
+      check(sd_track_set_tri_depth(batch.handle(), 1, k, 1, z.data(), kp_cap));
+      if (monocular) median[k] = pKF2->ComputeSceneMedianDepth(2);
+    }
+    check(sd_track_set_tri_median_depth(batch.handle(), 0, n, median.data()));
+    check(sd_track_set_next_map_id(batch.handle(), 0, 1, &nNextId));
+    batch.SetCurrentBroadcast(0);
+    int rc = sd_track_search_for_triangulation(batch.handle(), n, 0, 0);
+    if (rc == SD_OK) rc = sd_track_triangulate(batch.handle(), n, monocular ? 1 : 0);
+    NewPointRows rows;
+    if (rc == SD_OK) rc = DownloadNewPoints(batch, rows);
+    batch.SetCurrentBroadcast(-1);
+    check(rc);
+    return WalkNewPoints(rows, pKF1, vpNeighKFs, make_point, recent);
+  }
+  // The rows of sd_track_get_new_points, in (neighbour, idx1) order
+  struct NewPointRows {
+    std::vector<int32_t> kp1, slot, idx2, id;
+    std::vector<double> Xw, normal;        // [n][3]
+    std::vector<float> max_dist, min_dist;
+    std::vector<uint8_t> desc;             // [n][32]
+    size_t size() const { return kp1.size(); }
+  };
+  int DownloadNewPoints(TrackBatch& batch, NewPointRows& r) {
+    int32_t info[4] = {0, 0, 0, 0};
+    int rc = sd_track_get_new_points(batch.handle(), info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+    if (rc != SD_OK) return rc;
+    const size_t n = (size_t)info[0];
+    r.kp1.resize(n); r.slot.resize(n); r.idx2.resize(n); r.id.resize(n);
+    r.Xw.resize(n * 3); r.normal.resize(n * 3); r.max_dist.resize(n); r.min_dist.resize(n); r.desc.resize(n * 32);
+    if (n == 0) return SD_OK;
+    return sd_track_get_new_points(batch.handle(), info, r.kp1.data(), r.slot.data(), r.idx2.data(), r.id.data(), r.Xw.data(),
+                                   r.normal.data(), r.max_dist.data(), r.min_dist.data(), r.desc.data(), (int)n);
+  }
+  // :401-417 for every row, in order: the point, its two observations, both keyframes' AddMapPoint, descriptor, normal and
+  // distances from the device's fields, mlpRecentAddedMapPoints.  Host code only.
+  template <class KeyFrameT, class MakePoint, class RecentList>
+  static int WalkNewPoints(const NewPointRows& r, KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpNeighKFs, MakePoint make_point,
+                           RecentList& recent) {
+    int nnew = 0;
+    for (size_t p = 0; p < r.size(); p++) {
+      KeyFrameT* pKF2 = vpNeighKFs[(size_t)r.slot[p]];
+      auto* pMP = make_point(&r.Xw[p * 3], pKF1, r.id[p]);
+      pMP->AddObservation(pKF1, (size_t)r.kp1[p]);
+      pMP->AddObservation(pKF2, (size_t)r.idx2[p]);
+      pKF1->AddMapPoint(pMP, (size_t)r.kp1[p]);
+      pKF2->AddMapPoint(pMP, (size_t)r.idx2[p]);
+      pMP->SetDescriptor(&r.desc[p * 32]);
+      pMP->SetNormalVector(&r.normal[p * 3]);
+      pMP->SetMaxDistance(r.max_dist[p]);
+      pMP->SetMinDistance(r.min_dist[p]);
+      recent.push_back(pMP);
+      nnew++;
+    }
+    return nnew;
+  }
   int TriangulationResult(TrackBatch& batch, int frame, std::vector<std::pair<size_t, size_t> >& vMatchedPairs, int kp_cap) {
     std::vector<int32_t> m12(kp_cap);
     int32_t n = 0;

@@ -386,6 +386,64 @@ int sd_debug_search_for_triangulation(int n1, int n2, const sd_keypoint* kps1, c
                                       const float* uright2, const double* F12_rm9, const float* epipole2, const float* scale_factors,
                                       const float* level_sigma2, int nlevels, int check_ori, int32_t* matches12, int32_t* n_matches);
 
+/* LocalMapping::CreateNewMapPoints after the search (src/LocalMapping.cc:219-419 with KeyFrame::UnprojectStereo
+ *   src/KeyFrame.cc:572-585 and MapPoint::UpdateNormalAndDepth src/MapPoint.cc:304-343)
+ * on the live result of sd_track_search_for_triangulation, same pairing, poses, mvuRight rows and camera: every match is
+ * triangulated and tested as :268-399 does (operand widths and operation order: sdslam_amd/csrc/track_newpoints_tri.hip), and
+ * the accepted ones become map point rows.  Nothing is downloaded in between.
+ * sd_track_set_tri_depth: mvDepth rows, [n_frames][cap], rows shorter than the keypoint capacity leave the rest.  side 0: the
+ *   frames of `cur` (frame0 counts cur frames: in broadcast mode KF1's row is the broadcast frame's) -- the row
+ *   sd_track_stereo_from_depth / _device fill, so an RGB-D caller needs side 1 only; side 1: the frames of `ref`.  -1 everywhere
+ *   for a new handle.  Only rows of keypoints with mvuRight >= 0 are read.  Ordered on the tracking stream; returns once the
+ *   rows are read.
+ * sd_track_set_tri_median_depth: ComputeSceneMedianDepth(2) of KF2 per slot for the monocular baseline gate (:234-238); a
+ *   negative entry (the value of a new handle) switches the slot's gate off.  Queued on the tracking stream.
+ * sd_track_triangulate: monocular = mbMonocular (it selects the baseline gate of :230-239 only).  Queued on the tracking
+ *   stream: no host wait, no allocation.  SD_ERR_INVALID_ARG when no live search result covers the slots, and under the
+ *   broadcast when that search ran with check_ori = 1 (its rows are then not independent; the reference's matcher has it off).  Under
+ *   sd_track_set_current_broadcast a KF1 keypoint becomes a point of the FIRST slot that accepts it, which is the reference's
+ *   loop over the neighbours; ids count from slot 0's sd_track_set_next_map_id value, which advances.  Paired: every accepted
+ *   row is a point of its slot, ids count from the slot's own counter, which advances.
+ * sd_track_get_triangulated (synchronises; NULL outputs are skipped): verdict / branch [n_frames][cap], Xw [n_frames][cap][3],
+ *   cap >= keypoint capacity; n_accepted[f] = rows with verdict SD_TRI_ACCEPTED.  Xw is x3D of every row that chose a branch.
+ * sd_track_get_new_points (synchronises; NULL outputs are skipped): info4 = points, the broadcast setting, slots, the next id
+ *   (-1 when paired: the slots' counters); then per point in (slot, idx1) order, arrays of cap >= info4[0] entries: the KF1
+ *   keypoint, the slot, the KF2 keypoint, the id, Xw[3], mNormalVector[3], mfMaxDistance, mfMinDistance (sd_track_set_local
+ *   takes 1.2f * and 0.8f * these) and the descriptor (KF1's keypoint's: of two observations the reference returns the first
+ *   in pointer order).  SD_ERR_CAPACITY when cap is smaller; info4 is filled first.
+ * A result ends with whatever ends the search's result, and with sd_track_set_tri_depth / _set_tri_median_depth /
+ *   _set_camera / sd_track_stereo_from_depth / _device (they rewrite KF1's mvuRight and mvDepth, and end the search's result
+ *   too): the getters then fail with SD_ERR_INVALID_ARG until sd_track_triangulate has run again.
+ * sd_debug_triangulate: one keyframe pair and an explicit matches12 row (n1 entries, -1 or < n2) from host arrays through the
+ *   same kernel, synchronous, with buffers of its own.  kps*_un = mvKeysUn, kps* = mvKeys; cam5 = fx, fy, cx, cy, mbf;
+ *   scale_factor = mfScaleFactor; verdict / branch [n1], Xw [n1][3]. */
+#define SD_TRI_NO_MATCH 0
+#define SD_TRI_ACCEPTED 1
+#define SD_TRI_LOW_PARALLAX 2   /* no stereo and low parallax (:322) */
+#define SD_TRI_W_ZERO 3         /* x3D[3] == 0 (:311) */
+#define SD_TRI_Z1 4             /* z1 <= 0 */
+#define SD_TRI_Z2 5
+#define SD_TRI_REPROJ1 6        /* reprojection error in KF1 */
+#define SD_TRI_REPROJ2 7
+#define SD_TRI_DIST_ZERO 8      /* dist1 == 0 || dist2 == 0 */
+#define SD_TRI_SCALE 9          /* scale consistency (:398) */
+#define SD_TRI_SLOT_GATED 10    /* the neighbour's baseline is too short (:225-239) */
+#define SD_TRI_BRANCH_SVD 1
+#define SD_TRI_BRANCH_UNPROJECT1 2
+#define SD_TRI_BRANCH_UNPROJECT2 3
+int sd_track_set_tri_depth(sd_track* h, int side, int frame0, int n_frames, const float* depth, int cap);
+int sd_track_set_tri_median_depth(sd_track* h, int frame0, int n_frames, const float* median_depth);
+int sd_track_triangulate(sd_track* h, int n_frames, int monocular);
+int sd_track_get_triangulated(sd_track* h, int frame0, int n_frames, uint8_t* verdict, uint8_t* branch, double* Xw, int cap,
+                              int32_t* n_accepted);
+int sd_track_get_new_points(sd_track* h, int32_t* info4, int32_t* kp1, int32_t* slot, int32_t* idx2, int32_t* ids, double* Xw,
+                            double* normal, float* max_dist, float* min_dist, uint8_t* desc, int cap);
+int sd_debug_triangulate(int n1, int n2, const sd_keypoint* kps1_un, const sd_keypoint* kps1, const float* uright1, const float* depth1,
+                         const sd_keypoint* kps2_un, const sd_keypoint* kps2, const float* uright2, const float* depth2,
+                         const int32_t* matches12, const double* Tcw1_cm16, const double* Tcw2_cm16, const float* cam5,
+                         const float* scale_factors, const float* level_sigma2, int nlevels, float scale_factor, int monocular,
+                         float median_depth, uint8_t* verdict, uint8_t* branch, double* Xw);
+
 /* ORBmatcher::Fuse, both overloads: the search (src/ORBmatcher.cc:493-594 with a keyframe pose, :639-715 with a Sim3 Scw;
  *   KeyFrame::GetFeaturesInArea / IsInImage src/KeyFrame.cc:529-570; MapPoint::PredictScale src/MapPoint.cc:355-369; callers
  *   LocalMapping::SearchInNeighbors src/LocalMapping.cc:422-492 and LoopClosing::SearchAndFuse src/LoopClosing.cc:535-560)

@@ -112,6 +112,12 @@ _SIGNATURES = {
     "sd_track_search_for_triangulation": (_I, [_P, _I, _I, _I]),
     "sd_track_get_triangulation_matches": (_I, [_P, _I, _I, _P, _I, _P, _P, _P]),
     "sd_debug_search_for_triangulation": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "sd_track_set_tri_depth": (_I, [_P, _I, _I, _I, _P, _I]),
+    "sd_track_set_tri_median_depth": (_I, [_P, _I, _I, _P]),
+    "sd_track_triangulate": (_I, [_P, _I, _I]),
+    "sd_track_get_triangulated": (_I, [_P, _I, _I, _P, _P, _P, _I, _P]),
+    "sd_track_get_new_points": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
+    "sd_debug_triangulate": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _I, _F, _P, _P, _P]),
     "sd_track_set_fuse_scw": (_I, [_P, _I, _I, _P]),
     "sd_track_fuse": (_I, [_P, _I, _I, _I, _F, _I]),
     "sd_track_get_fuse": (_I, [_P, _I, _I, _P, _P, _I, _P]),
@@ -704,6 +710,40 @@ class Tracker:
         _check(self.L.sd_track_get_triangulation_matches(self.h, frame0, n, _p(m), self.cap, _p(nm), _p(F), _p(e)))
         return dict(matches12=m, n_matches=nm, F12=F.reshape(n, 3, 3), epipole=e)
 
+    # --- LocalMapping::CreateNewMapPoints after the search (track_newpoints_tri.hip) ---
+    def set_tri_depth(self, side, frame0, depth):
+        """mvDepth rows [n, cap'] of the cur (side 0, indexed by cur frame) or ref (side 1) extractor's frames."""
+        d = np.ascontiguousarray(depth, np.float32)
+        assert d.ndim == 2
+        _check(self.L.sd_track_set_tri_depth(self.h, int(side), frame0, d.shape[0], _p(d), d.shape[1]))
+
+    def set_tri_median_depth(self, frame0, median_depth):
+        """ComputeSceneMedianDepth(2) of every slot's KF2 (monocular baseline gate); negative: no gate."""
+        a = np.ascontiguousarray(median_depth, np.float32)
+        _check(self.L.sd_track_set_tri_median_depth(self.h, frame0, len(a), _p(a)))
+
+    def triangulate(self, n_frames, monocular=True):
+        """Triangulate and test every match of the live search_for_triangulation result, then number the new points."""
+        _check(self.L.sd_track_triangulate(self.h, n_frames, int(monocular)))
+
+    def get_triangulated(self, frame0, n):
+        v, b = np.zeros((n, self.cap), np.uint8), np.zeros((n, self.cap), np.uint8)
+        X, na = np.zeros((n, self.cap, 3)), np.zeros(n, np.int32)
+        _check(self.L.sd_track_get_triangulated(self.h, frame0, n, _p(v), _p(b), _p(X), self.cap, _p(na)))
+        return dict(verdict=v, branch=b, Xw=X, n_accepted=na)
+
+    def get_new_points(self):
+        """The points of the last triangulate() in (slot, idx1) order."""
+        info = np.zeros(4, np.int32)
+        _check(self.L.sd_track_get_new_points(self.h, _p(info), *[None] * 9, 0))
+        n = int(info[0])
+        i32 = [np.zeros(n, np.int32) for _ in range(4)]
+        X, N = np.zeros((n, 3)), np.zeros((n, 3))
+        mx, mn, d = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros((n, 32), np.uint8)
+        if n:
+            _check(self.L.sd_track_get_new_points(self.h, _p(info), *[_p(a) for a in i32], _p(X), _p(N), _p(mx), _p(mn), _p(d), n))
+        return dict(info=info, kp1=i32[0], slot=i32[1], idx2=i32[2], id=i32[3], Xw=X, normal=N, max_dist=mx, min_dist=mn, desc=d)
+
     # --- ORBmatcher::Fuse, both overloads (src/ORBmatcher.cc:477-732); the points are set_local's rows ---
     def set_fuse_scw(self, frame0, Scw):
         """The Sim3 Scw per slot, [n, 4, 4], for fuse(sim3=True)."""
@@ -962,6 +1002,28 @@ def debug_search_for_triangulation(kps1, desc1, has_mp1, uright1, kps2, desc2, h
     _check(L.sd_debug_search_for_triangulation(n1, n2, _p(k1), _p(d1), _p(h1), _p(u1), _p(k2), _p(d2), _p(h2), _p(u2), _p(F), _p(e),
                                                _p(sf), _p(s2), len(sf), int(check_ori), _p(m), _p(n)))
     return int(n[0]), m[:n1]
+
+
+def debug_triangulate(kps1_un, kps1, uright1, depth1, kps2_un, kps2, uright2, depth2, matches12, Tcw1, Tcw2, cam5, scale_factors,
+                      level_sigma2, scale_factor, monocular=True, median_depth=-1.0):
+    """One keyframe pair and a matches12 row from host arrays through k_triangulate (diagnostics): (verdict, branch, Xw)."""
+    L = lib()
+    k1u, k1 = np.ascontiguousarray(kps1_un, KP_DTYPE), np.ascontiguousarray(kps1, KP_DTYPE)
+    k2u, k2 = np.ascontiguousarray(kps2_un, KP_DTYPE), np.ascontiguousarray(kps2, KP_DTYPE)
+    n1, n2 = len(k1u), len(k2u)
+    u1, z1 = np.ascontiguousarray(uright1, np.float32), np.ascontiguousarray(depth1, np.float32)
+    u2, z2 = np.ascontiguousarray(uright2, np.float32), np.ascontiguousarray(depth2, np.float32)
+    m = np.ascontiguousarray(matches12, np.int32)
+    assert len(k1) == len(u1) == len(z1) == len(m) == n1 and len(k2) == len(u2) == len(z2) == n2
+    T1, T2 = _cm(Tcw1), _cm(Tcw2)
+    cam = np.ascontiguousarray(cam5, np.float32)
+    sf, s2 = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(level_sigma2, np.float32)
+    assert len(cam) == 5 and len(sf) == len(s2)
+    v, b, X = np.zeros(max(n1, 1), np.uint8), np.zeros(max(n1, 1), np.uint8), np.zeros((max(n1, 1), 3))
+    _check(L.sd_debug_triangulate(n1, n2, _p(k1u), _p(k1), _p(u1), _p(z1), _p(k2u), _p(k2), _p(u2), _p(z2), _p(m), _p(T1), _p(T2),
+                                  _p(cam), _p(sf), _p(s2), len(sf), float(scale_factor), int(monocular), float(median_depth), _p(v),
+                                  _p(b), _p(X)))
+    return v[:n1], b[:n1], X[:n1]
 
 
 def debug_fuse(kps, desc, uright, pts, T, cam9, scale_factors, inv_level_sigma2, scale_factor, th=3.0, sim3=False, kp_cap=None,

@@ -197,6 +197,17 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &tb.tri_epi, B * 2));
   A(dalloc<FILL_FF>(h, &tb.tri_match, B * K));
   A(dalloc(h, &tb.tri_n, B));
+  A(dalloc<FILL_MINUS_ONE>(h, &h->nb.depth_ref, B * K));
+  A(dalloc<FILL_MINUS_ONE>(h, &h->nb.median, B));
+  A(dalloc(h, &h->nb.verdict, B * K));
+  A(dalloc(h, &h->nb.branch, B * K));
+  A(dalloc(h, &h->nb.Xw, B * K * 3));
+  A(dalloc(h, &h->nb.count, B * 2));
+  A(dalloc(h, &h->nb.info, 4));
+  A(dalloc(h, &h->nb.pt, B * K * 4));
+  A(dalloc(h, &h->nb.geo, B * K * 6));
+  A(dalloc(h, &h->nb.dist, B * K * 2));
+  A(dalloc(h, &h->nb.desc, B * K * 32));
   A(dalloc(h, &h->fu.Scw, B * 16));
   A(dalloc(h, &h->fu.pose, B * 15));
   A(dalloc<FILL_FF>(h, &h->fu.idx, B * M));
@@ -325,6 +336,7 @@ int sd_track_set_camera(sd_track* h, float fx, float fy, float cx, float cy, flo
   c.mb = bf / fx;
   h->have_cam = true;
   fuse_end(h);           // a Fuse result was projected with the old K and image bounds
+  triang_end(h);         // ... and a triangulation used the old K and mbf
   return SD_OK;
 }
 
@@ -693,6 +705,7 @@ int sd_track_set_uright(sd_track* h, int frame0, int n_frames, const float* urig
 int sd_track_stereo_from_depth(sd_track* h, int n_frames, const float* depth, int w, int hgt, int stride_elems, size_t frame_stride_elems) {
   SD_TRY(check_ready(h, n_frames, true));
   SD_REQUIRE(depth && w >= 1 && hgt >= 1 && stride_elems >= w, SD_ERR_INVALID_ARG, "bad depth image");
+  tri_end(h);            // mvuRight and mvDepth of KF1 are being replaced
   SD_HIP_CHECK(hipStreamSynchronize(h->pnp_stream));   // a queued match may still read the stereo arrays
   float* d_depth = nullptr;
   const size_t total = (size_t)n_frames * w * hgt;
@@ -723,6 +736,7 @@ int sd_track_stereo_from_depth_device(sd_track* h, int n_frames, const void* d_d
              "bad depth image (NULL, unknown dtype, empty or stride < w)");
   SD_REQUIRE((uintptr_t)d_depth % (dtype == SD_DEPTH_U16 ? 2 : 4) == 0, SD_ERR_INVALID_ARG, "depth pointer not aligned to its element size");
   // mDepthMapFactor and the convertTo condition, in the reference's float arithmetic
+  tri_end(h);            // mvuRight and mvDepth of KF1 are being replaced
   const float scale = std::fabs(depth_map_factor) < 1e-5 ? 1.0f : 1.0f / depth_map_factor;
   const bool convert = std::fabs(scale - 1.0f) > 1e-5 || dtype != SD_DEPTH_F32;
   return run_stage(h, false, false, STAGE_NONE, [&](hipStream_t s) {

@@ -86,6 +86,10 @@ struct sd_track {
   RunStamp tri;                    // mode = the broadcast setting the search ran under
   unsigned long long tri_ref_serial = 0;   // ... and on THIS extraction of `ref`
   std::vector<uint8_t> f12_set;    // [max_batch] sd_track_set_f12 has covered the slot
+  // CreateNewMapPoints after the search (track_newpoints_tri.hip): the result sd_track_get_triangulated / _get_new_points
+  // return while the stamp AND the search's hold (tri_end ends both; triang_end this one alone)
+  RunStamp triang;                 // mode = the broadcast setting it ran under
+  sd::TriangBuffers nb{};
   // ORBmatcher::Fuse (track_fuse.hip): the result sd_track_get_fuse returns while the stamp holds (fuse_end)
   struct FuseStamp {
     int n = 0, kf_side = 0, bcast = -1;   // slots < n hold a result of this side, searched under this broadcast setting ...
@@ -139,7 +143,15 @@ inline bool RunStamp::covers(const sd_track* h, int n_frames) const {
 // Something a Sim3Solver was constructed from is being replaced: sd_track_sim3_iterate refuses until sd_track_sim3 runs again
 static inline void sim3_end(sd_track* h) { h->sim3 = RunStamp{}; }
 // Something a SearchForTriangulation result was computed from is being replaced: the getter refuses until the search runs again
-static inline void tri_end(sd_track* h) { h->tri = RunStamp{}; }
+static inline void triang_end(sd_track* h) { h->triang = RunStamp{}; }
+static inline void tri_end(sd_track* h) {
+  h->tri = RunStamp{};
+  triang_end(h);   // the triangulation of those matches goes with them
+}
+// The search's result for slots < n_frames is the one its inputs still describe
+static inline bool tri_live(const sd_track* h, int n_frames) {
+  return h->tri.covers(h, n_frames) && h->tri_ref_serial == h->ref->extract_serial && h->tri.mode == h->tb.cur_bcast;
+}
 // Something a Fuse result was computed from is being replaced: sd_track_get_fuse refuses until sd_track_fuse runs again
 static inline void fuse_end(sd_track* h) { h->fuse = sd_track::FuseStamp{}; }
 
@@ -283,6 +295,17 @@ static inline int wait_for(hipStream_t s) {
   SD_HIP_CHECK(hipStreamSynchronize(s));
   return SD_OK;
 }
+
+// One device allocation of a debug entry (sd_debug_search_for_triangulation, sd_debug_triangulate), carved in 16-byte steps
+struct Blob {
+  uint8_t* base = nullptr;
+  size_t bytes = 0;
+  size_t reserve(size_t n) {
+    const size_t off = bytes;
+    bytes += (n + 15) & ~(size_t)15;
+    return off;
+  }
+};
 
 // Slots frame0 .. frame0 + n - 1 of a device buffer with per_slot elements a slot, to / from a dense host array.  A NULL host
 // pointer is an output the caller does not want / an input it leaves as it is: no copy.

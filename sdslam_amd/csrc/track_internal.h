@@ -161,6 +161,12 @@ __device__ __forceinline__ double pose_product_entry(const double* __restrict__ 
   return v;
 }
 
+// (x0 * y0 + x1 * y1) + x2 * y2, every product and sum rounded on its own: the 3-vector product of track_tri.hip and
+// track_newpoints_tri.hip
+__device__ __forceinline__ double dot3(double x0, double x1, double x2, double y0, double y1, double y2) {
+  return __dadd_rn(__dadd_rn(__dmul_rn(x0, y0), __dmul_rn(x1, y1)), __dmul_rn(x2, y2));
+}
+
 // The map point mvpMapPoints[i] = m keeps after Tracking::Track's "Clean VO matches" (Observations() >= 1, reference
 // src/Tracking.cc:250-257) and outlier discard (:272-275): source 0 = cur_match after TrackWithMotionModel's discard (no
 // outlier flags left), 1 = un_match after TrackLocalMap, m >= M naming local point m - M, outl_i = &mvbOutlier[i].
@@ -234,6 +240,25 @@ struct FuseBuffers {
 int launch_fuse(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const FuseBuffers& fb, const TrackCam& cam, const float* d_sf,
                 const float* d_inv_sigma2, const float* d_scale_thr, int n_frames, int kf_side, int point_row, float th, int sim3,
                 hipStream_t s);
+// LocalMapping::CreateNewMapPoints after the search (track_newpoints_tri.hip): what triangulation owns besides the search's
+// result (tb.tri_match), the pairing's keypoints, mvuRight rows and poses it reads.  Kept out of TrackBuffers like FuseBuffers.
+struct TriangBuffers {
+  float* depth_ref;      // [B][kp_cap] mvDepth of the ref extractor's frames (the cur side's is tb.depth)
+  float* median;         // [B]   ComputeSceneMedianDepth(2) of KF2; negative: the slot's baseline gate is off
+  uint8_t* verdict;      // [B][kp_cap] 0 no match, 1 accepted, 2.. the gate that rejected (SD_TRI_* of sdslam_hip.h)
+  uint8_t* branch;       // [B][kp_cap] 0 none, 1 linear triangulation, 2 UnprojectStereo(idx1), 3 UnprojectStereo(idx2)
+  double* Xw;            // [B][kp_cap][3] x3D of every row that chose a branch
+  int32_t* count;        // [B][2] rows with verdict 1 | rows that became a point of this slot
+  // the new points in (slot, idx1) order, B * kp_cap rows
+  int32_t* info;         // [4]: points, the broadcast setting, slots, MapPoint::nNextId after the last one
+  int32_t* pt;           // [..][4] KF1 keypoint | the neighbour (slot) that triangulated it | KF2 keypoint | id
+  double* geo;           // [..][6] Xw | mNormalVector
+  float* dist;           // [..][2] mfMaxDistance | mfMinDistance
+  uint8_t* desc;         // [..][32] GetDescriptor()
+};
+// k_triangulate on the live search result of slots < n_frames, then k_new_points_resolve.  ratio_factor = 1.5f * mfScaleFactor
+int launch_triangulate(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const TriangBuffers& nb, const TrackCam& cam,
+                       const float* d_sf, const float* d_sigma2, float ratio_factor, int n_frames, int monocular, hipStream_t s);
 int launch_stereo_from_depth(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_depth, int w, int h,
                              int stride_elems, size_t frame_stride_elems, int n_frames, hipStream_t s);
 // the same on a depth map of uint16_t (u16 != 0, always converted) or float elements; convert: d = (float)raw * scale

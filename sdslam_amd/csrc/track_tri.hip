@@ -62,10 +62,6 @@ struct TriBuffers {
   int32_t* n;            // [B]
 };
 
-// (x0 * y0 + x1 * y1) + x2 * y2
-__device__ __forceinline__ double dot3(double x0, double x1, double x2, double y0, double y1, double y2) {
-  return __dadd_rn(__dadd_rn(__dmul_rn(x0, y0), __dmul_rn(x1, y1)), __dmul_rn(x2, y2));
-}
 // out = A * B, row-major 3 x 3
 __device__ __forceinline__ void mul33(const double* A, const double* B, double* out) {
   for (int r = 0; r < 3; r++)
@@ -326,19 +322,6 @@ int launch_tri(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& b, cons
 
 using namespace sd;
 
-// One device allocation of the debug entry, carved in 16-byte steps
-namespace {
-struct Blob {
-  uint8_t* base = nullptr;
-  size_t bytes = 0;
-  size_t reserve(size_t n) {
-    const size_t off = bytes;
-    bytes += (n + 15) & ~(size_t)15;
-    return off;
-  }
-};
-}  // namespace
-
 extern "C" {
 
 int sd_track_set_uright_ref(sd_track* h, int frame0, int n_frames, const float* uright, int cap) {
@@ -370,7 +353,7 @@ int sd_track_search_for_triangulation(sd_track* h, int n_frames, int use_set_f12
   SD_TRY(run_stage(h, true, false, STAGE_MATCH, [&](hipStream_t s) {   // timed in the matcher's slot
     return launch_tri(h->cur, h->ref, h->tb, h->cam, h->d_sf, h->d_sigma2, n_frames, use_set_f12, check_ori, s);
   }));
-  h->tri.set(h, n_frames, h->tb.cur_bcast);
+  h->tri.set(h, n_frames, h->tb.cur_bcast, check_ori != 0);   // source: the rotation check ran (sd_track_triangulate asks)
   h->tri_ref_serial = h->ref->extract_serial;
   return SD_OK;
 }
