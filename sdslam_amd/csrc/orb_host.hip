@@ -428,7 +428,7 @@ int sd_orb_download_undistorted(sd_orb* h, int frame0, int n_frames, sd_keypoint
   SD_TRY(check_frame_range(h, frame0, n_frames));
   std::vector<int32_t> n(n_frames);
   SD_TRY(download_counts(h, frame0, n_frames, cap_per_frame, false, n.data()));
-  SD_TRY(download_rows(h, h->have_dist ? h->d_kps_un : h->d_kps, sizeof(sd_keypoint), kps_un_out, frame0, n_frames, cap_per_frame, n.data()));
+  SD_TRY(download_rows(h, keys_un(h), sizeof(sd_keypoint), kps_un_out, frame0, n_frames, cap_per_frame, n.data()));
   SD_HIP_CHECK(hipStreamSynchronize(h->stream));
   return SD_OK;
 }

@@ -121,6 +121,9 @@ static inline int keypoint_capacity(const sd_orb* h) {
   return n;
 }
 
+// Frame::mvKeysUn of the most recent extraction: the keypoints themselves where the camera has no distortion
+static inline sd_keypoint* keys_un(const sd_orb* h) { return h->have_dist ? h->d_kps_un : h->d_kps; }
+
 static inline void select_set(sd_orb* h, int sidx) {
   h->set = sidx;
   h->d_pyr = h->pyr_set[sidx];

@@ -328,15 +328,9 @@ int sd_track_set_camera(sd_track* h, float fx, float fy, float cx, float cy, flo
                         float max_y) {
   SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
   SD_REQUIRE(fx > 0 && fy > 0 && max_x > min_x && max_y > min_y, SD_ERR_INVALID_ARG, "bad camera parameters");
-  TrackCam& c = h->cam;
-  c.ffx = fx; c.ffy = fy; c.fcx = cx; c.fcy = cy;
-  c.fx = fx; c.fy = fy; c.cx = cx; c.cy = cy;
-  c.min_x = min_x; c.max_x = max_x; c.min_y = min_y; c.max_y = max_y;
-  c.bf = bf;
-  c.mb = bf / fx;
+  h->cam = make_cam(fx, fy, cx, cy, bf, min_x, max_x, min_y, max_y);
   h->have_cam = true;
-  fuse_end(h);           // a Fuse result was projected with the old K and image bounds
-  triang_end(h);         // ... and a triangulation used the old K and mbf
+  END_RESULTS(h, "sd_track_set_camera");
   return SD_OK;
 }
 
@@ -344,7 +338,7 @@ int sd_track_set_last(sd_track* h, int frame0, int n_frames, const int32_t* n_la
                       const uint8_t* desc, const int32_t* octave, const float* angle, const int32_t* obs) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(n_last && valid && Xw && desc && octave && angle && obs, SD_ERR_INVALID_ARG, "NULL argument");
-  h->have_pnp = false;   // the solvers' 3-D points are being replaced
+  END_RESULTS(h, "sd_track_set_last");
   const size_t M = h->max_points, o = (size_t)frame0, n = (size_t)n_frames;
   for (int f = 0; f < n_frames; f++) SD_REQUIRE(n_last[f] >= 0 && n_last[f] <= h->max_points, SD_ERR_CAPACITY, "n_last exceeds max_points");
   // the octave indexes mvScaleFactors / mvLevelSigma2 on the device (search radius, level window)
@@ -368,9 +362,7 @@ int sd_track_set_last(sd_track* h, int frame0, int n_frames, const int32_t* n_la
 int sd_track_set_poses(sd_track* h, int frame0, int n_frames, const double* Tref_cm, const double* Tcur_cm) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(Tref_cm && Tcur_cm, SD_ERR_INVALID_ARG, "NULL argument");
-  sim3_end(h);           // the Sim3 solvers' keyframe poses are being replaced
-  tri_end(h);            // ... and the poses F12 and the epipole were computed from
-  fuse_end(h);           // ... and the keyframe pose of a Fuse result
+  END_RESULTS(h, "sd_track_set_poses");
   hipStream_t s = h->cur->stream;
   SD_TRY(upload(h->tb.Tref, Tref_cm, frame0, n_frames, 16, s));
   SD_TRY(upload(h->tb.Tprior, Tcur_cm, frame0, n_frames, 16, s));
@@ -381,8 +373,7 @@ int sd_track_set_poses(sd_track* h, int frame0, int n_frames, const double* Tref
 int sd_track_set_rand(sd_track* h, int frame0, int n_frames, const int32_t* rand_values, int per_frame) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(rand_values && per_frame >= 1 && per_frame <= h->rand_per_frame, SD_ERR_INVALID_ARG, "bad rand stream");
-  h->have_pnp = false;   // a resumed iterate() continues at a position of the OLD stream
-  sim3_end(h);
+  END_RESULTS(h, "sd_track_set_rand");
   SD_TRY(upload_rows(h->tb.rand_stream, h->rand_per_frame, rand_values, per_frame, frame0, n_frames, h->cur->stream));
   SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
   for (int f = 0; f < n_frames; f++) h->rand_len[(size_t)frame0 + f] = per_frame;
@@ -411,7 +402,7 @@ int sd_track_align(sd_track* h, int n_frames, int mode) {
 
 int sd_track_match(sd_track* h, int n_frames, float th, int mono, int check_ori) {
   SD_TRY(check_ready(h, n_frames));
-  h->have_pnp = false;   // mvpMapPoints is rewritten: solvers built on the old vector cannot be continued
+  END_RESULTS(h, "sd_track_match");
   return run_stage(h, false, false, STAGE_MATCH, [&](hipStream_t s) {
     return launch_match(h->cur, h->tb, h->cam, h->d_sf, n_frames, th, mono, check_ori, s);
   });
@@ -425,7 +416,7 @@ int sd_track_set_local(sd_track* h, int frame0, int n_frames, const int32_t* n_l
   SD_REQUIRE(n_local && cand && Xw && normal && min_dist && max_dist && mf_max_dist && desc && obs, SD_ERR_INVALID_ARG, "NULL argument");
   const size_t M = h->max_points, K = h->kp_cap, o = (size_t)frame0, n = (size_t)n_frames;
   for (int f = 0; f < n_frames; f++) SD_REQUIRE(n_local[f] >= 0 && n_local[f] <= h->max_points, SD_ERR_CAPACITY, "n_local exceeds max_points");
-  fuse_end(h);           // sd_track_fuse reads these rows too
+  END_RESULTS(h, "sd_track_set_local");
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
   SD_TRY(upload(tb.lm_n, n_local, o, n, 1, s));
@@ -457,7 +448,7 @@ int sd_track_set_local_view(sd_track* h, int frame0, int n_frames, const int32_t
       SD_REQUIRE(!in_view[(size_t)f * M + i] || (level[(size_t)f * M + i] >= 0 && level[(size_t)f * M + i] < h->cur->nlevels), SD_ERR_INVALID_ARG,
                  "mnTrackScaleLevel of an in-view point outside [0, nlevels)");
   }
-  fuse_end(h);           // lm_n and lm_desc are rows sd_track_fuse reads
+  END_RESULTS(h, "sd_track_set_local_view");
   hipStream_t s = h->cur->stream;
   const TrackBuffers& tb = h->tb;
   SD_TRY(upload(tb.lm_n, n_local, o, n, 1, s));
@@ -533,7 +524,7 @@ int sd_track_with_motion_model(sd_track* h, int n_frames, int align_mode, float 
   SD_REQUIRE(min_matches >= 3 && min_inliers >= 0, SD_ERR_INVALID_ARG, "bad gates (reference: 20 matches, 10 inliers)");
   hipStream_t s = h->pnp_stream;
   const TrackBuffers& tb = h->tb;
-  h->have_pnp = false;
+  END_RESULTS(h, "sd_track_with_motion_model");
   const bool use_ref = align_mode >= 0;
   if (use_ref) SD_TRY(require_ref_frames(h, n_frames, true));
   SD_TRY(wait_inputs(h, use_ref, use_ref));
@@ -695,8 +686,7 @@ int sd_track_get_pose_opt(sd_track* h, int frame0, int n_frames, double* Tcw_cm,
 int sd_track_set_uright(sd_track* h, int frame0, int n_frames, const float* uright, int cap) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(uright && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad uright array");
-  tri_end(h);            // KF1's stereo bits are being replaced
-  fuse_end(h);           // ... and the mvuRight row of a Fuse result's chi-square gate
+  END_RESULTS(h, "sd_track_set_uright");
   SD_TRY(upload_rows(h->tb.uright, h->kp_cap, uright, cap, frame0, n_frames, h->cur->stream));
   return wait_for(h->cur->stream);
 }
@@ -705,7 +695,7 @@ int sd_track_set_uright(sd_track* h, int frame0, int n_frames, const float* urig
 int sd_track_stereo_from_depth(sd_track* h, int n_frames, const float* depth, int w, int hgt, int stride_elems, size_t frame_stride_elems) {
   SD_TRY(check_ready(h, n_frames, true));
   SD_REQUIRE(depth && w >= 1 && hgt >= 1 && stride_elems >= w, SD_ERR_INVALID_ARG, "bad depth image");
-  tri_end(h);            // mvuRight and mvDepth of KF1 are being replaced
+  END_RESULTS(h, "sd_track_stereo_from_depth");
   SD_HIP_CHECK(hipStreamSynchronize(h->pnp_stream));   // a queued match may still read the stereo arrays
   float* d_depth = nullptr;
   const size_t total = (size_t)n_frames * w * hgt;
@@ -719,10 +709,7 @@ int sd_track_stereo_from_depth(sd_track* h, int n_frames, const float* depth, in
   if (e == hipSuccess) rc = launch_stereo_from_depth(h->cur, h->tb, h->cam, d_depth, w, hgt, w, (size_t)w * hgt, n_frames, s);
   hipError_t e2 = hipStreamSynchronize(s);
   (void)hipFree(d_depth);
-  if (e != hipSuccess || e2 != hipSuccess) {
-    set_error(std::string("sd_track_stereo_from_depth: ") + hipGetErrorString(e != hipSuccess ? e : e2));
-    return SD_ERR_HIP;
-  }
+  if (e != hipSuccess || e2 != hipSuccess) return hip_error("sd_track_stereo_from_depth", e != hipSuccess ? e : e2);
   return rc;
 }
 
@@ -736,7 +723,7 @@ int sd_track_stereo_from_depth_device(sd_track* h, int n_frames, const void* d_d
              "bad depth image (NULL, unknown dtype, empty or stride < w)");
   SD_REQUIRE((uintptr_t)d_depth % (dtype == SD_DEPTH_U16 ? 2 : 4) == 0, SD_ERR_INVALID_ARG, "depth pointer not aligned to its element size");
   // mDepthMapFactor and the convertTo condition, in the reference's float arithmetic
-  tri_end(h);            // mvuRight and mvDepth of KF1 are being replaced
+  END_RESULTS(h, "sd_track_stereo_from_depth_device");
   const float scale = std::fabs(depth_map_factor) < 1e-5 ? 1.0f : 1.0f / depth_map_factor;
   const bool convert = std::fabs(scale - 1.0f) > 1e-5 || dtype != SD_DEPTH_F32;
   return run_stage(h, false, false, STAGE_NONE, [&](hipStream_t s) {
@@ -761,8 +748,7 @@ int sd_track_get_stereo(sd_track* h, int frame0, int n_frames, float* uright, fl
 int sd_track_set_point_flags(sd_track* h, int frame0, int n_frames, const uint8_t* has_mp_cur, const uint8_t* has_mp_ref, int cap) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(has_mp_cur && has_mp_ref && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad flag arrays (cap must be 1..keypoint capacity)");
-  sim3_end(h);           // the Sim3 solvers' validity test is being replaced
-  tri_end(h);            // ... and the map-point flags of a SearchForTriangulation result
+  END_RESULTS(h, "sd_track_set_point_flags");
   hipStream_t s = h->cur->stream;
   const size_t K = h->kp_cap, o = (size_t)frame0 * K;
   SD_HIP_CHECK(hipMemsetAsync(h->tb.sp_valid1 + o, 0, (size_t)n_frames * K, s));
@@ -774,9 +760,8 @@ int sd_track_set_point_flags(sd_track* h, int frame0, int n_frames, const uint8_
 
 int sd_track_search_by_points(sd_track* h, int n_frames, float nnratio, int check_ori) {
   SD_TRY(check_ready(h, n_frames));
-  SD_TRY(require_ref_frames(h, n_frames, false));
-  SD_REQUIRE(keypoint_capacity(h->ref) == h->kp_cap, SD_ERR_INVALID_ARG, "cur / ref extractors must share the keypoint capacity");
-  sim3_end(h);           // matches12 is rewritten: Sim3 solvers built on the old vector cannot be continued
+  SD_TRY(require_ref_frames(h, n_frames, false, true));
+  END_RESULTS(h, "sd_track_search_by_points");
   return run_stage(h, true, false, STAGE_MATCH, [&](hipStream_t s) {   // timed in the matcher's slot
     return launch_search_points(h->cur, h->ref, h->tb, n_frames, nnratio, check_ori, s);
   });
@@ -797,7 +782,7 @@ int sd_track_get_point_matches(sd_track* h, int frame0, int n_frames, int32_t* m
 int sd_track_set_matches(sd_track* h, int frame0, int n_frames, const int32_t* cur_match, int cap) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(cur_match && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad match array (cap must be 1..keypoint capacity)");
-  h->have_pnp = false;   // the saved best-inlier mask indexes the old correspondence list
+  END_RESULTS(h, "sd_track_set_matches");
   std::vector<int32_t> full((size_t)n_frames * h->kp_cap, -1), cnt((size_t)n_frames, 0);
   for (int f = 0; f < n_frames; f++)
     for (int i = 0; i < cap; i++) {
@@ -849,10 +834,8 @@ int sd_track_pnp(sd_track* h, int n_frames, double probability, int min_inliers,
   pp.rand_per_frame = h->rand_per_frame;
   pp.resume = 0;
   SD_TRY(run_pnp(h, n_frames, pp));
-  h->have_pnp = true;
-  h->pnp_serial = h->cur->extract_serial;
+  h->res.pnp.set(n_frames, BIND_PNP, inputs_now(h));
   h->pnp_params = pp;
-  h->pnp_frames = n_frames;
   h->pnp_iter_upper = (int)upper;
   return SD_OK;
 }
@@ -863,9 +846,9 @@ int sd_track_pnp(sd_track* h, int n_frames, double probability, int min_inliers,
 // n_iterations).  The match vector must not have been changed in between (the reference's solver holds its own copy).
 int sd_track_pnp_iterate(sd_track* h, int n_frames, int n_iterations) {
   SD_TRY(check_ready(h, n_frames));
-  SD_REQUIRE(h->have_pnp && n_frames <= h->pnp_frames, SD_ERR_INVALID_ARG,
+  SD_REQUIRE(h->res.pnp.covers(n_frames), SD_ERR_INVALID_ARG,
              "sd_track_pnp has not constructed solvers for these slots (or their matches / map points / rand stream were replaced since)");
-  SD_REQUIRE(h->pnp_serial == h->cur->extract_serial, SD_ERR_INVALID_ARG,
+  SD_REQUIRE(h->res.pnp.live(n_frames, inputs_now(h)), SD_ERR_INVALID_ARG,
              "the current frames were re-extracted since sd_track_pnp: the solvers' keypoints are gone");
   SD_REQUIRE(n_iterations >= 0, SD_ERR_INVALID_ARG, "bad n_iterations");
   PnpParams pp = h->pnp_params;
@@ -964,7 +947,7 @@ int sd_track_debug_features_in_area(sd_track* h, int frame, float x, float y, fl
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   (void)hipFree(d);
   SD_TRY(rc);
-  if (e != hipSuccess) { set_error(std::string("sd_track_debug_features_in_area: ") + hipGetErrorString(e)); return SD_ERR_HIP; }
+  if (e != hipSuccess) return hip_error("sd_track_debug_features_in_area", e);
   const int n = host[h->kp_cap];
   *n_out = n;
   SD_REQUIRE(n <= cap, SD_ERR_CAPACITY, "indices array too small");

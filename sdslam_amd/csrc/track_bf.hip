@@ -242,8 +242,8 @@ int launch_search_points(const sd_orb* cur, const sd_orb* ref, const TrackBuffer
   // option "track.bf_list_k" = 1..3 (tests): phase 2 sees only the first keys of every list, so the whole-wave recomputation -- rare on real
   // data -- runs for most points
   const int klist = std::min(BF_K, std::max(1, opt(OPT_BF_LIST_K)));
-  hipLaunchKernelGGL(k_search_points, dim3(n_frames), dim3(BF_THREADS), LdsSearchPoints(capw).bytes, s, (cur->have_dist ? cur->d_kps_un : cur->d_kps), cur->d_desc,
-                     cur->d_nout, (ref->have_dist ? ref->d_kps_un : ref->d_kps), ref->d_desc, ref->d_nout, tb, nnratio, check_ori, capw, klist);
+  hipLaunchKernelGGL(k_search_points, dim3(n_frames), dim3(BF_THREADS), LdsSearchPoints(capw).bytes, s, keys_un(cur), cur->d_desc,
+                     cur->d_nout, keys_un(ref), ref->d_desc, ref->d_nout, tb, nnratio, check_ori, capw, klist);
   SD_HIP_CHECK(hipGetLastError());
   return SD_OK;
 }

@@ -237,7 +237,7 @@ int launch_fuse(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, co
                 hipStream_t s) {
   const sd_orb* kf = kf_side ? ref : cur;
   FuseArgs a{};
-  a.kps = kf->have_dist ? kf->d_kps_un : kf->d_kps;
+  a.kps = keys_un(kf);
   a.desc = kf->d_desc;
   a.nkp = kf->d_nout;
   a.uright = kf_side ? tb.uright_ref : tb.uright;
@@ -276,7 +276,7 @@ extern "C" {
 int sd_track_set_fuse_scw(sd_track* h, int frame0, int n_frames, const double* Scw_cm16) {
   QUEUE_RANGE(h, frame0, n_frames);
   SD_REQUIRE(Scw_cm16, SD_ERR_INVALID_ARG, "NULL argument");
-  fuse_end(h);
+  END_RESULTS(h, "sd_track_set_fuse_scw");
   SD_TRY(h->pose_ring.upload(h->fu.Scw + (size_t)frame0 * 16, Scw_cm16, (size_t)n_frames * 16, h->pnp_stream));
   std::fill(h->scw_set.begin() + frame0, h->scw_set.begin() + frame0 + n_frames, (uint8_t)1);
   return SD_OK;
@@ -290,8 +290,7 @@ int sd_track_fuse(sd_track* h, int n_frames, int kf_side, int point_row, float t
   SD_REQUIRE(std::isfinite(th) && th > 0, SD_ERR_INVALID_ARG, "th must be finite and positive");
   SD_REQUIRE(point_row >= -1 && point_row < h->max_batch, SD_ERR_INVALID_ARG, "point_row outside [-1, max_batch)");
   if (kf_side) {
-    SD_TRY(require_ref_frames(h, n_frames, false));
-    SD_REQUIRE(keypoint_capacity(h->ref) == h->kp_cap, SD_ERR_INVALID_ARG, "cur / ref extractors must share the keypoint capacity");
+    SD_TRY(require_ref_frames(h, n_frames, false, true));
   } else {
     const int need = h->tb.cur_bcast >= 0 ? h->tb.cur_bcast + 1 : n_frames;
     SD_REQUIRE(h->cur->have_geom && h->cur->last_frames >= need, SD_ERR_INVALID_ARG, "current frames have not been extracted");
@@ -300,23 +299,18 @@ int sd_track_fuse(sd_track* h, int n_frames, int kf_side, int point_row, float t
     for (int f = 0; f < n_frames; f++)
       SD_REQUIRE(h->scw_set[f], SD_ERR_INVALID_ARG, "sim3 = 1, but sd_track_set_fuse_scw has not covered these slots");
   SD_HIP_CHECK(hipSetDevice(h->device));
-  fuse_end(h);
+  END_RESULTS(h, "sd_track_fuse");
   SD_TRY(run_stage(h, kf_side != 0, false, STAGE_NONE, [&](hipStream_t s) {
     return launch_fuse(h->cur, h->ref, h->tb, h->fu, h->cam, h->d_sf, h->d_inv_sigma2, h->d_scale_thr, n_frames, kf_side, point_row, th,
                        sim3, s);
   }));
-  h->fuse.n = n_frames;
-  h->fuse.kf_side = kf_side;
-  h->fuse.bcast = h->tb.cur_bcast;
-  h->fuse.serial = (kf_side ? h->ref : h->cur)->extract_serial;
+  h->res.fuse.set(n_frames, bind_fuse(kf_side), inputs_now(h), kf_side);
   return SD_OK;
 }
 
 int sd_track_get_fuse(sd_track* h, int frame0, int n_frames, int32_t* best_idx, int32_t* best_dist, int cap, int32_t* n_found) {
   TRACK_RANGE(h, frame0, n_frames);
-  SD_REQUIRE(frame0 + n_frames <= h->fuse.n && h->fuse.serial == (h->fuse.kf_side ? h->ref : h->cur)->extract_serial &&
-                 h->fuse.bcast == h->tb.cur_bcast,
-             SD_ERR_INVALID_ARG,
+  SD_REQUIRE(h->res.fuse.live(frame0 + n_frames, inputs_now(h)), SD_ERR_INVALID_ARG,
              "sd_track_fuse has not run on these slots (or their keyframes, points, mvuRight, poses, Scw, the camera or the broadcast "
              "setting were replaced since)");
   SD_REQUIRE((!best_idx && !best_dist) || cap >= h->max_points, SD_ERR_CAPACITY, "cap smaller than max_points");
@@ -342,63 +336,34 @@ int sd_debug_fuse(int n_kp, const sd_keypoint* kps, const uint8_t* desc, const f
                  best_idx && best_dist && n_found && (sim3 == 0 || sim3 == 1) && std::isfinite(th) && th > 0 && cam9[0] > 0 &&
                  cam9[1] > 0 && cam9[6] > cam9[5] && cam9[8] > cam9[7],
              SD_ERR_INVALID_ARG, "bad arguments");
-  TrackCam cam{};
-  cam.ffx = cam9[0]; cam.ffy = cam9[1]; cam.fcx = cam9[2]; cam.fcy = cam9[3];
-  cam.fx = cam9[0]; cam.fy = cam9[1]; cam.cx = cam9[2]; cam.cy = cam9[3];
-  cam.bf = cam9[4];
-  cam.mb = cam9[4] / cam9[0];
-  cam.min_x = cam9[5]; cam.max_x = cam9[6]; cam.min_y = cam9[7]; cam.max_y = cam9[8];
+  const TrackCam cam = make_cam(cam9[0], cam9[1], cam9[2], cam9[3], cam9[4], cam9[5], cam9[6], cam9[7], cam9[8]);
   float thr[SD_MAX_LEVELS];
   predict_scale_thresholds(scale_factor, thr);
   const size_t K = (size_t)kp_cap, M = (size_t)max_points;
-  struct Blob {   // one device allocation, carved in 16-byte steps
-    size_t bytes = 0;
-    size_t reserve(size_t n) {
-      const size_t off = bytes;
-      bytes += (n + 15) & ~(size_t)15;
-      return off;
-    }
-  } b;
-  const size_t o_k = b.reserve(K * sizeof(sd_keypoint)), o_d = b.reserve(K * 32), o_u = b.reserve(K * 4), o_n = b.reserve(4 * 4);
-  const size_t o_T = b.reserve(16 * 8), o_c = b.reserve(M), o_X = b.reserve(M * 24), o_N = b.reserve(M * 24), o_mn = b.reserve(M * 4);
-  const size_t o_mx = b.reserve(M * 4), o_mf = b.reserve(M * 4), o_pd = b.reserve(M * 32), o_sf = b.reserve((size_t)nlevels * 4);
-  const size_t o_is = b.reserve((size_t)nlevels * 4), o_th = b.reserve(sizeof(thr)), o_bi = b.reserve(M * 4), o_bd = b.reserve(M * 4);
-  const size_t o_p = b.reserve(15 * 8);
-  std::vector<uint8_t> host(b.bytes, 0);
-  auto put = [&](size_t off, const void* src, size_t n) { if (n) std::memcpy(host.data() + off, src, n); };
-  put(o_k, kps, (size_t)n_kp * sizeof(sd_keypoint)); put(o_d, desc, (size_t)n_kp * 32); put(o_u, uright, (size_t)n_kp * 4);
+  Blob b;
   const int32_t counts[4] = {n_kp, n_pts, 0, 0};
-  put(o_n, counts, sizeof(counts));
-  put(o_T, T_cm16, 128); put(o_c, cand, (size_t)n_pts); put(o_X, Xw, (size_t)n_pts * 24); put(o_N, normal, (size_t)n_pts * 24);
-  put(o_mn, min_dist, (size_t)n_pts * 4); put(o_mx, max_dist, (size_t)n_pts * 4); put(o_mf, mf_max_dist, (size_t)n_pts * 4);
-  put(o_pd, pt_desc, (size_t)n_pts * 32); put(o_sf, scale_factors, (size_t)nlevels * 4); put(o_is, inv_level_sigma2, (size_t)nlevels * 4);
-  put(o_th, thr, sizeof(thr));
-  uint8_t* d = nullptr;
-  SD_HIP_CHECK(hipMalloc(&d, b.bytes));
-  hipError_t e = hipMemcpy(d, host.data(), b.bytes, hipMemcpyHostToDevice);
-  int rc = SD_OK;
-  if (e == hipSuccess) {
+  const size_t o_k = b.reserve(K, kps, n_kp), o_d = b.reserve(K * 32, desc, (size_t)n_kp * 32), o_u = b.reserve(K, uright, n_kp);
+  const size_t o_n = b.reserve(4, counts, 4), o_T = b.reserve(16, T_cm16, 16), o_c = b.reserve(M, cand, n_pts);
+  const size_t o_X = b.reserve(M * 3, Xw, (size_t)n_pts * 3), o_N = b.reserve(M * 3, normal, (size_t)n_pts * 3);
+  const size_t o_mn = b.reserve(M, min_dist, n_pts), o_mx = b.reserve(M, max_dist, n_pts), o_mf = b.reserve(M, mf_max_dist, n_pts);
+  const size_t o_pd = b.reserve(M * 32, pt_desc, (size_t)n_pts * 32), o_sf = b.reserve(nlevels, scale_factors, nlevels);
+  const size_t o_is = b.reserve(nlevels, inv_level_sigma2, nlevels), o_th = b.reserve(SD_MAX_LEVELS, thr, SD_MAX_LEVELS);
+  const size_t o_bi = b.reserve<int32_t>(M), o_bd = b.reserve<int32_t>(M), o_p = b.reserve<double>(15);
+  SD_TRY(b.run("sd_debug_fuse", [&] {
     FuseArgs a{};
-    a.kps = (const sd_keypoint*)(d + o_k); a.desc = d + o_d; a.nkp = (const int32_t*)(d + o_n); a.uright = (const float*)(d + o_u);
-    a.T = (const double*)(d + o_T); a.n_pts = (const int32_t*)(d + o_n) + 1; a.cand = d + o_c; a.Xw = (const double*)(d + o_X);
-    a.normal = (const double*)(d + o_N); a.dmin = (const float*)(d + o_mn); a.dmax = (const float*)(d + o_mx);
-    a.mfmax = (const float*)(d + o_mf); a.pdesc = d + o_pd; a.sf = (const float*)(d + o_sf); a.inv_sigma2 = (const float*)(d + o_is);
-    a.scale_thr = (const float*)(d + o_th); a.best_idx = (int32_t*)(d + o_bi); a.best_dist = (int32_t*)(d + o_bd);
-    a.n_found = (int32_t*)(d + o_n) + 2; a.pose = (double*)(d + o_p);
+    a.kps = b.dev<sd_keypoint>(o_k); a.desc = b.dev<uint8_t>(o_d); a.nkp = b.dev<int32_t>(o_n); a.uright = b.dev<float>(o_u);
+    a.T = b.dev<double>(o_T); a.n_pts = b.dev<int32_t>(o_n) + 1; a.cand = b.dev<uint8_t>(o_c); a.Xw = b.dev<double>(o_X);
+    a.normal = b.dev<double>(o_N); a.dmin = b.dev<float>(o_mn); a.dmax = b.dev<float>(o_mx); a.mfmax = b.dev<float>(o_mf);
+    a.pdesc = b.dev<uint8_t>(o_pd); a.sf = b.dev<float>(o_sf); a.inv_sigma2 = b.dev<float>(o_is); a.scale_thr = b.dev<float>(o_th);
+    a.best_idx = b.dev<int32_t>(o_bi); a.best_dist = b.dev<int32_t>(o_bd); a.n_found = b.dev<int32_t>(o_n) + 2;
+    a.pose = b.dev<double>(o_p);
     a.kf_bcast = -1; a.point_row = -1; a.cap = kp_cap; a.max_points = max_points; a.nlevels = nlevels; a.sim3 = sim3; a.th = th;
-    rc = launch_fuse_args(a, cam, 1, 0);
-    if (rc == SD_OK) e = hipMemcpy(host.data(), d, b.bytes, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(d);
-  if (e != hipSuccess) {
-    set_error(std::string("sd_debug_fuse: ") + hipGetErrorString(e));
-    return SD_ERR_HIP;
-  }
-  SD_TRY(rc);
-  std::memcpy(best_idx, host.data() + o_bi, M * 4);
-  std::memcpy(best_dist, host.data() + o_bd, M * 4);
-  std::memcpy(n_found, host.data() + o_n + 8, 4);
-  if (pose15) std::memcpy(pose15, host.data() + o_p, 15 * 8);
+    return launch_fuse_args(a, cam, 1, 0);
+  }));
+  b.take(best_idx, o_bi, M * 4);
+  b.take(best_dist, o_bd, M * 4);
+  b.take(n_found, o_n + 8, 4);
+  if (pose15) b.take(pose15, o_p, 15 * 8);
   return SD_OK;
 }
 

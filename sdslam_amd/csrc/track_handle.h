@@ -1,18 +1,21 @@
 // The sd_track handle and the host helpers its entry points share (track.hip: creation and the batched stages;
 // track_seq.hip: sequential tracking).  Not part of the ABI.  In order: UploadRing and RunStamp (the sequential loop's two
-// small types), the handle, wait_inputs / mark_reads (ordering against the extractors), the argument preambles (check_ready,
-// check_batch / check_paired, check_range with TRACK_RANGE / QUEUE_RANGE, require_ref_frames), the stage timers and run_stage
-// (the bracket every batched stage launches in), and the typed copies between host arrays and the per-slot device buffers
-// (download / upload, download_rows / upload_rows), whose byte counts come from the buffer's element type.
+// small types), the handle, what the cached results are stamped with and what ends them (inputs_now / END_RESULTS over track_results.h),
+// wait_inputs / mark_reads (ordering against the extractors), the argument preambles (check_ready, check_batch / check_paired,
+// check_range with TRACK_RANGE / QUEUE_RANGE, require_ref_frames), the stage timers and run_stage (the bracket every batched
+// stage launches in), hip_error and Blob (the scaffold of the debug entries), and the typed copies between host arrays and the
+// per-slot device buffers (download / upload, download_rows / upload_rows), whose byte counts come from the buffer's element type.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "orb_internal.h"
 #include "track_internal.h"
+#include "track_results.h"
 
 // Small host arrays on their way into device memory without a host wait: the next of kSlots pinned buffers takes a copy, which
 // goes to the device on the caller's stream, behind whatever that stream has queued.  A buffer is written again once the copy
@@ -71,30 +74,18 @@ struct sd_track {
   int max_points = 0, max_batch = 0, kp_cap = 0, device = 0;
   int rand_per_frame = 0;
   std::vector<int> rand_len;      // rand() values actually supplied per slot (sd_track_set_rand)
-  bool have_pnp = false;          // sd_track_pnp has constructed the solvers sd_track_pnp_iterate continues ...
-  unsigned long long pnp_serial = 0;   // ... on the keypoints of THIS extraction of `cur` (the reference's solver owns copies of its inputs)
+  // What the stages that cache a result between calls left, and on which inputs (track_results.h: stamps, and the table of
+  // what ends them).  pnp: the solvers sd_track_pnp_iterate continues; sim3: those of sd_track_sim3_iterate; tri: the matches of
+  // sd_track_get_triangulation_matches; triang: sd_track_get_triangulated / _get_new_points; fuse: sd_track_get_fuse.
+  sd::Results res;
   sd::PnpParams pnp_params{};
-  int pnp_frames = 0, pnp_iter_upper = 0;   // slots / upper bound of mnIterations of those solvers
-  // Sim3Solver (track_sim3.hip): sd_track_sim3 constructs, sd_track_sim3_iterate continues while the stamp holds (sim3_end)
-  RunStamp sim3;                   // mode = the broadcast setting the solvers were built under
-  unsigned long long sim3_ref_serial = 0;   // ... and on THIS extraction of `ref`
+  int pnp_iter_upper = 0;          // upper bound of mnIterations of the PnP solvers
   sd::Sim3Params sim3_params{};
-  int sim3_max_its = 0, sim3_iter_upper = 0;   // maxIterations argument / upper bound of mnIterations of those solvers
+  int sim3_max_its = 0, sim3_iter_upper = 0;   // maxIterations argument / upper bound of mnIterations of the Sim3 solvers
   UploadRing sim3_ring;            // [kp_cap + 1] int32: the mRansacMaxIts table of a sd_track_sim3 call
   int32_t* d_sim3_max_its = nullptr;
-  // SearchForTriangulation (track_tri.hip): the result sd_track_get_triangulation_matches returns while the stamp holds (tri_end)
-  RunStamp tri;                    // mode = the broadcast setting the search ran under
-  unsigned long long tri_ref_serial = 0;   // ... and on THIS extraction of `ref`
   std::vector<uint8_t> f12_set;    // [max_batch] sd_track_set_f12 has covered the slot
-  // CreateNewMapPoints after the search (track_newpoints_tri.hip): the result sd_track_get_triangulated / _get_new_points
-  // return while the stamp AND the search's hold (tri_end ends both; triang_end this one alone)
-  RunStamp triang;                 // mode = the broadcast setting it ran under
   sd::TriangBuffers nb{};
-  // ORBmatcher::Fuse (track_fuse.hip): the result sd_track_get_fuse returns while the stamp holds (fuse_end)
-  struct FuseStamp {
-    int n = 0, kf_side = 0, bcast = -1;   // slots < n hold a result of this side, searched under this broadcast setting ...
-    unsigned long long serial = 0;        // ... on THIS extraction of the side's extractor
-  } fuse;
   std::vector<uint8_t> scw_set;    // [max_batch] sd_track_set_fuse_scw has covered the slot
   sd::FuseBuffers fu{};
   sd::TrackBuffers tb{};
@@ -140,20 +131,15 @@ inline bool RunStamp::covers(const sd_track* h, int n_frames) const {
   return cur == h->cur && serial == h->cur->extract_serial && n_frames <= n;
 }
 
-// Something a Sim3Solver was constructed from is being replaced: sd_track_sim3_iterate refuses until sd_track_sim3 runs again
-static inline void sim3_end(sd_track* h) { h->sim3 = RunStamp{}; }
-// Something a SearchForTriangulation result was computed from is being replaced: the getter refuses until the search runs again
-static inline void triang_end(sd_track* h) { h->triang = RunStamp{}; }
-static inline void tri_end(sd_track* h) {
-  h->tri = RunStamp{};
-  triang_end(h);   // the triangulation of those matches goes with them
-}
-// The search's result for slots < n_frames is the one its inputs still describe
-static inline bool tri_live(const sd_track* h, int n_frames) {
-  return h->tri.covers(h, n_frames) && h->tri_ref_serial == h->ref->extract_serial && h->tri.mode == h->tb.cur_bcast;
-}
-// Something a Fuse result was computed from is being replaced: sd_track_get_fuse refuses until sd_track_fuse runs again
-static inline void fuse_end(sd_track* h) { h->fuse = sd_track::FuseStamp{}; }
+// What a stage that runs now computes its result on: h->res.x.set(n, BIND_X, inputs_now(h)) after it, h->res.x.live(n, inputs_now(h)) later
+static inline sd::ResultInputs inputs_now(const sd_track* h) { return {h->cur->extract_serial, h->ref->extract_serial, h->tb.cur_bcast}; }
+// The entry point named ends the results of its row of kEnds
+#define END_RESULTS(h, entry)                                                  \
+  do {                                                                         \
+    constexpr int ends_ = sd::ends_of(entry);                                  \
+    static_assert(ends_ >= 0, "no row of kEnds (track_results.h) for " entry); \
+    sd::end_results((h)->res, (unsigned)ends_);                                \
+  } while (0)
 
 // MapPoint::PredictScale (src/MapPoint.cc:355-385): nScale = ceil(log(ratio) / mfLogScaleFactor), float overloads,
 // mfLogScaleFactor = log(mfScaleFactor) (src/Frame.cc:80).  thr[n] = smallest float ratio that reaches level n,
@@ -251,14 +237,17 @@ static inline int check_range(const sd_track* h, int frame0, int n, RangeUse use
 #define TRACK_RANGE(h, frame0, n) SD_TRY(check_range((h), (frame0), (n), RANGE_SYNC))
 #define QUEUE_RANGE(h, frame0, n) SD_TRY(check_range((h), (frame0), (n), RANGE_QUEUE))
 
-// Frames 0 .. n_frames - 1 of the `ref` extractor exist; same_size: and have the geometry of the current frames (ImageAlign)
-static inline int require_ref_frames(const sd_track* h, int n_frames, bool same_size) {
+// Frames 0 .. n_frames - 1 of the `ref` extractor exist; same_size: and have the geometry of the current frames (ImageAlign);
+// same_capacity: and a keypoint row of theirs is as long as one of `cur` (the two-extractor stages index both with kp_cap)
+static inline int require_ref_frames(const sd_track* h, int n_frames, bool same_size, bool same_capacity = false) {
   const bool extracted = h->ref->have_geom && h->ref->last_frames >= n_frames;
   if (same_size)
     SD_REQUIRE(extracted && h->ref->cur_w == h->cur->cur_w && h->ref->cur_h == h->cur->cur_h, SD_ERR_INVALID_ARG,
                "reference frames not extracted or of different size");
   else
     SD_REQUIRE(extracted, SD_ERR_INVALID_ARG, "keyframes of the ref extractor have not been extracted");
+  if (same_capacity)
+    SD_REQUIRE(keypoint_capacity(h->ref) == h->kp_cap, SD_ERR_INVALID_ARG, "cur / ref extractors must share the keypoint capacity");
   return SD_OK;
 }
 
@@ -296,15 +285,43 @@ static inline int wait_for(hipStream_t s) {
   return SD_OK;
 }
 
-// One device allocation of a debug entry (sd_debug_search_for_triangulation, sd_debug_triangulate), carved in 16-byte steps
+// "<entry point>: <HIP's message>" where a call has to free what it allocated before it reports
+static inline int hip_error(const char* name, hipError_t e) {
+  sd::set_error(std::string(name) + ": " + hipGetErrorString(e));
+  return SD_ERR_HIP;
+}
+
+// The device memory of a debug entry: one allocation carved in 16-byte steps, with a zeroed host mirror.  reserve every array
+// (inputs with their source), run the launch on pointers from dev<T>(), take the outputs.
 struct Blob {
   uint8_t* base = nullptr;
-  size_t bytes = 0;
-  size_t reserve(size_t n) {
-    const size_t off = bytes;
-    bytes += (n + 15) & ~(size_t)15;
+  std::vector<uint8_t> host;   // the mirror: its size is the allocation's
+  // `count` elements of T, the first n of them copied from src; returns the array's offset
+  template <typename T>
+  size_t reserve(size_t count, const T* src = nullptr, size_t n = 0) {
+    const size_t off = host.size();
+    host.resize(off + ((count * sizeof(T) + 15) & ~(size_t)15), 0);
+    put(off, src, n * sizeof(T));
     return off;
   }
+  void put(size_t off, const void* src, size_t n) { if (n) std::memcpy(host.data() + off, src, n); }
+  template <typename T>
+  T* dev(size_t off) const { return (T*)(base + off); }
+  // Allocate, copy the mirror in, launch() on the null stream, copy everything back, free -- whatever failed
+  template <typename Launch>
+  int run(const char* name, Launch&& launch) {
+    SD_HIP_CHECK(hipMalloc(&base, host.size()));
+    hipError_t e = hipMemcpy(base, host.data(), host.size(), hipMemcpyHostToDevice);
+    int rc = SD_OK;
+    if (e == hipSuccess) {
+      rc = launch();
+      if (rc == SD_OK) e = hipMemcpy(host.data(), base, host.size(), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(base);
+    base = nullptr;
+    return e != hipSuccess ? hip_error(name, e) : rc;
+  }
+  void take(void* dst, size_t off, size_t n) const { if (n) std::memcpy(dst, host.data() + off, n); }
 };
 
 // Slots frame0 .. frame0 + n - 1 of a device buffer with per_slot elements a slot, to / from a dense host array.  A NULL host

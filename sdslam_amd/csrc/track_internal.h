@@ -195,6 +195,9 @@ struct TrackCam {
   float min_x, max_x, min_y, max_y;      // Frame::mnMinX ...
   float bf, mb;                          // Frame::mbf, mb = mbf / fx
 };
+static inline TrackCam make_cam(float fx, float fy, float cx, float cy, float bf, float min_x, float max_x, float min_y, float max_y) {
+  return TrackCam{fx, fy, cx, cy, fx, fy, cx, cy, min_x, max_x, min_y, max_y, bf, bf / fx};
+}
 
 struct PnpParams {
   double probability;

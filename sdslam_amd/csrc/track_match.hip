@@ -965,7 +965,7 @@ template <typename T, bool kConvert>
 static int launch_stereo_from_depth_t(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const T* d_depth, int w, int h,
                                       int stride_elems, size_t frame_stride_elems, float scale, int n_frames, hipStream_t s) {
   hipLaunchKernelGGL((k_stereo_from_depth<T, kConvert>), dim3((tb.kp_cap + 255) / 256, n_frames), dim3(256), 0, s, cur->d_kps,
-                     (cur->have_dist ? cur->d_kps_un : cur->d_kps), cur->d_nout, tb, cam, d_depth, w, h, stride_elems, frame_stride_elems,
+                     keys_un(cur), cur->d_nout, tb, cam, d_depth, w, h, stride_elems, frame_stride_elems,
                      scale);
   SD_HIP_CHECK(hipGetLastError());
   return SD_OK;
@@ -1040,7 +1040,7 @@ int launch_features_in_area(const sd_orb* cur, const TrackBuffers& tb, const Tra
                             int min_level, int max_level, int32_t* d_out, int out_cap, int32_t* d_n, int32_t* d_grid, hipStream_t s) {
   int KP2;
   SD_TRY(matcher_kp2(tb, &KP2));
-  const sd_keypoint* kps = (cur->have_dist ? cur->d_kps_un : cur->d_kps) + (size_t)frame * tb.kp_cap;
+  const sd_keypoint* kps = keys_un(cur) + (size_t)frame * tb.kp_cap;
   hipLaunchKernelGGL(k_features_in_area, dim3(1), dim3(64 * MT_WAVES), LdsFeaturesInArea(KP2).bytes, s, kps, cur->d_desc + (size_t)frame * tb.kp_cap * 32,
                      cur->d_nout + frame, tb.uright + (size_t)frame * tb.kp_cap, cam, tb.kp_cap, KP2, x, y, r, min_level, max_level, d_out,
                      out_cap, d_n, d_grid);
@@ -1059,7 +1059,7 @@ int launch_match_local(const sd_orb* cur, const TrackBuffers& tb, const TrackCam
     hipLaunchKernelGGL(k_seen_ids, dim3(n_frames), dim3(256), LdsSeenIds(KP2).bytes, s, tb, KP2);
     SD_HIP_CHECK(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_match_local, dim3(n_frames), dim3(64 * MT_WAVES), LdsMatchLocal(KP2, MP).bytes, s, (cur->have_dist ? cur->d_kps_un : cur->d_kps), cur->d_desc,
+  hipLaunchKernelGGL(k_match_local, dim3(n_frames), dim3(64 * MT_WAVES), LdsMatchLocal(KP2, MP).bytes, s, keys_un(cur), cur->d_desc,
                      cur->d_nout, tb, cam, d_sf, d_scale_thr, nlevels, th, nnratio, cos_limit, KP2, claim_from_matches, frustum_given,
                      exclude_seen ? 1 : 0);
   SD_HIP_CHECK(hipGetLastError());
@@ -1071,7 +1071,7 @@ int launch_match(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam,
   int KP2;
   SD_TRY(matcher_kp2(tb, &KP2));
   const int MP = tb.max_points;
-  const sd_keypoint* kps = cur->have_dist ? cur->d_kps_un : cur->d_kps;
+  const sd_keypoint* kps = keys_un(cur);
   if (opt(OPT_MATCH_SPLIT)) {   // candidates -> HBM list -> one-wave assignment
     const size_t lds_c = LdsMatchCand(KP2, MP).bytes, lds_a = LdsMatchAssign(KP2, MP).bytes;
     // first pass: one workgroup per frame (note_below > 0: frames with fewer matches are listed for a retry pass);

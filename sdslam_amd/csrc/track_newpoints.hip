@@ -217,7 +217,7 @@ __global__ void k_set_keyframe_state(TrackBuffers tb, const int32_t* __restrict_
 int launch_new_points(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, float inv_fx, float inv_fy, int n_frames, int mode,
                       int source, float th_depth, int use_flags, int frame_id, int min_keypoints, hipStream_t s) {
   SD_REQUIRE(tb.kp_cap <= NP_KEYS, SD_ERR_CAPACITY, "map point creation sorts at most 2048 keypoints per frame");
-  hipLaunchKernelGGL(k_new_points, dim3(n_frames), dim3(256), 0, s, cur->have_dist ? cur->d_kps_un : cur->d_kps, cur->d_nout, tb, cam.fcx,
+  hipLaunchKernelGGL(k_new_points, dim3(n_frames), dim3(256), 0, s, keys_un(cur), cur->d_nout, tb, cam.fcx,
                      cam.fcy, inv_fx, inv_fy, mode, source, th_depth, use_flags, frame_id, min_keypoints);
   SD_HIP_CHECK(hipGetLastError());
   return SD_OK;

@@ -434,6 +434,14 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void k_new_points_resolve(ResolveI
   }
 }
 
+// The camera and gate constants of a TriangIn, in Frame's float arithmetic (invfx = 1.0f / fx, mb = mbf / fx of make_cam)
+static void set_camera(TriangIn& a, const TrackCam& cam, float ratio_factor) {
+  a.fx = cam.ffx; a.fy = cam.ffy; a.cx = cam.fcx; a.cy = cam.fcy;
+  a.invfx = 1.0f / cam.ffx; a.invfy = 1.0f / cam.ffy;
+  a.bf = cam.bf; a.mb = cam.mb;
+  a.ratio_factor = ratio_factor;
+}
+
 static int launch_k_triangulate(const TriangIn& a, int n_frames, hipStream_t s) {
   hipLaunchKernelGGL(k_triangulate, dim3((a.cap + TRIANG_THREADS - 1) / TRIANG_THREADS, n_frames), dim3(TRIANG_THREADS), 0, s, a);
   SD_HIP_CHECK(hipGetLastError());
@@ -443,11 +451,12 @@ static int launch_k_triangulate(const TriangIn& a, int n_frames, hipStream_t s) 
 int launch_triangulate(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const TriangBuffers& nb, const TrackCam& cam,
                        const float* d_sf, const float* d_sigma2, float ratio_factor, int n_frames, int monocular, hipStream_t s) {
   SD_REQUIRE(tb.kp_cap <= RESOLVE_KEYS, SD_ERR_CAPACITY, "triangulation supports at most 2048 keypoints per keyframe");
-  const sd_keypoint* k1u = cur->have_dist ? cur->d_kps_un : cur->d_kps;
-  const sd_keypoint* k2u = ref->have_dist ? ref->d_kps_un : ref->d_kps;
-  const TriangIn a = {k1u, cur->d_kps, k2u, ref->d_kps, tb.tri_match, tb.uright, tb.uright_ref, tb.depth, nb.depth_ref, tb.Tcur, tb.Tref,
-                      nb.median, d_sf, d_sigma2, cam.ffx, cam.ffy, cam.fcx, cam.fcy, 1.0f / cam.ffx, 1.0f / cam.ffy, cam.bf, cam.mb,
-                      ratio_factor, cur->nlevels, tb.kp_cap, tb.cur_bcast, monocular, nb.verdict, nb.branch, nb.Xw};
+  const sd_keypoint* k1u = keys_un(cur);
+  const sd_keypoint* k2u = keys_un(ref);
+  TriangIn a = {k1u, cur->d_kps, k2u, ref->d_kps, tb.tri_match, tb.uright, tb.uright_ref, tb.depth, nb.depth_ref, tb.Tcur, tb.Tref,
+                nb.median, d_sf, d_sigma2, 0, 0, 0, 0, 0, 0, 0, 0, 0, cur->nlevels, tb.kp_cap, tb.cur_bcast, monocular, nb.verdict,
+                nb.branch, nb.Xw};
+  set_camera(a, cam, ratio_factor);
   SD_TRY(launch_k_triangulate(a, n_frames, s));
   const ResolveIn r = {k1u, cur->d_desc, tb.tri_match, tb.Tcur, tb.Tref, d_sf, cur->nlevels, tb.kp_cap, tb.cur_bcast, n_frames, tb.next_id};
   hipLaunchKernelGGL(k_new_points_resolve, dim3(1), dim3(RESOLVE_THREADS), 0, s, r, nb);
@@ -470,7 +479,7 @@ extern "C" {
 int sd_track_set_tri_depth(sd_track* h, int side, int frame0, int n_frames, const float* depth, int cap) {
   QUEUE_RANGE(h, frame0, n_frames);
   SD_REQUIRE((side == 0 || side == 1) && depth && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad side or depth array");
-  triang_end(h);
+  END_RESULTS(h, "sd_track_set_tri_depth");
   SD_TRY(upload_rows(side == 0 ? h->tb.depth : h->nb.depth_ref, h->kp_cap, depth, cap, frame0, n_frames, h->pnp_stream));
   return wait_for(h->pnp_stream);   // the rows are the caller's pageable memory: back once they are read
 }
@@ -478,7 +487,7 @@ int sd_track_set_tri_depth(sd_track* h, int side, int frame0, int n_frames, cons
 int sd_track_set_tri_median_depth(sd_track* h, int frame0, int n_frames, const float* median_depth) {
   QUEUE_RANGE(h, frame0, n_frames);
   SD_REQUIRE(median_depth, SD_ERR_INVALID_ARG, "NULL argument");
-  triang_end(h);
+  END_RESULTS(h, "sd_track_set_tri_median_depth");
   return h->small_ring.upload(h->nb.median + frame0, median_depth, (size_t)n_frames, h->pnp_stream);
 }
 
@@ -486,23 +495,23 @@ int sd_track_triangulate(sd_track* h, int n_frames, int monocular) {
   SD_TRY(check_ready(h, n_frames));
   SD_TRY(require_ref_frames(h, n_frames, false));
   SD_REQUIRE(monocular == 0 || monocular == 1, SD_ERR_INVALID_ARG, "monocular must be 0 or 1");
-  SD_REQUIRE(tri_live(h, n_frames), SD_ERR_INVALID_ARG,
+  SD_REQUIRE(h->res.tri.live(n_frames, inputs_now(h)), SD_ERR_INVALID_ARG,
              "no live result of sd_track_search_for_triangulation covers these slots (see sd_track_get_triangulation_matches)");
   // with the rotation check a row's match depends on the other rows: "the first accepting slot" is then not the reference's loop
-  SD_REQUIRE(h->tb.cur_bcast < 0 || h->tri.source == 0, SD_ERR_INVALID_ARG,
+  SD_REQUIRE(h->tb.cur_bcast < 0 || h->res.tri.payload == 0, SD_ERR_INVALID_ARG,
              "broadcast mode needs a search with check_ori = 0 (CreateNewMapPoints' matcher has mbCheckOrientation off)");
   const float ratio_factor = 1.5f * h->cur->scaleFactor;
   SD_TRY(run_stage(h, true, false, STAGE_NONE, [&](hipStream_t s) {
     return launch_triangulate(h->cur, h->ref, h->tb, h->nb, h->cam, h->d_sf, h->d_sigma2, ratio_factor, n_frames, monocular, s);
   }));
-  h->triang.set(h, n_frames, h->tb.cur_bcast);
+  h->res.triang.set(n_frames, BIND_TRIANG, inputs_now(h));
   return SD_OK;
 }
 
 int sd_track_get_triangulated(sd_track* h, int frame0, int n_frames, uint8_t* verdict, uint8_t* branch, double* Xw, int cap,
                               int32_t* n_accepted) {
   TRACK_RANGE(h, frame0, n_frames);
-  SD_REQUIRE(tri_live(h, frame0 + n_frames) && h->triang.covers(h, frame0 + n_frames), SD_ERR_INVALID_ARG, kNoTriangulation);
+  SD_REQUIRE(h->res.triang_live(frame0 + n_frames, inputs_now(h)), SD_ERR_INVALID_ARG, kNoTriangulation);
   SD_REQUIRE(!(verdict || branch || Xw) || cap >= h->kp_cap, SD_ERR_CAPACITY, "cap smaller than the keypoint capacity");
   hipStream_t s = h->cur->stream;
   const size_t K = h->kp_cap;
@@ -518,7 +527,7 @@ int sd_track_get_triangulated(sd_track* h, int frame0, int n_frames, uint8_t* ve
 int sd_track_get_new_points(sd_track* h, int32_t* info4, int32_t* kp1, int32_t* slot, int32_t* idx2, int32_t* ids, double* Xw,
                             double* normal, float* max_dist, float* min_dist, uint8_t* desc, int cap) {
   TRACK_RANGE(h, 0, 1);
-  SD_REQUIRE(h->triang.n >= 1 && tri_live(h, h->triang.n) && h->triang.covers(h, h->triang.n), SD_ERR_INVALID_ARG, kNoTriangulation);
+  SD_REQUIRE(h->res.triang_live(h->res.triang.n, inputs_now(h)), SD_ERR_INVALID_ARG, kNoTriangulation);
   SD_REQUIRE(info4 && cap >= 0, SD_ERR_INVALID_ARG, "info4 is NULL or cap negative");
   hipStream_t s = h->cur->stream;
   SD_TRY(download(info4, h->nb.info, 0, 1, 4, s));
@@ -561,46 +570,28 @@ int sd_debug_triangulate(int n1, int n2, const sd_keypoint* kps1_un, const sd_ke
     SD_REQUIRE(matches12[i] >= -1 && matches12[i] < n2, SD_ERR_INVALID_ARG, "matches12 entry outside [-1, n2)");
   if (n1 == 0) return SD_OK;
   const size_t cap = (size_t)std::max(std::max(n1, n2), 1);
-  Blob b;
-  const size_t o_k1u = b.reserve(cap * sizeof(sd_keypoint)), o_k1 = b.reserve(cap * sizeof(sd_keypoint));
-  const size_t o_k2u = b.reserve(cap * sizeof(sd_keypoint)), o_k2 = b.reserve(cap * sizeof(sd_keypoint));
-  const size_t o_u1 = b.reserve(cap * 4), o_u2 = b.reserve(cap * 4), o_z1 = b.reserve(cap * 4), o_z2 = b.reserve(cap * 4);
-  const size_t o_m = b.reserve(cap * 4), o_T1 = b.reserve(128), o_T2 = b.reserve(128), o_med = b.reserve(4);
-  const size_t o_sf = b.reserve((size_t)nlevels * 4), o_s2 = b.reserve((size_t)nlevels * 4);
-  const size_t o_v = b.reserve(cap), o_b = b.reserve(cap), o_X = b.reserve(cap * 24);
-  std::vector<uint8_t> host(b.bytes, 0);
-  auto put = [&](size_t off, const void* src, size_t n) { if (n) std::memcpy(host.data() + off, src, n); };
   std::vector<int32_t> m(cap, -1);
   std::memcpy(m.data(), matches12, (size_t)n1 * 4);
-  put(o_k1u, kps1_un, (size_t)n1 * sizeof(sd_keypoint)); put(o_k1, kps1, (size_t)n1 * sizeof(sd_keypoint));
-  put(o_k2u, kps2_un, (size_t)n2 * sizeof(sd_keypoint)); put(o_k2, kps2, (size_t)n2 * sizeof(sd_keypoint));
-  put(o_u1, uright1, (size_t)n1 * 4); put(o_u2, uright2, (size_t)n2 * 4);
-  put(o_z1, depth1, (size_t)n1 * 4); put(o_z2, depth2, (size_t)n2 * 4);
-  put(o_m, m.data(), cap * 4); put(o_T1, Tcw1_cm16, 128); put(o_T2, Tcw2_cm16, 128); put(o_med, &median_depth, 4);
-  put(o_sf, scale_factors, (size_t)nlevels * 4); put(o_s2, level_sigma2, (size_t)nlevels * 4);
-  SD_HIP_CHECK(hipMalloc(&b.base, b.bytes));
-  uint8_t* d = b.base;
-  hipError_t e = hipMemcpy(d, host.data(), b.bytes, hipMemcpyHostToDevice);
-  int rc = SD_OK;
-  if (e == hipSuccess) {
-    const TriangIn a = {(const sd_keypoint*)(d + o_k1u), (const sd_keypoint*)(d + o_k1), (const sd_keypoint*)(d + o_k2u),
-                        (const sd_keypoint*)(d + o_k2), (const int32_t*)(d + o_m), (const float*)(d + o_u1), (const float*)(d + o_u2),
-                        (const float*)(d + o_z1), (const float*)(d + o_z2), (const double*)(d + o_T1), (const double*)(d + o_T2),
-                        (const float*)(d + o_med), (const float*)(d + o_sf), (const float*)(d + o_s2), cam5[0], cam5[1], cam5[2], cam5[3],
-                        1.0f / cam5[0], 1.0f / cam5[1], cam5[4], cam5[4] / cam5[0], 1.5f * scale_factor, nlevels, (int)cap, -1, monocular,
-                        d + o_v, d + o_b, (double*)(d + o_X)};
-    rc = launch_k_triangulate(a, 1, 0);
-    if (rc == SD_OK) e = hipMemcpy(host.data(), d, b.bytes, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(b.base);
-  if (e != hipSuccess) {
-    set_error(std::string("sd_debug_triangulate: ") + hipGetErrorString(e));
-    return SD_ERR_HIP;
-  }
-  SD_TRY(rc);
-  std::memcpy(verdict, host.data() + o_v, (size_t)n1);
-  std::memcpy(branch, host.data() + o_b, (size_t)n1);
-  std::memcpy(Xw, host.data() + o_X, (size_t)n1 * 24);
+  Blob b;
+  const size_t o_k1u = b.reserve(cap, kps1_un, n1), o_k1 = b.reserve(cap, kps1, n1);
+  const size_t o_k2u = b.reserve(cap, kps2_un, n2), o_k2 = b.reserve(cap, kps2, n2);
+  const size_t o_u1 = b.reserve(cap, uright1, n1), o_u2 = b.reserve(cap, uright2, n2);
+  const size_t o_z1 = b.reserve(cap, depth1, n1), o_z2 = b.reserve(cap, depth2, n2), o_m = b.reserve(cap, m.data(), cap);
+  const size_t o_T1 = b.reserve(16, Tcw1_cm16, 16), o_T2 = b.reserve(16, Tcw2_cm16, 16), o_med = b.reserve(1, &median_depth, 1);
+  const size_t o_sf = b.reserve(nlevels, scale_factors, nlevels), o_s2 = b.reserve(nlevels, level_sigma2, nlevels);
+  const size_t o_v = b.reserve<uint8_t>(cap), o_b = b.reserve<uint8_t>(cap), o_X = b.reserve<double>(cap * 3);
+  SD_TRY(b.run("sd_debug_triangulate", [&] {
+    TriangIn a = {b.dev<sd_keypoint>(o_k1u), b.dev<sd_keypoint>(o_k1), b.dev<sd_keypoint>(o_k2u), b.dev<sd_keypoint>(o_k2),
+                  b.dev<int32_t>(o_m), b.dev<float>(o_u1), b.dev<float>(o_u2), b.dev<float>(o_z1), b.dev<float>(o_z2),
+                  b.dev<double>(o_T1), b.dev<double>(o_T2), b.dev<float>(o_med), b.dev<float>(o_sf), b.dev<float>(o_s2),
+                  0, 0, 0, 0, 0, 0, 0, 0, 0, nlevels, (int)cap, -1, monocular, b.dev<uint8_t>(o_v), b.dev<uint8_t>(o_b),
+                  b.dev<double>(o_X)};
+    set_camera(a, make_cam(cam5[0], cam5[1], cam5[2], cam5[3], cam5[4], 0, 0, 0, 0), 1.5f * scale_factor);   // (no image bounds here)
+    return launch_k_triangulate(a, 1, 0);
+  }));
+  b.take(verdict, o_v, (size_t)n1);
+  b.take(branch, o_b, (size_t)n1);
+  b.take(Xw, o_X, (size_t)n1 * 24);
   return SD_OK;
 }
 

@@ -1647,8 +1647,7 @@ int read_pnp_prof(unsigned long long* out32, int reset) {
 
 int launch_pnp(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_sigma2, const PnpParams& pp,
                int n_frames, hipStream_t s) {
-  hipLaunchKernelGGL(pp.min_set == 4 ? k_pnp<false> : k_pnp<true>, dim3(n_frames), dim3(64), 0, s, (cur->have_dist ? cur->d_kps_un : cur->d_kps), cur->d_nout, tb, cam, d_sigma2, pp,
-                     n_frames);
+  hipLaunchKernelGGL(pp.min_set == 4 ? k_pnp<false> : k_pnp<true>, dim3(n_frames), dim3(64), 0, s, keys_un(cur), cur->d_nout, tb, cam, d_sigma2, pp, n_frames);
   SD_HIP_CHECK(hipGetLastError());
   return SD_OK;
 }

@@ -747,7 +747,7 @@ int launch_pose_opt(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& c
   // waves per frame by batch size: option "track.poseopt_waves" = 1 | 4 overrides (tests, experiments)
   const int forced = opt(OPT_POSEOPT_WAVES);
   const int waves = forced ? forced : (n_frames <= 256 ? 4 : 1);
-  const sd_keypoint* kps = cur->have_dist ? cur->d_kps_un : cur->d_kps;
+  const sd_keypoint* kps = keys_un(cur);
   if (waves == 4)
     hipLaunchKernelGGL(k_pose_opt<4>, dim3(n_frames), dim3(256), 0, s, kps, cur->d_nout, tb, cam, d_inv_sigma2, source, n_frames, min_matches,
                        min_inliers);

@@ -182,7 +182,7 @@ int sd_track_advance(sd_track* h, int n_frames, int source) {
   SD_TRY(orb_enable_double_buffer(h->ref));
   SD_TRY(wait_inputs(h, false));
   const sd_orb* c = h->cur;
-  hipLaunchKernelGGL(k_advance, dim3(h->max_batch), dim3(256), 0, h->pnp_stream, c->d_kps, c->have_dist ? c->d_kps_un : c->d_kps, c->d_nout, h->tb, source,
+  hipLaunchKernelGGL(k_advance, dim3(h->max_batch), dim3(256), 0, h->pnp_stream, c->d_kps, keys_un(c), c->d_nout, h->tb, source,
                      n_frames, c->d_desc, created_n);
   SD_HIP_CHECK(hipGetLastError());
   SD_TRY(mark_reads(h, false));
@@ -195,7 +195,8 @@ int sd_track_advance(sd_track* h, int n_frames, int source) {
   std::swap(tb.obs, tb.obs2);
   std::swap(tb.last_id, tb.last_id2);
   std::swap(h->cur, h->ref);   // this frame's pyramid and keypoints are the next ImageAlign / match reference
-  h->have_pnp = false;
+  if (h->cur != h->ref) h->res.swap_roles();
+  END_RESULTS(h, "sd_track_advance");
   h->ran[0] = h->ran[1] = h->close = h->made = RunStamp{};   // nothing has run on the new `cur` yet
   return SD_OK;
 }
@@ -274,7 +275,7 @@ int sd_track_stereo_init(sd_track* h, int n_frames, int min_keypoints) {
   SD_TRY(check_paired(h));
   SD_REQUIRE(h->cur->have_geom && h->cur->last_frames >= n_frames, SD_ERR_INVALID_ARG, "current frames have not been extracted");
   SD_HIP_CHECK(hipSetDevice(h->device));
-  h->have_pnp = false;
+  END_RESULTS(h, "sd_track_stereo_init");
   return new_points(h, n_frames, 2, 0, 0.f, 0, 0, min_keypoints);
 }
 

@@ -505,8 +505,7 @@ __global__ __launch_bounds__(64) void k_sim3(const sd_keypoint* __restrict__ kps
 int launch_sim3(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const TrackCam& cam, const float* d_sigma2,
                 const int32_t* d_max_its, const Sim3Params& sp, int n_frames, hipStream_t s) {
   SD_REQUIRE(tb.kp_cap <= S3_MAXN, SD_ERR_CAPACITY, "Sim3Solver supports at most 2048 keypoints per keyframe");
-  hipLaunchKernelGGL(k_sim3, dim3(n_frames), dim3(64), 0, s, (cur->have_dist ? cur->d_kps_un : cur->d_kps), cur->d_nout,
-                     (ref->have_dist ? ref->d_kps_un : ref->d_kps), ref->d_nout, tb, cam, d_sigma2, cur->nlevels, d_max_its, sp);
+  hipLaunchKernelGGL(k_sim3, dim3(n_frames), dim3(64), 0, s, keys_un(cur), cur->d_nout, keys_un(ref), ref->d_nout, tb, cam, d_sigma2, cur->nlevels, d_max_its, sp);
   SD_HIP_CHECK(hipGetLastError());
   return SD_OK;
 }
@@ -550,7 +549,7 @@ extern "C" {
 int sd_track_set_sim3_points(sd_track* h, int frame0, int n_frames, const double* Xw_cur, const double* Xw_ref, int cap) {
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(Xw_cur && Xw_ref && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad point arrays (cap must be 1..keypoint capacity)");
-  sim3_end(h);
+  END_RESULTS(h, "sd_track_set_sim3_points");
   hipStream_t s = h->cur->stream;
   const size_t K3 = (size_t)h->kp_cap * 3;
   SD_TRY(upload_rows(h->tb.s3_Xw1, K3, Xw_cur, (size_t)cap * 3, frame0, n_frames, s));
@@ -563,7 +562,7 @@ int sd_track_set_point_matches(sd_track* h, int frame0, int n_frames, const int3
   SD_REQUIRE(matches12 && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad match array (cap must be 1..keypoint capacity)");
   for (size_t i = 0; i < (size_t)n_frames * cap; i++)
     SD_REQUIRE(matches12[i] >= -1 && matches12[i] < h->kp_cap, SD_ERR_INVALID_ARG, "match index outside [-1, keypoint capacity)");
-  sim3_end(h);
+  END_RESULTS(h, "sd_track_set_point_matches");
   hipStream_t s = h->cur->stream;
   const size_t K = h->kp_cap;
   SD_HIP_CHECK(hipMemsetAsync(h->tb.sp_match + (size_t)frame0 * K, 0xFF, (size_t)n_frames * K * sizeof(int32_t), s));   // the rest: NULL
@@ -573,12 +572,11 @@ int sd_track_set_point_matches(sd_track* h, int frame0, int n_frames, const int3
 
 int sd_track_sim3(sd_track* h, int n_frames, int fix_scale, double probability, int min_inliers, int max_iterations, int n_iterations) {
   SD_TRY(check_ready(h, n_frames));
-  SD_TRY(require_ref_frames(h, n_frames, false));
-  SD_REQUIRE(keypoint_capacity(h->ref) == h->kp_cap, SD_ERR_INVALID_ARG, "cur / ref extractors must share the keypoint capacity");
+  SD_TRY(require_ref_frames(h, n_frames, false, true));
   SD_REQUIRE(probability > 0.0 && probability < 1.0, SD_ERR_INVALID_ARG, "probability must lie in (0, 1)");
   SD_REQUIRE(min_inliers >= 3 && max_iterations >= 1 && n_iterations >= 1, SD_ERR_INVALID_ARG,
              "bad RANSAC parameters (min_inliers >= 3, max_iterations >= 1, n_iterations >= 1)");
-  sim3_end(h);
+  END_RESULTS(h, "sd_track_sim3");
   // mnIterations never passes mRansacMaxIts <= max_iterations
   SD_TRY(sim3_check_rand(h, n_frames, std::min(max_iterations, n_iterations)));
   std::vector<int32_t> table((size_t)h->kp_cap + 1);
@@ -591,8 +589,7 @@ int sd_track_sim3(sd_track* h, int n_frames, int fix_scale, double probability, 
   sp.rand_per_frame = h->rand_per_frame;
   sp.resume = 0;
   SD_TRY(run_sim3(h, n_frames, sp));
-  h->sim3.set(h, n_frames, h->tb.cur_bcast);
-  h->sim3_ref_serial = h->ref->extract_serial;
+  h->res.sim3.set(n_frames, BIND_SIM3, inputs_now(h));
   h->sim3_params = sp;
   h->sim3_max_its = max_iterations;
   h->sim3_iter_upper = std::min(max_iterations, n_iterations);
@@ -601,8 +598,7 @@ int sd_track_sim3(sd_track* h, int n_frames, int fix_scale, double probability, 
 
 int sd_track_sim3_iterate(sd_track* h, int n_frames, int n_iterations) {
   SD_TRY(check_ready(h, n_frames));
-  SD_REQUIRE(h->sim3.covers(h, n_frames) && h->sim3_ref_serial == h->ref->extract_serial && h->sim3.mode == h->tb.cur_bcast,
-             SD_ERR_INVALID_ARG,
+  SD_REQUIRE(h->res.sim3.live(n_frames, inputs_now(h)), SD_ERR_INVALID_ARG,
              "sd_track_sim3 has not constructed solvers for these slots (or their keyframes, matches, points, flags, poses or rand stream "
              "were replaced since)");
   SD_REQUIRE(n_iterations >= 1, SD_ERR_INVALID_ARG, "bad n_iterations");

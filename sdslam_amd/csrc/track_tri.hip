@@ -313,9 +313,8 @@ int launch_tri(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& b, cons
                      use_set_f12 ? (const double*)b.tri_F12_set : (const double*)nullptr, b.tri_F12, b.tri_epi, n_frames);
   SD_HIP_CHECK(hipGetLastError());
   const TriBuffers tb = {b.sp_valid1, b.sp_valid2, b.uright, b.uright_ref, b.tri_F12, b.tri_epi, d_sf, d_sigma2, b.tri_match, b.tri_n};
-  return launch_search_triangulation(cur->have_dist ? cur->d_kps_un : cur->d_kps, cur->d_desc, cur->d_nout,
-                                     ref->have_dist ? ref->d_kps_un : ref->d_kps, ref->d_desc, ref->d_nout, tb, b.cur_bcast, b.kp_cap,
-                                     cur->nlevels, n_frames, check_ori, s);
+  return launch_search_triangulation(keys_un(cur), cur->d_desc, cur->d_nout, keys_un(ref), ref->d_desc, ref->d_nout, tb, b.cur_bcast,
+                                     b.kp_cap, cur->nlevels, n_frames, check_ori, s);
 }
 
 }  // namespace sd
@@ -327,8 +326,7 @@ extern "C" {
 int sd_track_set_uright_ref(sd_track* h, int frame0, int n_frames, const float* uright, int cap) {
   QUEUE_RANGE(h, frame0, n_frames);
   SD_REQUIRE(uright && cap >= 1 && cap <= h->kp_cap, SD_ERR_INVALID_ARG, "bad uright array");
-  tri_end(h);
-  fuse_end(h);
+  END_RESULTS(h, "sd_track_set_uright_ref");
   SD_TRY(upload_rows(h->tb.uright_ref, h->kp_cap, uright, cap, frame0, n_frames, h->pnp_stream));
   return wait_for(h->pnp_stream);   // the rows are the caller's pageable memory: back once they are read
 }
@@ -336,7 +334,7 @@ int sd_track_set_uright_ref(sd_track* h, int frame0, int n_frames, const float* 
 int sd_track_set_f12(sd_track* h, int frame0, int n_frames, const double* F12_rm9) {
   QUEUE_RANGE(h, frame0, n_frames);
   SD_REQUIRE(F12_rm9, SD_ERR_INVALID_ARG, "NULL argument");
-  tri_end(h);
+  END_RESULTS(h, "sd_track_set_f12");
   SD_TRY(h->pose_ring.upload(h->tb.tri_F12_set + (size_t)frame0 * 9, F12_rm9, (size_t)n_frames * 9, h->pnp_stream));
   std::fill(h->f12_set.begin() + frame0, h->f12_set.begin() + frame0 + n_frames, (uint8_t)1);
   return SD_OK;
@@ -344,25 +342,22 @@ int sd_track_set_f12(sd_track* h, int frame0, int n_frames, const double* F12_rm
 
 int sd_track_search_for_triangulation(sd_track* h, int n_frames, int use_set_f12, int check_ori) {
   SD_TRY(check_ready(h, n_frames));
-  SD_TRY(require_ref_frames(h, n_frames, false));
-  SD_REQUIRE(keypoint_capacity(h->ref) == h->kp_cap, SD_ERR_INVALID_ARG, "cur / ref extractors must share the keypoint capacity");
+  SD_TRY(require_ref_frames(h, n_frames, false, true));
   if (use_set_f12)
     for (int f = 0; f < n_frames; f++)
       SD_REQUIRE(h->f12_set[f], SD_ERR_INVALID_ARG, "use_set_f12 = 1, but sd_track_set_f12 has not covered these slots");
-  tri_end(h);
+  END_RESULTS(h, "sd_track_search_for_triangulation");
   SD_TRY(run_stage(h, true, false, STAGE_MATCH, [&](hipStream_t s) {   // timed in the matcher's slot
     return launch_tri(h->cur, h->ref, h->tb, h->cam, h->d_sf, h->d_sigma2, n_frames, use_set_f12, check_ori, s);
   }));
-  h->tri.set(h, n_frames, h->tb.cur_bcast, check_ori != 0);   // source: the rotation check ran (sd_track_triangulate asks)
-  h->tri_ref_serial = h->ref->extract_serial;
+  h->res.tri.set(n_frames, BIND_TRI, inputs_now(h), check_ori != 0);   // payload: the rotation check ran (sd_track_triangulate asks)
   return SD_OK;
 }
 
 int sd_track_get_triangulation_matches(sd_track* h, int frame0, int n_frames, int32_t* matches12, int cap, int32_t* n_matches,
                                        double* F12_rm9, float* epipole2) {
   TRACK_RANGE(h, frame0, n_frames);
-  SD_REQUIRE(h->tri.covers(h, frame0 + n_frames) && h->tri_ref_serial == h->ref->extract_serial && h->tri.mode == h->tb.cur_bcast,
-             SD_ERR_INVALID_ARG,
+  SD_REQUIRE(h->res.tri.live(frame0 + n_frames, inputs_now(h)), SD_ERR_INVALID_ARG,
              "sd_track_search_for_triangulation has not run on these slots (or their keyframes, flags, mvuRight, poses, F12 or the "
              "broadcast setting were replaced since)");
   SD_REQUIRE(!matches12 || cap >= h->kp_cap, SD_ERR_CAPACITY, "cap smaller than the keypoint capacity");
@@ -385,42 +380,22 @@ int sd_debug_search_for_triangulation(int n1, int n2, const sd_keypoint* kps1, c
              SD_ERR_INVALID_ARG, "bad arguments");
   const size_t cap = (size_t)std::max(std::max(n1, n2), 1);
   Blob b;
-  const size_t o_k1 = b.reserve(cap * sizeof(sd_keypoint)), o_k2 = b.reserve(cap * sizeof(sd_keypoint));
-  const size_t o_d1 = b.reserve(cap * 32), o_d2 = b.reserve(cap * 32);
-  const size_t o_h1 = b.reserve(cap), o_h2 = b.reserve(cap);
-  const size_t o_u1 = b.reserve(cap * 4), o_u2 = b.reserve(cap * 4);
-  const size_t o_F = b.reserve(9 * 8), o_e = b.reserve(2 * 4), o_sf = b.reserve((size_t)nlevels * 4), o_s2 = b.reserve((size_t)nlevels * 4);
-  const size_t o_n = b.reserve(3 * 4), o_m = b.reserve(cap * 4);
-  std::vector<uint8_t> host(b.bytes, 0);
-  auto put = [&](size_t off, const void* src, size_t n) { if (n) std::memcpy(host.data() + off, src, n); };
-  put(o_k1, kps1, (size_t)n1 * sizeof(sd_keypoint)); put(o_k2, kps2, (size_t)n2 * sizeof(sd_keypoint));
-  put(o_d1, desc1, (size_t)n1 * 32); put(o_d2, desc2, (size_t)n2 * 32);
-  put(o_h1, has_mp1, (size_t)n1); put(o_h2, has_mp2, (size_t)n2);
-  put(o_u1, uright1, (size_t)n1 * 4); put(o_u2, uright2, (size_t)n2 * 4);
-  put(o_F, F12_rm9, 72); put(o_e, epipole2, 8);
-  put(o_sf, scale_factors, (size_t)nlevels * 4); put(o_s2, level_sigma2, (size_t)nlevels * 4);
   const int32_t counts[3] = {n1, n2, 0};
-  put(o_n, counts, sizeof(counts));
-  SD_HIP_CHECK(hipMalloc(&b.base, b.bytes));
-  uint8_t* d = b.base;
-  hipError_t e = hipMemcpy(d, host.data(), b.bytes, hipMemcpyHostToDevice);
-  int rc = SD_OK;
-  if (e == hipSuccess) {
-    const TriBuffers tb = {d + o_h1, d + o_h2, (const float*)(d + o_u1), (const float*)(d + o_u2), (const double*)(d + o_F),
-                           (const float*)(d + o_e), (const float*)(d + o_sf), (const float*)(d + o_s2), (int32_t*)(d + o_m),
-                           (int32_t*)(d + o_n) + 2};
-    rc = launch_search_triangulation((const sd_keypoint*)(d + o_k1), d + o_d1, (const int32_t*)(d + o_n), (const sd_keypoint*)(d + o_k2),
-                                     d + o_d2, (const int32_t*)(d + o_n) + 1, tb, -1, (int)cap, nlevels, 1, check_ori, 0);
-    if (rc == SD_OK) e = hipMemcpy(host.data(), d, b.bytes, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(b.base);
-  if (e != hipSuccess) {
-    set_error(std::string("sd_debug_search_for_triangulation: ") + hipGetErrorString(e));
-    return SD_ERR_HIP;
-  }
-  SD_TRY(rc);
-  if (n1) std::memcpy(matches12, host.data() + o_m, (size_t)n1 * 4);
-  std::memcpy(n_matches, host.data() + o_n + 8, 4);
+  const size_t o_k1 = b.reserve(cap, kps1, n1), o_k2 = b.reserve(cap, kps2, n2);
+  const size_t o_d1 = b.reserve(cap * 32, desc1, (size_t)n1 * 32), o_d2 = b.reserve(cap * 32, desc2, (size_t)n2 * 32);
+  const size_t o_h1 = b.reserve(cap, has_mp1, n1), o_h2 = b.reserve(cap, has_mp2, n2);
+  const size_t o_u1 = b.reserve(cap, uright1, n1), o_u2 = b.reserve(cap, uright2, n2);
+  const size_t o_F = b.reserve(9, F12_rm9, 9), o_e = b.reserve(2, epipole2, 2);
+  const size_t o_sf = b.reserve(nlevels, scale_factors, nlevels), o_s2 = b.reserve(nlevels, level_sigma2, nlevels);
+  const size_t o_n = b.reserve(3, counts, 3), o_m = b.reserve<int32_t>(cap);
+  SD_TRY(b.run("sd_debug_search_for_triangulation", [&] {
+    const TriBuffers tb = {b.dev<uint8_t>(o_h1), b.dev<uint8_t>(o_h2), b.dev<float>(o_u1), b.dev<float>(o_u2), b.dev<double>(o_F),
+                           b.dev<float>(o_e), b.dev<float>(o_sf), b.dev<float>(o_s2), b.dev<int32_t>(o_m), b.dev<int32_t>(o_n) + 2};
+    return launch_search_triangulation(b.dev<sd_keypoint>(o_k1), b.dev<uint8_t>(o_d1), b.dev<int32_t>(o_n), b.dev<sd_keypoint>(o_k2),
+                                       b.dev<uint8_t>(o_d2), b.dev<int32_t>(o_n) + 1, tb, -1, (int)cap, nlevels, 1, check_ori, 0);
+  }));
+  b.take(matches12, o_m, (size_t)n1 * 4);
+  b.take(n_matches, o_n + 8, 4);
   return SD_OK;
 }
 

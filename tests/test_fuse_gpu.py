@@ -195,6 +195,24 @@ def test_debug_entry_is_bit_exact_on_every_case(sd, sim3):
     assert total > 500
 
 
+@pytest.mark.parametrize("n_kp,n_pts", [(0, 0), (1, 3)])
+def test_debug_entry_on_empty_and_unaligned_inputs(sd, n_kp, n_pts):
+    """Nothing at all (the entry still launches, on capacities of 1, and returns the untouched rest of a row), and counts that
+    are no multiple of the 16 bytes the entry's device arrays are carved in."""
+    from sdslam_amd import capi
+    c = FC.shape_case("tiny_%dx%d" % (n_kp, n_pts), 40, n_kp, n_pts)
+    for sim3 in (0, 1):
+        (want_idx, want_dist), T = FC.reference(c, sim3)
+        assert (want_idx >= 0).sum() == (2 if n_pts else 0)          # the one keypoint is found by two of the three points
+        g = capi.debug_fuse(c["kps"], c["desc"], c["uright"], c["pts"], T, c["cam"], FC.SF, FC.INV_SIGMA2, FC.SCALE, c["th"], bool(sim3))
+        assert len(g["best_idx"]) == n_pts and np.array_equal(g["best_idx"], want_idx) and np.array_equal(g["best_dist"], want_dist)
+        assert g["n_found"] == int((want_idx >= 0).sum())
+        assert (g["rest_idx"] == -1).all() and (g["rest_dist"] == 256).all() and len(g["rest_idx"]) == (1 if n_pts == 0 else 0)
+        if not sim3:
+            R, t, Ow = FR.decompose(T, False)
+            assert np.array_equal(g["pose"][0], R) and np.array_equal(g["pose"][1], t) and np.array_equal(g["pose"][2], Ow)
+
+
 # ------------------------------------------------------------------------------------------------ 2. through extraction
 @pytest.mark.parametrize("cfg", CONFIGS, ids=lambda c: "side%d-bc%d-row%d-sim%d" % c)
 @pytest.mark.parametrize("name", list(RIGS))

@@ -186,3 +186,16 @@ def test_match_lds_layouts_under_sanitizers(tmp_path):
                            "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "match_lds_check OK" in out.stdout, out.stdout + out.stderr
+
+
+def test_result_lifetimes_plain_and_under_sanitizers(tmp_path):
+    """The lifetime of every cached result (track_results.h): which entry point ends which of the PnP / Sim3 / tri / triang /
+    Fuse results, against a matrix typed into the check itself, and which change of an extraction serial or of the broadcast
+    setting ends which.  The header alone, stand-alone program, built plain and with AddressSanitizer and UBSan."""
+    for tag, flags in (("plain", ["-O2"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])):
+        exe = str(tmp_path / f"result_stamps_check_{tag}")
+        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror"] + flags +
+                              ["-I", os.path.join(ROOT, "sdslam_amd", "csrc"),
+                               os.path.join(ROOT, "tests", "native", "result_stamps_check.cpp"), "-o", exe])
+        out = subprocess.run([exe], capture_output=True, text=True)
+        assert out.returncode == 0 and "result_stamps_check OK" in out.stdout, out.stdout + out.stderr

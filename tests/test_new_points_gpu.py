@@ -93,6 +93,28 @@ def test_debug_entry_is_bit_exact_on_every_case(sd):
     assert set(seen) == set(range(11))
 
 
+def test_debug_entry_on_empty_and_unaligned_inputs(sd):
+    """Both keyframes empty (nothing runs, nothing is written), and 1 keypoint against 3: counts that are no multiple of the 16
+    bytes the entry's device arrays are carved in, KF1 shorter than the padded capacity."""
+    from sdslam_amd import capi
+    c = NC.count_case(1, 11)
+    side1, side2 = ("k1u", "k1", "ur1", "z1"), ("k2u", "k2", "ur2", "z2")
+
+    def run(c):
+        return capi.debug_triangulate(c["k1u"], c["k1"], c["ur1"], c["z1"], c["k2u"], c["k2"], c["ur2"], c["z2"], c["m"], c["T1"], c["T2"],
+                                      c["cam5"], c["sf"], c["sigma2"], c["scale_factor"], c["monocular"], c["median"])
+    v, b, X = run(dict(c, m=c["m"][:0], **{k: c[k][:0] for k in side1 + side2}))
+    assert len(v) == len(b) == len(X) == 0
+    i = int(np.flatnonzero(c["m"] >= 0)[0])
+    j = int(c["m"][i])
+    rest = [k for k in range(len(c["k2"])) if k != j]
+    one = dict(c, m=np.array([1], np.int32), **{k: c[k][[i]] for k in side1}, **{k: c[k][[rest[0], j, rest[1]]] for k in side2})
+    want_v, want_b, want_X = NC.reference(one)
+    v, b, X = run(one)
+    assert want_v[0] == NR.ACCEPTED                            # the row does go through the triangulation
+    assert np.array_equal(v, want_v) and np.array_equal(b, want_b) and X.tobytes() == want_X.tobytes()
+
+
 # ------------------------------------------------------------------------------------------------ 2. the batched path, 3. resolve
 @pytest.mark.parametrize("mix,monocular", [("mono", True), ("stereo", False)])
 @pytest.mark.parametrize("bc", [False, True])

@@ -126,6 +126,19 @@ def test_debug_entry_is_bit_exact_on_every_case(sd, ori):
     assert total > 200      # the restatement's own count (242 with the rotation check, more without): not vacuous
 
 
+@pytest.mark.parametrize("n1,n2", [(0, 0), (1, 3)])
+def test_debug_entry_on_empty_and_unaligned_inputs(sd, n1, n2):
+    """Both sides empty (the entry still launches, on a capacity of 1), and counts that are no multiple of the 16 bytes the
+    entry's device arrays are carved in."""
+    from sdslam_amd import capi
+    c = TC.shape_case("tiny_%dx%d" % (n1, n2), 40 + n1, n1, n2, flagged=0.0)
+    for ori in (0, 1):
+        want_n, want_m = TC.reference(c, ori)
+        n, m = capi.debug_search_for_triangulation(c["k1"], c["d1"], c["h1"], c["u1"], c["k2"], c["d2"], c["h2"], c["u2"], c["F12"],
+                                                   c["epi"], c["sf"], c["sigma2"], ori)
+        assert n == want_n and len(m) == n1 and np.array_equal(m, want_m), (n1, n2, ori, n, want_n, m, want_m)
+
+
 # ------------------------------------------------------------------------------------------------ 2. through extraction
 @pytest.mark.parametrize("name", list(RIGS))
 def test_batched_path_through_extraction(sd, name):
