@@ -396,7 +396,8 @@ class ORBmatcher {
   // between neighbours is not taken: all neighbours are done in one call.
   // KeyFrameT needs, besides what SearchForTriangulation needs, mvDepth, ComputeSceneMedianDepth(q) and AddMapPoint(pMP, idx);
   // MapPointT needs AddObservation(pKF, idx), SetDescriptor(const uint8_t*), SetNormalVector(const double*),
-  // SetMaxDistance(float) and SetMinDistance(float): what ComputeDistinctiveDescriptors and UpdateNormalAndDepth would compute.
+  // SetMaxDistance(float) and SetMinDistance(float): what ComputeDistinctiveDescriptors and UpdateNormalAndDepth would compute
+  // (for two observations; RefreshMapPoints below runs both functions for any list).
   template <class KeyFrameT, class MakePoint, class RecentList>
   int CreateNewMapPoints(TrackBatch& batch, KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpNeighKFs, bool monocular, int32_t nNextId,
                          MakePoint make_point, RecentList& recent, int kp_cap) {
@@ -617,6 +618,106 @@ class ORBmatcher {
     if (pKF->N > 0) check(sd_track_set_uright_ref(batch.handle(), slot, 1, pKF->mvuRight.data(), pKF->N));
     const auto T = pKF->GetPose();
     batch.SetPoses(slot, T.data(), T.data());
+  }
+
+  // pMP->ComputeDistinctiveDescriptors(); pMP->UpdateNormalAndDepth(); for every point of a list
+  //                                   src/MapPoint.cc:225-343; callers src/LocalMapping.cc:478-488, :140-147, src/LoopClosing.cc:457-484
+  // The loop that ends SearchInNeighbors, on the device (sd_track_refresh_points, write_local = 1).  vpMapPoints are the points of
+  // local row `point_row` as the last Fuse call (or sd_track_set_local) uploaded them, entry i = vpMapPoints[i]; pKF is the current
+  // keyframe (the broadcast frame of the cur extractor, or its frame 0; pose Tcur of slot 0); frameOf(KeyFrameT*) returns the
+  // frame of the ref extractor that holds a keyframe's image (its pose is Tref of that slot), or a negative number when the
+  // keyframe is not resident.  Each point's GetObservations() is walked in ITS iteration order, which defines the tie-break of
+  // the descriptor and the order of the normal's sum.  Points the device refreshed get SetDescriptor / SetNormalVector /
+  // SetMaxDistance / SetMinDistance (the parts their status names) and the row holds the same values: the next Fuse or
+  // TrackLocalMap search needs no upload.  Returns the points left to the caller's own two calls: those with a keyframe that is
+  // not resident, with more than SD_REFRESH_MAX_OBS observations, or whose reference keyframe is not among the observations.
+  // KeyFrameT needs isBad(); MapPointT needs isBad(), GetObservations() (pairs of KeyFrameT* and keypoint index),
+  // GetReferenceKeyFrame() and the four setters.
+  template <class KeyFrameT, class MapPointT, class FrameOf>
+  std::vector<MapPointT*> RefreshMapPoints(TrackBatch& batch, KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, FrameOf frameOf,
+                                           int point_row = 0) {
+    if (vpMapPoints.size() > (size_t)batch.max_points())
+      throw Error(SD_ERR_CAPACITY, "RefreshMapPoints: more points than the batch's max_points (split the list)");
+    ObservationLists L;
+    BuildObservationLists(pKF, vpMapPoints, frameOf, L);
+    const int n = (int)vpMapPoints.size();
+    if (n == 0) return {};
+    check(sd_track_set_observations(batch.handle(), n, L.off.data(), L.frame.data(), L.kp.data(), L.kf_bad.data(), L.ref_obs.data(),
+                                    L.point_bad.data()));
+    check(sd_track_refresh_points(batch.handle(), point_row, 1));
+    RefreshedRows r(n);
+    check(sd_track_get_refreshed(batch.handle(), r.status.data(), nullptr, nullptr, r.desc.data(), r.normal.data(), r.max_dist.data(),
+                                 r.min_dist.data(), n));
+    return ApplyRefreshed(L, r, vpMapPoints);   // (the lists and the results, not the batch: host code, tests/native/facade_refresh.cc)
+  }
+  // The CSR lists of sd_track_set_observations.  left[i]: the point goes back to the caller whatever the device says.
+  struct ObservationLists {
+    std::vector<int32_t> off, frame, kp, ref_obs;
+    std::vector<uint8_t> kf_bad, point_bad, left;
+  };
+  struct RefreshedRows {
+    std::vector<uint8_t> status, desc;
+    std::vector<double> normal;
+    std::vector<float> max_dist, min_dist;
+    explicit RefreshedRows(size_t n) : status(n, 0), desc(n * 32, 0), normal(n * 3, 0.0), max_dist(n, 0.f), min_dist(n, 0.f) {}
+  };
+  // Host code only: every point's observations in iteration order.  A NULL point is sent as a bad one (both functions skip it).
+  template <class KeyFrameT, class MapPointT, class FrameOf>
+  static void BuildObservationLists(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, FrameOf frameOf, ObservationLists& L) {
+    const size_t n = vpMapPoints.size();
+    L.off.assign(1, 0);
+    L.frame.clear(); L.kp.clear(); L.kf_bad.clear();
+    L.ref_obs.assign(n, 0);
+    L.point_bad.assign(n, 0);
+    L.left.assign(n, 0);
+    for (size_t i = 0; i < n; i++) {
+      MapPointT* pMP = vpMapPoints[i];
+      if (!pMP || pMP->isBad()) {
+        L.point_bad[i] = 1;
+        L.off.push_back((int32_t)L.frame.size());
+        continue;
+      }
+      const auto observations = pMP->GetObservations();
+      const KeyFrameT* pRefKF = pMP->GetReferenceKeyFrame();
+      int32_t pos = 0, ref_pos = -1;
+      for (const auto& ob : observations) {
+        KeyFrameT* pKFi = ob.first;
+        L.frame.push_back(pKFi == pKF ? -1 : ((int)frameOf(pKFi) < 0 ? -2 : (int)frameOf(pKFi)));
+        L.kp.push_back((int32_t)ob.second);
+        L.kf_bad.push_back(pKFi->isBad() ? 1 : 0);
+        if (pKFi == pRefKF) ref_pos = pos;
+        pos++;
+      }
+      if (pos > 0 && ref_pos < 0) {   // (the reference would read observations[pRefKF] of a keyframe that is not there)
+        L.left[i] = 1;
+        L.frame[(size_t)L.off.back()] = -2;   // the device leaves the point, and its row, alone
+      }
+      L.ref_obs[i] = ref_pos < 0 ? 0 : ref_pos;
+      L.off.push_back((int32_t)L.frame.size());
+    }
+    if (L.frame.empty()) L.frame.push_back(0), L.kp.push_back(0), L.kf_bad.push_back(0);   // (data() of an empty vector may be NULL)
+  }
+  // Host code only: the setters for what the status names; returns the points that stay with the caller
+  template <class MapPointT>
+  static std::vector<MapPointT*> ApplyRefreshed(const ObservationLists& L, const RefreshedRows& r, const std::vector<MapPointT*>& vpMapPoints) {
+    std::vector<MapPointT*> left;
+    for (size_t i = 0; i < vpMapPoints.size(); i++) {
+      MapPointT* pMP = vpMapPoints[i];
+      if (!pMP || L.point_bad[i]) continue;
+      const int st = r.status[i];
+      if (L.left[i] || (st & (SD_REFRESH_NOT_RESIDENT | SD_REFRESH_TOO_MANY))) {
+        left.push_back(pMP);
+        continue;
+      }
+      if (st & SD_REFRESH_BAD_INDEX) throw Error(SD_ERR_INVALID_ARG, "RefreshMapPoints: an observation's keypoint index is outside its keyframe");
+      if (st & SD_REFRESH_DESC) pMP->SetDescriptor(&r.desc[i * 32]);
+      if (st & SD_REFRESH_NORMAL) {
+        pMP->SetNormalVector(&r.normal[i * 3]);
+        pMP->SetMaxDistance(r.max_dist[i]);
+        pMP->SetMinDistance(r.min_dist[i]);
+      }
+    }
+    return left;
   }
 
  protected:

@@ -492,6 +492,64 @@ int sd_debug_fuse(int n_kp, const sd_keypoint* kps, const uint8_t* desc, const f
                   const float* inv_level_sigma2, int nlevels, float scale_factor, float th, int kp_cap, int max_points,
                   int32_t* best_idx, int32_t* best_dist, int32_t* n_found, double* pose15);
 
+/* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:225-284) and MapPoint::UpdateNormalAndDepth (:304-343) for a list of map
+ *   points: what LocalMapping::SearchInNeighbors (src/LocalMapping.cc:478-488), CreateNewMapPoints' recent points (:140-147),
+ *   LoopClosing::SearchAndFuse (src/LoopClosing.cc:457-484) and Tracking::CreateNewKeyFrame (src/Tracking.cc:874-875) call per point.
+ *   Their outputs are the desc, normal, min_dist, max_dist and mf_max_dist fields of sd_track_set_local.
+ * Keyframes are frames of the extractors.  An observation is (obs_frame, obs_kp): obs_frame >= 0 is a frame of the ref extractor,
+ *   with pose Tref of that slot (sd_track_set_poses); -1 is the current keyframe: the broadcast frame of the cur extractor
+ *   (sd_track_set_current_broadcast), or its frame 0 without a broadcast, with pose Tcur of slot 0; -2 is a keyframe that is not
+ *   resident on the device.  obs_kp indexes that frame's keypoints.
+ * sd_track_set_observations: the observations of n_points <= max_points points as CSR -- point i owns entries obs_off[i] ..
+ *   obs_off[i + 1] - 1 of obs_frame / obs_kp / obs_kf_bad, obs_off[0] = 0 -- IN THE ORDER IN WHICH THE CALLER ITERATES mObservations.
+ *   The reference's order is that of a std::map keyed by pointer; it decides ties of the least median (strict <: the first wins)
+ *   and the order of the normal's sum, so the result is defined as the reference's loops run over the list as given.
+ *   ref_obs[i] = the position of mpRefKF in point i's own list.  obs_kf_bad (may be NULL) marks observations whose keyframe
+ *   isBad(): ComputeDistinctiveDescriptors skips them (:246), UpdateNormalAndDepth does not and counts them in n (:323-329).
+ *   point_bad (may be NULL) marks points that are bad.  The host arrays are copied before the call returns; the upload itself is
+ *   queued on the tracking stream.  The device block for the lists is allocated by sd_track_create for max_points points of 16
+ *   observations each; a call that needs more replaces it by a larger one (this, and only this, waits for the tracking stream and
+ *   allocates), and it never shrinks.
+ *   SD_ERR_INVALID_ARG: obs_off[0] != 0 or not monotone, obs_frame outside [-2, max_batch), ref_obs outside its (non-empty) list;
+ *   SD_ERR_CAPACITY: n_points > max_points.  Keypoint indices are checked on the device against the frame's keypoint count.
+ * sd_track_refresh_points: both functions for every point of the list; world positions are Xw of row point_row of the
+ *   sd_track_set_local buffers, point i of the list = entry i of the row.  Queued on the tracking stream: no host wait, no
+ *   allocation.  write_local = 1 also writes desc, normal, mf_max_dist = mfMaxDistance, max_dist = 1.2f * mfMaxDistance and
+ *   min_dist = 0.8f * mfMinDistance (GetMaxDistanceInvariance / GetMinDistanceInvariance) into that row, for the parts the status
+ *   says were written; everything else keeps its bytes.  A later sd_track_fuse / sd_track_match_local sees the refreshed points
+ *   without an upload.  A write-through ends the cached results sd_track_set_local ends (sd_track_get_fuse); write_local = 0 ends none.
+ * sd_track_get_refreshed (synchronises; NULL outputs are skipped; cap >= n_points entries each): status[i] = SD_REFRESH_DESC |
+ *   SD_REFRESH_NORMAL for what was written, or one reason and nothing written: SD_REFRESH_SKIPPED (point bad or no observations:
+ *   both functions return early), SD_REFRESH_NOT_RESIDENT (an observation with frame -2), SD_REFRESH_TOO_MANY (more than
+ *   SD_REFRESH_MAX_OBS observations) -- these two leave the point to the caller -- or SD_REFRESH_BAD_INDEX (a keypoint index
+ *   outside its frame; nothing is read through it).  A point whose observing keyframes are all bad has SD_REFRESH_NORMAL alone.
+ *   best_obs = BestIdx as a position in the caller's list, best_median = BestMedian, desc [.][32], normal [.][3],
+ *   max_dist = mfMaxDistance, min_dist = mfMinDistance.  Entries that were not written hold what an earlier call left.
+ *   The result ends with a new extraction on either side, sd_track_set_poses, _set_local, _set_observations or another broadcast
+ *   setting: the getter then fails with SD_ERR_INVALID_ARG until sd_track_refresh_points has run again.
+ * sd_debug_refresh_points: the same kernel from host arrays, synchronous, with buffers of its own (no extractor, no tracker):
+ *   per observation its descriptor [32], its keyframe's camera centre [3] (double) and its keypoint's octave; the CSR offsets, flags
+ *   and ref_obs as above; Xw [n_points][3]; mvScaleFactors [nlevels].  The outputs are read AND written: entries the kernel does
+ *   not write come back as they went in.
+ * Arithmetic (operation order: sdslam_amd/csrc/track_refresh.hip): double where the reference has double, float where it has
+ *   float, every operation rounded on its own; distances are sd_hamming's. */
+#define SD_REFRESH_MAX_OBS 256
+#define SD_REFRESH_DESC 1
+#define SD_REFRESH_NORMAL 2
+#define SD_REFRESH_SKIPPED 16
+#define SD_REFRESH_NOT_RESIDENT 32
+#define SD_REFRESH_TOO_MANY 64
+#define SD_REFRESH_BAD_INDEX 128
+int sd_track_set_observations(sd_track* h, int n_points, const int32_t* obs_off, const int32_t* obs_frame, const int32_t* obs_kp,
+                              const uint8_t* obs_kf_bad, const int32_t* ref_obs, const uint8_t* point_bad);
+int sd_track_refresh_points(sd_track* h, int point_row, int write_local);
+int sd_track_get_refreshed(sd_track* h, uint8_t* status, int32_t* best_obs, int32_t* best_median, uint8_t* desc, double* normal,
+                           float* max_dist, float* min_dist, int cap);
+int sd_debug_refresh_points(int n_points, const int32_t* obs_off, const uint8_t* obs_desc, const double* obs_centre,
+                            const int32_t* obs_octave, const uint8_t* obs_kf_bad, const int32_t* ref_obs, const uint8_t* point_bad,
+                            const double* Xw, const float* scale_factors, int nlevels, uint8_t* status, int32_t* best_obs,
+                            int32_t* best_median, uint8_t* desc, double* normal, float* max_dist, float* min_dist);
+
 int sd_track_align(sd_track* h, int n_frames, int mode);
 int sd_track_match(sd_track* h, int n_frames, float th, int mono, int check_ori);
 /* sd_track_pnp = PnPsolver(CurrentFrame, CurrentFrame.mvpMapPoints) + SetRansacParameters(...) + iterate(n_iterations)

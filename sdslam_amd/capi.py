@@ -122,6 +122,10 @@ _SIGNATURES = {
     "sd_track_fuse": (_I, [_P, _I, _I, _I, _F, _I]),
     "sd_track_get_fuse": (_I, [_P, _I, _I, _P, _P, _I, _P]),
     "sd_debug_fuse": (_I, [_I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _F, _F, _I, _I, _P, _P, _P, _P]),
+    "sd_track_set_observations": (_I, [_P, _I, _P, _P, _P, _P, _P, _P]),
+    "sd_track_refresh_points": (_I, [_P, _I, _I]),
+    "sd_track_get_refreshed": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I]),
+    "sd_debug_refresh_points": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sd_track_align": (_I, [_P, _I, _I]),
     "sd_track_match": (_I, [_P, _I, _F, _I, _I]),
     "sd_track_pnp": (_I, [_P, _I, _D, _I, _I, _I, _F, _F, _I]),
@@ -767,6 +771,36 @@ class Tracker:
         _check(self.L.sd_track_debug_read(self.h, 2, frame, _p(p), p.nbytes))
         return p[:9].reshape(3, 3), p[9:12], p[12:]
 
+    # --- MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (src/MapPoint.cc:225-343); points = a set_local row ---
+    def set_observations(self, obs, ref_obs, point_bad=None):
+        """obs: per point a list of (frame, kp) or (frame, kp, kf_bad) in the caller's iteration order; frame >= 0 a ref frame,
+        -1 the current keyframe, -2 not resident.  ref_obs[i]: position of mpRefKF in point i's list."""
+        off, fr, kp, kb = _refresh_csr(obs)
+        ro = np.ascontiguousarray(ref_obs, np.int32)
+        pb = None if point_bad is None else np.ascontiguousarray(point_bad, np.uint8)
+        assert len(ro) == len(obs) and (pb is None or len(pb) == len(obs))
+        _check(self.L.sd_track_set_observations(self.h, len(obs), _p(off), _p(fr), _p(kp), _p(kb), _p(ro), _p(pb)))
+        self._n_refresh = len(obs)
+
+    def refresh_points(self, point_row=0, write_local=True):
+        """Both functions for the points of set_observations at Xw of local row `point_row`; write_local: into that row too."""
+        _check(self.L.sd_track_refresh_points(self.h, int(point_row), int(write_local)))
+
+    def get_refreshed(self, fill=None):
+        """dict(status, best_obs, best_median, desc, normal, max_dist, min_dist) of the last refresh_points()."""
+        out = _refresh_outputs(self._n_refresh, fill)
+        _check(self.L.sd_track_get_refreshed(self.h, *[_p(out[k]) for k in _REFRESH_FIELDS], self._n_refresh))
+        return out
+
+    def read_local_row(self, frame):
+        """The refreshable fields of local row `frame` as they are on the device: dict(desc, normal, min_dist, max_dist, mf_max_dist)."""
+        M = self.M
+        out = dict(desc=np.zeros((M, 32), np.uint8), normal=np.zeros((M, 3)), min_dist=np.zeros(M, np.float32),
+                   max_dist=np.zeros(M, np.float32), mf_max_dist=np.zeros(M, np.float32))
+        for which, key in enumerate(("desc", "normal", "min_dist", "max_dist", "mf_max_dist"), start=3):
+            _check(self.L.sd_track_debug_read(self.h, which, frame, _p(out[key]), out[key].nbytes))
+        return out
+
     # --- Sim3Solver on the SearchByPoints pairing (src/Sim3Solver.cc; caller LoopClosing::ComputeSim3) ---
     def set_sim3_points(self, frame0, Xw_cur, Xw_ref):
         """GetWorldPos() of the two keyframes' map points, [n, cap', 3] each, by that keyframe's keypoint index."""
@@ -1050,3 +1084,49 @@ def debug_fuse(kps, desc, uright, pts, T, cam9, scale_factors, inv_level_sigma2,
                            _p(sf), _p(is2), len(sf), float(scale_factor), float(th), K, M, _p(bi), _p(bd), _p(nf), _p(pose)))
     return dict(best_idx=bi[:n], best_dist=bd[:n], n_found=int(nf[0]), pose=(pose[:9].reshape(3, 3), pose[9:12], pose[12:]),
                 rest_idx=bi[n:], rest_dist=bd[n:])
+
+
+REFRESH_MAX_OBS = 256
+REFRESH_DESC, REFRESH_NORMAL, REFRESH_SKIPPED, REFRESH_NOT_RESIDENT, REFRESH_TOO_MANY, REFRESH_BAD_INDEX = 1, 2, 16, 32, 64, 128
+_REFRESH_FIELDS = ("status", "best_obs", "best_median", "desc", "normal", "max_dist", "min_dist")
+
+
+def _refresh_csr(obs):
+    """Per-point observation lists of (frame, kp[, kf_bad]) -> (obs_off, obs_frame, obs_kp, obs_kf_bad)."""
+    off = np.zeros(len(obs) + 1, np.int32)
+    off[1:] = np.cumsum([len(o) for o in obs])
+    flat = [t for o in obs for t in o]
+    fr = np.array([t[0] for t in flat], np.int32)
+    kp = np.array([t[1] for t in flat], np.int32)
+    kb = np.array([t[2] if len(t) > 2 else 0 for t in flat], np.uint8)
+    return off, fr, kp, kb
+
+
+def _refresh_outputs(n, fill=None):
+    """The seven output arrays for n points; fill: a dict of arrays to start from (copied), else zeros."""
+    shapes = dict(status=((n,), np.uint8), best_obs=((n,), np.int32), best_median=((n,), np.int32), desc=((n, 32), np.uint8),
+                  normal=((n, 3), np.float64), max_dist=((n,), np.float32), min_dist=((n,), np.float32))
+    return {k: (np.zeros(sh, dt) if fill is None else np.ascontiguousarray(fill[k], dt).reshape(sh).copy())
+            for k, (sh, dt) in shapes.items()}
+
+
+def debug_refresh_points(obs_off, obs_desc, obs_centre, obs_octave, ref_obs, Xw, scale_factors, obs_kf_bad=None, point_bad=None,
+                         fill=None):
+    """Observation lists from host arrays through k_refresh_points (diagnostics).  fill: what the outputs hold before the call
+    (entries the kernel does not write come back unchanged).  Returns dict(status, best_obs, best_median, desc, normal,
+    max_dist, min_dist)."""
+    L = lib()
+    off = np.ascontiguousarray(obs_off, np.int32)
+    n, total = len(off) - 1, int(off[-1])
+    d = np.ascontiguousarray(obs_desc, np.uint8).reshape(total, 32)
+    c = np.ascontiguousarray(obs_centre, np.float64).reshape(total, 3)
+    oc = np.ascontiguousarray(obs_octave, np.int32)
+    ro, X = np.ascontiguousarray(ref_obs, np.int32), np.ascontiguousarray(Xw, np.float64).reshape(n, 3)
+    kb = None if obs_kf_bad is None else np.ascontiguousarray(obs_kf_bad, np.uint8)
+    pb = None if point_bad is None else np.ascontiguousarray(point_bad, np.uint8)
+    sf = np.ascontiguousarray(scale_factors, np.float32)
+    assert len(oc) == total and len(ro) == n and (kb is None or len(kb) == total) and (pb is None or len(pb) == n)
+    out = _refresh_outputs(n, fill)
+    _check(L.sd_debug_refresh_points(n, _p(off), _p(d), _p(c), _p(oc), _p(kb), _p(ro), _p(pb), _p(X), _p(sf), len(sf),
+                                     *[_p(out[k]) for k in _REFRESH_FIELDS]))
+    return out

@@ -76,7 +76,8 @@ struct sd_track {
   std::vector<int> rand_len;      // rand() values actually supplied per slot (sd_track_set_rand)
   // What the stages that cache a result between calls left, and on which inputs (track_results.h: stamps, and the table of
   // what ends them).  pnp: the solvers sd_track_pnp_iterate continues; sim3: those of sd_track_sim3_iterate; tri: the matches of
-  // sd_track_get_triangulation_matches; triang: sd_track_get_triangulated / _get_new_points; fuse: sd_track_get_fuse.
+  // sd_track_get_triangulation_matches; triang: sd_track_get_triangulated / _get_new_points; fuse: sd_track_get_fuse;
+  // refresh: sd_track_get_refreshed.
   sd::Results res;
   sd::PnpParams pnp_params{};
   int pnp_iter_upper = 0;          // upper bound of mnIterations of the PnP solvers
@@ -88,6 +89,7 @@ struct sd_track {
   sd::TriangBuffers nb{};
   std::vector<uint8_t> scw_set;    // [max_batch] sd_track_set_fuse_scw has covered the slot
   sd::FuseBuffers fu{};
+  sd::RefreshBuffers rf{};         // sd_track_set_observations / _refresh_points (track_refresh.hip; refresh_create / refresh_destroy)
   sd::TrackBuffers tb{};
   sd::TrackCam cam{};
   bool have_cam = false;
@@ -130,6 +132,10 @@ inline void RunStamp::set(const sd_track* h, int n_frames, int mode_, int source
 inline bool RunStamp::covers(const sd_track* h, int n_frames) const {
   return cur == h->cur && serial == h->cur->extract_serial && n_frames <= n;
 }
+
+// track_refresh.hip: the observation block and its pinned mirror, which sd_track_set_observations may replace (not in `allocs`)
+int refresh_create(sd_track* h);
+void refresh_destroy(sd_track* h);
 
 // What a stage that runs now computes its result on: h->res.x.set(n, BIND_X, inputs_now(h)) after it, h->res.x.live(n, inputs_now(h)) later
 static inline sd::ResultInputs inputs_now(const sd_track* h) { return {h->cur->extract_serial, h->ref->extract_serial, h->tb.cur_bcast}; }

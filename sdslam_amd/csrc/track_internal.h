@@ -167,6 +167,13 @@ __device__ __forceinline__ double dot3(double x0, double x1, double x2, double y
   return __dadd_rn(__dadd_rn(__dmul_rn(x0, y0), __dmul_rn(x1, y1)), __dmul_rn(x2, y2));
 }
 
+// KeyFrame::GetCameraCenter, Ow = -Rcw^T * tcw, of a pose T (column-major, Rcw[r][c] = T[c * 4 + r], tcw = T[12..14]):
+// Ow[r] = -dot3(Rwc row r, tcw).  The one statement of it: k_triangulate / k_new_points_resolve (fill_pose) and
+// k_refresh_centres must agree bit for bit, and tests/new_points_ref.py restates this order.
+__device__ __forceinline__ double camera_centre(const double* __restrict__ T, int r) {
+  return -dot3(T[r * 4], T[r * 4 + 1], T[r * 4 + 2], T[12], T[13], T[14]);
+}
+
 // The map point mvpMapPoints[i] = m keeps after Tracking::Track's "Clean VO matches" (Observations() >= 1, reference
 // src/Tracking.cc:250-257) and outlier discard (:272-275): source 0 = cur_match after TrackWithMotionModel's discard (no
 // outlier flags left), 1 = un_match after TrackLocalMap, m >= M naming local point m - M, outl_i = &mvbOutlier[i].
@@ -262,6 +269,36 @@ struct TriangBuffers {
 // k_triangulate on the live search result of slots < n_frames, then k_new_points_resolve.  ratio_factor = 1.5f * mfScaleFactor
 int launch_triangulate(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const TriangBuffers& nb, const TrackCam& cam,
                        const float* d_sf, const float* d_sigma2, float ratio_factor, int n_frames, int monocular, hipStream_t s);
+// MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (track_refresh.hip): what the refresh owns besides the point
+// row (lm_*) it reads and, with write_local, rewrites.  Kept out of TrackBuffers like FuseBuffers.
+struct RefreshBuffers {
+  // The observation lists of the last sd_track_set_observations: ONE device block and its pinned mirror, packed per call as
+  // obs_off | ref_obs | obs_frame | obs_kp | point_bad | obs_kf_bad.  Allocated by sd_track_create for max_points points of 16
+  // observations each; sd_track_set_observations replaces both by larger ones (after a wait for the tracking stream) when a call
+  // needs more, and never shrinks them.  Nothing is allocated in sd_track_refresh_points.
+  uint8_t* obs;          // device
+  uint8_t* stage;        // pinned host
+  size_t obs_bytes;      // capacity of either
+  hipEvent_t ev_staged;  // the copy out of `stage` has run
+  bool staged;
+  size_t o_off, o_ref, o_frame, o_kp, o_pbad, o_kbad;   // byte offsets of the arrays of the last upload; o_pbad / o_kbad 0: NULL
+  int n_points;          // -1: no observations have been set
+  int n_obs;
+  int max_ref_frame;     // largest obs_frame of the last upload (-1: none)
+  bool has_cur;          // an observation names the current keyframe (-1)
+  double* centre;        // [B + 1][3] camera centres of the ref frames (Tref), then of the current keyframe (Tcur of slot 0)
+  // results, one entry per point of the list
+  uint8_t* status;       // [M] SD_REFRESH_* bits
+  int32_t* best_obs;     // [M] BestIdx as a position in the caller's list
+  int32_t* best_median;  // [M]
+  uint8_t* desc;         // [M][32]
+  double* normal;        // [M][3]
+  float* max_dist;       // [M] mfMaxDistance
+  float* min_dist;       // [M] mfMinDistance
+};
+// k_refresh_centres, then k_refresh_points on the points of row `point_row`; write_local: the results also go into that row
+int launch_refresh(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const RefreshBuffers& rf, const float* d_sf, int n_batch,
+                   int point_row, int write_local, hipStream_t s);
 int launch_stereo_from_depth(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_depth, int w, int h,
                              int stride_elems, size_t frame_stride_elems, int n_frames, hipStream_t s);
 // the same on a depth map of uint16_t (u16 != 0, always converted) or float elements; convert: d = (float)raw * scale

@@ -89,7 +89,7 @@ __device__ __forceinline__ void fill_pose(LdsPose* p, const double* __restrict__
   for (int i = 0; i < 9; i++) p->R[i] = R[i];
   for (int r = 0; r < 3; r++) {
     p->t[r] = t[r];
-    p->Ow[r] = -dot3(R[r], R[3 + r], R[6 + r], t[0], t[1], t[2]);
+    p->Ow[r] = camera_centre(T, r);
   }
 }
 // Rwc * v

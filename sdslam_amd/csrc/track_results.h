@@ -1,12 +1,12 @@
 // The lifetime of every result a tracker caches between calls: the PnP and Sim3 solvers an iterate() continues, the
-// SearchForTriangulation matches, their triangulation, the Fuse search.  One stamp type says what a result was computed on, one
+// SearchForTriangulation matches, their triangulation, the Fuse search, the map-point refresh.  One stamp type says what a result was computed on, one
 // table says which entry point ends which results.  Plain C++ on plain values (extraction serials, the broadcast setting, slot
 // counts), no HIP and no handle: tests/native/result_stamps_check.cpp checks the table and the bindings on the host.
 #pragma once
 
 namespace sd {
 
-enum Result : unsigned { R_PNP = 1, R_SIM3 = 2, R_TRI = 4, R_TRIANG = 8, R_FUSE = 16 };
+enum Result : unsigned { R_PNP = 1, R_SIM3 = 2, R_TRI = 4, R_TRIANG = 8, R_FUSE = 16, R_REFRESH = 32 };
 
 // What a result is bound to: it dies when that extractor extracts again / when the broadcast setting changes
 enum Bind : unsigned { BIND_CUR = 1, BIND_REF = 2, BIND_BCAST = 4 };
@@ -15,6 +15,8 @@ constexpr unsigned BIND_SIM3 = BIND_CUR | BIND_REF | BIND_BCAST;
 constexpr unsigned BIND_TRI = BIND_CUR | BIND_REF | BIND_BCAST;
 constexpr unsigned BIND_TRIANG = BIND_CUR;   // ... and lives only while the search it triangulated does (Results::triang_live)
 constexpr unsigned bind_fuse(int kf_side) { return (kf_side ? BIND_REF : BIND_CUR) | BIND_BCAST; }   // the side it searched
+
+constexpr unsigned BIND_REFRESH = BIND_CUR | BIND_REF | BIND_BCAST;   // observations name frames of both extractors and the cur frame in use
 
 // What a tracker's results are computed on: the serials of the cur and ref extractions, the broadcast setting
 struct ResultInputs {
@@ -27,7 +29,7 @@ struct ResultStamp {
   int n = 0;
   unsigned bind = 0;
   ResultInputs on;
-  int payload = 0;        // tri: the rotation check ran; Fuse: kf_side
+  int payload = 0;        // tri: the rotation check ran; Fuse: kf_side; refresh: the number of points
   // RunStamp::covers compares the `cur` pointer as well.  The pointer changes in one place, sd_track_advance, which swaps the
   // extractors' roles: a Sim3 / tri / triang result does not answer for the swapped pair (Results::swap_roles), and does
   // again once a second advance has swapped them back.  Fuse never compared it: its serial is its side's, whoever holds it.
@@ -43,7 +45,7 @@ struct ResultStamp {
 };
 
 struct Results {
-  ResultStamp pnp, sim3, tri, triang, fuse;
+  ResultStamp pnp, sim3, tri, triang, fuse, refresh;
   bool triang_live(int n_frames, const ResultInputs& now) const { return tri.live(n_frames, now) && triang.live(n_frames, now); }
   void swap_roles() { sim3.swapped ^= true, tri.swapped ^= true, triang.swapped ^= true; }
 };
@@ -56,13 +58,14 @@ inline void end_results(Results& r, unsigned mask) {
   if (mask & R_TRI) r.tri = ResultStamp{};
   if (mask & R_TRIANG) r.triang = ResultStamp{};
   if (mask & R_FUSE) r.fuse = ResultStamp{};
+  if (mask & R_REFRESH) r.refresh = ResultStamp{};
 }
 
 // What each entry point ends, and why.  An entry point calls end_results with its own row and nothing else (END_RESULTS).
 struct EndsRow { const char* entry; unsigned mask; };
 constexpr EndsRow kEnds[] = {
     {"sd_track_set_camera", R_FUSE | R_TRIANG},           // a Fuse result was projected with the old K and image bounds, a triangulation used K and mbf
-    {"sd_track_set_poses", R_SIM3 | R_TRI | R_FUSE},      // the Sim3 solvers' keyframe poses; the poses F12 and the epipole came from; Fuse's keyframe pose
+    {"sd_track_set_poses", R_SIM3 | R_TRI | R_FUSE | R_REFRESH},   // the Sim3 solvers' keyframe poses; the poses F12 and the epipole came from; Fuse's keyframe pose; the refresh's camera centres
     {"sd_track_set_rand", R_PNP | R_SIM3},                // a resumed iterate() continues at a position of the OLD stream
     {"sd_track_set_last", R_PNP},                         // the solvers' 3-D points are being replaced
     {"sd_track_set_matches", R_PNP},                      // the saved best-inlier mask indexes the old correspondence list
@@ -70,7 +73,7 @@ constexpr EndsRow kEnds[] = {
     {"sd_track_with_motion_model", R_PNP},                // ... likewise
     {"sd_track_stereo_init", R_PNP},                      // ... likewise
     {"sd_track_advance", R_PNP},                          // ... and `cur` becomes the other extractor
-    {"sd_track_set_local", R_FUSE},                       // sd_track_fuse reads these rows too
+    {"sd_track_set_local", R_FUSE | R_REFRESH},           // sd_track_fuse reads these rows too; the refresh read Xw of one
     {"sd_track_set_local_view", R_FUSE},                  // lm_n and lm_desc are rows sd_track_fuse reads
     {"sd_track_set_uright", R_TRI | R_FUSE},              // KF1's stereo bits, and the mvuRight row of a Fuse result's chi-square gate
     {"sd_track_set_uright_ref", R_TRI | R_FUSE},          // KF2's
@@ -89,6 +92,16 @@ constexpr EndsRow kEnds[] = {
     {"sd_track_set_fuse_scw", R_FUSE},                    // the Scw a search with sim3 = 1 projects with
 };
 
+// The map-point refresh's own entry points (track_refresh.hip).  A table beside kEnds, not more rows of it:
+// tests/native/result_stamps_check.cpp holds kEnds to a matrix typed in when the results were five, and
+// tests/native/refresh_stamps_check.cpp holds these rows and the R_REFRESH bits above to one of its own.
+constexpr EndsRow kEndsRefresh[] = {
+    {"sd_track_set_observations", R_REFRESH},             // the lists the result was computed on
+    {"sd_track_refresh_points", R_REFRESH},               // a stage ends its own old result before it runs
+    // write_local = 1 rewrites desc, normal and the distances of a local row: whatever a sd_track_set_local on that row ends
+    {"sd_track_refresh_points(write_local)", R_FUSE | R_REFRESH},
+};
+
 constexpr bool same_name(const char* a, const char* b) {
   while (*a && *a == *b) ++a, ++b;
   return *a == *b;
@@ -97,7 +110,12 @@ constexpr bool same_name(const char* a, const char* b) {
 constexpr int ends_of(const char* entry) {
   for (const EndsRow& row : kEnds)
     if (same_name(row.entry, entry)) return (int)row.mask;
+  for (const EndsRow& row : kEndsRefresh)
+    if (same_name(row.entry, entry)) return (int)row.mask;
   return -1;
 }
+
+static_assert(ends_of("sd_track_refresh_points(write_local)") == (ends_of("sd_track_set_local") | (int)R_REFRESH),
+              "a write-through ends what sd_track_set_local ends");
 
 }  // namespace sd
