@@ -37,7 +37,8 @@ def ratio_for(level):
 class Builder:
     """A keyframe at the identity pose (unit camera) and points at depth 2, added one by one."""
 
-    def __init__(self, seed):
+    def __init__(self, seed, cam=CAM_UNIT):
+        self.cam = cam
         self.rng = np.random.default_rng(seed)
         self.k, self.d, self.u = [], [], []
         self.p = {k: [] for k in ("cand", "Xw", "normal", "min_dist", "max_dist", "mf_max_dist", "desc")}
@@ -50,7 +51,8 @@ class Builder:
         return len(self.k) - 1
 
     def pt(self, u, v, level, desc, want, want_sim3=None, z=2.0, normal=None, min_dist=None, max_dist=None, cand=1):
-        X = np.array([(u - 320.0) / 512.0 * z, (v - 240.0) / 512.0 * z, z])
+        fx, fy, cx, cy = (float(c) for c in self.cam[:4])
+        X = np.array([(u - cx) / fx * z, (v - cy) / fy * z, z])
         dist = float(F32(np.linalg.norm(X * np.sign(z))))
         self.p["cand"].append(cand)
         self.p["Xw"].append(X)
@@ -71,7 +73,7 @@ class Builder:
                    max_dist=np.array(self.p["max_dist"], F32), mf_max_dist=np.array(self.p["mf_max_dist"], F32),
                    desc=np.array(self.p["desc"], np.uint8).reshape(-1, 32))
         return dict(name=name, kps=kps, desc=np.array(self.d, np.uint8).reshape(-1, 32), uright=np.array(self.u, F32), pts=pts,
-                    T=np.eye(4), scale=2.0, cam=CAM_UNIT, th=th, kp_cap=None, max_points=None, expect=self.expect,
+                    T=np.eye(4), scale=2.0, cam=self.cam, th=th, kp_cap=None, max_points=None, expect=self.expect,
                     expect_sim3=self.expect_sim3, claims=tuple(claims))
 
 
@@ -84,9 +86,13 @@ def unit_depth_and_cand():
     return b.case("unit_depth_and_cand", ("depth", "cand"))
 
 
-def unit_image_edges():
+def unit_image_edges(cam=None):
     """KeyFrame::IsInImage is >= min && < max: u == 640 and v == 480 are OUTSIDE (Frame::isInFrustum keeps them), 0 is inside.
-    Level 7 windows (radius 10.7) reach the nearest keypoints the grid holds (x < 635, y < 475: PosInGrid rounds)."""
+    Level 7 windows (radius 10.7) reach the nearest keypoints the grid holds (x < 635, y < 475: PosInGrid rounds).
+    With a camera (9 floats: K, bf, bounds) the same eight points sit a hair (0.01 px: the projection of such a camera is not
+    exact in float, its error is some 1e-4 px) inside and outside each of its four bounds."""
+    if cam is not None:
+        return _image_edges_at(np.asarray(cam, F32))
     b = Builder(2)
     right, left, bottom, top = b.kp(633, 100, 7), b.kp(3, 100, 7), b.kp(100, 474, 7), b.kp(100, 3, 7)
     outside = b.kp(637, 100, 7)                                    # PosInGrid = 64: AssignFeaturesToGrid skips it
@@ -102,6 +108,21 @@ def unit_image_edges():
     c = b.case("unit_image_edges", ("image",))
     c["outside"] = outside
     return c
+
+
+def _image_edges_at(cam, hair=0.01):
+    x0, x1, y0, y1 = (float(c) for c in cam[5:9])
+    b = Builder(2, cam)
+    right, left, bottom, top = b.kp(x1 - 7.0, 100, 7), b.kp(x0 + 3.0, 100, 7), b.kp(100, y1 - 6.0, 7), b.kp(100, y0 + 3.0, 7)
+    b.pt(x1 + hair, 100, 7, b.d[right], -1)
+    b.pt(x1 - hair, 100, 7, b.d[right], right)
+    b.pt(x0 + hair, 100, 7, b.d[left], left)
+    b.pt(x0 - hair, 100, 7, b.d[left], -1)
+    b.pt(100, y1 + hair, 7, b.d[bottom], -1)
+    b.pt(100, y1 - hair, 7, b.d[bottom], bottom)
+    b.pt(100, y0 + hair, 7, b.d[top], top)
+    b.pt(100, y0 - hair, 7, b.d[top], -1)
+    return b.case("unit_image_edges_at_bounds", ("image",))
 
 
 def unit_distance_and_angle():
@@ -177,7 +198,7 @@ def unit_th_low_and_ties():
     return c
 
 
-def shape_case(name, seed, n_kp, n_pts, kp_cap=None, max_points=None, th=3.0, scale=1.7, crowd=0, stereo=0.3, claims=()):
+def shape_case(name, seed, n_kp, n_pts, kp_cap=None, max_points=None, th=3.0, scale=1.7, crowd=0, stereo=0.3, claims=(), cam=None):
     """Random keyframe (keypoints up to the image border, so some lie outside the grid) at a random pose; the first points see
     keypoints (descriptor distances on both sides of TH_LOW, predicted levels around the keypoint's octave), the rest miss."""
     rng = np.random.default_rng(seed)
@@ -195,7 +216,7 @@ def shape_case(name, seed, n_kp, n_pts, kp_cap=None, max_points=None, th=3.0, sc
     uright = np.where(rng.random(n_kp) < stereo, rng.choice([0.0, 1.0], n_kp) * (kps["x"] - 8.0), -1.0).astype(F32)
     R, t = T[:3, :3], T[:3, 3]
     Ow = -R.T @ t
-    cam = CAM_SYNTH
+    cam = CAM_SYNTH if cam is None else np.asarray(cam, F32)
     pts = {k: [] for k in ("cand", "Xw", "normal", "min_dist", "max_dist", "mf_max_dist", "desc")}
     for i in range(n_pts):
         seen = n_kp > 0 and rng.random() < 0.8

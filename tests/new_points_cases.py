@@ -21,6 +21,25 @@ T2 = synth.se3_exp((-0.25, 0.02, 0.01), (0.0, 0.0, 0.0)) @ T1              # KF2
 MARGIN = 1e-5
 
 
+class _camera:
+    """with _camera(cam5): the builders below read the module's CAM5 when they run; a case built under another camera is built
+    inside this block (None: today's camera)."""
+
+    def __init__(self, cam5):
+        self.cam5 = cam5
+
+    def __enter__(self):
+        global CAM5
+        self.saved = CAM5
+        if self.cam5 is not None:
+            CAM5 = np.asarray(self.cam5, F32)
+
+    def __exit__(self, *exc):
+        global CAM5
+        CAM5 = self.saved
+        return False
+
+
 def project(T, X):
     """(u, v, z) of a world point, float64 (the cases round it to float keypoints)."""
     c = np.asarray(T, F64)[:3, :3] @ np.asarray(X, F64) + np.asarray(T, F64)[:3, 3]
@@ -109,7 +128,12 @@ def step_pair(make_row, lo, hi):
 X0 = world_point(T1, 300.0, 200.0, 3.0)                  # a well-conditioned point: parallax 0.25 / 3
 
 
-def thresholds_case():
+def thresholds_case(cam5=None):
+    with _camera(cam5):
+        return _thresholds_case()
+
+
+def _thresholds_case():
     """Every gate of the mono path with a twin one float step away, and the plain rows of every verdict."""
     pr = Pair("thresholds")
     pr.row(X0, claim=(NR.ACCEPTED, NR.BR_SVD))
@@ -142,7 +166,12 @@ def thresholds_case():
     return c
 
 
-def stereo_case():
+def stereo_case(cam5=None):
+    with _camera(cam5):
+        return _stereo_case()
+
+
+def _stereo_case():
     """Both unproject branches, the stereo reprojection forms (KF2's with KF1's mbf), mvuRight == 0, mvDepth <= 0, and the
     `if (bStereo1) ... else if (bStereo2)` asymmetry: with both sides stereo only KF1's cosine is computed."""
     Tf = synth.se3_exp((0.0, 0.0, -0.3), (0.0, 0.0, 0.0)) @ T1                  # KF2 0.3 ahead of KF1 (> mb: the slot is not gated)
@@ -257,7 +286,12 @@ def late_gate_cases():
     return out
 
 
-def count_case(n, seed):
+def count_case(n, seed, cam5=None):
+    with _camera(cam5):
+        return _count_case(n, seed)
+
+
+def _count_case(n, seed):
     """n matched rows among 2 n + 3 keypoints (match counts 0, 1, 64, 65: none, one lane, a full wave, a wave and one lane)."""
     rng = np.random.default_rng(seed)
     pr = Pair("count_%d" % n)

@@ -145,13 +145,13 @@ def sigma2(pyr):
     return R3.level_sigma2(PYR[pyr][1], PYR[pyr][2])
 
 
-def solver(slot, rand_row, pyr, fix_scale, cache=None):
+def solver(slot, rand_row, pyr, fix_scale, cache=None, K=K):
     s = R3.Sim3Solver(slot["kf1"], slot["kf2"], slot["matches12"], fix_scale, K, sigma2(pyr), rand_row, cache=cache)
     s.set_ransac_parameters(PROB, MIN_INLIERS, MAX_ITS)
     return s
 
 
-def reference_runs(slots, rand, pyr, fix_scale, chunk=5):
+def reference_runs(slots, rand, pyr, fix_scale, chunk=5, K=K):
     """What the GPU test replays, on the restatement: every slot once as find(), and once as iterate(chunk) calls on ALL slots
     until each has returned a matrix or reported bNoMore at least once (a solver that has returned goes on iterating with the
     batch: its state allows it).  -> dict(find=[(result, info8, solver)], rounds=[[(result, info8, R, t, s)] per call],
@@ -159,10 +159,10 @@ def reference_runs(slots, rand, pyr, fix_scale, chunk=5):
     caches = [dict() for _ in slots]
     found = []
     for b, sl in enumerate(slots):
-        sv = solver(sl, rand[b], pyr, fix_scale, caches[b])
+        sv = solver(sl, rand[b], pyr, fix_scale, caches[b], K)
         res = sv.find()
         found.append((res, sv.info8(res), sv))
-    solvers = [solver(sl, rand[b], pyr, fix_scale, caches[b]) for b, sl in enumerate(slots)]
+    solvers = [solver(sl, rand[b], pyr, fix_scale, caches[b], K) for b, sl in enumerate(slots)]
     done, rounds = [False] * len(slots), []
     while not all(done):
         row = []

@@ -57,7 +57,7 @@ class Rig:
     """B RGB-D streams with depth maps in device memory; frame 0 in `ref` with a static map of it as last frame and local map
     (Observations() 0 for every 7th point); the last slot has no usable points, so it is never tracked."""
 
-    def __init__(self, sd, cfg, seeds, T, u16=False, distorted=False, static=True):
+    def __init__(self, sd, cfg, seeds, T, u16=False, distorted=False, static=True, K=K):
         self.sd, self.B, self.T, self.u16, self.distorted = sd, len(seeds), T, u16, distorted
         self.seqs = [synth.make_sequence(s, T, with_depth=True) for s in seeds]
         self.views = np.stack([s["views"] for s in self.seqs], 1)

@@ -97,6 +97,43 @@ def test_against_restatement(oracle, pyr, fix):
     print("k_sim3 vs restatement, largest deviation", pyr, "fix_scale", fix, worst)
 
 
+K_ANISO = tuple(float(np.float32(v)) for v in (4000.0, 3200.0, 148.5, 131.25))      # fx != fy, principal point off the centre
+
+
+@pytest.mark.parametrize("fix", [0, 1])
+def test_against_restatement_anisotropic_camera(oracle, fix):
+    """Project's fx / fy and cx / cy told apart: the n70_out30 and mixed_octaves slots under K_ANISO, as find() and as
+    iterate(5) calls, to test_against_restatement's bounds.  (SC.K has fx = fy and the principal point at the centre.)  The
+    planted outliers of these slots miss by hundreds of pixels under either camera, so this pins the projection at the
+    inliers' errors only: a camera mix-up that leaves every inlier under its threshold would pass."""
+    r = _rig(oracle, "p8")
+    trk, slots = r["trk"], r["slots"]
+    picked = [SC.SLOTS.index("n70_out30"), SC.SLOTS.index("mixed_octaves")]
+    want = SC.reference_runs([slots[b] for b in picked], r["rand"][picked], "p8", fix, K=K_ANISO)
+    worst = dict(T12=0.0, R=0.0, t=0.0, scale=0.0)
+    try:
+        trk.set_camera(*K_ANISO, 0.0, SC.BOUNDS)
+        SC.upload(trk, slots, r["rand"])
+        trk.sim3(B, fix, SC.PROB, SC.MIN_INLIERS, SC.MAX_ITS, SC.MAX_ITS)
+        g = trk.get_sim3(0, B)
+        for j, b in enumerate(picked):
+            res, info, sv = want["find"][j]
+            _compare(g, b, res, info, sv.best_R, sv.best_t, float(sv.best_s), ("aniso", fix, "find", slots[b]["kind"]), worst)
+        for c, row in enumerate(want["rounds"]):
+            if c == 0:
+                trk.sim3(B, fix, SC.PROB, SC.MIN_INLIERS, SC.MAX_ITS, 5)
+            else:
+                trk.sim3_iterate(B, 5)
+            g = trk.get_sim3(0, B)
+            for j, b in enumerate(picked):
+                res, info, R, t, s = row[j]
+                _compare(g, b, res, info, R, t, s, ("aniso", fix, "call %d" % c, slots[b]["kind"]), worst)
+        print("k_sim3 vs restatement under K_ANISO, largest deviation, fix_scale", fix, worst)
+    finally:
+        trk.set_camera(*SC.K, 0.0, SC.BOUNDS)
+        SC.upload(trk, slots, r["rand"])
+
+
 def test_broadcast_equals_paired(oracle):
     r = _rig(oracle, "p8")
     trk = r["trk"]

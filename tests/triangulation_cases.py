@@ -53,7 +53,7 @@ SIDEWAYS = (synth.se3_exp((0.25, 0.02, 0.01), (0.5, -1.0, 0.8)), np.eye(4))     
 FORWARD = (synth.se3_exp((0.01, -0.005, -0.3), (0.3, 0.2, -0.4)), np.eye(4))    # epipole inside the image
 
 
-def shape_case(name, seed, n1, n2, motion=SIDEWAYS, flagged=0.5, stereo=0.0, claims=()):
+def shape_case(name, seed, n1, n2, motion=SIDEWAYS, flagged=0.5, stereo=0.0, claims=(), K=K):
     rng = np.random.default_rng(seed)
     T1, T2 = motion
     F12, epi = TR.compute_f12(T1, T2, K), TR.epipole(T1, T2, K)
