@@ -19,10 +19,13 @@
 #include <hip/hip_runtime.h>
 
 #include "introselect.h"
+#include "sd_wave.h"
 
 namespace sdsel {
 
-__device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
+using sd::lanemask_lt;
+using sd::wave_append;
+using sd::wave_fence;
 
 #define WAVE_SEL_CAP 256
 typedef __attribute__((address_space(3))) uint16_t lds_u16;
@@ -30,7 +33,7 @@ typedef __attribute__((address_space(3))) uint16_t lds_u16;
 template <typename P>
 __device__ __forceinline__ void wave_nth_element(P a, int n, int nth, lds_u16* tmp) {
   const int lane = threadIdx.x & 63;
-  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt = lanemask_lt(lane);
   const int BIG = 0x7fffffff;
   lds_u16* tmpL = tmp;
   lds_u16* tmpR = tmp + WAVE_SEL_CAP;
@@ -75,12 +78,9 @@ __device__ __forceinline__ void wave_nth_element(P a, int n, int nth, lds_u16* t
         const bool in = q < m;
         const uint32_t vL = in ? a[lo0 + q] : 0u, vR = in ? a[hi0 - 1 - q] : 0u;
         const bool sL = in && !gt(vL, pivot), sR = in && !gt(pivot, vR);
-        const unsigned long long bL = __ballot(sL), bR = __ballot(sR);
-        const int rL = cntL + __popcll(bL & lt), rR = cntR + __popcll(bR & lt);
+        const int rL = wave_append(sL, lt, cntL), rR = wave_append(sR, lt, cntR);
         if (sL && rL < WAVE_SEL_CAP) tmpL[rL] = (uint16_t)q;
         if (sR && rR < WAVE_SEL_CAP) tmpR[rR] = (uint16_t)q;
-        cntL += __popcll(bL);
-        cntR += __popcll(bR);
         if (cntL >= WAVE_SEL_CAP && cntR >= WAVE_SEL_CAP) break;   // both tables full: later stops pair in the next round
       }
       wave_fence();

@@ -69,11 +69,6 @@ __device__ __forceinline__ int reflect101(int p, int len) {
   return p;
 }
 
-__device__ __forceinline__ unsigned long long lanemask_lt() {
-  unsigned lane = __lane_id();
-  return lane == 0 ? 0ull : (~0ull >> (64 - lane));
-}
-
 // ------------------------------------------------------------------------------------------
 // k_pyr_level: one pyramid level, written over its whole padded domain in a single pass.
 // level 0 : copyMakeBorder(image, REFLECT_101)
@@ -525,8 +520,6 @@ __device__ unsigned long long g_fast_prof_wg[(size_t)FPROF_FRAMES * FPROF_CELLS 
 //      re-compacted in place (still raster order) and their scores go to the LDS score map;
 //   C. after a block barrier, NMS on the queued corners against the LDS score map, then ordered
 //      emission (wave bands are contiguous in raster order, so per-wave counts give offsets).
-extern "C" __device__ __attribute__((const)) int __ockl_wfred_add_i32(int);
-
 #ifndef FAST_STAGE_DEPTH
 #define FAST_STAGE_DEPTH 12   // tile dwords in flight per thread while staging (256 threads x 12 x 4 B = 12 KB per round trip)
 #endif
@@ -586,7 +579,7 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
   const unsigned magic_tp = 0xFFFFFFFFu / (unsigned)TP + 1u;   // queue entry / TP (entries < 2^16: the tile is < 64 KB)
   const uint8_t* tile0 = tile + 3 * TP + 3 + sh;   // zone pixel (0, 0) of the strip
   uint8_t* sc0 = sc + TP + 1;                      // its score
-  const unsigned long long lt = lanemask_lt();
+  const unsigned long long lt = lanemask_lt((int)__lane_id());
   int total = 0;
   FPROF_DECL;
 
@@ -714,12 +707,10 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
         if (corner_a && sa > 0) sc0[qa] = (uint8_t)sa;
         if (corner_b && sb > 0) sc0[qb] = (uint8_t)sb;
       }
-      const unsigned long long ma = __builtin_amdgcn_ballot_w64(corner_a);
-      if (corner_a) queue[cn + __popcll(ma & lt)] = (uint16_t)qa;
-      cn += __popcll(ma);
-      const unsigned long long mb = __builtin_amdgcn_ballot_w64(corner_b);
-      if (corner_b) queue[cn + __popcll(mb & lt)] = (uint16_t)qb;
-      cn += __popcll(mb);
+      const int pa = wave_append(corner_a, lt, cn);
+      if (corner_a) queue[pa] = (uint16_t)qa;
+      const int pb = wave_append(corner_b, lt, cn);
+      if (corner_b) queue[pb] = (uint16_t)qb;
     }
     qn = cn;
 #ifdef FAST_SKIP_C
@@ -762,7 +753,7 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
       const int strip_total = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
       for (int j = 0; j < nj; j++) {
         const bool keep = (bits >> j) & 1ull;
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
+        const unsigned long long m = __ballot(keep);   // (wave_append here would merge the two branches below: kept as measured)
         if (keep) {
           const unsigned q = queue[j * 64 + lane];
           const int y = (int)__umulhi(q, magic_tp), x = (int)q - __mul24(y, TP);   // the one place that needs (y, x): the key of a survivor
@@ -821,7 +812,7 @@ __global__ __launch_bounds__(64) void k_select_quota(const OrbPlan* __restrict__
     s_total[c] = cc[c];
     s_flag[c] = cells[c].evaluated;
   }
-  sdsel::wave_fence();
+  wave_fence();
   if (lane < P->nlevels) {
     const LevelGeom& L = P->lv[lane];
     int M = 0;
@@ -873,7 +864,7 @@ __global__ __launch_bounds__(64) void k_select_quota(const OrbPlan* __restrict__
     }
     lvl_m[(size_t)frame * P->nlevels + lane] = M;
   }
-  sdsel::wave_fence();
+  wave_fence();
   for (int c = lane; c < nc; c += 64) {
     cell_keep[(size_t)frame * nc + c] = s_retain[c];
     cell_off[(size_t)frame * nc + c] = s_offv[c];
@@ -895,7 +886,7 @@ __global__ __launch_bounds__(64) void k_select_cells(const OrbPlan* __restrict__
   if (n > buf_cap) return;   // k_select_bigcells
   lds_u32* buf = (lds_u32*)s_cellbuf;
   for (int i = lane; i < n; i += 64) buf[i] = src[i];
-  sdsel::wave_fence();
+  wave_fence();
   if (n > keep) sdsel::wave_nth_element(buf, n, keep, (sdsel::lds_u16*)(s_cellbuf + buf_cap));
   for (int i = lane; i < keep; i += 64) glist[i] = buf[i];
 }
@@ -924,10 +915,10 @@ __global__ __launch_bounds__(64) void k_select_bigcells(const OrbPlan* __restric
       if (n <= big_cap) {
         lds_u32* buf = (lds_u32*)s_cellbuf;
         for (int i = lane; i < n; i += 64) buf[i] = src[i];
-        sdsel::wave_fence();
+        wave_fence();
         if (n > keep) sdsel::wave_nth_element(buf, n, keep, (sdsel::lds_u16*)(s_cellbuf + big_cap));
         for (int i = lane; i < keep; i += 64) glist[i] = buf[i];
-        sdsel::wave_fence();   // the buffer is reused by the next cell
+        wave_fence();   // the buffer is reused by the next cell
       } else if (lane == 0) {
         if (n > keep) sdsel::nth_element(src, n, keep);
         for (int i = 0; i < keep; i++) glist[i] = src[i];
@@ -956,12 +947,12 @@ __global__ __launch_bounds__(64) void k_select_final(const OrbPlan* __restrict__
     Mout = L.quota;
     if (M <= SEL_LIST_CAP) {
       for (int i = lane; i < M; i += 64) s_list[i] = glist[i];
-      sdsel::wave_fence();
+      wave_fence();
       sdsel::wave_nth_element((lds_u32*)s_list, M, L.quota, (sdsel::lds_u16*)s_tmp);
       for (int i = lane; i < Mout; i += 64) dst[i] = s_list[i];
     } else {
       if (lane == 0) sdsel::nth_element(glist, M, L.quota);
-      sdsel::wave_fence();
+      wave_fence();
       for (int i = lane; i < Mout; i += 64) dst[i] = glist[i];
     }
   } else {
@@ -1251,8 +1242,8 @@ __global__ __launch_bounds__(256) void k_orient_desc(const OrbPlan* __restrict__
     }
 #pragma unroll
     for (int q = 0; q < DESC_KPW; q++) {   // DPP reduction of the device library
-      m10[q] = __ockl_wfred_add_i32(u * colsum[q]);
-      m01[q] = __ockl_wfred_add_i32(half ? -vsum[q] : vsum[q]);
+      m10[q] = wave_sum_i32(u * colsum[q]);
+      m01[q] = wave_sum_i32(half ? -vsum[q] : vsum[q]);
     }
   }
   // ---- angle, cos, sin: keypoint 0 in lanes 0..31, keypoint 1 in lanes 32..63, one evaluation
@@ -1273,7 +1264,7 @@ __global__ __launch_bounds__(256) void k_orient_desc(const OrbPlan* __restrict__
   }
   // ---- steered rBRIEF on the blurred level
   unsigned long long words[DESC_KPW][4];
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // this wave's own patch stores before its sample reads
+  wave_fence();   // this wave's own patch stores before its sample reads
 #pragma unroll
   for (int j = 0; j < 4; j++) {
     const int t = j * 64 + lane;

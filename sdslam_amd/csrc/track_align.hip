@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "orb_internal.h"
+#include "sd_wave.h"
 #include "track_internal.h"
 
 namespace sd {
@@ -41,9 +42,6 @@ __device__ unsigned long long g_align_prof[16];
 #endif
 
 #define AL_MAXP 300
-
-extern "C" __device__ __attribute__((const)) double __ockl_wfred_add_f64(double);
-extern "C" __device__ __attribute__((const)) int __ockl_wfred_add_i32(int);
 
 // The serial pieces of an iteration (6 x 6 LDLT solve, Exp, 4 x 4 products) run on ONE lane beside 319 lanes whose point
 // data must stay in registers: they work on LDS-resident operands through address-space-3 pointers with rolled loops, so
@@ -286,7 +284,7 @@ __global__ __launch_bounds__(AL_PT_THREADS, MINW) void k_align(const OrbPlan* __
     __syncthreads();
     int off = running;
     for (int w = 0; w < wave; w++) off += s_cnt[w];
-    int pos = off + __popcll(m & (lane == 0 ? 0ull : (~0ull >> (64 - lane))));
+    int pos = off + __popcll(m & lanemask_lt(lane));
     if (fl && pos < max_pts) {
       s_pts[pos * 3 + 0] = Xw[(size_t)i * 3 + 0];
       s_pts[pos * 3 + 1] = Xw[(size_t)i * 3 + 1];
@@ -447,7 +445,7 @@ __global__ __launch_bounds__(AL_PT_THREADS, MINW) void k_align(const OrbPlan* __
       for (int a = 0; a < 6; a++)
 #pragma unroll
         for (int b = a; b < 6; b++) {
-          const double v = __ockl_wfred_add_f64(ha * (J0[a] * J0[b]) + hb * (J0[a] * J1[b] + J1[a] * J0[b]) + hc * (J1[a] * J1[b]));
+          const double v = wave_sum(ha * (J0[a] * J0[b]) + hb * (J0[a] * J1[b] + J1[a] * J0[b]) + hc * (J1[a] * J1[b]));
           if (lane == 0) s_redH[wave][q] = v;
           q++;
         }
@@ -532,7 +530,7 @@ __global__ __launch_bounds__(AL_PT_THREADS, MINW) void k_align(const OrbPlan* __
         J1[0] = 0.0; J1[1] = -z_inv; J1[2] = Y * z_inv_2; J1[3] = 1.0 + Y * J1[2]; J1[4] = -J0[3]; J1[5] = -X * z_inv;
 #pragma unroll
         for (int a = 0; a < 6; a++) {
-          const double v = __ockl_wfred_add_f64(-(J0[a] * t1 + J1[a] * t2) * fscale);
+          const double v = wave_sum(-(J0[a] * t1 + J1[a] * t2) * fscale);
           if (lane == 0) s_red[wave][21 + a] = v;
         }
         const bool out = has_jac && !measured;
@@ -545,12 +543,12 @@ __global__ __launch_bounds__(AL_PT_THREADS, MINW) void k_align(const OrbPlan* __
           for (int a = 0; a < 6; a++)
 #pragma unroll
             for (int b = a; b < 6; b++) {
-              const double v = __ockl_wfred_add_f64(ha * (J0[a] * J0[b]) + hb * (J0[a] * J1[b] + J1[a] * J0[b]) + hc * (J1[a] * J1[b]));
+              const double v = wave_sum(ha * (J0[a] * J0[b]) + hb * (J0[a] * J1[b] + J1[a] * J0[b]) + hc * (J1[a] * J1[b]));
               if (lane == 0) s_red[wave][q] = v;
               q++;
             }
         }
-        nmeas = __ockl_wfred_add_i32(nmeas);
+        nmeas = wave_sum_i32(nmeas);
         if (lane == 0) {
           s_cnt[wave] = nmeas;
           s_delta[wave] = any_out ? 1 : 0;

@@ -147,7 +147,7 @@ __device__ __forceinline__ uint32_t fuse_point(const FuseArgs& a, const TrackCam
         }
         if ((double)__fmul_rn(e2, a.inv_sigma2[min(max(koct, 0), a.nlevels - 1)]) > limit) continue;
       }
-      const int dist = __popcll(k0 ^ d0) + __popcll(k1 ^ d1) + __popcll(k2 ^ d2) + __popcll(k3 ^ d3);
+      const int dist = hamming256(k0, k1, k2, k3, d0, d1, d2, d3);
       best = min(best, ((uint32_t)dist << 22) | ((uint32_t)(seq0 + (e - ca)) << 11) | (uint32_t)idx);
     }
     seq0 += cb - ca;

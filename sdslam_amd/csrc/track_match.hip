@@ -47,8 +47,6 @@ struct MatchLds {
   const uint32_t* s_kclaim;   // bit idx: keypoint idx already held such a point before the call (may be null)
 };
 
-__device__ __forceinline__ void sdsel_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
-
 // Candidates of one search window: GetFeaturesInArea(u, v, radius, minLevel, maxLevel) (src/Frame.cc:271-321) in
 // the reference's order, then the stereo gate |ur - mvuRight[idx]| <= radius for keypoints with a right
 // coordinate (src/ORBmatcher.cc:76-80, 1020-1025) and, in MODE 2, the "already holds a map point with
@@ -124,7 +122,7 @@ __device__ __forceinline__ uint32_t match_window(float u, float v, float radius,
       } else {
         uint32_t key = 0;
         if (okc) {
-          const int dist = __popcll(k0 ^ d0) + __popcll(k1 ^ d1) + __popcll(k2 ^ d2) + __popcll(k3 ^ d3);
+          const int dist = hamming256(k0, k1, k2, k3, d0, d1, d2, d3);
           // NB: candidates failing the window test do not advance the reference's vIndices order
           // relative to each other, so the sorted-array position is a valid order key
           key = ((uint32_t)dist << 22) | ((uint32_t)(seq0 + (e - a)) << 11) | (uint32_t)idx;
@@ -141,21 +139,6 @@ __device__ __forceinline__ uint32_t match_window(float u, float v, float radius,
   }
   *seq_total = seq0;
   return MODE == 2 ? best : (uint32_t)w;
-}
-
-// Flags pred(i), i in [0, n_bits), packed into the 32-bit words dst[0 .. (n_bits + 31) / 32): one flag per thread and round,
-// a wave's 64 flags are one ballot = two words.  All NT threads call (NT a multiple of 64; tid = lane for a single wave).
-template <typename Pred>
-__device__ __forceinline__ void pack_flags(Pred pred, int n_bits, uint32_t* dst, int tid, int NT) {
-  const int lane = tid & 63, wave = tid >> 6, n_words = (n_bits + 31) >> 5;
-  for (int i0 = 0; i0 < ((n_bits + 63) & ~63); i0 += NT) {
-    const unsigned long long b = __ballot(pred(i0 + tid));
-    const int w = (i0 >> 5) + 2 * wave;
-    if (lane == 0 && w < n_words) {
-      dst[w] = (uint32_t)b;
-      if (w + 1 < n_words) dst[w + 1] = (uint32_t)(b >> 32);
-    }
-  }
 }
 
 // Phase 1 of k_match / k_match_local for one point and its group of GL lanes: count_fn(&seq) counts the candidates, one atomic
@@ -263,7 +246,7 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match(const sd_keypoint* __re
   int* s_hist = lds_at<int>(smem, L.hist);
   int* s_nlist = lds_at<int>(smem, L.nlist);
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NT = 64 * MT_WAVES;
-  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt = lanemask_lt(lane);
   const int cap = tb.kp_cap;
   const int fc = tb.cur_bcast >= 0 ? tb.cur_bcast : f;   // current-frame slot (TrackBuffers::cur_bcast)
   const sd_keypoint* kps = kps_all + (size_t)fc * cap;
@@ -407,7 +390,6 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match(const sd_keypoint* __re
 // ------------------------------------------------------------------------------------------------
 #define MT_HBM_LIST 8192
 #define MT_HBM_CSTART (GRID_COLS * GRID_ROWS + 4)
-extern "C" __device__ __attribute__((const)) int __ockl_wfred_add_i32(int);
 
 __device__ __forceinline__ void match_cand_frame(const int f, uint8_t* smem, const sd_keypoint* __restrict__ kps_all,
                                                  const uint8_t* __restrict__ desc_all, const int32_t* __restrict__ nkp_all, const TrackBuffers& tb,
@@ -541,7 +523,7 @@ __device__ __forceinline__ void match_assign_frame(const int f, uint8_t* smem, c
   const int n_last = min(tb.n_last[f], MP);
   const uint32_t* g_list = tb.mt_list + (size_t)f * MT_HBM_LIST;
   const uint32_t* g_pt = tb.mt_pt + (size_t)f * MP;
-  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt = lanemask_lt(lane);
   // the first three chunks of the list and the first group of per-point words are on their way while LDS is initialised
   uint32_t c0 = 0, c1 = 0, c2 = 0;
   if (!RETRY) { c0 = g_list[lane]; c1 = g_list[64 + lane]; c2 = g_list[128 + lane]; }
@@ -569,7 +551,7 @@ __device__ __forceinline__ void match_assign_frame(const int f, uint8_t* smem, c
     }
   }
   if (lane < HISTO_LENGTH) s_hist[lane] = 0;
-  sdsel_fence();
+  wave_fence();
   int nmatches = 0, nev = 0, cbase = 0;
   for (int base = 0; base < n_last; base += 64) {
     const uint32_t pcv = pcv_next;
@@ -621,7 +603,7 @@ __device__ __forceinline__ void match_assign_frame(const int f, uint8_t* smem, c
       }
     }
   }
-  sdsel_fence();
+  wave_fence();
   // ---- rotation consistency (src/ORBmatcher.cc:1041-1072): bins of all recorded assignments, three dominant bins stay
   if (check_ori) {
     for (int e = lane; e < nev; e += 64) {
@@ -630,7 +612,7 @@ __device__ __forceinline__ void match_assign_frame(const int f, uint8_t* smem, c
       atomicAdd(&s_hist[bin], 1);
       s_ev[e] = ev | ((uint32_t)bin << 22);
     }
-    sdsel_fence();
+    wave_fence();
     int ind1, ind2, ind3;
     three_maxima(s_hist, ind1, ind2, ind3);
     int bad = 0;
@@ -642,8 +624,8 @@ __device__ __forceinline__ void match_assign_frame(const int f, uint8_t* smem, c
         bad++;
       }
     }
-    nmatches -= __ockl_wfred_add_i32(bad);
-    sdsel_fence();
+    nmatches -= wave_sum_i32(bad);
+    wave_fence();
   }
   int32_t* out = tb.cur_match + (size_t)f * cap;
   for (int i = lane; i < cap; i += 64) {
@@ -722,7 +704,7 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_match_local(const sd_keypoint
   uint8_t* s_koct = lds_at<uint8_t>(smem, L.koct);
   int* s_nlist = lds_at<int>(smem, L.nlist);
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NT = 64 * MT_WAVES;
-  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt = lanemask_lt(lane);
   const int cap = tb.kp_cap, M = MP;
   const int fc = tb.cur_bcast >= 0 ? tb.cur_bcast : f;   // current-frame slot (TrackBuffers::cur_bcast)
   const sd_keypoint* kps = kps_all + (size_t)fc * cap;
@@ -1005,7 +987,7 @@ __global__ __launch_bounds__(64 * MT_WAVES) void k_features_in_area(const sd_key
   uint32_t* s_list = lds_at<uint32_t>(smem, L.list);
   uint16_t* s_cstart = lds_at<uint16_t>(smem, L.cstart);
   const int tid = threadIdx.x, lane = tid & 63, NT = 64 * MT_WAVES;
-  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt = lanemask_lt(lane);
   const int N = min(nkp[0], min(cap, KP2));
   const float invW = (float)GRID_COLS / (float)(cam.max_x - cam.min_x);
   const float invH = (float)GRID_ROWS / (float)(cam.max_y - cam.min_y);

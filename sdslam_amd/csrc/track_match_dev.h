@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "orb_internal.h"
+#include "sd_wave.h"
 #include "track_internal.h"
 #include "track_match_lds.h"
 
@@ -12,11 +13,20 @@ namespace sd {
 template <typename T>
 __device__ __forceinline__ T* lds_at(uint8_t* smem, uint32_t off) { return (T*)(smem + off); }
 
-// Minimum over the wave, every lane gets it: the device library's DPP reduction instead of six LDS-crossbar shuffles
-// (the serial phase-2 chain of the matchers does one per point: single-frame search 1.25 -> 0.97 ms; A/B on one box at
-// 1024 frames: 129.6 k vs 129.2 k frames/s).
-extern "C" __device__ __attribute__((const)) unsigned int __ockl_wfred_min_u32(unsigned int);
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return __ockl_wfred_min_u32(v); }
+// Flags pred(i), i in [0, n_bits), packed into the 32-bit words dst[0 .. (n_bits + 31) / 32): one flag per thread and round,
+// a wave's 64 flags are one ballot = two words.  All NT threads call (NT a multiple of 64; tid = lane for a single wave).
+template <typename Pred>
+__device__ __forceinline__ void pack_flags(Pred pred, int n_bits, uint32_t* dst, int tid, int NT) {
+  const int lane = tid & 63, wave = tid >> 6, n_words = (n_bits + 31) >> 5;
+  for (int i0 = 0; i0 < ((n_bits + 63) & ~63); i0 += NT) {
+    const unsigned long long b = __ballot(pred(i0 + tid));
+    const int w = (i0 >> 5) + 2 * wave;
+    if (lane == 0 && w < n_words) {
+      dst[w] = (uint32_t)b;
+      if (w + 1 < n_words) dst[w + 1] = (uint32_t)(b >> 32);
+    }
+  }
+}
 
 // Bin of the rotation histogram for the angle difference a - b (src/ORBmatcher.cc:1043-1049)
 __device__ __forceinline__ int rot_bin(float a, float b) {
@@ -49,7 +59,6 @@ __device__ __forceinline__ void three_maxima(const int* hist, int& ind1, int& in
   else if (max3 < 0.1f * (float)max1) i3 = -1;
   ind1 = i1; ind2 = i2; ind3 = i3;
 }
-
 
 // GL lanes of a wave work on one point.  64: the whole wave (`lane`, `lt` as usual, gm = ~0).  Fewer: one point per group, `glane` =
 // lane within the group, `glt` = the lower lanes OF THE GROUP and `gm` = the group's lanes, both as bit masks of the 64-bit wave

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "orb_internal.h"
+#include "sd_wave.h"
 #include "track_internal.h"
 
 namespace sd {
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(256) void k_new_points(const sd_keypoint* __restric
     for (int w = 0; w < wave; w++) off += s_cnt[w];
     total += s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     if (create) {
-      const int rank = off + __popcll(b & ((1ull << lane) - 1ull));
+      const int rank = off + __popcll(b & lanemask_lt(lane));
       const float x = __fmul_rn(__fmul_rn(__fsub_rn(kps[i].x, fcx), z), inv_fx);
       const float y = __fmul_rn(__fmul_rn(__fsub_rn(kps[i].y, fcy), z), inv_fy);
       const double xd = (double)x, yd = (double)y, zd = (double)z;

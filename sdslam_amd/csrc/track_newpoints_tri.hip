@@ -52,6 +52,7 @@
 
 #include "sd_hypot.h"
 #include "sd_sincosf.h"
+#include "sd_wave.h"
 #include "track_handle.h"
 
 namespace sd {
@@ -352,7 +353,7 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void k_new_points_resolve(ResolveI
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int cap = a.cap, n = a.n_frames;
   const bool bcast = a.cur_bcast >= 0;
-  const unsigned long long lt = (1ull << lane) - 1ull;
+  const unsigned long long lt = lanemask_lt(lane);
   // the first slot that accepts the keypoint
   int first[PT];
 #pragma unroll

@@ -21,6 +21,7 @@
 
 #include "orb_internal.h"
 #include "sd_hypot.h"
+#include "sd_wave.h"
 #include "track_internal.h"
 #include "track_pnp_lds.h"   // PNP_CHUNK and the LDS address maps
 
@@ -1265,7 +1266,7 @@ __global__ __launch_bounds__(64, 2) __attribute__((disable_tail_calls)) void k_p
   uint8_t* inl_out = tb.pnp_inliers + (size_t)f * cap;
   float* T_out = tb.pnp_T + (size_t)f * 16;
   const EpnpCam cam = {(double)tcam.ffx, (double)tcam.ffy, (double)tcam.fcx, (double)tcam.fcy};
-  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt = lanemask_lt(lane);
   float* g_p = tb.pnp_pts + (size_t)f * cap * 6;
   uint16_t* g_idx = tb.pnp_kpidx + (size_t)f * cap;
   const int hyp = lane % PNP_CHUNK, variant = lane / PNP_CHUNK + 1;   // lanes >= 3 * PNP_CHUNK: no hypothesis
@@ -1281,8 +1282,7 @@ __global__ __launch_bounds__(64, 2) __attribute__((disable_tail_calls)) void k_p
     const int i = base + lane;
     const int m = i < nkp ? cm[i] : -1;
     const bool fl = m >= 0;
-    const unsigned long long bal = __ballot(fl);
-    const int pos = N + __popcll(bal & lt);
+    const int pos = wave_append(fl, lt, N);
     if (fl && pos < PNP_MAXN) {
       const sd_keypoint kp = kps[i];
       float* q = g_p + (size_t)pos * 6;
@@ -1294,7 +1294,6 @@ __global__ __launch_bounds__(64, 2) __attribute__((disable_tail_calls)) void k_p
       q[5] = sigma2[kp.octave] * pp.th2;
       g_idx[pos] = (uint16_t)i;
     }
-    N += __popcll(bal);
   }
   N = min(N, PNP_MAXN);
   __syncthreads();

@@ -28,6 +28,7 @@
 #include <cstdlib>
 
 #include "orb_internal.h"
+#include "sd_wave.h"
 #include "track_internal.h"
 
 namespace sd {
@@ -242,11 +243,8 @@ __device__ __forceinline__ double po_error(const Se3q& T, const double* Xw, doub
   return (e[0] * (info * e[0]) + e[1] * (info * e[1])) + e[2] * (info * e[2]);
 }
 
-// sum over the wave, every lane gets the same bits (device library's DPP reduction; the order is a fixed tree, like the
-// xor-butterfly it replaces -- this stage is compared at a tolerance, see the header)
-extern "C" __device__ __attribute__((const)) double __ockl_wfred_add_f64(double);
-__device__ __forceinline__ double wave_sum(double v) { return __ockl_wfred_add_f64(v); }
-
+// wave_sum (sd_wave.h): every lane gets the same bits; the order is a fixed tree, like the xor-butterfly it replaces -- this stage
+// is compared at a tolerance, see the header.
 // One frame = one workgroup of W waves (W = 1 for large batches, where the waves of other frames fill the SIMDs and the
 // replicated scalar LM logic of extra waves would only cost; W = 4 for small batches, where the edge loops are the
 // critical path): the edges are spread over all threads; sums are combined per wave by butterflies and across waves
@@ -407,17 +405,13 @@ __global__ __launch_bounds__(64 * W) void k_pose_opt(const sd_keypoint* __restri
     // keypoints matched the longest list of a wave was about twice the mean, and the edge loops run to the longest list.
     int nInitial = 0;
     {
-      const unsigned long long lt_ = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+      const unsigned long long lt = lanemask_lt(lane);
       int wbase = 0;   // edges of this wave so far
       for (int i0 = 0; i0 < nkp; i0 += PO_THREADS) {
         const int i = i0 + tid;
         const bool has = i < nkp && match[i] >= 0;
-        const unsigned long long bal = __ballot(has);
-        if (has) {
-          const int p = wbase + __popcll(bal & lt_);
-          s_idx[p >> 6][(wave << 6) + (p & 63)] = (uint16_t)i;
-        }
-        wbase += __popcll(bal);
+        const int p = wave_append(has, lt, wbase);
+        if (has) s_idx[p >> 6][(wave << 6) + (p & 63)] = (uint16_t)i;
       }
       nInitial = wbase;
       my_edges = (wbase + 63 - lane) >> 6;   // positions p < wbase with p % 64 == lane

@@ -228,18 +228,16 @@ __global__ __launch_bounds__(64 * REFRESH_WAVES) void k_refresh_points(RefreshAr
     for (int o_base = 0; o_base < n; o_base += 64) {
       const int o = o_base + lane;
       const bool take = o < n && !(a.kf_bad && a.kf_bad[o0 + o]);
-      const unsigned long long mask = __ballot(take);
+      const int j = wave_append(take, lanemask_lt(lane), N);
       if (take) {
         ObsAt at;
         (void)locate_obs(a, a.frame[o0 + o], a.kp[o0 + o], &at);
-        const int j = N + __popcll(mask & ((1ull << lane) - 1ull));
-        const uint4 lo = ((const uint4*)at.desc)[0], hi = ((const uint4*)at.desc)[1];
-        const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        uint32_t w[8];
+        load_desc8((const uint32_t*)at.desc, 0, w);
 #pragma unroll
         for (int k = 0; k < 8; k++) s_desc[LdsRefreshWave::desc_word(k, j)] = w[k];
         s_pos[j] = (uint16_t)o;
       }
-      N += __popcll(mask);
     }
   __syncthreads();
   uint32_t best = 0xFFFFFFFFu;

@@ -21,6 +21,7 @@
 #include <climits>
 #include <cmath>
 
+#include "sd_wave.h"
 #include "track_handle.h"
 
 namespace sd {
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(64) void k_sim3(const sd_keypoint* __restrict__ kps
                                              TrackCam cam, const float* __restrict__ sigma2, int nlevels,
                                              const int32_t* __restrict__ max_its_tab, Sim3Params sp) {
   const int f = blockIdx.x, lane = threadIdx.x;
-  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt = lanemask_lt(lane);
   const int K = tb.kp_cap;
   const size_t fK = (size_t)f * K;
   double* __restrict__ GX = tb.s3_X + fK * 6;
@@ -323,9 +324,8 @@ __global__ __launch_bounds__(64) void k_sim3(const sd_keypoint* __restrict__ kps
         m = m12[i1];
         ok = m >= 0 && m < N2 && v1[i1] != 0 && v2[m] != 0;
       }
-      const unsigned long long b = __ballot(ok);
+      const int pos = wave_append(ok, lt, n);
       if (ok) {
-        const int pos = n + __popcll(b & lt);
         const int o1 = min(max(kps1[i1].octave, 0), nlevels - 1), o2 = min(max(kps2[m].octave, 0), nlevels - 1);
         // mvnMaxError is a vector<size_t>: 9.210 * sigma2 (double) is truncated
         GF[4 * K + pos] = (float)(unsigned long long)(9.210 * (double)sigma2[o1]);
@@ -343,7 +343,6 @@ __global__ __launch_bounds__(64) void k_sim3(const sd_keypoint* __restrict__ kps
         s3_to_image(c1[0], c1[1], c1[2], cam, &GF[0 * K + pos], &GF[1 * K + pos]);
         s3_to_image(c2[0], c2[1], c2[2], cam, &GF[2 * K + pos], &GF[3 * K + pos]);
       }
-      n += __popcll(b);
     }
     N = n;
     max_its = max_its_tab[N];

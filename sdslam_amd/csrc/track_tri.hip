@@ -16,9 +16,9 @@
 //     ex = (float)((fx * C2x) * invz + cx), ey likewise.
 //
 //   k_search_triangulation, one workgroup per slot.  This variant of the matcher never sets vbMatched2, so every idx1 row is
-//   independent: one lane owns TRI_PT rows (descriptor, epipolar line a, b, c, den and the stereo bit in registers), KF2 goes
-//   through LDS in tiles of BF_TILE keypoints (descriptor + x, y, gate threshold) read as broadcasts, and the loop runs over
-//   the set bits of the tile's eligibility mask (idx2 < N2, no map point) on the scalar unit.  Every gate of the reference is
+//   independent and the scaffold of track_bf_dev.h does the scan: a lane's BF_PT rows carry the descriptor, the epipolar line
+//   a, b, c, den and the stereo bit in registers, a KF2 tile carries x, y and the gate threshold beside the descriptor, and
+//   the eligibility mask is idx2 < N2, no map point.  Every gate of the reference is
 //   a pure filter and `dist > bestDist -> continue` keeps the smallest distance, the LARGEST idx2 among equals, so a row's
 //   result is min over the passing candidates of dist << 11 | (2047 - idx2).
 //   What depends on the KF2 keypoint alone is evaluated once per keypoint instead of once per pair, in the reference's
@@ -31,22 +31,17 @@
 //   when one of them passes.  The gate passes so few candidates that this beats computing both and selecting, although a wave
 //   skips only when all of its rows reject (measured: DESIGN.md section 6, SearchForTriangulation).
 //   Rotation check (:434-463): the bin arithmetic is that of SearchByPoints (:1269-1278, rot_bin) and the cut is the same
-//   ComputeThreeMaxima, so both helpers of track_match_dev.h are used as they are; the bins never feed back into the scan.
+//   ComputeThreeMaxima: bf_rotation_cut (track_bf_dev.h) serves both matchers.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <string>
 #include <vector>
 
+#include "track_bf_dev.h"
 #include "track_handle.h"
-#include "track_match_dev.h"
 
 namespace sd {
-
-#define TRI_THREADS 256
-#define TRI_PT 2          // KF1 rows per lane
-#define TRI_TH_LOW 50
-#define TRI_NONE 0xFFFFFFFFu
 
 // What the matcher reads and writes besides the two keyframes' keypoints: rows of `cap` entries per slot
 struct TriBuffers {
@@ -120,19 +115,12 @@ __global__ __launch_bounds__(64) void k_tri_geometry(const double* __restrict__ 
   epi_out[(size_t)f * 2 + 1] = (float)__dadd_rn(__dmul_rn(__dmul_rn(cam.fy, C2[1]), (double)invz), cam.cy);
 }
 
-__device__ __forceinline__ int tri_dist(const uint32_t (&a)[8], const uint32_t (&b)[8]) {
-  int d = 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) d += __popc(a[k] ^ b[k]);
-  return d;
-}
-
 // Dynamic LDS: LdsSearchTri (track_match_lds.h)
-__global__ __launch_bounds__(TRI_THREADS) void k_search_triangulation(const sd_keypoint* __restrict__ kps1_all, const uint8_t* __restrict__ desc1_all,
-                                                                      const int32_t* __restrict__ n1_all, const sd_keypoint* __restrict__ kps2_all,
-                                                                      const uint8_t* __restrict__ desc2_all, const int32_t* __restrict__ n2_all,
-                                                                      TriBuffers tb, int cur_bcast, int cap, int capw /* cap rounded up to 64 */,
-                                                                      int nlevels, int check_ori) {
+__global__ __launch_bounds__(BF_THREADS) void k_search_triangulation(const sd_keypoint* __restrict__ kps1_all, const uint8_t* __restrict__ desc1_all,
+                                                                     const int32_t* __restrict__ n1_all, const sd_keypoint* __restrict__ kps2_all,
+                                                                     const uint8_t* __restrict__ desc2_all, const int32_t* __restrict__ n2_all,
+                                                                     TriBuffers tb, int cur_bcast, int cap, int capw /* cap rounded up to 64 */,
+                                                                     int nlevels, int check_ori) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const LdsSearchTri L(capw);
   uint32_t* s_tile = lds_at<uint32_t>(smem, L.tile);
@@ -144,99 +132,70 @@ __global__ __launch_bounds__(TRI_THREADS) void k_search_triangulation(const sd_k
   int* s_hist = lds_at<int>(smem, L.hist);
   int* s_n1v = lds_at<int>(smem, L.n1v);
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-  const int fc = cur_bcast >= 0 ? cur_bcast : f;
-  const sd_keypoint* kps1 = kps1_all + (size_t)fc * cap;
-  const sd_keypoint* kps2 = kps2_all + (size_t)f * cap;
-  const uint32_t* desc1 = (const uint32_t*)(desc1_all + (size_t)fc * cap * 32);
-  const uint32_t* desc2 = (const uint32_t*)(desc2_all + (size_t)f * cap * 32);
-  const int N1 = min(max(n1_all[fc], 0), cap), N2 = min(max(n2_all[f], 0), cap);
+  const BfSlot S(kps1_all, desc1_all, n1_all, kps2_all, desc2_all, n2_all, f, cur_bcast, cap);
+  const int N2 = S.N2;
   const uint8_t* has1 = tb.has1 + (size_t)f * cap;
   const uint8_t* has2 = tb.has2 + (size_t)f * cap;
-  const float* ur1 = tb.ur1 + (size_t)fc * cap;
+  const float* ur1 = tb.ur1 + (size_t)S.fc * cap;
   const float* ur2 = tb.ur2 + (size_t)f * cap;
   const double* F = tb.F12 + (size_t)f * 9;
   const float ex = tb.epi[(size_t)f * 2], ey = tb.epi[(size_t)f * 2 + 1];
 
   // ---- KF2 as bits: eligible (idx2 < N2, no map point); mono and inside the epipole's radius (:418-423)
-  for (int i0 = 0; i0 < capw; i0 += TRI_THREADS) {
-    const int i = i0 + tid;
-    const bool el = i < N2 && has2[i] == 0;
-    bool rj = false;
-    if (el && !(ur2[i] >= 0)) {
-      const sd_keypoint kp = kps2[i];
-      const float distex = ex - kp.x, distey = ey - kp.y;
-      rj = distex * distex + distey * distey < 100.0f * tb.sf[min(max(kp.octave, 0), nlevels - 1)];
-    }
-    const unsigned long long be = __ballot(el), br = __ballot(rj);
-    if (lane == 0 && i < capw) {
-      s_elig[i >> 5] = (uint32_t)be;
-      s_elig[(i >> 5) + 1] = (uint32_t)(be >> 32);
-      s_erej[i >> 5] = (uint32_t)br;
-      s_erej[(i >> 5) + 1] = (uint32_t)(br >> 32);
-    }
-  }
-  for (int i = tid; i < capw; i += TRI_THREADS) s_match[i] = -1;
+  const auto eligible = [&](int i) { return i < N2 && has2[i] == 0; };
+  pack_flags(eligible, capw, s_elig, tid, BF_THREADS);
+  pack_flags([&](int i) {
+    if (i >= N2) return false;
+    const bool el = has2[i] == 0, mono = !(ur2[i] >= 0);   // three independent loads, not a chain: few slots leave the latency bare
+    const sd_keypoint kp = S.kps2[i];
+    const float distex = ex - kp.x, distey = ey - kp.y;
+    return el && mono && distex * distex + distey * distey < 100.0f * tb.sf[min(max(kp.octave, 0), nlevels - 1)];
+  }, capw, s_erej, tid, BF_THREADS);
+  for (int i = tid; i < capw; i += BF_THREADS) s_match[i] = -1;
   if (tid < 32) s_hist[tid] = 0;
   // ---- the KF1 rows without a map point, ascending
-  if (wave == 0) {
-    int n = 0;
-    for (int i0 = 0; i0 < capw; i0 += 64) {
-      const int i = i0 + lane;
-      const bool ok = i < N1 && has1[i] == 0;
-      const unsigned long long b = __ballot(ok);
-      if (ok) s_i1[n + __popcll(b & lt)] = (uint16_t)i;
-      n += __popcll(b);
-    }
-    if (lane == 0) *s_n1v = n;
-  }
+  if (wave == 0) bf_compact_rows([&](int i) { return i < S.N1 && has1[i] == 0; }, capw, s_i1, s_n1v, lane);
   __syncthreads();
   const int n1v = *s_n1v;
   const int ntiles = (N2 + BF_TILE - 1) / BF_TILE;
 
-  for (int e0 = 0; e0 < n1v; e0 += TRI_THREADS * TRI_PT) {
-    uint32_t d1[TRI_PT][8], best[TRI_PT];
-    float la[TRI_PT], lb[TRI_PT], lc[TRI_PT], den[TRI_PT];
-    bool mono1[TRI_PT];
-    int ent[TRI_PT];
+  for (int e0 = 0; e0 < n1v; e0 += BF_THREADS * BF_PT) {
+    uint32_t d1[BF_PT][8], best[BF_PT];
+    float la[BF_PT], lb[BF_PT], lc[BF_PT], den[BF_PT];
+    bool mono1[BF_PT];
+    int ent[BF_PT];
 #pragma unroll
-    for (int p = 0; p < TRI_PT; p++) {
-      ent[p] = e0 + p * TRI_THREADS + tid;
+    for (int p = 0; p < BF_PT; p++) {
+      ent[p] = e0 + p * BF_THREADS + tid;
       const int i1 = ent[p] < n1v ? s_i1[ent[p]] : s_i1[0];   // n1v >= 1 here: entry 0 exists
-      const uint4 a = ((const uint4*)(desc1 + (size_t)i1 * 8))[0], b = ((const uint4*)(desc1 + (size_t)i1 * 8))[1];
-      d1[p][0] = a.x; d1[p][1] = a.y; d1[p][2] = a.z; d1[p][3] = a.w;
-      d1[p][4] = b.x; d1[p][5] = b.y; d1[p][6] = b.z; d1[p][7] = b.w;
+      load_desc8(S.desc1, i1, d1[p]);
       // l = x1' F12 = [a b c] (:130-132): double, left to right, rounded to float once
-      const double x1 = (double)kps1[i1].x, y1 = (double)kps1[i1].y;
+      const double x1 = (double)S.kps1[i1].x, y1 = (double)S.kps1[i1].y;
       la[p] = (float)__dadd_rn(__dadd_rn(__dmul_rn(x1, F[0]), __dmul_rn(y1, F[3])), F[6]);
       lb[p] = (float)__dadd_rn(__dadd_rn(__dmul_rn(x1, F[1]), __dmul_rn(y1, F[4])), F[7]);
       lc[p] = (float)__dadd_rn(__dadd_rn(__dmul_rn(x1, F[2]), __dmul_rn(y1, F[5])), F[8]);
       den[p] = __fadd_rn(__fmul_rn(la[p], la[p]), __fmul_rn(lb[p], lb[p]));
       mono1[p] = !(ur1[i1] >= 0);
-      best[p] = TRI_NONE;
+      best[p] = BF_NONE;
     }
     for (int t = 0; t < ntiles; t++) {
-      __syncthreads();   // previous tile fully consumed
       const int j0 = t * BF_TILE, jn = min(BF_TILE, N2 - j0);
-      for (int w = tid; w < jn * 2; w += TRI_THREADS) ((uint4*)s_tile)[w] = ((const uint4*)(desc2 + (size_t)j0 * 8))[w];
-      for (int j = tid; j < jn; j += TRI_THREADS) {
-        const sd_keypoint kp = kps2[j0 + j];
-        const double thr = __dmul_rn(3.84, (double)tb.sigma2[min(max(kp.octave, 0), nlevels - 1)]);
-        s_aux[j] = make_float4(kp.x, kp.y, __double2float_ru(thr), 0.f);
-      }
-      __syncthreads();
+      bf_stage_tile(S.desc2, j0, jn, s_tile, tid, [&] {
+        for (int j = tid; j < jn; j += BF_THREADS) {
+          const sd_keypoint kp = S.kps2[j0 + j];
+          const double thr = __dmul_rn(3.84, (double)tb.sigma2[min(max(kp.octave, 0), nlevels - 1)]);
+          s_aux[j] = make_float4(kp.x, kp.y, __double2float_ru(thr), 0.f);
+        }
+      });
       for (int wd = 0; wd < (jn + 31) >> 5; wd++) {
-        uint32_t mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_elig[(j0 >> 5) + wd]);   // wave-uniform: scalar loop
         const uint32_t rej = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_erej[(j0 >> 5) + wd]);
-        while (mask) {
-          const int bit = __ffs((int)mask) - 1;
-          mask &= mask - 1;
+        for_each_set_bit(s_elig[(j0 >> 5) + wd], [&](int bit) {
           const int jl = wd * 32 + bit;
           const float4 q = s_aux[jl];                                                                       // LDS broadcasts
           const bool mono_rej = (rej >> bit) & 1u;
-          bool pass[TRI_PT];
+          bool pass[BF_PT];
 #pragma unroll
-          for (int p = 0; p < TRI_PT; p++) {
+          for (int p = 0; p < BF_PT; p++) {
             // CheckDistEpipolarLine (:134-143), all float
             const float num = __fadd_rn(__fadd_rn(__fmul_rn(la[p], q.x), __fmul_rn(lb[p], q.y)), lc[p]);
             const float dsqr = __fdiv_rn(__fmul_rn(num, num), den[p]);
@@ -244,56 +203,31 @@ __global__ __launch_bounds__(TRI_THREADS) void k_search_triangulation(const sd_k
           }
           bool any = false;
 #pragma unroll
-          for (int p = 0; p < TRI_PT; p++) any |= pass[p];
-          if (!__ballot(any)) continue;   // wave-uniform: no row of this wave takes the candidate
-          const uint4 a = ((const uint4*)(s_tile + jl * 8))[0], b = ((const uint4*)(s_tile + jl * 8))[1];
-          const uint32_t d2[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+          for (int p = 0; p < BF_PT; p++) any |= pass[p];
+          if (!__ballot(any)) return;   // wave-uniform: no row of this wave takes the candidate
+          uint32_t d2[8];
+          load_desc8(s_tile, jl, d2);
           const uint32_t low = (uint32_t)(2047 - (j0 + jl));
 #pragma unroll
-          for (int p = 0; p < TRI_PT; p++) {
-            const int dist = tri_dist(d1[p], d2);
+          for (int p = 0; p < BF_PT; p++) {
+            const int dist = hamming256(d1[p], d2);
             const uint32_t key = ((uint32_t)dist << 11) | low;
-            if (pass[p] && dist <= TRI_TH_LOW) best[p] = min(best[p], key);
+            best[p] = pass[p] && dist <= BF_TH_LOW ? min(best[p], key) : best[p];   // a select, not a branch
           }
-        }
+        });
       }
     }
 #pragma unroll
-    for (int p = 0; p < TRI_PT; p++)
-      if (ent[p] < n1v && best[p] != TRI_NONE && den[p] != 0.f) s_match[s_i1[ent[p]]] = (int16_t)(2047 - (int)(best[p] & 2047u));
+    for (int p = 0; p < BF_PT; p++)
+      if (ent[p] < n1v && best[p] != BF_NONE && den[p] != 0.f) s_match[s_i1[ent[p]]] = (int16_t)(2047 - (int)(best[p] & 2047u));
   }
   __syncthreads();
   if (tid >= 64) return;   // one wavefront counts and runs the rotation check
 
   int nmatches = 0;
-  for (int e0 = 0; e0 < n1v; e0 += 64) {
-    const int e = e0 + lane;
-    const int i1 = e < n1v ? s_i1[e] : 0;
-    const int j = e < n1v ? s_match[i1] : -1;
-    nmatches += __popcll(__ballot(j >= 0));
-    if (check_ori && j >= 0) atomicAdd(&s_hist[rot_bin(kps1[i1].angle, kps2[j].angle)], 1);
-  }
-  if (check_ori) {
-    __threadfence_block();
-    int ind1, ind2, ind3;
-    three_maxima(s_hist, ind1, ind2, ind3);
-    for (int e0 = 0; e0 < n1v; e0 += 64) {
-      const int e = e0 + lane;
-      bool drop = false;
-      if (e < n1v) {
-        const int i1 = s_i1[e], j = s_match[i1];
-        if (j >= 0) {
-          const int bin = rot_bin(kps1[i1].angle, kps2[j].angle);
-          drop = bin != ind1 && bin != ind2 && bin != ind3;
-          if (drop) s_match[i1] = -1;
-        }
-      }
-      nmatches -= __popcll(__ballot(drop));
-    }
-  }
-  int32_t* out = tb.match + (size_t)f * cap;
-  for (int i = lane; i < cap; i += 64) out[i] = (int32_t)s_match[i];
-  if (lane == 0) tb.n[f] = nmatches;
+  for (int e0 = 0; e0 < n1v; e0 += 64) nmatches += __popcll(__ballot(e0 + lane < n1v && s_match[s_i1[e0 + lane]] >= 0));
+  if (check_ori) nmatches -= bf_rotation_cut(S, s_i1, n1v, s_match, s_hist, lane);
+  bf_write_out(s_match, cap, nmatches, tb.match + (size_t)f * cap, tb.n + f, lane);
 }
 
 static int launch_search_triangulation(const sd_keypoint* kps1, const uint8_t* desc1, const int32_t* n1, const sd_keypoint* kps2,
@@ -301,7 +235,7 @@ static int launch_search_triangulation(const sd_keypoint* kps1, const uint8_t* d
                                        int n_frames, int check_ori, hipStream_t s) {
   const int capw = (cap + 63) & ~63;
   SD_REQUIRE(capw <= 2048, SD_ERR_CAPACITY, "SearchForTriangulation supports at most 2048 keypoints per keyframe");
-  hipLaunchKernelGGL(k_search_triangulation, dim3(n_frames), dim3(TRI_THREADS), LdsSearchTri(capw).bytes, s, kps1, desc1, n1, kps2, desc2, n2,
+  hipLaunchKernelGGL(k_search_triangulation, dim3(n_frames), dim3(BF_THREADS), LdsSearchTri(capw).bytes, s, kps1, desc1, n1, kps2, desc2, n2,
                      tb, cur_bcast, cap, capw, nlevels, check_ori != 0);
   SD_HIP_CHECK(hipGetLastError());
   return SD_OK;
