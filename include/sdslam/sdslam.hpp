@@ -386,6 +386,14 @@ class ORBmatcher {
     batch.SetCurrentBroadcast(-1);
     check(rc);
   }
+  // The rows of sd_track_get_new_points, in (neighbour, idx1) order
+  struct NewPointRows {
+    std::vector<int32_t> kp1, slot, idx2, id;
+    std::vector<double> Xw, normal;        // [n][3]
+    std::vector<float> max_dist, min_dist;
+    std::vector<uint8_t> desc;             // [n][32]
+    size_t size() const { return kp1.size(); }
+  };
   // void LocalMapping::CreateNewMapPoints()                                                  src/LocalMapping.cc:187-420
   // pKF1 = mpCurrentKeyFrame (frame 0 of the cur extractor, broadcast), vpNeighKFs = GetBestCovisibilityKeyFrames(nn) (frame i
   // of the ref extractor).  The device searches every neighbour, triangulates every match with the reference's tests and
@@ -403,6 +411,49 @@ class ORBmatcher {
                          MakePoint make_point, RecentList& recent, int kp_cap) {
     const int n = (int)vpNeighKFs.size();
     if (n == 0) return 0;
+    UploadNewPointSlots(batch, pKF1, vpNeighKFs, monocular, nNextId, kp_cap);
+    batch.SetCurrentBroadcast(0);
+    int rc = sd_track_search_for_triangulation(batch.handle(), n, 0, 0);
+    if (rc == SD_OK) rc = sd_track_triangulate(batch.handle(), n, monocular ? 1 : 0);
+    NewPointRows rows;
+    if (rc == SD_OK) rc = DownloadNewPoints(batch, rows);
+    batch.SetCurrentBroadcast(-1);
+    check(rc);
+    return WalkNewPoints(rows, pKF1, vpNeighKFs, make_point, recent);
+  }
+  // The same with the new points appended to local row point_row ON THE DEVICE (sd_track_append_new_points, mark_flags = 1), behind
+  // the points the row holds: the row is then what the first loop of SearchInNeighbors hands to Fuse (sd_track_fuse with this
+  // point_row), with cand of rows < n_cand_rows = the Fuse targets, the neighbours in the first ref frames.  Only kp1, slot, idx2
+  // and id of every point come back; position, normal, distances and descriptor stay on the device (sd_track_get_local_points
+  // reads them when the caller wants them, RefreshMapPoints rewrites them).  make_point(pKF1, id, pos) makes the caller's object of
+  // the point at position pos of the row; the objects are made in creation order and vnRowPos[i] is the position of the i-th --
+  // what Fuse's walk indexes best_idx with.  Points that did not fit into the row were dropped on the device (neither appended nor
+  // flagged): no object is made for them.  Returns nnew = the number appended.
+  template <class KeyFrameT, class MakePoint, class RecentList>
+  int CreateNewMapPoints(TrackBatch& batch, KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpNeighKFs, bool monocular, int32_t nNextId,
+                         MakePoint make_point, RecentList& recent, int kp_cap, int point_row, int n_cand_rows,
+                         std::vector<int32_t>& vnRowPos) {
+    vnRowPos.clear();
+    const int n = (int)vpNeighKFs.size();
+    if (n == 0) return 0;
+    UploadNewPointSlots(batch, pKF1, vpNeighKFs, monocular, nNextId, kp_cap);
+    batch.SetCurrentBroadcast(0);
+    int rc = sd_track_search_for_triangulation(batch.handle(), n, 0, 0);
+    if (rc == SD_OK) rc = sd_track_triangulate(batch.handle(), n, monocular ? 1 : 0);
+    if (rc == SD_OK) rc = sd_track_append_new_points(batch.handle(), point_row, n_cand_rows, 1);
+    NewPointRows rows;
+    int32_t base = 0, appended = 0;
+    if (rc == SD_OK) rc = DownloadNewPointIndices(batch, rows);
+    if (rc == SD_OK) rc = sd_track_get_appended(batch.handle(), point_row, 1, &base, &appended, nullptr);
+    batch.SetCurrentBroadcast(-1);
+    check(rc);
+    return WalkAppendedPoints(rows, base, appended, pKF1, vpNeighKFs, make_point, recent, vnRowPos);
+  }
+  // What both overloads upload: mvDepth of both sides, every slot's flags, mvuRight and poses, the median depths, nNextId
+  template <class KeyFrameT>
+  void UploadNewPointSlots(TrackBatch& batch, KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpNeighKFs, bool monocular, int32_t nNextId,
+                           int kp_cap) {
+    const int n = (int)vpNeighKFs.size();
     std::vector<float> z(kp_cap, -1.f), median(n, -1.f);
     for (int i = 0; i < pKF1->N && i < kp_cap; i++) z[i] = pKF1->mvDepth[i];
     check(sd_track_set_tri_depth(batch.handle(), 0, 0, 1, z.data(), kp_cap));
@@ -416,23 +467,38 @@ class ORBmatcher {
     }
     check(sd_track_set_tri_median_depth(batch.handle(), 0, n, median.data()));
     check(sd_track_set_next_map_id(batch.handle(), 0, 1, &nNextId));
-    batch.SetCurrentBroadcast(0);
-    int rc = sd_track_search_for_triangulation(batch.handle(), n, 0, 0);
-    if (rc == SD_OK) rc = sd_track_triangulate(batch.handle(), n, monocular ? 1 : 0);
-    NewPointRows rows;
-    if (rc == SD_OK) rc = DownloadNewPoints(batch, rows);
-    batch.SetCurrentBroadcast(-1);
-    check(rc);
-    return WalkNewPoints(rows, pKF1, vpNeighKFs, make_point, recent);
   }
-  // The rows of sd_track_get_new_points, in (neighbour, idx1) order
-  struct NewPointRows {
-    std::vector<int32_t> kp1, slot, idx2, id;
-    std::vector<double> Xw, normal;        // [n][3]
-    std::vector<float> max_dist, min_dist;
-    std::vector<uint8_t> desc;             // [n][32]
-    size_t size() const { return kp1.size(); }
-  };
+  // kp1, slot, idx2 and id of sd_track_get_new_points, nothing else: the other arrays of `r` stay empty
+  int DownloadNewPointIndices(TrackBatch& batch, NewPointRows& r) {
+    int32_t info[4] = {0, 0, 0, 0};
+    int rc = sd_track_get_new_points(batch.handle(), info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+    if (rc != SD_OK) return rc;
+    const size_t n = (size_t)info[0];
+    r.kp1.resize(n); r.slot.resize(n); r.idx2.resize(n); r.id.resize(n);
+    if (n == 0) return SD_OK;
+    return sd_track_get_new_points(batch.handle(), info, r.kp1.data(), r.slot.data(), r.idx2.data(), r.id.data(), nullptr, nullptr, nullptr,
+                                   nullptr, nullptr, (int)n);
+  }
+  // :401-417 for the first `appended` rows, in order, without the fields: the point at row position base + p, its two observations,
+  // both keyframes' AddMapPoint, mlpRecentAddedMapPoints.  Host code only.
+  template <class KeyFrameT, class MakePoint, class RecentList>
+  static int WalkAppendedPoints(const NewPointRows& r, int32_t base, int32_t appended, KeyFrameT* pKF1,
+                                const std::vector<KeyFrameT*>& vpNeighKFs, MakePoint make_point, RecentList& recent,
+                                std::vector<int32_t>& vnRowPos) {
+    int nnew = 0;
+    for (size_t p = 0; p < r.size() && p < (size_t)(appended > 0 ? appended : 0); p++) {
+      KeyFrameT* pKF2 = vpNeighKFs[(size_t)r.slot[p]];
+      auto* pMP = make_point(pKF1, r.id[p], base + (int32_t)p);
+      pMP->AddObservation(pKF1, (size_t)r.kp1[p]);
+      pMP->AddObservation(pKF2, (size_t)r.idx2[p]);
+      pKF1->AddMapPoint(pMP, (size_t)r.kp1[p]);
+      pKF2->AddMapPoint(pMP, (size_t)r.idx2[p]);
+      recent.push_back(pMP);
+      vnRowPos.push_back(base + (int32_t)p);
+      nnew++;
+    }
+    return nnew;
+  }
   int DownloadNewPoints(TrackBatch& batch, NewPointRows& r) {
     int32_t info[4] = {0, 0, 0, 0};
     int rc = sd_track_get_new_points(batch.handle(), info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);

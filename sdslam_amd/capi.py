@@ -118,6 +118,9 @@ _SIGNATURES = {
     "sd_track_get_triangulated": (_I, [_P, _I, _I, _P, _P, _P, _I, _P]),
     "sd_track_get_new_points": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "sd_debug_triangulate": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _I, _F, _P, _P, _P]),
+    "sd_track_append_new_points": (_I, [_P, _I, _I, _I]),
+    "sd_track_get_appended": (_I, [_P, _I, _I, _P, _P, _P]),
+    "sd_track_get_local_points": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "sd_track_set_fuse_scw": (_I, [_P, _I, _I, _P]),
     "sd_track_fuse": (_I, [_P, _I, _I, _I, _F, _I]),
     "sd_track_get_fuse": (_I, [_P, _I, _I, _P, _P, _I, _P]),
@@ -747,6 +750,28 @@ class Tracker:
         if n:
             _check(self.L.sd_track_get_new_points(self.h, _p(info), *[_p(a) for a in i32], _p(X), _p(N), _p(mx), _p(mn), _p(d), n))
         return dict(info=info, kp1=i32[0], slot=i32[1], idx2=i32[2], id=i32[3], Xw=X, normal=N, max_dist=mx, min_dist=mn, desc=d)
+
+    # --- the new points as local-map rows, on the device (track_append.hip) ---
+    def append_new_points(self, point_row=0, n_cand_rows=0, mark_flags=False):
+        """The points of the live triangulate() result behind the points of local row point_row (cand of rows < n_cand_rows:
+        f != the point's slot), or with point_row = -1 behind those of each point's own slot's row.  Queued, no host wait."""
+        _check(self.L.sd_track_append_new_points(self.h, int(point_row), int(n_cand_rows), int(mark_flags)))
+
+    def get_appended(self, frame0, n):
+        """dict(base, appended, dropped) per local row of the last append_new_points()."""
+        out = [np.zeros(n, np.int32) for _ in range(3)]
+        _check(self.L.sd_track_get_appended(self.h, frame0, n, *[_p(a) for a in out]))
+        return dict(base=out[0], appended=out[1], dropped=out[2])
+
+    def get_local_points(self, row):
+        """Local row `row` as it is on the device: dict(n, cand, Xw, normal, min_dist, max_dist, mf_max_dist, desc, obs), M entries."""
+        M = self.M
+        n = np.zeros(1, np.int32)
+        out = dict(cand=np.zeros(M, np.uint8), Xw=np.zeros((M, 3)), normal=np.zeros((M, 3)), min_dist=np.zeros(M, np.float32),
+                   max_dist=np.zeros(M, np.float32), mf_max_dist=np.zeros(M, np.float32), desc=np.zeros((M, 32), np.uint8),
+                   obs=np.zeros(M, np.int32))
+        _check(self.L.sd_track_get_local_points(self.h, int(row), _p(n), *[_p(a) for a in out.values()], M))
+        return dict(n=int(n[0]), **out)
 
     # --- ORBmatcher::Fuse, both overloads (src/ORBmatcher.cc:477-732); the points are set_local's rows ---
     def set_fuse_scw(self, frame0, Scw):

@@ -208,6 +208,7 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &h->nb.geo, B * K * 6));
   A(dalloc(h, &h->nb.dist, B * K * 2));
   A(dalloc(h, &h->nb.desc, B * K * 32));
+  A(dalloc(h, &h->nb.appended, B * 3));
   A(dalloc(h, &h->fu.Scw, B * 16));
   A(dalloc(h, &h->fu.pose, B * 15));
   A(dalloc<FILL_FF>(h, &h->fu.idx, B * M));

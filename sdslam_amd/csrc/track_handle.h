@@ -77,7 +77,7 @@ struct sd_track {
   // What the stages that cache a result between calls left, and on which inputs (track_results.h: stamps, and the table of
   // what ends them).  pnp: the solvers sd_track_pnp_iterate continues; sim3: those of sd_track_sim3_iterate; tri: the matches of
   // sd_track_get_triangulation_matches; triang: sd_track_get_triangulated / _get_new_points; fuse: sd_track_get_fuse;
-  // refresh: sd_track_get_refreshed.
+  // refresh: sd_track_get_refreshed; append: sd_track_get_appended (and sd_track_get_new_points after an append).
   sd::Results res;
   sd::PnpParams pnp_params{};
   int pnp_iter_upper = 0;          // upper bound of mnIterations of the PnP solvers

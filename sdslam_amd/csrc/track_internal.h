@@ -265,10 +265,15 @@ struct TriangBuffers {
   double* geo;           // [..][6] Xw | mNormalVector
   float* dist;           // [..][2] mfMaxDistance | mfMinDistance
   uint8_t* desc;         // [..][32] GetDescriptor()
+  int32_t* appended;     // [B][3] the last sd_track_append_new_points, per local row: base | appended | dropped (track_append.hip)
 };
 // k_triangulate on the live search result of slots < n_frames, then k_new_points_resolve.  ratio_factor = 1.5f * mfScaleFactor
 int launch_triangulate(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const TriangBuffers& nb, const TrackCam& cam,
                        const float* d_sf, const float* d_sigma2, float ratio_factor, int n_frames, int monocular, hipStream_t s);
+// k_append_points, then k_append_commit (track_append.hip): the points of the resolve result behind the points of local row
+// point_row (>= 0, cand of rows < n_cand_rows) or of each point's own slot's row (-1); mark_flags: sp_valid1 / sp_valid2 too
+int launch_append_points(const TrackBuffers& tb, const TriangBuffers& nb, int max_batch, int point_row, int n_cand_rows, int mark_flags,
+                         hipStream_t s);
 // MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (track_refresh.hip): what the refresh owns besides the point
 // row (lm_*) it reads and, with write_local, rewrites.  Kept out of TrackBuffers like FuseBuffers.
 struct RefreshBuffers {

@@ -502,6 +502,7 @@ int sd_track_triangulate(sd_track* h, int n_frames, int monocular) {
   SD_REQUIRE(h->tb.cur_bcast < 0 || h->res.tri.payload == 0, SD_ERR_INVALID_ARG,
              "broadcast mode needs a search with check_ori = 0 (CreateNewMapPoints' matcher has mbCheckOrientation off)");
   const float ratio_factor = 1.5f * h->cur->scaleFactor;
+  END_RESULTS(h, "sd_track_triangulate");   // the point list an append left readable is overwritten
   SD_TRY(run_stage(h, true, false, STAGE_NONE, [&](hipStream_t s) {
     return launch_triangulate(h->cur, h->ref, h->tb, h->nb, h->cam, h->d_sf, h->d_sigma2, ratio_factor, n_frames, monocular, s);
   }));
@@ -528,7 +529,10 @@ int sd_track_get_triangulated(sd_track* h, int frame0, int n_frames, uint8_t* ve
 int sd_track_get_new_points(sd_track* h, int32_t* info4, int32_t* kp1, int32_t* slot, int32_t* idx2, int32_t* ids, double* Xw,
                             double* normal, float* max_dist, float* min_dist, uint8_t* desc, int cap) {
   TRACK_RANGE(h, 0, 1);
-  SD_REQUIRE(h->res.triang_live(h->res.triang.n, inputs_now(h)), SD_ERR_INVALID_ARG, kNoTriangulation);
+  // after sd_track_append_new_points the list is the record of what went into the rows: readable until the append's result ends,
+  // also where the append itself (mark_flags) or a later call ended the triangulation
+  SD_REQUIRE(h->res.triang_live(h->res.triang.n, inputs_now(h)) || h->res.append.live(1, inputs_now(h)), SD_ERR_INVALID_ARG,
+             kNoTriangulation);
   SD_REQUIRE(info4 && cap >= 0, SD_ERR_INVALID_ARG, "info4 is NULL or cap negative");
   hipStream_t s = h->cur->stream;
   SD_TRY(download(info4, h->nb.info, 0, 1, 4, s));

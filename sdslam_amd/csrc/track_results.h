@@ -1,12 +1,12 @@
 // The lifetime of every result a tracker caches between calls: the PnP and Sim3 solvers an iterate() continues, the
-// SearchForTriangulation matches, their triangulation, the Fuse search, the map-point refresh.  One stamp type says what a result was computed on, one
+// SearchForTriangulation matches, their triangulation, the Fuse search, the map-point refresh, the append of new points.  One stamp type says what a result was computed on, one
 // table says which entry point ends which results.  Plain C++ on plain values (extraction serials, the broadcast setting, slot
 // counts), no HIP and no handle: tests/native/result_stamps_check.cpp checks the table and the bindings on the host.
 #pragma once
 
 namespace sd {
 
-enum Result : unsigned { R_PNP = 1, R_SIM3 = 2, R_TRI = 4, R_TRIANG = 8, R_FUSE = 16, R_REFRESH = 32 };
+enum Result : unsigned { R_PNP = 1, R_SIM3 = 2, R_TRI = 4, R_TRIANG = 8, R_FUSE = 16, R_REFRESH = 32, R_APPEND = 64 };
 
 // What a result is bound to: it dies when that extractor extracts again / when the broadcast setting changes
 enum Bind : unsigned { BIND_CUR = 1, BIND_REF = 2, BIND_BCAST = 4 };
@@ -17,6 +17,9 @@ constexpr unsigned BIND_TRIANG = BIND_CUR;   // ... and lives only while the sea
 constexpr unsigned bind_fuse(int kf_side) { return (kf_side ? BIND_REF : BIND_CUR) | BIND_BCAST; }   // the side it searched
 
 constexpr unsigned BIND_REFRESH = BIND_CUR | BIND_REF | BIND_BCAST;   // observations name frames of both extractors and the cur frame in use
+// An append's result is a record of what went into the rows (base / appended / dropped, and the list of the points, which only
+// the next triangulation overwrites): no later change of an input makes it wrong, only the entry points of kEnds / kEndsAppend end it
+constexpr unsigned BIND_APPEND = 0;
 
 // What a tracker's results are computed on: the serials of the cur and ref extractions, the broadcast setting
 struct ResultInputs {
@@ -29,7 +32,8 @@ struct ResultStamp {
   int n = 0;
   unsigned bind = 0;
   ResultInputs on;
-  int payload = 0;        // tri: the rotation check ran; Fuse: kf_side; refresh: the number of points
+  int payload = 0;        // tri: the rotation check ran; triang: its points have been appended to the local rows; Fuse: kf_side;
+                          // refresh: the number of points; append: the slots of the triangulation it appended
   // RunStamp::covers compares the `cur` pointer as well.  The pointer changes in one place, sd_track_advance, which swaps the
   // extractors' roles: a Sim3 / tri / triang result does not answer for the swapped pair (Results::swap_roles), and does
   // again once a second advance has swapped them back.  Fuse never compared it: its serial is its side's, whoever holds it.
@@ -45,7 +49,7 @@ struct ResultStamp {
 };
 
 struct Results {
-  ResultStamp pnp, sim3, tri, triang, fuse, refresh;
+  ResultStamp pnp, sim3, tri, triang, fuse, refresh, append;
   bool triang_live(int n_frames, const ResultInputs& now) const { return tri.live(n_frames, now) && triang.live(n_frames, now); }
   void swap_roles() { sim3.swapped ^= true, tri.swapped ^= true, triang.swapped ^= true; }
 };
@@ -59,6 +63,7 @@ inline void end_results(Results& r, unsigned mask) {
   if (mask & R_TRIANG) r.triang = ResultStamp{};
   if (mask & R_FUSE) r.fuse = ResultStamp{};
   if (mask & R_REFRESH) r.refresh = ResultStamp{};
+  if (mask & R_APPEND) r.append = ResultStamp{};
 }
 
 // What each entry point ends, and why.  An entry point calls end_results with its own row and nothing else (END_RESULTS).
@@ -73,8 +78,8 @@ constexpr EndsRow kEnds[] = {
     {"sd_track_with_motion_model", R_PNP},                // ... likewise
     {"sd_track_stereo_init", R_PNP},                      // ... likewise
     {"sd_track_advance", R_PNP},                          // ... and `cur` becomes the other extractor
-    {"sd_track_set_local", R_FUSE | R_REFRESH},           // sd_track_fuse reads these rows too; the refresh read Xw of one
-    {"sd_track_set_local_view", R_FUSE},                  // lm_n and lm_desc are rows sd_track_fuse reads
+    {"sd_track_set_local", R_FUSE | R_REFRESH | R_APPEND},   // sd_track_fuse reads these rows too; the refresh read Xw of one; an append's positions are overwritten
+    {"sd_track_set_local_view", R_FUSE | R_APPEND},       // lm_n and lm_desc are rows sd_track_fuse reads, and an append counted from lm_n
     {"sd_track_set_uright", R_TRI | R_FUSE},              // KF1's stereo bits, and the mvuRight row of a Fuse result's chi-square gate
     {"sd_track_set_uright_ref", R_TRI | R_FUSE},          // KF2's
     {"sd_track_stereo_from_depth", R_TRI},                // mvuRight and mvDepth of KF1 are being replaced
@@ -99,7 +104,17 @@ constexpr EndsRow kEndsRefresh[] = {
     {"sd_track_set_observations", R_REFRESH},             // the lists the result was computed on
     {"sd_track_refresh_points", R_REFRESH},               // a stage ends its own old result before it runs
     // write_local = 1 rewrites desc, normal and the distances of a local row: whatever a sd_track_set_local on that row ends
-    {"sd_track_refresh_points(write_local)", R_FUSE | R_REFRESH},
+    {"sd_track_refresh_points(write_local)", R_FUSE | R_REFRESH | R_APPEND},
+};
+
+// The append of new points to the local rows (track_append.hip), a table of its own for the same reason;
+// tests/native/append_stamps_check.cpp holds these rows and the R_APPEND bits above to a matrix of its own.
+constexpr EndsRow kEndsAppend[] = {
+    // it rewrites lm_n and the fields of local rows: whatever a sd_track_set_local on them ends (its own old result among them)
+    {"sd_track_append_new_points", R_FUSE | R_REFRESH | R_APPEND},
+    // mark_flags = 1 also rewrites the "holds a map point" flags: whatever sd_track_set_point_flags ends besides
+    {"sd_track_append_new_points(mark_flags)", R_FUSE | R_REFRESH | R_APPEND | R_SIM3 | R_TRI},
+    {"sd_track_triangulate", R_APPEND},                   // the point list sd_track_get_new_points reads after an append is overwritten
 };
 
 constexpr bool same_name(const char* a, const char* b) {
@@ -112,10 +127,15 @@ constexpr int ends_of(const char* entry) {
     if (same_name(row.entry, entry)) return (int)row.mask;
   for (const EndsRow& row : kEndsRefresh)
     if (same_name(row.entry, entry)) return (int)row.mask;
+  for (const EndsRow& row : kEndsAppend)
+    if (same_name(row.entry, entry)) return (int)row.mask;
   return -1;
 }
 
 static_assert(ends_of("sd_track_refresh_points(write_local)") == (ends_of("sd_track_set_local") | (int)R_REFRESH),
               "a write-through ends what sd_track_set_local ends");
+static_assert(ends_of("sd_track_append_new_points") == ends_of("sd_track_set_local"), "an append ends what sd_track_set_local ends");
+static_assert(ends_of("sd_track_append_new_points(mark_flags)") == (ends_of("sd_track_set_local") | ends_of("sd_track_set_point_flags")),
+              "... and with mark_flags what sd_track_set_point_flags ends");
 
 }  // namespace sd

@@ -1,9 +1,15 @@
-"""Time LocalMapping::CreateNewMapPoints for one keyframe of 1000 keypoints against 20 neighbours, two ways:
+"""Time LocalMapping::CreateNewMapPoints for one keyframe of 1000 keypoints against 20 neighbours, two ways, and then the chain
+into SearchInNeighbors' first Fuse loop, two ways:
 
   (a) the path before sd_track_triangulate: the device search, sd_track_get_triangulation_matches for all neighbours, the
       triangulation on the host, and the upload of the new points through sd_track_set_local (one row, as Fuse reads it);
   (b) the device search and sd_track_triangulate queued back to back, ended by sd_track_get_new_points (which the caller's
-      MapPoint objects need in either path).
+      MapPoint objects need in either path);
+  (c) the chain search -> triangulate -> sd_track_append_new_points -> sd_track_fuse(kf_side 1, point_row 0), queued back to back
+      and ended by sd_track_get_fuse, against
+  (d) the same chain with the round trip the append replaces: search -> triangulate -> sd_track_get_new_points -> the rows and
+      cand flags built on the host (numpy) -> sd_track_set_local -> sd_track_fuse -> sd_track_get_fuse.
+      Both in the same run, one after the other; their Fuse results must be equal.
 
     python tools/bench_new_points.py [--neighbours 20] [--host-slots 2] [--out profiles/new_points_bench.jsonl]
 
@@ -96,13 +102,46 @@ def main():
                max_dist=1.2 * pts["max_dist"], mf_max_dist=pts["max_dist"], desc=pts["desc"], obs=np.full(n_pts, 2, np.int32))
     row = {k: v[:trk.M] for k, v in row.items()}
     ms_upload = timed(lambda: trk.set_local(0, [row]), lambda: None)     # sd_track_set_local waits for its copies
+    # (c) / (d): the chain into Fuse.  Row 0 starts empty each time (the n_local upload of an empty row); cand of all B rows.
+    M = trk.M
+    zero = dict(cand=np.zeros(0, np.uint8), Xw=np.zeros((0, 3)), normal=np.zeros((0, 3)), min_dist=np.zeros(0, np.float32),
+                max_dist=np.zeros(0, np.float32), mf_max_dist=np.zeros(0, np.float32), desc=np.zeros((0, 32), np.uint8),
+                obs=np.zeros(0, np.int32))
+
+    def chain_device():
+        trk.set_local(0, [zero])
+        device()
+        trk.append_new_points(0, B, False)
+        trk.fuse(B, kf_side=1, point_row=0, th=3.0)
+
+    def chain_host():
+        device()
+        p = trk.get_new_points()
+        n = min(int(p["info"][0]), M)
+        cand = np.ones((B, n), np.uint8)
+        cand[p["slot"][:n], np.arange(n)] = 0
+        shared = dict(Xw=p["Xw"][:n], normal=p["normal"][:n], min_dist=np.float32(0.8) * p["min_dist"][:n],
+                      max_dist=np.float32(1.2) * p["max_dist"][:n], mf_max_dist=p["max_dist"][:n], desc=p["desc"][:n],
+                      obs=np.full(n, 2, np.int32))
+        trk.set_local(0, [dict(shared, cand=cand[f]) for f in range(B)])
+        trk.fuse(B, kf_side=1, point_row=0, th=3.0)
+    get_fuse = lambda: trk.get_fuse(0, B)
+    ms_c = timed(chain_device, get_fuse)
+    fuse_c = get_fuse()
+    ms_d = timed(chain_host, get_fuse)
+    fuse_d = get_fuse()
+    n_app = min(n_pts, M)
+    for k in ("best_idx", "best_dist", "n_found"):
+        assert np.array_equal(fuse_c[k][..., :n_app] if fuse_c[k].ndim == 2 else fuse_c[k], fuse_d[k][..., :n_app] if fuse_d[k].ndim == 2 else fuse_d[k]), k
     trk.set_current_broadcast(-1)
     lower = ms_search_download + ms_upload
     out = dict(bench="new_points", keypoints=int(n1[0]), neighbours=B, matches=int((g["matches12"] >= 0).sum()), new_points=n_pts,
                ms_b_search_triangulate_get_new_points=round(ms_b, 4), ms_a_search_and_download=round(ms_search_download, 4),
                ms_a_upload_set_local=round(ms_upload, 4), ms_a_without_host_triangulation=round(lower, 4),
                ms_host_triangulation_numpy=round(ms_host, 1), host_slots_timed=hs, ms_a_with_numpy=round(lower + ms_host, 1),
-               ratio_b_to_a_lower_bound=round(ms_b / lower, 3), host_triangulation="numpy restatement (tests/new_points_ref.py), extrapolated",
+               ratio_b_to_a_lower_bound=round(ms_b / lower, 3), ms_c_chain_append_fuse_get_fuse=round(ms_c, 4),
+               ms_d_chain_get_new_points_set_local_fuse_get_fuse=round(ms_d, 4), ratio_c_to_d=round(ms_c / ms_d, 3),
+               fused_found=int(fuse_c["n_found"].sum()), host_triangulation="numpy restatement (tests/new_points_ref.py), extrapolated",
                method="20 warm-up calls, batches of 20 synchronised calls for >= 1 s, host wall clock", lib=os.path.basename(sd.lib_path()))
     line = json.dumps(out)
     print(line)
