@@ -202,18 +202,18 @@ class MLoop(SQ.Loop):
         pr = [O[0].level(l) for l in range(NL)]
         mono = not self.rgbd
         kw = dict(u_right=u_right, mbf=self.bf, mb=mb) if not mono else {}
-        r = oracle.track_with_motion_model(pc, pr, tab, ck, cd, SQ.BOUNDS, Kc, self.o_T[b], T_pred, last, th_mm, mono=mono, align_mode=0, **kw)
+        r = oracle.track_with_motion_model(pc, pr, tab, ck, cd, self.bounds, Kc, self.o_T[b], T_pred, last, th_mm, mono=mono, align_mode=0, **kw)
         seen = r["match"]
         if r["status"] != 0:
             retried = bool(r["retried"])
             T_s = T_pred if retried or not r["align"]["ok"] else r["align"]["T"]
-            _, seen = oracle.search_by_projection(ck, cd, tab["sf"], SQ.BOUNDS, Kc, T_s, self.o_T[b], last, th=2 * th_mm if retried else th_mm,
+            _, seen = oracle.search_by_projection(ck, cd, tab["sf"], self.bounds, Kc, T_s, self.o_T[b], last, th=2 * th_mm if retried else th_mm,
                                                   mono=mono, check_ori=True, **kw)
             assert np.array_equal(np.where(r["match"] >= 0, seen, -1), r["match"])
         seen_ids = set(self.o_ids[b][seen[seen >= 0]].tolist()) - {-1}
         local = dict(self.local[b])
         local["cand"] = np.array([0 if i in seen_ids else 1 for i in self.lids[b]], np.uint8)
-        rl = oracle.track_local_map(ck, cd, tab, np.log(np.float32(self.cfg[1])), SQ.BOUNDS, Kc, r["T"], r["match"], last, local, th=th_lm,
+        rl = oracle.track_local_map(ck, cd, tab, np.log(np.float32(self.cfg[1])), self.bounds, Kc, r["T"], r["match"], last, local, th=th_lm,
                                     min_inliers=30, u_right=u_right, mbf=self.bf)
         un = np.where(rl["local_match"] >= 0, rl["local_match"] + M, rl["frame_match"])
         N = len(ck)

@@ -77,16 +77,18 @@ def check_last(got, f, want, N, what):
 
 
 class Loop:
-    """B streams of one sequence seed each: device tracker and the oracle's restatement of the same loop."""
+    """B streams of one sequence seed each: device tracker and the oracle's restatement of the same loop.  w x h: the frame size
+    (synth's camera K behind bounds (0, w, 0, h))."""
 
-    def __init__(self, sd, oracle, cfg, seeds, T, rgbd=False):
+    def __init__(self, sd, oracle, cfg, seeds, T, rgbd=False, w=640, h=480):
         self.cfg, self.B, self.T, self.rgbd = cfg, len(seeds), T, rgbd
-        self.seqs = [synth.make_sequence(s, T, with_depth=rgbd) for s in seeds]
+        self.bounds = (0.0, float(w), 0.0, float(h))
+        self.seqs = [synth.make_sequence(s, T, w=w, h=h, with_depth=rgbd) for s in seeds]
         self.views = np.stack([s["views"] for s in self.seqs], 1)          # [T][B][H][W]
-        self.ext = [sd.ORBextractor(*cfg, 640, 480, self.B) for _ in range(2)]
+        self.ext = [sd.ORBextractor(*cfg, w, h, self.B) for _ in range(2)]
         self.trk = sd.Tracker(self.ext[0], self.ext[1], max_points=M, max_batch=self.B, pnp_max_iterations=100)
         self.bf = 4.0 if rgbd else 0.0
-        self.trk.set_camera(*K, self.bf, BOUNDS)
+        self.trk.set_camera(*K, self.bf, self.bounds)
         rk, rd, rn = self.trk.ref.extract_batch(self.views[0])
         self.local, self.lids, lasts, self.o_last, self.o_ids = [], [], [], [], []
         self.o_ext = []
@@ -140,19 +142,19 @@ class Loop:
         T_pred = prior_product(self.vel(t)[b], self.o_T[b])
         mono = not self.rgbd
         kw = dict(u_right=u_right, mbf=self.bf, mb=mb) if not mono else {}
-        r = oracle.track_with_motion_model(pc, pr, tab, ck, cd, BOUNDS, K, self.o_T[b], T_pred, last, th_mm, mono=mono, align_mode=0, **kw)
+        r = oracle.track_with_motion_model(pc, pr, tab, ck, cd, self.bounds, K, self.o_T[b], T_pred, last, th_mm, mono=mono, align_mode=0, **kw)
         seen = r["match"]
         if r["status"] != 0:                                                   # the final search again: its matches before the discard
             retried = bool(r["retried"])
             T_s = T_pred if retried or not r["align"]["ok"] else r["align"]["T"]
             kws = dict(u_right=u_right, mbf=self.bf, mb=mb) if not mono else {}
-            _, seen = oracle.search_by_projection(ck, cd, tab["sf"], BOUNDS, K, T_s, self.o_T[b], last, th=2 * th_mm if retried else th_mm,
+            _, seen = oracle.search_by_projection(ck, cd, tab["sf"], self.bounds, K, T_s, self.o_T[b], last, th=2 * th_mm if retried else th_mm,
                                                   mono=mono, check_ori=True, **kws)
             assert np.array_equal(np.where(r["match"] >= 0, seen, -1), r["match"])
         seen_ids = set(self.o_ids[b][seen[seen >= 0]].tolist()) - {-1}
         local = dict(self.local[b])
         local["cand"] = np.array([0 if i in seen_ids else 1 for i in self.lids[b]], np.uint8)
-        rl = oracle.track_local_map(ck, cd, tab, np.log(np.float32(self.cfg[1])), BOUNDS, K, r["T"], r["match"], last, local, th=th_lm,
+        rl = oracle.track_local_map(ck, cd, tab, np.log(np.float32(self.cfg[1])), self.bounds, K, r["T"], r["match"], last, local, th=th_lm,
                                     min_inliers=30, u_right=u_right, mbf=self.bf)
         un = np.where(rl["local_match"] >= 0, rl["local_match"] + M, rl["frame_match"])
         N = len(ck)
