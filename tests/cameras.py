@@ -253,14 +253,14 @@ def mutations(cam):
     return out
 
 
-# ---- the cases of the sweep ----------------------------------------------------------------------------------------
+# ---- the cases of the sweep (SEEDS ... BF are every sweep's: sweep_rig and world_frames take them from here) ------------------
 CFG = (1000, 1.2, 8, 20)                           # the P8 pyramid
 MP = 1300                                          # the tracker's max_points: 1000 keypoints' points + 300 extra local points
 N_EXTRA = 300
 SEEDS = (20, 21)
 MOTIONS = [((0.02, -0.01, 0.015), (0.4, -0.3, 0.5)), ((-0.03, 0.02, -0.01), (-0.6, 0.2, 0.3))]
 START = se3_exp((0.003, -0.002, 0.001), (0.05, 0.02, -0.04))      # e2e_cases.prior: the perturbed start is START @ T_cur
-POSE_BOUND = 5e-3                                  # world_frames.POSE_BOUND
+POSE_BOUND = 5e-3                                  # tests/test_pnp_ransac.py's "converges to the truth" bound
 BF = 40.0
 
 
@@ -274,70 +274,11 @@ def undistorted(O, kps, cam):
     return out
 
 
-_RIGS = {}
-
-
 def oracle_rig(O, name):
     """The two VGA scenes through camera `name` with the oracle's extraction, undistorted keypoints, pyramids and tables, and the
-    last-frame and local-map cases built from the undistorted keypoints."""
-    if name in _RIGS:
-        return _RIGS[name]
-    cam = CAMERAS[name]
-    scenes = [make_scene(s, cam, *m) for s, m in zip(SEEDS, MOTIONS)]
-    fr = []
-    for i, s in enumerate(scenes):
-        oc, orf = O.OrbOracle(*CFG), O.OrbOracle(*CFG)
-        ck, cd = oc.extract(s["cur"])
-        rk, rd = orf.extract(s["ref"])
-        cku, rku = undistorted(O, ck, cam), undistorted(O, rk, cam)
-        last = tracking_case(i, rku, rd, cam, max_points=CFG[0])
-        local = local_map_case(100 + i, cku, cd, s["T_cur"], cam, n_extra=N_EXTRA)
-        fr.append(dict(ck_raw=ck, ck=cku, cd=cd, rk_raw=rk, rk=rku, rd=rd, tab=oc.tables(), last=last, local=local,
-                       pc=[oc.level(l) for l in range(CFG[2])], pr=[orf.level(l) for l in range(CFG[2])]))
-    _RIGS[name] = dict(cam=cam, scenes=scenes, fr=fr, B=len(scenes))
-    return _RIGS[name]
-
-
-def planted_case(rig, i):
-    """world_frames.planted_case through the rig's camera: (last, cm, truth)."""
-    f = rig["fr"][i]
-    return planted_matches(11 + i, f["ck"], rig["scenes"][i]["T_cur"], rig["cam"], n_match=min(300, len(f["ck"])), outlier_frac=0.3, noise_px=0.5)
-
-
-def planted_uright(rig, i, last, cm, truth, bf=BF):
-    """world_frames.planted_uright on the undistorted keypoints."""
-    ck, T = rig["fr"][i]["ck"], rig["scenes"][i]["T_cur"]
-    zc = (last["Xw"] @ T[:3, :3].T + T[:3, 3])[:, 2]
-    zc = np.where(truth, zc, 3.0)
-    return np.where((np.arange(len(ck)) % 3 == 0) & (cm >= 0), ck["x"] - bf / zc, -1.0).astype(np.float32)
-
-
-def matched_points(last, cm):
-    Xw = np.zeros((len(cm), 3))
-    Xw[cm >= 0] = last["Xw"][cm[cm >= 0]]
-    return Xw
-
-
-def pnp_case(rig, i, scenario):
-    """pnp_cases.SCENARIOS[scenario] planted through the rig's camera: (last, cm, truth, params, calls)."""
-    import pnp_cases as PC
-    kw, params, calls = PC.SCENARIOS[scenario]
-    f = rig["fr"][i]
-    last, cm, truth = planted_matches(7 + i, f["ck"], rig["scenes"][i]["T_cur"], rig["cam"], **dict(kw, n_match=min(kw["n_match"], len(f["ck"]))))
-    return last, cm, truth, params, calls
-
-
-def run_pnp_oracle(O, kps, sigma2, last, cm, K, params, calls, rs):
-    """pnp_cases.run_oracle with the camera as an argument."""
-    valid = (cm >= 0).astype(np.uint8)
-    p = O.PnPOracle(valid, np.stack([kps["x"], kps["y"]], 1), kps["octave"], sigma2, matched_points(last, cm), K)
-    p.set_ransac(*params)
-    out, consumed = [], 0
-    for n in calls:
-        r = p.iterate(n, rs[consumed:])
-        consumed = params[3] * r["iterations"]
-        out.append(r)
-    return out, p.params()
+    last-frame and local-map cases built from the undistorted keypoints (sweep_rig.oracle_rig with this sweep's parameters)."""
+    import sweep_rig as SR      # (it imports this module for the builders above)
+    return SR.oracle_rig(O, ("cameras", name), CAMERAS[name], W, H, CFG, MP, n_extra=N_EXTRA)
 
 
 def area_queries(cam):

@@ -34,6 +34,7 @@ from collections import namedtuple
 import numpy as np
 
 import cameras as CM
+import sweep_rig as SR
 from sdslam_amd.synth import intersect_surface
 
 Geometry = namedtuple("Geometry", "name w h cfg cam")
@@ -159,40 +160,28 @@ DEPTH_CALLS = [("f32", 0, 1.0, False), ("f32", 0, 2.0, True), ("u16", 1, DEPTH_F
 
 
 # ---- the cases of the sweep ------------------------------------------------------------------------------------------------
-_RIGS = {}
+def _plant_and_add_depth(O, rig):
+    """On top of sweep_rig.oracle_rig: the level shapes, the planted points behind the last frame's 300 - 12 keypoint points,
+    mode 3's own last frame, the padded aligned levels and the depth maps of the current views."""
+    geo, cam = GEOMETRIES[rig["cam"].name], rig["cam"]
+    for i, f in enumerate(rig["fr"]):
+        shapes = [a.shape for a in f["pr"]]
+        Xp, claims = planted_points(geo, f["tab"]["inv_sf"], shapes)
+        Xp3, claims3 = planted_points(geo, {4: kf_scale(f["tab"]["sf"])}, shapes, levels=(4,))
+        last3 = with_planted(CM.tracking_case(i, f["rk"], f["rd"], cam, max_points=N_ALIGNED_KF - len(Xp3)), Xp3)
+        f.update(last=with_planted(f["last"], Xp), shapes=shapes, Xp=Xp, claims=claims, last3=last3, Xp3=Xp3, claims3=claims3,
+                 pc_pad=[f["oc"].level(l, padded=True) for l in ALIGNED_LEVELS], pr_pad=[f["orf"].level(l, padded=True) for l in ALIGNED_LEVELS])
+    depth = np.stack([surface_depth(s["T_cur"], geo) for s in rig["scenes"]])
+    depth[:, :, ::7] = 0.0                                              # holes: keypoints without depth
+    raw = np.round(depth.astype(np.float64) * DEPTH_FACTOR).astype(np.uint16)
+    rig.update(geo=geo, depth_f32=depth, depth_u16=raw, buf_f32=strided(depth, POISON_F32), buf_u16=strided(raw, POISON_U16))
 
 
 def oracle_rig(O, name):
     """The two scenes of geometry `name` with the oracle's extraction, pyramids and tables, the last frame with its planted
-    points, the local map and the depth maps of the current views."""
-    if name in _RIGS:
-        return _RIGS[name]
+    points, the local map (filling max_points) and the depth maps of the current views."""
     geo = GEOMETRIES[name]
-    cam, cfg = geo.cam, geo.cfg
-    scenes = [CM.make_scene(s, cam, *m, w=geo.w, h=geo.h) for s, m in zip(CM.SEEDS, CM.MOTIONS)]
-    fr = []
-    for i, s in enumerate(scenes):
-        oc, orf = O.OrbOracle(*cfg), O.OrbOracle(*cfg)
-        ck, cd = oc.extract(s["cur"])
-        rk, rd = orf.extract(s["ref"])
-        tab = oc.tables()
-        pc, pr = [oc.level(l) for l in range(cfg[2])], [orf.level(l) for l in range(cfg[2])]
-        shapes = [a.shape for a in pr]
-        Xp, claims = planted_points(geo, tab["inv_sf"], shapes)
-        plain = CM.tracking_case(i, rk, rd, cam, max_points=N_ALIGNED - N_PLANTED)
-        last = with_planted(plain, Xp)
-        Xp3, claims3 = planted_points(geo, {4: kf_scale(tab["sf"])}, shapes, levels=(4,))
-        last3 = with_planted(CM.tracking_case(i, rk, rd, cam, max_points=N_ALIGNED_KF - len(Xp3)), Xp3)
-        local = CM.local_map_case(100 + i, ck, cd, s["T_cur"], cam, n_extra=MP - len(ck), scale_factor=cfg[1], nlevels=cfg[2])
-        fr.append(dict(ck=ck, cd=cd, rk=rk, rd=rd, tab=tab, last=last, local=local, pc=pc, pr=pr, shapes=shapes, Xp=Xp, claims=claims,
-                       last3=last3, Xp3=Xp3, claims3=claims3,
-                       pc_pad=[oc.level(l, padded=True) for l in ALIGNED_LEVELS], pr_pad=[orf.level(l, padded=True) for l in ALIGNED_LEVELS]))
-    depth = np.stack([surface_depth(s["T_cur"], geo) for s in scenes])
-    depth[:, :, ::7] = 0.0                                              # holes: keypoints without depth
-    raw = np.round(depth.astype(np.float64) * DEPTH_FACTOR).astype(np.uint16)
-    _RIGS[name] = dict(geo=geo, cam=cam, scenes=scenes, fr=fr, B=len(scenes), depth_f32=depth, depth_u16=raw,
-                       buf_f32=strided(depth, POISON_F32), buf_u16=strided(raw, POISON_U16))
-    return _RIGS[name]
+    return SR.oracle_rig(O, ("geometries", name), geo.cam, geo.w, geo.h, geo.cfg, MP, n_last=N_ALIGNED - N_PLANTED, extend=_plant_and_add_depth)
 
 
 def align_points(last):

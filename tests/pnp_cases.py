@@ -13,12 +13,15 @@ K = (synth.FX, synth.FY, synth.CX, synth.CY)
 planted = synth.planted_matches
 
 
-def oracle_solver(O, kps, sigma2, last, cm):
-    n = len(kps)
-    valid = (cm >= 0).astype(np.uint8)
-    Xw = np.zeros((n, 3))
-    Xw[valid != 0] = last["Xw"][cm[valid != 0]]
-    return O.PnPOracle(valid, np.stack([kps["x"], kps["y"]], 1), kps["octave"], sigma2, Xw, K)
+def matched_points(last, cm):
+    """The world point behind every keypoint's match (zeros where it has none)."""
+    Xw = np.zeros((len(cm), 3))
+    Xw[cm >= 0] = last["Xw"][cm[cm >= 0]]
+    return Xw
+
+
+def oracle_solver(O, kps, sigma2, last, cm, K=K):
+    return O.PnPOracle((cm >= 0).astype(np.uint8), np.stack([kps["x"], kps["y"]], 1), kps["octave"], sigma2, matched_points(last, cm), K)
 
 
 # name -> (planted kwargs, SetRansacParameters args (prob, minInliers, maxIts, minSet, eps, th2), iterate() call sequence)
@@ -53,9 +56,10 @@ def rand_needed(params, calls):
     return params[3] * upper
 
 
-def run_oracle(O, kps, sigma2, last, cm, params, calls, rs):
-    """The oracle's solver through the call sequence; returns the list of iterate() results (+ solver parameters)."""
-    p = oracle_solver(O, kps, sigma2, last, cm)
+def run_oracle(O, kps, sigma2, last, cm, params, calls, rs, K=K):
+    """The oracle's solver (for camera K, synth's by default) through the call sequence; returns the list of iterate() results
+    (+ solver parameters)."""
+    p = oracle_solver(O, kps, sigma2, last, cm, K)
     p.set_ransac(*params)
     out, consumed = [], 0
     for n in calls:

@@ -8,6 +8,7 @@ import pytest
 
 import cameras as CM
 import pnp_cases as PC
+import sweep_rig as SR
 import world_frames as WF
 from sdslam_amd import synth
 
@@ -65,15 +66,15 @@ def _area(O, rig, i, cam, kps):
 
 def _pose_opt(O, rig, i, cam, kps):
     f, s = rig["fr"][i], rig["scenes"][i]
-    last, cm, truth = CM.planted_case(rig, i)
-    return O.pose_optimization(kps, cm >= 0, CM.matched_points(last, cm), f["tab"]["inv_sigma2"], cam.K, CM.START @ s["T_cur"]), cm, truth
+    last, cm, truth = SR.planted_case(rig, i)
+    return O.pose_optimization(kps, cm >= 0, SR.matched_points(last, cm), f["tab"]["inv_sigma2"], cam.K, CM.START @ s["T_cur"]), cm, truth
 
 
 def _pnp(O, rig, i, cam, kps):
     f = rig["fr"][i]
-    last, cm, truth, params, calls = CM.pnp_case(rig, i, "out30_c4")
+    last, cm, truth, params, calls = SR.pnp_case(rig, i, "out30_c4")
     rs = synth.glibc_rand_stream(PC.rand_needed(params, calls))
-    return CM.run_pnp_oracle(O, kps, f["tab"]["sigma2"], last, cm, cam.K, params, calls, rs)[0], truth
+    return PC.run_oracle(O, kps, f["tab"]["sigma2"], last, cm, params, calls, rs, K=cam.K)[0], truth
 
 
 def _track(O, rig, i, cam, kps):

@@ -10,10 +10,12 @@ import pytest
 
 import cameras as CM
 import geometries as G
+import stage_parity as SP
+import sweep_rig as SR
 from sdslam_amd import synth
 
 pytestmark = pytest.mark.gpu
-POSE_TOL = 1e-5
+POSE_TOL = SP.POSE_TOL
 MP = G.MP
 
 
@@ -21,61 +23,27 @@ MP = G.MP
 def rigs(oracle):
     """name -> rig, built on first use: the oracle's rig of the geometry, two extractors of its frame size holding the two
     scenes, and a tracker.  The oracle's keypoints, descriptors and padded levels 2-4 equal the device's, asserted once."""
-    import sdslam_amd as sd
-    if sd.device_count() < 1:
-        pytest.fail("no HIP device: the gpu-marked tests need a real MI355X")
+    SR.device()
     built = {}
 
     def get(name):
         if name in built:
-            return built[name]
-        r = dict(G.oracle_rig(oracle, name))
-        geo, B, scenes, fr = r["geo"], r["B"], r["scenes"], r["fr"]
-        cur, ref = sd.ORBextractor(*geo.cfg, geo.w, geo.h, B), sd.ORBextractor(*geo.cfg, geo.w, geo.h, B)
-        ck, cd, cn = cur.extract_batch(np.stack([s["cur"] for s in scenes]))
-        rk, rd, rn = ref.extract_batch(np.stack([s["ref"] for s in scenes]))
-        for i in range(B):
-            assert np.array_equal(fr[i]["ck"], ck[i, :cn[i]]) and np.array_equal(fr[i]["cd"], cd[i, :cn[i]]), (name, i)
-            assert np.array_equal(fr[i]["rk"], rk[i, :rn[i]]) and np.array_equal(fr[i]["rd"], rd[i, :rn[i]]), (name, i)
+            return built[name][0]
+        r, close = built[name] = SR.device_rig(G.oracle_rig(oracle, name), pnp_max_iterations=100)
+        (cur, ref), fr = r["ext"], r["fr"]
+        for i in range(r["B"]):
             for k, l in enumerate(G.ALIGNED_LEVELS):
                 assert cur.level_size(l) == fr[i]["shapes"][l][::-1], (name, l)
                 assert np.array_equal(cur.level(l, i, padded=True), fr[i]["pc_pad"][k]), (name, i, l, "cur")
                 assert np.array_equal(ref.level(l, i, padded=True), fr[i]["pr_pad"][k]), (name, i, l, "ref")
-        trk = sd.Tracker(cur, ref, max_points=MP, max_batch=B, pnp_max_iterations=100)
-        r.update(sd=sd, trk=trk, ext=(cur, ref), cap=ck.shape[1], bufs={})
-        _restore(r)
-        built[name] = r
+        r["bufs"] = {}
         return r
 
     yield get
-    for r in built.values():
+    for r, close in built.values():
         for b in r["bufs"].values():
             b.free()
-        r["trk"].close()
-        for e in r["ext"]:
-            e.close()
-
-
-def _restore(rig):
-    """Camera, last frames, local maps, right coordinates and poses as the fixture leaves them."""
-    trk, B, cam, geo = rig["trk"], rig["B"], rig["cam"], rig["geo"]
-    trk.set_camera(*cam.K, 0.0, cam.bounds)
-    trk.stereo_from_depth(np.zeros((B, geo.h, geo.w), np.float32))      # resets every mvuRight to -1
-    trk.set_last(0, [f["last"] for f in rig["fr"]])
-    trk.set_local(0, [f["local"] for f in rig["fr"]])
-    trk.set_poses(0, _refs(rig), [s["T_cur"] for s in rig["scenes"]])
-
-
-def _refs(rig):
-    return [s["T_ref"] for s in rig["scenes"]]
-
-
-def _starts(rig):
-    return [CM.START @ s["T_cur"] for s in rig["scenes"]]
-
-
-def _log_sf(rig):
-    return np.log(np.float32(rig["geo"].cfg[1]))
+        close()
 
 
 def _depth_buffer(rig, tag):
@@ -102,102 +70,26 @@ def test_image_align(oracle, rigs, name):
     and in mode 3 (keyframe against keyframe: level 4 alone, the first 100 valid points, scale (float)(1 / sf[4])) on the last
     frame built for it, whose 100 points end with the four level-4 points planted for that scale: ok and per-level iterations
     equal, error to a relative 1e-7, pose within 1e-5; in mode 3 the pose is untouched."""
-    rig = rigs(name)
-    trk, B, fr, cam = rig["trk"], rig["B"], rig["fr"], rig["cam"]
-    worst, worst_e = 0.0, 0.0
-    try:
-        for mode in (0, 1, 3):
-            which = "last3" if mode == 3 else "last"
-            trk.set_last(0, [f[which] for f in fr])
-            trk.set_poses(0, _refs(rig), _starts(rig))
-            trk.align(B, mode=mode)
-            g = trk.get_align(0, B)
-            for i in range(B):
-                key = (name, mode, i)
-                r = oracle.align(fr[i]["pc"], fr[i]["pr"], fr[i]["tab"]["inv_sf"], fr[i]["tab"]["sf"], G.align_points(fr[i][which]),
-                                 rig["scenes"][i]["T_ref"], _starts(rig)[i], cam.K, mode=mode)
-                assert g["ok"][i] == r["ok"] and r["ok"], key
-                assert np.array_equal(g["iters"][i][:len(r["iters"])], r["iters"]), (key, g["iters"][i][:len(r["iters"])], r["iters"])
-                if mode != 3:
-                    d = np.abs(g["T"][i] - r["T"]).max()
-                    worst = max(worst, d)
-                    assert d <= POSE_TOL, (key, d)
-                else:
-                    assert np.abs(g["T"][i] - _starts(rig)[i]).max() == 0      # pose untouched
-                e = abs(g["error"][i] - r["error"]) / max(1.0, abs(r["error"]))
-                worst_e = max(worst_e, e)
-                assert e <= 1e-7, (key, e)
-        print(f"align {name}: largest device-oracle pose difference {worst:.3e}, relative error difference {worst_e:.3e}")
-    finally:
-        _restore(rig)
+    res = SP.image_align(oracle, rigs(name), name, modes=[(0, "last"), (1, "last"), (3, "last3")])
+    print(f"align {name}: largest device-oracle pose difference {res['worst']:.3e}, relative error difference {res['worst_error']:.3e}")
 
 
-def _planted_cur_uright(rig, i, bf):
-    """mvuRight for every third current keypoint from the depth of the surface point it sees; -1 for the others."""
-    f, T, cam = rig["fr"][i], rig["scenes"][i]["T_cur"], rig["cam"]
-    Xw = CM.keyframe_case(f["ck"], f["cd"], T, cam)["Xw"]
-    zc = (Xw @ T[:3, :3].T + T[:3, 3])[:, 2]
-    return np.where(np.arange(len(zc)) % 3 == 0, f["ck"]["x"] - bf / zc, -1.0).astype(np.float32)
+RUNS = [(mono, th, None) for mono in (True, False) for th in (8.0, 1.0)]        # (mono, th, no match_split option)
 
 
 @pytest.mark.parametrize("name", G.NAMES)
 def test_search_by_projection(oracle, rigs, name):
     """SearchByProjection(Frame, Frame), mono and with planted uRight and bf = 40, th = 8 and th = 1: the match vector and the
     count equal the oracle's."""
-    rig = rigs(name)
-    trk, B, fr, cam = rig["trk"], rig["B"], rig["fr"], rig["cam"]
-    bf = G.BF
-    mb = np.float32(bf) / np.float32(cam.K[0])
-    T_cur = [s["T_cur"] for s in rig["scenes"]]
-    total = 0
-    try:
-        for mono in (True, False):
-            urs = [None] * B
-            if not mono:
-                ur = np.full((B, rig["cap"]), -1, np.float32)
-                for i in range(B):
-                    urs[i] = _planted_cur_uright(rig, i, bf)
-                    ur[i, :len(urs[i])] = urs[i]
-                trk.set_camera(*cam.K, bf, cam.bounds)
-                trk.set_uright(0, ur)
-            for th in (8.0, 1.0):
-                trk.set_poses(0, _refs(rig), T_cur)
-                trk.match(B, th=th, mono=mono, check_ori=True)
-                cm, nm = trk.get_matches(0, B)
-                for i in range(B):
-                    kw = {} if mono else dict(u_right=urs[i], mbf=bf, mb=mb)
-                    n, ocm = oracle.search_by_projection(fr[i]["ck"], fr[i]["cd"], fr[i]["tab"]["sf"], cam.bounds, cam.K, T_cur[i],
-                                                         rig["scenes"][i]["T_ref"], fr[i]["last"], th=th, mono=mono, check_ori=True, **kw)
-                    assert nm[i] == n, (name, mono, th, i, nm[i], n)
-                    assert np.array_equal(cm[i, :len(ocm)], ocm) and (cm[i, len(ocm):] == -1).all(), (name, mono, th, i)
-                    assert n >= (60 if th == 8.0 else 10), (name, mono, th, i, n)
-                    total += n
-        print(f"search_by_projection {name}: {total} matches identical, largest device-oracle difference 0")
-    finally:
-        _restore(rig)
+    res = SP.search_by_projection(oracle, rigs(name), name, RUNS, {8.0: 60, 1.0: 10})
+    print(f"search_by_projection {name}: {res['total']} matches identical, largest device-oracle difference 0")
 
 
 @pytest.mark.parametrize("name", G.NAMES)
 def test_local_map_search(oracle, rigs, name):
     """isInFrustum, PredictScale (the 1.5 pyramid's levels in small15) and the search: every output equals the oracle's."""
-    rig = rigs(name)
-    trk, B, fr, cam = rig["trk"], rig["B"], rig["fr"], rig["cam"]
-    try:
-        trk.match_local(B, th=1.0, nnratio=0.8)
-        g = trk.get_local(0, B)
-        for i in range(B):
-            n, M = len(fr[i]["ck"]), len(fr[i]["local"]["cand"])
-            r = oracle.search_local_points(fr[i]["ck"], fr[i]["cd"], fr[i]["tab"]["sf"], _log_sf(rig), cam.bounds, cam.K, 0.0, rig["scenes"][i]["T_cur"],
-                                           fr[i]["local"], th=1.0, nnratio=0.8)
-            assert np.array_equal(g["in_view"][i, :M], r["in_view"]), (name, i)
-            assert np.array_equal(g["proj"][i, :M], r["proj"]) and np.array_equal(g["level"][i, :M], r["level"]), (name, i)
-            assert np.array_equal(g["cos"][i, :M], r["cos"]), (name, i)
-            assert g["n"][i] == r["n"], (name, i, g["n"][i], r["n"])
-            assert np.array_equal(g["match"][i, :n], r["match"]) and (g["match"][i, n:] == -1).all(), (name, i)
-            assert r["n"] >= 60, (name, i, r["n"])
-        print(f"match_local {name}: every output identical, largest device-oracle difference 0")
-    finally:
-        _restore(rig)
+    SP.local_map_search(oracle, rigs(name), name, 60, some_out_of_view=False)
+    print(f"match_local {name}: every output identical, largest device-oracle difference 0")
 
 
 @pytest.mark.parametrize("name", G.NAMES)
@@ -207,18 +99,12 @@ def test_features_in_area_and_grid(oracle, rigs, name):
     grid occupancy [64][48] equals Frame::AssignFeaturesToGrid's."""
     rig = rigs(name)
     trk, fr, cam, geo = rig["trk"], rig["fr"], rig["cam"], rig["geo"]
-    total = 0
     for i in range(rig["B"]):
         _, grid = trk.features_in_area(i, 0.5 * geo.w, 0.5 * geo.h, 10.0, want_grid=True)
         want_grid = G.grid_occupancy(fr[i]["ck"], cam.bounds)
         assert np.array_equal(grid, want_grid), (name, i, np.argwhere(grid != want_grid)[:8])
         assert grid.sum() == len(fr[i]["ck"])
-        for q in G.area_queries(geo):
-            got = trk.features_in_area(i, *q)
-            want = oracle.features_in_area(fr[i]["ck"], cam.bounds, *q)
-            assert np.array_equal(got, want), (name, i, q, got, want)
-            total += len(want)
-    assert total > 100, (name, total)
+    total = SP.features_in_area(oracle, rig, name, G.area_queries(geo))
     print(f"features_in_area {name}: {total} indices and the grid occupancy identical, largest device-oracle difference 0")
 
 
@@ -244,90 +130,15 @@ def test_stereo_from_depth_device(rigs, name):
                 assert not (dd[i] == poison).any() and (wd > 0).sum() >= 100 and (wd < 0).sum() >= 10, (name, which, i)
         print(f"stereo_from_depth_device {name}: 4 calls x {B} frames bit-exact, largest device-restatement difference 0")
     finally:
-        _restore(rig)
-
-
-def _track_pair(oracle, rig, mono, th_lm):
-    """TrackWithMotionModel then TrackLocalMap on the device against the oracle's composition; RGB-D (mono False) takes mvuRight
-    from the 16-bit strided maps in device memory and ends with close_points.  Returns the largest pose difference."""
-    trk, B, fr, cam, name = rig["trk"], rig["B"], rig["fr"], rig["cam"], rig["geo"].name
-    lasts = [dict(f["last"]) for f in fr]
-    for i, l in enumerate(lasts):       # a third of the last frame's points are not in the map yet
-        l["obs"] = (np.arange(len(l["obs"])) % 3 != i % 3).astype(np.int32)
-    locals_ = [f["local"] for f in fr]
-    T_ref, T0 = _refs(rig), _starts(rig)
-    bf = 0.0 if mono else G.BF
-    mb = np.float32(bf) / np.float32(cam.K[0])
-    worst = 0.0
-    trk.set_camera(*cam.K, bf, cam.bounds)
-    ur = dd = None
-    if not mono:
-        ur, dd = _stereo_device(rig, G.DEPTH_CALLS[2])
-    trk.set_last(0, lasts)
-    trk.set_poses(0, T_ref, T0)
-    trk.align(B, 0)             # the device's aligned poses: the matcher is compared on these
-    T_al = trk.get_align(0, B)["T"]
-    trk.set_poses(0, T_ref, T0)
-    trk.track_with_motion_model(B, th=8.0, mono=mono, align_mode=0)
-    tw, gp, (fm, nm), ga = trk.get_tracked(0, B), trk.get_pose_opt(0, B), trk.get_matches(0, B), trk.get_align(0, B)
-    T_mm = gp["T"]
-    for i in range(B):
-        n, key = len(fr[i]["ck"]), (name, mono, "motion model", i)
-        kw = {} if mono else dict(u_right=ur[i, :n], mbf=bf, mb=mb)
-        r = oracle.track_with_motion_model(fr[i]["pc"], fr[i]["pr"], fr[i]["tab"], fr[i]["ck"], fr[i]["cd"], cam.bounds, cam.K, T_ref[i], T0[i],
-                                           lasts[i], 8.0, mono=mono, align_mode=0, T_aligned=T_al[i], **kw)
-        assert (tw["status"][i], tw["retried"][i], tw["nmatches"][i], tw["nmatches_map"][i]) == \
-            (r["status"], r["retried"], r["nmatches"], r["nmatches_map"]), key
-        assert np.array_equal(fm[i, :n], r["match"]) and (fm[i, n:] == -1).all(), key
-        d = np.abs(gp["T"][i] - r["T"]).max()
-        worst = max(worst, d)
-        assert d <= POSE_TOL, (key, d)
-        assert np.abs(ga["T"][i] - r["T"]).max() <= POSE_TOL and not gp["outlier"][i].any(), key
-        assert r["status"] == 2, key
-    trk.track_local_map(B, th=th_lm, min_inliers=30)
-    g, gp, gl = trk.get_local_map(0, B), trk.get_pose_opt(0, B), trk.get_local(0, B)
-    for i in range(B):
-        n, key = len(fr[i]["ck"]), (name, mono, "local map", i)
-        kw = {} if mono else dict(u_right=ur[i, :n], mbf=bf)
-        r = oracle.track_local_map(fr[i]["ck"], fr[i]["cd"], fr[i]["tab"], _log_sf(rig), cam.bounds, cam.K, T_mm[i], fm[i, :n], lasts[i], locals_[i],
-                                   th=th_lm, min_inliers=30, **kw)
-        assert np.array_equal(gl["match"][i, :n], r["local_match"]), key
-        want = np.where(r["local_match"] >= 0, r["local_match"] + MP, r["frame_match"])
-        assert np.array_equal(g["match"][i, :n], want) and (g["match"][i, n:] == -1).all(), key
-        assert g["n_points"][i] == r["n_points"] and g["n_local"][i] == r["n_local"], key
-        assert np.array_equal(gp["outlier"][i, :n], r["outlier"]), key
-        assert g["n_inliers"][i] == r["n_inliers"] and g["status"][i] == r["status"], (key, g["n_inliers"][i], r["n_inliers"])
-        d = np.abs(gp["T"][i] - r["T"]).max()
-        worst = max(worst, d)
-        assert d <= POSE_TOL, (key, d)
-        assert r["n_inliers"] >= 30 and r["status"] == 2, key
-    if not mono:
-        # Tracking::NeedNewKeyFrame's close-point counts on the sampled depths: th_depth is one keypoint's depth exactly
-        pos = np.sort(dd[0, :len(fr[0]["ck"])][dd[0, :len(fr[0]["ck"])] > 0])
-        th = pos[len(pos) // 2]
-        trk.close_points(B, 1, th)
-        got = trk.get_close_points(0, B)
-        for i in range(B):
-            n = len(fr[i]["ck"])
-            d, m, ol = dd[i, :n], g["match"][i, :n], gp["outlier"][i, :n].astype(bool)
-            obs = np.where(m >= MP, locals_[i]["obs"][np.clip(m - MP, 0, len(locals_[i]["obs"]) - 1)], lasts[i]["obs"][np.clip(m, 0, len(lasts[i]["obs"]) - 1)])
-            kept = (m >= 0) & (obs >= 1) & ~ol
-            close = (d > 0) & (d < th)
-            assert (got["tracked"][i], got["non_tracked"][i]) == ((close & kept).sum(), (close & ~kept).sum()), (name, "close points", i)
-            assert got["tracked"][i] > 0 and got["non_tracked"][i] > 0, (name, "close points", i)
-    return worst
+        SR.restore(rig)
 
 
 @pytest.mark.parametrize("name", G.NAMES)
 def test_motion_model_then_local_map(oracle, rigs, name):
     """TrackWithMotionModel and TrackLocalMap chained on the device, monocular: status, counts, the retried flag, match vectors and
     outlier flags identical, poses within 1e-5."""
-    rig = rigs(name)
-    try:
-        worst = _track_pair(oracle, rig, True, 1.0)
-        print(f"track {name}: largest device-oracle pose difference {worst:.3e}")
-    finally:
-        _restore(rig)
+    res = SP.motion_model_then_local_map(oracle, rigs(name), name, ("n_inliers", 30))
+    print(f"track {name}: largest device-oracle pose difference {res['worst']:.3e}")
 
 
 @pytest.mark.parametrize("name", G.NAMES)
@@ -335,11 +146,9 @@ def test_motion_model_then_local_map_rgbd(oracle, rigs, name):
     """The same chain on RGB-D frames whose mvuRight / mvDepth are sampled on the device from the 16-bit strided maps (bf = 40),
     TrackLocalMap at th 3, then close_points on the result against the host restatement of its counts."""
     rig = rigs(name)
-    try:
-        worst = _track_pair(oracle, rig, False, 3.0)
-        print(f"track rgbd {name}: largest device-oracle pose difference {worst:.3e}")
-    finally:
-        _restore(rig)
+    res = SP.motion_model_then_local_map(oracle, rig, name, ("n_inliers", 30), mono=False, th_lm=3.0,
+                                         sample_depth=lambda: _stereo_device(rig, G.DEPTH_CALLS[2]))
+    print(f"track rgbd {name}: largest device-oracle pose difference {res['worst']:.3e}")
 
 
 # ---- wide and portrait only: the keyframe map and the sequential loop ------------------------------------------------------------

@@ -12,7 +12,10 @@ against R X.  The two tie frames are written down entry by entry (0, 1 and -1 on
 that the ties are ties; the asserts at the bottom of the module pin that."""
 import numpy as np
 
+import cameras as CM
+import sweep_rig as SR
 from sdslam_amd import synth
+from sweep_rig import MOTIONS, POSE_BOUND, START, matched_points, planted_case, planted_uright      # noqa: F401  (named WF.* by the tests)
 
 
 def _rot(omega_deg, t=(0.0, 0.0, 0.0)):
@@ -138,48 +141,19 @@ K = (synth.FX, synth.FY, synth.CX, synth.CY)
 CFG = (300, 1.2, 8, 20)
 BOUNDS = (0.0, 640.0, 0.0, 480.0)
 MP = 300                                           # the tracker's max_points
-MOTIONS = [((0.02, -0.01, 0.015), (0.4, -0.3, 0.5)), ((-0.03, 0.02, -0.01), (-0.6, 0.2, 0.3))]
-START = synth.se3_exp((0.003, -0.002, 0.001), (0.05, 0.02, -0.04))      # the perturbed start: START @ T_cur
-POSE_BOUND = 5e-3                                  # tests/test_pnp_ransac.py's "converges to the truth" bound
+
+
+def _cut_to_max_points(O, rig):
+    for f in rig["fr"]:
+        f["last"] = {k: v[:MP] for k, v in f["last"].items()}
+        f["local"] = {k: v[:MP] for k, v in f["local"].items()}
 
 
 def oracle_rig(oracle):
-    """The two VGA scenes of the sweep with the oracle's extraction, pyramids and tables, and the last-frame and
-    local-map cases in the scenes' own frame."""
-    scenes = [synth.make_scene(20 + i, *m) for i, m in enumerate(MOTIONS)]
-    fr = []
-    for i, s in enumerate(scenes):
-        oc, orf = oracle.OrbOracle(*CFG), oracle.OrbOracle(*CFG)
-        ck, cd = oc.extract(s["cur"])
-        rk, rd = orf.extract(s["ref"])
-        last = {k: v[:MP] for k, v in synth.tracking_case(i, rk, rd, max_points=MP).items()}
-        local = {k: v[:MP] for k, v in synth.local_map_case(100 + i, ck, cd, s["T_cur"], n_extra=30).items()}
-        fr.append(dict(ck=ck, cd=cd, rk=rk, rd=rd, tab=oc.tables(), last=last, local=local, pc=[oc.level(l) for l in range(CFG[2])],
-                       pr=[orf.level(l) for l in range(CFG[2])]))
-    return dict(scenes=scenes, fr=fr, B=len(scenes))
-
-
-def planted_case(rig, i, seed=None):
-    """The planted 30 %-outlier match vector of tests/test_pnp_ransac.py::test_pose_optimization_on_caller_matches on
-    frame i's keypoints: (last, cm, truth), in the scene's own frame."""
-    f = rig["fr"][i]
-    return synth.planted_matches(11 + i if seed is None else seed, f["ck"], rig["scenes"][i]["T_cur"], n_match=min(300, len(f["ck"])),
-                                 outlier_frac=0.3, noise_px=0.5)
-
-
-def planted_uright(rig, i, last, cm, truth, bf=40.0):
-    """A right-image coordinate for every third matched keypoint: the planted inliers' from their true depth, the
-    outliers' from a depth of 3 m (wrong like the rest of them)."""
-    ck, T = rig["fr"][i]["ck"], rig["scenes"][i]["T_cur"]
-    zc = (last["Xw"] @ T[:3, :3].T + T[:3, 3])[:, 2]
-    zc = np.where(truth, zc, 3.0)
-    return np.where((np.arange(len(ck)) % 3 == 0) & (cm >= 0), ck["x"] - bf / zc, -1.0).astype(np.float32)
-
-
-def matched_points(last, cm):
-    Xw = np.zeros((len(cm), 3))
-    Xw[cm >= 0] = last["Xw"][cm[cm >= 0]]
-    return Xw
+    """The two VGA scenes of the sweep through synth's camera with the oracle's extraction, pyramids and tables, and the
+    last-frame and local-map cases (30 points beside the keypoints' own, the rows the tracker has room for) in the scenes'
+    own frame."""
+    return SR.oracle_rig(oracle, "world_frames", CM.CAMERAS["synth"], 640, 480, CFG, MP, n_extra=30, extend=_cut_to_max_points)
 
 
 def pose_error(T_est, T_true, G):
@@ -197,13 +171,6 @@ def assert_converged(T_est, T_true, G, what):
     assert np.abs(T_est[:3, :3] - move_pose(T_true, G)[:3, :3]).max() <= POSE_BOUND, what
     if not G[:3, 3].any():
         assert new <= POSE_BOUND, (what, new)
-
-
-def pnp_scenario(name, n_kp):
-    """pnp_cases.SCENARIOS[name] with the match count capped at the frame's keypoint count."""
-    import pnp_cases as PC
-    kw, params, calls = PC.SCENARIOS[name]
-    return dict(kw, n_match=min(kw["n_match"], n_kp)), params, calls
 
 
 def epnp_trials(G):
