@@ -135,6 +135,14 @@ int sd_orb_level_copy(sd_orb* h, int frame, int level, int padded, uint8_t* out,
 int sd_orb_debug_blurred(sd_orb* h, int frame, int level, uint8_t* out, int out_stride);
 int sd_orb_debug_cell_counts(sd_orb* h, int frame, int level, int32_t* out, int cap, int* n_cells);
 int sd_orb_debug_level_keys(sd_orb* h, int frame, int level, uint32_t* keys_out, int cap, int* n);
+/* Plants the caller's keypoints and descriptors in frames frame0 .. frame0 + n_frames - 1 of the current output set, where an
+ * extraction would have left them: n[f] keypoints from row f of kps / desc (rows of `cap` entries).  Host code only -- copies
+ * on the handle's stream, which the call waits for.  To a tracker it is an extraction into those slots: the results it holds
+ * from before are refused afterwards.  The frames of the set that the call does not name keep what they hold; the pyramid is
+ * not touched.  Refused: a handle that has not extracted yet (no geometry), a distortion with k1 != 0 (mvKeysUn would be a
+ * second array), n[f] above the keypoint capacity or `cap`, frame0 + n_frames above max_batch. */
+int sd_debug_orb_set_keypoints(sd_orb* h, int frame0, int n_frames, const int32_t* n, const sd_keypoint* kps,
+                               const uint8_t* desc, int cap);
 
 /* Stream / timing plumbing (bench + rocprof).  sd_orb_set_stream: run on a caller-owned
  * hipStream_t (NULL restores the handle's own stream); it first waits for the work queued on the

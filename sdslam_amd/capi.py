@@ -61,6 +61,7 @@ _SIGNATURES = {
     "sd_orb_debug_blurred": (_I, [_P, _I, _I, _P, _I]),
     "sd_orb_debug_cell_counts": (_I, [_P, _I, _I, _P, _I, _P]),
     "sd_orb_debug_level_keys": (_I, [_P, _I, _I, _P, _I, _P]),
+    "sd_debug_orb_set_keypoints": (_I, [_P, _I, _I, _P, _P, _P, _I]),
     "sd_orb_set_stream": (_I, [_P, _P]),
     "sd_orb_stream_fence": (_I, [_P, _P, _I]),
     "sd_orb_sync": (_I, [_P]),
@@ -433,6 +434,15 @@ class ORBextractor:
         n = C.c_int()
         _check(self.L.sd_orb_debug_level_keys(self.h, frame, level, _p(out), len(out), C.byref(n)))
         return out[:n.value].copy()
+
+    def set_keypoints(self, frame0, kps_list, desc_list):
+        """sd_debug_orb_set_keypoints: plant per-frame keypoints [n_f] (KP_DTYPE) and descriptors [n_f, 32] in the slots from
+        frame0 on, as an extraction would have left them (needs one earlier extraction for the geometry; refuses a distortion)."""
+        cap = max([len(k) for k in kps_list] + [1])
+        kps, n = _padded(kps_list, (len(kps_list), cap), KP_DTYPE)
+        desc, nd = _padded([np.asarray(d, np.uint8).reshape(-1, 32) for d in desc_list], (len(desc_list), cap, 32), np.uint8)
+        assert np.array_equal(n, nd)
+        _check(self.L.sd_debug_orb_set_keypoints(self.h, frame0, len(n), _p(n), _p(kps), _p(desc), cap))
 
     # --- stream / timing ---
     def set_stream(self, stream_ptr):

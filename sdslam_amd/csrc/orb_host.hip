@@ -482,6 +482,39 @@ int sd_orb_debug_level_keys(sd_orb* h, int frame, int level, uint32_t* keys_out,
   return SD_OK;
 }
 
+// Caller-made keypoints and descriptors in place of an extraction's (the hand-worked matcher cases of tests/match_cases.py).  What
+// orb_launch_pipeline does around its kernels happens around the copies, except that the output set stays the current one: wait
+// for a tracker that still reads it, record the end, count an extraction.
+int sd_debug_orb_set_keypoints(sd_orb* h, int frame0, int n_frames, const int32_t* n, const sd_keypoint* kps, const uint8_t* desc,
+                               int cap) {
+  SD_REQUIRE(h && n && kps && desc, SD_ERR_INVALID_ARG, "NULL argument");
+  SD_REQUIRE(frame0 >= 0 && n_frames >= 1 && frame0 + n_frames <= h->max_batch, SD_ERR_CAPACITY, "frame range exceeds max_batch");
+  SD_REQUIRE(h->have_geom, SD_ERR_INVALID_ARG, "no extraction has run on this handle (the output set has no geometry yet)");
+  SD_REQUIRE(!h->have_dist, SD_ERR_INVALID_ARG, "a distortion is set: the undistorted keypoints would be a second array");
+  const int kcap = h->hp.plan.nsel;
+  for (int f = 0; f < n_frames; f++)
+    SD_REQUIRE(n[f] >= 0 && n[f] <= kcap && n[f] <= cap, SD_ERR_CAPACITY, "keypoint count exceeds the keypoint capacity");
+  SD_HIP_CHECK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  if (h->set_busy[h->set]) {
+    SD_HIP_CHECK(hipStreamWaitEvent(s, h->ev_set_free[h->set], 0));
+    h->set_busy[h->set] = false;
+  }
+  for (int f = 0; f < n_frames; f++) {
+    if (n[f] == 0) continue;
+    const size_t row = (size_t)(frame0 + f) * kcap;
+    SD_HIP_CHECK(hipMemcpyAsync(h->d_kps + row, kps + (size_t)f * cap, (size_t)n[f] * sizeof(sd_keypoint), hipMemcpyHostToDevice, s));
+    SD_HIP_CHECK(hipMemcpyAsync(h->d_desc + row * 32, desc + (size_t)f * cap * 32, (size_t)n[f] * 32, hipMemcpyHostToDevice, s));
+  }
+  SD_HIP_CHECK(hipMemcpyAsync(h->d_nout + frame0, n, (size_t)n_frames * 4, hipMemcpyHostToDevice, s));
+  SD_HIP_CHECK(hipEventRecord(h->ev_extract_done, s));
+  h->extract_recorded = true;
+  h->extract_serial++;
+  h->last_frames = std::max(h->last_frames, frame0 + n_frames);
+  SD_HIP_CHECK(hipStreamSynchronize(s));   // the caller's arrays are its own again
+  return SD_OK;
+}
+
 int sd_orb_set_stream(sd_orb* h, void* hip_stream) {
   SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
   SD_HIP_CHECK(hipSetDevice(h->device));
