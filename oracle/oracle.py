@@ -291,8 +291,17 @@ def search_local_points(kps_un, desc, sf, log_sf, bounds, K, mbf, T_cw, pts, th=
     return dict(n=n, match=match, in_view=inv.astype(bool), proj=proj, level=lvl, cos=cs)
 
 
-def pose_optimization(kps_un, has_mp, Xw, inv_sigma2, K, T_cw, u_right=None, bf=0.0):
-    """Optimizer::PoseOptimization (g2o Levenberg, Huber, 4 x 10 iterations).  Returns dict(n_inliers, T, outlier[N], info[5])."""
+COUNTERFACTUALS = ("none", "classify_at_est", "huber_off_early", "huber_round4", "no_restart", "stereo_delta", "gate_le10")
+LM_EXITS = ("not_run", "nbad", "qmax", "rho_zero", "iterations")     # the exit codes of orc_pose_optimization_trace
+
+
+def pose_optimization(kps_un, has_mp, Xw, inv_sigma2, K, T_cw, u_right=None, bf=0.0, trace=False, counterfactual=0):
+    """Optimizer::PoseOptimization (g2o Levenberg, Huber, 4 x 10 iterations).  Returns dict(n_inliers, T, outlier[N], info[5]);
+    with trace=True (orc_pose_optimization_trace, the same code path) also round_outlier[4][N], round_its[4], round_trials[4],
+    round_exit[4] (names of LM_EXITS) and chi2[N], the float chi2 of every edge at the last classification.  counterfactual (trace only): 0 is
+    the reference; COUNTERFACTUALS names the deliberately wrong variants that test cases are shown to notice."""
+    counterfactual = COUNTERFACTUALS.index(counterfactual) if isinstance(counterfactual, str) else int(counterfactual)
+    assert trace or counterfactual == 0
     L = lib()
     kps_un = np.ascontiguousarray(kps_un)
     N = len(kps_un)
@@ -306,10 +315,17 @@ def pose_optimization(kps_un, has_mp, Xw, inv_sigma2, K, T_cw, u_right=None, bf=
     To = np.zeros(16)
     out = np.zeros(N, np.uint8)
     info = np.zeros(5, np.int32)
+    args = (N, _p(hm), _p(xy), _p(oc), _p(ur), _p(isg), _p(X), float(K[0]), float(K[1]), float(K[2]), float(K[3]), float(bf), _p(Tc), _p(To),
+            _p(out), _p(info))
     L.orc_pose_optimization.argtypes = [C.c_int] + [C.c_void_p] * 6 + [C.c_float] * 5 + [C.c_void_p] * 4
-    n = L.orc_pose_optimization(N, _p(hm), _p(xy), _p(oc), _p(ur), _p(isg), _p(X), float(K[0]), float(K[1]), float(K[2]), float(K[3]),
-                                float(bf), _p(Tc), _p(To), _p(out), _p(info))
-    return dict(n_inliers=n, T=_from_cm(To), outlier=out.astype(bool), info=info)
+    if not trace:
+        n = L.orc_pose_optimization(*args)
+        return dict(n_inliers=n, T=_from_cm(To), outlier=out.astype(bool), info=info)
+    ro, ri, chi2 = np.zeros((4, max(N, 1)), np.uint8), np.zeros((4, 3), np.int32), np.zeros(max(N, 1), np.float32)
+    L.orc_pose_optimization_trace.argtypes = L.orc_pose_optimization.argtypes + [C.c_void_p] * 3 + [C.c_int]
+    n = L.orc_pose_optimization_trace(*args, _p(ro), _p(ri), _p(chi2), counterfactual)
+    return dict(n_inliers=n, T=_from_cm(To), outlier=out.astype(bool), info=info, round_outlier=ro[:, :N].astype(bool), round_its=ri[:, 0],
+                round_trials=ri[:, 1], round_exit=[LM_EXITS[e] for e in ri[:, 2]], chi2=chi2[:N])
 
 
 def stereo_from_rgbd(kps, kps_un, depth, mbf):

@@ -221,6 +221,7 @@ struct Problem {
   double fx, fy, cx, cy, bf;
   std::vector<Edge> edges;
   SE3Quat est;
+  double x[6] = {0, 0, 0, 0, 0, 0};   // _solver->x(): one per problem, kept across failed solves and across the four optimize() calls
 };
 
 void map_point(const SE3Quat& T, const double* X, double* out) {   // _r * xyz + _t
@@ -335,8 +336,12 @@ void build_system(const Problem& P, double H[36], double b[6]) {
   }
 }
 
+// How an optimize() call ended (the per-round trace of orc_pose_optimization_trace)
+enum LmExit { EXIT_NOT_RUN = 0, EXIT_NBAD = 1, EXIT_QMAX = 2, EXIT_RHO_ZERO = 3, EXIT_ITERATIONS = 4 };
+
 // SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg; returns iterations run
-int optimize(Problem& P, int iterations, int* lm_trials_total) {
+int optimize(Problem& P, int iterations, int* lm_trials_total, int* exit_taken) {
+  *exit_taken = EXIT_NOT_RUN;
   double lambda = -1., ni = 2.;
   int nBad = 0, done = 0;
   const int maxTrials = 10;
@@ -348,7 +353,7 @@ int optimize(Problem& P, int iterations, int* lm_trials_total) {
     double currentChi = active_robust_chi2(P), tempChi = currentChi;
     const double iniChi = currentChi;
     double H[36], b[6];
-    static thread_local double x[6] = {0, 0, 0, 0, 0, 0};   // _solver->x() persists across failed solves
+    double* const x = P.x;   // persists across failed solves
     build_system(P, H, b);
     if (it == 0) {
       double maxDiagonal = 0.;
@@ -390,13 +395,42 @@ int optimize(Problem& P, int iterations, int* lm_trials_total) {
       if (lm_trials_total) (*lm_trials_total)++;
     } while (rho < 0 && qmax < maxTrials);
     done++;
-    if (qmax == maxTrials || rho == 0) break;   // Terminate
+    *exit_taken = EXIT_ITERATIONS;
+    if (qmax == maxTrials || rho == 0) {   // Terminate
+      *exit_taken = qmax == maxTrials ? EXIT_QMAX : EXIT_RHO_ZERO;
+      break;
+    }
     if ((iniChi - currentChi) * 1e3 < iniChi) nBad++;
     else nBad = 0;
-    if (nBad >= 3) break;
+    if (nBad >= 3) {
+      *exit_taken = EXIT_NBAD;
+      break;
+    }
   }
   return done;
 }
+
+// Ways of getting PoseOptimization wrong that a test case should notice (orc_pose_optimization_trace only)
+enum Counterfactual {
+  CF_NONE = 0,
+  CF_CLASSIFY_AT_EST = 1,   // every edge classified at the current estimate, not with the errors of the last computeActiveErrors
+  CF_HUBER_OFF_EARLY = 2,   // the robust kernel dropped after the second round
+  CF_HUBER_ROUND4 = 3,      // ... or never
+  CF_NO_RESTART = 4,        // rounds 1 .. 3 continue from the previous round's estimate
+  CF_STEREO_DELTA = 5,      // sqrt(7.815) as the Huber delta of monocular edges
+  CF_GATE_LE10 = 6,         // the one-round gate taken at 10 edges too
+};
+
+// What orc_pose_optimization_trace reports on top of orc_pose_optimization (all optional)
+struct Trace {
+  uint8_t* round_outlier;   // [4][N]: mvbOutlier after each round's classification (rounds not run: 0)
+  int* round_info;          // [4][3]: g2o iterations, LM trials, LmExit of each round's optimize()
+  float* chi2;              // [N]: the float chi2 the last classification compared with its threshold (no edge: 0)
+};
+
+int pose_optimization(int N, const uint8_t* has_mp, const float* kp_xy, const int* kp_octave, const float* uright,
+                      const float* inv_level_sigma2, const double* Xw, float fx, float fy, float cx, float cy, float bf,
+                      const double* Tcw_in, double* Tcw_out, uint8_t* outlier_out, int* info, const Trace* trace, int counterfactual);
 
 }  // namespace
 
@@ -409,6 +443,30 @@ extern "C" {
 int orc_pose_optimization(int N, const uint8_t* has_mp, const float* kp_xy, const int* kp_octave, const float* uright,
                           const float* inv_level_sigma2, const double* Xw, float fx, float fy, float cx, float cy, float bf,
                           const double* Tcw_in, double* Tcw_out, uint8_t* outlier_out, int* info) {
+  return pose_optimization(N, has_mp, kp_xy, kp_octave, uright, inv_level_sigma2, Xw, fx, fy, cx, cy, bf, Tcw_in, Tcw_out, outlier_out, info,
+                           nullptr, CF_NONE);
+}
+
+// The same call with a per-round trace: round_outlier [4][N], round_info [4][3] = (iterations, LM trials, exit: 0 optimize() did not
+// iterate / round not run, 1 nBad >= 3, 2 ten trials of one iteration rejected, 3 rho == 0, 4 ten iterations used), chi2 [N] = the float
+// chi2 of every edge at the last classification.  counterfactual: 0 is the reference (and what orc_pose_optimization does); 1 .. 6
+// (enum Counterfactual) each break ONE of its quirks, so that tests/test_poseopt_cases_cpu.py can show which cases notice.
+int orc_pose_optimization_trace(int N, const uint8_t* has_mp, const float* kp_xy, const int* kp_octave, const float* uright,
+                                const float* inv_level_sigma2, const double* Xw, float fx, float fy, float cx, float cy, float bf,
+                                const double* Tcw_in, double* Tcw_out, uint8_t* outlier_out, int* info, uint8_t* round_outlier,
+                                int* round_info, float* chi2, int counterfactual) {
+  const Trace t = {round_outlier, round_info, chi2};
+  return pose_optimization(N, has_mp, kp_xy, kp_octave, uright, inv_level_sigma2, Xw, fx, fy, cx, cy, bf, Tcw_in, Tcw_out, outlier_out, info,
+                           &t, counterfactual);
+}
+
+}  // extern "C"
+
+namespace {
+
+int pose_optimization(int N, const uint8_t* has_mp, const float* kp_xy, const int* kp_octave, const float* uright,
+                      const float* inv_level_sigma2, const double* Xw, float fx, float fy, float cx, float cy, float bf,
+                      const double* Tcw_in, double* Tcw_out, uint8_t* outlier_out, int* info, const Trace* trace, int counterfactual) {
   Problem P;
   P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.bf = bf;
   const float deltaMono = std::sqrt(5.991), deltaStereo = std::sqrt(7.815);
@@ -426,7 +484,7 @@ int orc_pose_optimization(int N, const uint8_t* has_mp, const float* kp_xy, cons
     e.obs[2] = e.stereo ? uright[i] : 0;
     const float invSigma2 = inv_level_sigma2[kp_octave[i]];
     e.info = invSigma2;
-    e.delta = e.stereo ? deltaStereo : deltaMono;
+    e.delta = (e.stereo || counterfactual == CF_STEREO_DELTA) ? deltaStereo : deltaMono;
     e.robust = true;
     e.level = 0;
     for (int k = 0; k < 3; k++) e.Xw[k] = Xw[3 * i + k];
@@ -435,6 +493,11 @@ int orc_pose_optimization(int N, const uint8_t* has_mp, const float* kp_xy, cons
   }
   for (int k = 0; k < 5; k++) info[k] = 0;
   info[0] = nInitialCorrespondences;
+  if (trace) {
+    for (int i = 0; i < 4 * N; i++) trace->round_outlier[i] = 0;
+    for (int i = 0; i < 12; i++) trace->round_info[i] = 0;
+    for (int i = 0; i < N; i++) trace->chi2[i] = 0;
+  }
   if (nInitialCorrespondences < 3) return 0;
   double R[3][3], t[3];
   for (int r = 0; r < 3; r++) {
@@ -443,13 +506,23 @@ int orc_pose_optimization(int N, const uint8_t* has_mp, const float* kp_xy, cons
   }
   const float chi2Mono[4] = {5.991, 5.991, 5.991, 5.991}, chi2Stereo[4] = {7.815, 7.815, 7.815, 7.815};
   int nBad = 0;
+  const int huber_rounds = counterfactual == CF_HUBER_OFF_EARLY ? 2 : counterfactual == CF_HUBER_ROUND4 ? 4 : 3;
   for (int it = 0; it < 4; it++) {
-    P.est = se3_from_Rt(R, t);   // vSE3->setEstimate(Converter::toSE3Quat(pFrame->GetPose()))
-    info[3] += optimize(P, 10, &info[4]);
+    if (it == 0 || counterfactual != CF_NO_RESTART)
+      P.est = se3_from_Rt(R, t);   // vSE3->setEstimate(Converter::toSE3Quat(pFrame->GetPose()))
+    const int trials_before = info[4];
+    int exit_taken = EXIT_NOT_RUN;
+    const int its = optimize(P, 10, &info[4], &exit_taken);
+    info[3] += its;
     info[2]++;
+    if (trace) {
+      trace->round_info[it * 3 + 0] = its;
+      trace->round_info[it * 3 + 1] = info[4] - trials_before;
+      trace->round_info[it * 3 + 2] = exit_taken;
+    }
     nBad = 0;
     for (Edge& e : P.edges) {   // mono edges then stereo edges in the reference; the two loops are independent
-      if (outlier_out[e.kp]) compute_error(P, e);
+      if (outlier_out[e.kp] || counterfactual == CF_CLASSIFY_AT_EST) compute_error(P, e);
       const float chi2 = edge_chi2(e);
       const float thr = e.stereo ? chi2Stereo[it] : chi2Mono[it];
       if (chi2 > thr) {
@@ -460,9 +533,13 @@ int orc_pose_optimization(int N, const uint8_t* has_mp, const float* kp_xy, cons
         outlier_out[e.kp] = 0;
         e.level = 0;
       }
-      if (it == 2) e.robust = false;
+      if (it == huber_rounds - 1) e.robust = false;   // the reference: if(it==2) e->setRobustKernel(0)
+      if (trace) {
+        trace->round_outlier[(size_t)it * N + e.kp] = outlier_out[e.kp];
+        trace->chi2[e.kp] = chi2;
+      }
     }
-    if (P.edges.size() < 10) break;
+    if (P.edges.size() < 10 || (counterfactual == CF_GATE_LE10 && P.edges.size() == 10)) break;
   }
   double Ro[3][3];
   quat_to_R(P.est.q, Ro);
@@ -475,4 +552,4 @@ int orc_pose_optimization(int N, const uint8_t* has_mp, const float* kp_xy, cons
   return nInitialCorrespondences - nBad;
 }
 
-}  // extern "C"
+}  // namespace
