@@ -803,6 +803,183 @@ class Optimizer {
     check(sd_track_get_pose_opt(batch.handle(), frame, 1, Tcw, mvbOutlier.data(), kp_cap, info));
     return info[5];
   }
+
+  // void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap)          src/Optimizer.cc:417-714
+  // on the device (sd_track_local_ba with write_back = 1).  pKF is the current keyframe (frame 0 of the cur extractor, or the
+  // broadcast frame; Tcur of slot 0); frameOf(KeyFrameT*) returns the frame of the ref extractor that holds a keyframe, or a
+  // negative number when it is not resident.  The three lists are built as :418-460 builds them (the marks mnBALocalForKF /
+  // mnBAFixedForKF are written as there); the points go into local row `point_row` in lLocalMapPoints order, the poses and
+  // mvuRight rows of every resident keyframe of the problem into its slot (Tcur of those slots is overwritten with the same
+  // pose, as by ORBmatcher::Fuse), roles and observations behind them.  Then, in the reference's order: EraseMapPointMatch /
+  // EraseObservation for the erase flags (all mono edges, then all stereo edges, each in edge order), SetPose on every local
+  // keyframe, SetWorldPos on every local point, and the refresh that is UpdateNormalAndDepth (SetNormalVector / SetMaxDistance /
+  // SetMinDistance; the observations are uploaded again only when something was erased).  *pbStopFlag is read once, where the
+  // reference reads it before optimize() (:604); inside the run it is not modelled.  Returns false, with no object touched, when
+  // the flag is set or the device refuses the problem (a local point seen by a keyframe that is not resident, more than
+  // SD_BA_MAX_FREE_KF local keyframes, a keypoint index outside its frame); the marks and the uploads have happened by then.
+  // KeyFrameT needs mnId, mnBALocalForKF, mnBAFixedForKF, N, mvuRight, isBad(), GetVectorCovisibleKeyFrames(),
+  // GetMapPointMatches(), GetPose() (16 doubles column-major behind .data()), SetPose(const double*), EraseMapPointMatch(pMP).
+  // MapPointT needs what ORBmatcher::Fuse's point upload needs, and mnBALocalForKF, GetObservations(), GetReferenceKeyFrame(),
+  // EraseObservation(pKF), SetWorldPos(const double*) and the three setters of the refresh.
+  template <class KeyFrameT, class FrameOf>
+  static bool LocalBundleAdjustment(TrackBatch& batch, KeyFrameT* pKF, bool* pbStopFlag, FrameOf frameOf, int point_row = 0) {
+    using MapPointT = typename std::remove_pointer<typename std::decay<decltype(pKF->GetMapPointMatches())>::type::value_type>::type;
+    LocalBaLists<KeyFrameT, MapPointT> L;
+    BuildLocalBaLists(pKF, frameOf, L);
+    if (pbStopFlag && *pbStopFlag) return false;
+    if (L.points.size() > (size_t)batch.max_points())
+      throw Error(SD_ERR_CAPACITY, "LocalBundleAdjustment: more local points than the batch's max_points");
+    sd_track* h = batch.handle();
+    ORBmatcher matcher(0.6f, false);
+    matcher.UploadFusePoints(batch, point_row, L.points, true, [](MapPointT*) { return false; });
+    const auto Tc = pKF->GetPose();
+    check(sd_track_set_poses(h, 0, 1, Tc.data(), Tc.data()));
+    if (pKF->N > 0) batch.SetURight(0, pKF->mvuRight.data(), pKF->N);
+    for (size_t k = 0; k < L.resident.size(); k++) {
+      KeyFrameT* kf = L.resident[k];
+      const int f = L.resident_frame[k];
+      const auto T = kf->GetPose();
+      check(sd_track_set_poses(h, f, 1, T.data(), f == 0 ? Tc.data() : T.data()));
+      if (kf->N > 0) check(sd_track_set_uright_ref(h, f, 1, kf->mvuRight.data(), kf->N));
+    }
+    const int n = (int)L.points.size(), n_ref = (int)L.kf_role.size();
+    check(sd_track_set_ba_keyframes(h, n_ref, L.kf_role.data(), L.cur_role));
+    check(sd_track_set_observations(h, n, L.obs.off.data(), L.obs.frame.data(), L.obs.kp.data(), L.obs.kf_bad.data(), L.obs.ref_obs.data(),
+                                    L.obs.point_bad.data()));
+    check(sd_track_local_ba(h, point_row, 1));
+    LocalBaResult r((size_t)n_ref, (size_t)n, L.edge_kf.size());
+    check(sd_track_get_local_ba(h, r.T_ref.data(), r.T_cur, r.Xw.data(), r.point_status.data(), r.obs_erase.data(), r.info, n, (int)L.edge_kf.size()));
+    if (r.info[0] != SD_BA_OK) return false;
+    const bool erased = ApplyLocalBa(pKF, L, r);
+    if (n == 0) return true;
+    if (erased) {   // the lists the refresh reads are the points' observations as they are now
+      BuildBaObservations(pKF, frameOf, L);
+      check(sd_track_set_observations(h, n, L.obs.off.data(), L.obs.frame.data(), L.obs.kp.data(), L.obs.kf_bad.data(), L.obs.ref_obs.data(),
+                                      L.obs.point_bad.data()));
+    }
+    check(sd_track_refresh_points(h, point_row, 1));
+    ORBmatcher::RefreshedRows rr((size_t)n);
+    check(sd_track_get_refreshed(h, rr.status.data(), nullptr, nullptr, nullptr, rr.normal.data(), rr.max_dist.data(), rr.min_dist.data(), n));
+    for (int i = 0; i < n; i++)   // pMP->UpdateNormalAndDepth() (:712); a point whose reference keyframe does not observe it stays as it is
+      if ((rr.status[i] & SD_REFRESH_NORMAL) && !L.obs.left[i]) {
+        L.points[i]->SetNormalVector(&rr.normal[(size_t)i * 3]);
+        L.points[i]->SetMaxDistance(rr.max_dist[i]);
+        L.points[i]->SetMinDistance(rr.min_dist[i]);
+      }
+    return true;
+  }
+  // lLocalKeyFrames, lLocalMapPoints and (through `resident`) lFixedCameras, and what the device is given for them
+  template <class KeyFrameT, class MapPointT>
+  struct LocalBaLists {
+    std::vector<KeyFrameT*> local, fixed;        // lLocalKeyFrames, lFixedCameras, in the reference's order
+    std::vector<MapPointT*> points;              // lLocalMapPoints
+    std::vector<KeyFrameT*> resident;            // the keyframes of both lists that are frames of the ref extractor ...
+    std::vector<int> resident_frame;             // ... and their frames
+    std::vector<uint8_t> kf_role;                // sd_track_set_ba_keyframes
+    int cur_role = 1;
+    ORBmatcher::ObservationLists obs;            // sd_track_set_observations; left[i]: the reference keyframe is not an observation
+    std::vector<KeyFrameT*> edge_kf;             // per CSR entry: its keyframe ...
+    std::vector<int32_t> edge_pt;                // ... its point ...
+    std::vector<uint8_t> edge_stereo;            // ... and mvuRight >= 0
+  };
+  struct LocalBaResult {
+    std::vector<double> T_ref, Xw;
+    double T_cur[16] = {};
+    std::vector<uint8_t> point_status, obs_erase;
+    int32_t info[16] = {};
+    LocalBaResult(size_t n_ref, size_t n, size_t e) : T_ref(n_ref * 16 + 16, 0.0), Xw(n * 3 + 3, 0.0), point_status(n + 1, 0), obs_erase(e + 1, 0) {}
+  };
+  // Host code only: :418-460, then the roles and the CSR lists
+  template <class KeyFrameT, class MapPointT, class FrameOf>
+  static void BuildLocalBaLists(KeyFrameT* pKF, FrameOf frameOf, LocalBaLists<KeyFrameT, MapPointT>& L) {
+    L.local.assign(1, pKF);
+    pKF->mnBALocalForKF = pKF->mnId;
+    for (KeyFrameT* pKFi : pKF->GetVectorCovisibleKeyFrames()) {
+      pKFi->mnBALocalForKF = pKF->mnId;
+      if (!pKFi->isBad()) L.local.push_back(pKFi);
+    }
+    L.points.clear();
+    for (KeyFrameT* kf : L.local)
+      for (MapPointT* pMP : kf->GetMapPointMatches())
+        if (pMP && !pMP->isBad() && pMP->mnBALocalForKF != pKF->mnId) {
+          L.points.push_back(pMP);
+          pMP->mnBALocalForKF = pKF->mnId;
+        }
+    L.fixed.clear();
+    for (MapPointT* pMP : L.points)
+      for (const auto& ob : pMP->GetObservations()) {
+        KeyFrameT* pKFi = ob.first;
+        if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) {
+          pKFi->mnBAFixedForKF = pKF->mnId;
+          if (!pKFi->isBad()) L.fixed.push_back(pKFi);
+        }
+      }
+    L.resident.clear(); L.resident_frame.clear(); L.kf_role.clear();
+    L.cur_role = pKF->mnId == 0 ? 2 : 1;
+    for (int pass = 0; pass < 2; pass++)
+      for (KeyFrameT* kf : pass ? L.fixed : L.local) {
+        const int f = kf == pKF ? -1 : (int)frameOf(kf);
+        if (f < 0) continue;
+        L.resident.push_back(kf);
+        L.resident_frame.push_back(f);
+        if (pass == 0) {
+          if (L.kf_role.size() <= (size_t)f) L.kf_role.resize((size_t)f + 1, 0);
+          L.kf_role[(size_t)f] = kf->mnId == 0 ? 2 : 1;
+        }
+      }
+    BuildBaObservations(pKF, frameOf, L);
+  }
+  // Host code only: the observations of L.points as they are now, in iteration order
+  template <class KeyFrameT, class MapPointT, class FrameOf>
+  static void BuildBaObservations(KeyFrameT* pKF, FrameOf frameOf, LocalBaLists<KeyFrameT, MapPointT>& L) {
+    ORBmatcher::ObservationLists& O = L.obs;
+    const size_t n = L.points.size();
+    O.off.assign(1, 0);
+    O.frame.clear(); O.kp.clear(); O.kf_bad.clear();
+    O.ref_obs.assign(n, 0); O.point_bad.assign(n, 0); O.left.assign(n, 0);
+    L.edge_kf.clear(); L.edge_pt.clear(); L.edge_stereo.clear();
+    for (size_t i = 0; i < n; i++) {
+      MapPointT* pMP = L.points[i];
+      const KeyFrameT* pRefKF = pMP->GetReferenceKeyFrame();
+      int32_t pos = 0, ref_pos = -1;
+      for (const auto& ob : pMP->GetObservations()) {
+        KeyFrameT* pKFi = ob.first;
+        const int f = pKFi == pKF ? -1 : (int)frameOf(pKFi);
+        O.frame.push_back(pKFi == pKF ? -1 : (f < 0 ? -2 : f));
+        O.kp.push_back((int32_t)ob.second);
+        O.kf_bad.push_back(pKFi->isBad() ? 1 : 0);
+        L.edge_kf.push_back(pKFi);
+        L.edge_pt.push_back((int32_t)i);
+        L.edge_stereo.push_back(ob.second < pKFi->mvuRight.size() && !(pKFi->mvuRight[ob.second] < 0) ? 1 : 0);
+        if (pKFi == pRefKF) ref_pos = pos;
+        pos++;
+      }
+      if (pos > 0 && ref_pos < 0) O.left[i] = 1;
+      O.ref_obs[i] = ref_pos < 0 ? 0 : ref_pos;
+      O.off.push_back((int32_t)O.frame.size());
+    }
+    if (O.frame.empty()) O.frame.push_back(0), O.kp.push_back(0), O.kf_bad.push_back(0);   // (data() of an empty vector may be NULL)
+    if (O.ref_obs.empty()) O.ref_obs.push_back(0), O.point_bad.push_back(0);
+  }
+  // Host code only: :685-713 without the refresh.  Returns whether anything was erased.
+  template <class KeyFrameT, class MapPointT>
+  static bool ApplyLocalBa(KeyFrameT* pKF, const LocalBaLists<KeyFrameT, MapPointT>& L, const LocalBaResult& r) {
+    bool erased = false;
+    for (int stereo = 0; stereo < 2; stereo++)   // vToErase: the mono loop's entries, then the stereo loop's
+      for (size_t e = 0; e < L.edge_kf.size(); e++)
+        if (r.obs_erase[e] && L.edge_stereo[e] == stereo) {
+          L.edge_kf[e]->EraseMapPointMatch(L.points[(size_t)L.edge_pt[e]]);
+          L.points[(size_t)L.edge_pt[e]]->EraseObservation(L.edge_kf[e]);
+          erased = true;
+        }
+    for (KeyFrameT* kf : L.local) {
+      if (kf == pKF) { kf->SetPose(r.T_cur); continue; }
+      for (size_t k = 0; k < L.resident.size(); k++)
+        if (L.resident[k] == kf) kf->SetPose(&r.T_ref[(size_t)L.resident_frame[k] * 16]);
+    }
+    for (size_t i = 0; i < L.points.size(); i++) L.points[i]->SetWorldPos(&r.Xw[i * 3]);
+    return erased;
+  }
 };
 
 // Tracking::Relocalization (src/Tracking.cc:1064-1097): every keyframe attempt of the loop is one slot of `batch`

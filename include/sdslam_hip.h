@@ -592,6 +592,62 @@ int sd_debug_refresh_points(int n_points, const int32_t* obs_off, const uint8_t*
                             const double* Xw, const float* scale_factors, int nlevels, uint8_t* status, int32_t* best_obs,
                             int32_t* best_median, uint8_t* desc, double* normal, float* max_dist, float* min_dist);
 
+/* Optimizer::LocalBundleAdjustment (src/Optimizer.cc:417-714) on the lists of sd_track_set_observations: the last step of the
+ *   LocalMapping chain, behind sd_track_append_new_points / _fuse / _refresh_points, without taking the map to the host.
+ * The problem.  Points: point i of the list = entry i of row point_row of the sd_track_set_local buffers; the caller builds
+ *   lLocalMapPoints in the reference's order (:432-445).  A point with point_bad set is not in the problem; an observation with
+ *   obs_kf_bad set gives no edge (:541).  Keyframes: obs_frame >= 0 is a frame of the ref extractor with pose Tref, -1 the current
+ *   keyframe with Tcur of slot 0 (as for the refresh).  sd_track_set_ba_keyframes gives their roles: kf_role[f], f < n_ref_frames,
+ *   is 1 for a local keyframe, 2 for a local keyframe that is fixed (mnId == 0, :484), 0 otherwise; cur_role is 1 or 2.  Every
+ *   other resident frame that a point of the list observes is a fixed camera (:447-460, :496).  A local keyframe that no point
+ *   observes is a vertex without edges and keeps its pose.  Edges, in CSR order: mono where mvuRight < 0, else stereo; the
+ *   measurement is the undistorted keypoint (and mvuRight), the information mvInvLevelSigma2[octave] * I, the Huber deltas
+ *   (float)sqrt(5.991) and (float)sqrt(7.815), camera and bf the handle's (sd_track_set_camera).
+ * The run (:608-683): optimize(5) with the robust kernel on every edge; every edge with chi2 > 5.991 (mono) / 7.815 (stereo) or
+ *   !isDepthPositive goes to level 1 and the robust kernel comes off every edge; initializeOptimization(0) and optimize(10)
+ *   (vertices without a level-0 edge leave the active set); the same test again gives obs_erase, one byte per CSR entry: 1 =
+ *   vToErase would hold it.  g2o's Levenberg driver and Schur-complement block solver are restated
+ *   (sdslam_amd/csrc/track_ba.hip, tests/ba_ref.py), three quirks included: lambda is re-initialised at iteration 0 of each
+ *   optimize(); Terminate on rho == 0, after ten trials, and at _nBad >= 3; chi2() in both classifications is the error of the LAST
+ *   computeActiveErrors (after a rejected last trial that of the rejected step; for a level-1 edge in round 2 round 1's last).
+ *   pbStopFlag is not modelled: the caller checks it before the call, the device runs both rounds.  Double throughout; no
+ *   floating-point atomics, every sum has one owner and a fixed order: two runs of one problem give the same bytes.
+ * sd_track_local_ba is queued on the tracking stream: no host wait, no allocation (its scratch is allocated by sd_track_create for
+ *   max_points points of 16 observations and max_batch + 1 cameras, and grows where sd_track_set_observations grows its block).
+ *   write_back = 1, and only on SD_BA_OK: the optimised poses of the local keyframes with role 1 that some point observes go to
+ *   Tref / Tcur, the positions of the SD_BA_POINT_OPTIMISED points to Xw of the row; everything else keeps its bytes.  It ends
+ *   the cached results that sd_track_set_poses and a write-through refresh end; write_back = 0 ends none.  A
+ *   sd_track_refresh_points queued behind it is the UpdateNormalAndDepth of :712, provided no observation was erased.
+ *   SD_ERR_INVALID_ARG: no sd_track_set_observations / sd_track_set_ba_keyframes / sd_track_set_camera before it.
+ * sd_track_get_local_ba (synchronises; NULL outputs are skipped): T_ref_cm16 [n_ref_frames][16] and T_cur_cm16 [16] column-major,
+ *   Xw [cap_points][3], point_status [cap_points] = SD_BA_POINT_OPTIMISED, _SKIPPED (bad, or no edge) or _BAD_INDEX (a keypoint
+ *   index outside its frame; nothing is read through it), obs_erase [cap_obs], info16 = {status, n_local_free, n_fixed, n_points,
+ *   n_edges_mono, n_edges_stereo, round-1 iterations, trials, exit, round-2 iterations, trials, exit, n_level1 after round 1,
+ *   n_erase, 0, 0}; exits: 0 optimize() did not iterate, 1 _nBad >= 3, 2 ten trials rejected, 3 rho == 0, 4 the iterations were
+ *   used.  status is SD_BA_OK or a refusal -- the problem is not run, nothing is written, poses and points are the inputs:
+ *   SD_BA_NOT_RESIDENT (an observation of a live point with frame -2), SD_BA_TOO_MANY_KF (more than SD_BA_MAX_FREE_KF keyframes
+ *   with role 1), SD_BA_BAD_INDEX (a keypoint index outside its frame).  The number of fixed cameras is bounded by max_batch only.
+ * sd_debug_local_ba: the same kernels from host arrays, synchronous, with buffers of its own: per observation its keyframe
+ *   obs_kf (an index into the n_kf poses and roles; -2: not resident; anything else outside [0, n_kf): a bad index), obs_uv [.][2],
+ *   obs_ur and obs_inv_sigma2; the CSR offsets and flags; T_cm16 [n_kf][16]; kf_role [n_kf]; Xw; cam9 as for sd_debug_fuse
+ *   (fx, fy, cx, cy, bf, ...).  T_out_cm16 [n_kf][16], Xw_out, point_status, obs_erase and info16 as the getter's. */
+#define SD_BA_MAX_FREE_KF 32
+#define SD_BA_OK 0
+#define SD_BA_NOT_RESIDENT 1
+#define SD_BA_TOO_MANY_KF 2
+#define SD_BA_BAD_INDEX 3
+#define SD_BA_POINT_SKIPPED 0
+#define SD_BA_POINT_OPTIMISED 1
+#define SD_BA_POINT_BAD_INDEX 2
+int sd_track_set_ba_keyframes(sd_track* h, int n_ref_frames, const uint8_t* kf_role, int cur_role);
+int sd_track_local_ba(sd_track* h, int point_row, int write_back);
+int sd_track_get_local_ba(sd_track* h, double* T_ref_cm16, double* T_cur_cm16, double* Xw, uint8_t* point_status, uint8_t* obs_erase,
+                          int32_t* info16, int cap_points, int cap_obs);
+int sd_debug_local_ba(int n_points, const int32_t* obs_off, const int32_t* obs_kf, const float* obs_uv, const float* obs_ur,
+                      const float* obs_inv_sigma2, const uint8_t* obs_kf_bad, const uint8_t* point_bad, int n_kf, const double* T_cm16,
+                      const uint8_t* kf_role, const double* Xw, const float* cam9, double* T_out_cm16, double* Xw_out,
+                      uint8_t* point_status, uint8_t* obs_erase, int32_t* info16);
+
 int sd_track_align(sd_track* h, int n_frames, int mode);
 int sd_track_match(sd_track* h, int n_frames, float th, int mono, int check_ori);
 /* sd_track_pnp = PnPsolver(CurrentFrame, CurrentFrame.mvpMapPoints) + SetRansacParameters(...) + iterate(n_iterations)

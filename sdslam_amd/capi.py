@@ -130,6 +130,10 @@ _SIGNATURES = {
     "sd_track_refresh_points": (_I, [_P, _I, _I]),
     "sd_track_get_refreshed": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "sd_debug_refresh_points": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "sd_track_set_ba_keyframes": (_I, [_P, _I, _P, _I]),
+    "sd_track_local_ba": (_I, [_P, _I, _I]),
+    "sd_track_get_local_ba": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I]),
+    "sd_debug_local_ba": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sd_track_align": (_I, [_P, _I, _I]),
     "sd_track_match": (_I, [_P, _I, _F, _I, _I]),
     "sd_track_pnp": (_I, [_P, _I, _D, _I, _I, _I, _F, _F, _I]),
@@ -815,7 +819,7 @@ class Tracker:
         pb = None if point_bad is None else np.ascontiguousarray(point_bad, np.uint8)
         assert len(ro) == len(obs) and (pb is None or len(pb) == len(obs))
         _check(self.L.sd_track_set_observations(self.h, len(obs), _p(off), _p(fr), _p(kp), _p(kb), _p(ro), _p(pb)))
-        self._n_refresh = len(obs)
+        self._n_refresh, self._n_refresh_obs = len(obs), len(fr)
 
     def refresh_points(self, point_row=0, write_local=True):
         """Both functions for the points of set_observations at Xw of local row `point_row`; write_local: into that row too."""
@@ -834,6 +838,36 @@ class Tracker:
                    max_dist=np.zeros(M, np.float32), mf_max_dist=np.zeros(M, np.float32))
         for which, key in enumerate(("desc", "normal", "min_dist", "max_dist", "mf_max_dist"), start=3):
             _check(self.L.sd_track_debug_read(self.h, which, frame, _p(out[key]), out[key].nbytes))
+        return out
+
+    # --- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:417-714) on the lists of set_observations ---
+    def set_ba_keyframes(self, kf_role, cur_role=1):
+        """kf_role[f] of the ref frames (1 local, 2 local and fixed, 0 otherwise) and the current keyframe's role (1 or 2)."""
+        r = np.ascontiguousarray(kf_role, np.uint8)
+        _check(self.L.sd_track_set_ba_keyframes(self.h, len(r), _p(r), int(cur_role)))
+        self._n_ba_ref = len(r)
+
+    def local_ba(self, point_row=0, write_back=True):
+        """Both rounds on the points of set_observations at row `point_row`; write_back: poses and positions into Tref / Tcur / Xw."""
+        _check(self.L.sd_track_local_ba(self.h, int(point_row), int(write_back)))
+        self._n_ba = (self._n_refresh, self._n_refresh_obs)
+
+    def read_poses(self, n):
+        """Tref and Tcur of slots 0 .. n - 1 as they are on the device: ([n, 4, 4], [n, 4, 4])."""
+        out = np.zeros((2, n, 16))
+        for side in range(2):
+            for f in range(n):
+                _check(self.L.sd_track_debug_read(self.h, 8 + side, f, _p(out[side, f]), 128))
+        return np.stack([_from_cm(t) for t in out[0]]), np.stack([_from_cm(t) for t in out[1]])
+
+    def get_local_ba(self):
+        """dict(T_ref [n_ref, 4, 4], T_cur [4, 4], Xw, point_status, obs_erase, info16) of the last local_ba()."""
+        n, e = self._n_ba
+        Tr, Tc = np.zeros((self._n_ba_ref, 16)), np.zeros(16)
+        out = dict(Xw=np.zeros((n, 3)), point_status=np.zeros(n, np.uint8), obs_erase=np.zeros(e, np.uint8), info16=np.zeros(16, np.int32))
+        _check(self.L.sd_track_get_local_ba(self.h, _p(Tr), _p(Tc), _p(out["Xw"]), _p(out["point_status"]), _p(out["obs_erase"]),
+                                            _p(out["info16"]), n, e))
+        out.update(T_ref=np.stack([_from_cm(t) for t in Tr]) if len(Tr) else np.zeros((0, 4, 4)), T_cur=_from_cm(Tc))
         return out
 
     # --- Sim3Solver on the SearchByPoints pairing (src/Sim3Solver.cc; caller LoopClosing::ComputeSim3) ---
@@ -1165,3 +1199,29 @@ def debug_refresh_points(obs_off, obs_desc, obs_centre, obs_octave, ref_obs, Xw,
     _check(L.sd_debug_refresh_points(n, _p(off), _p(d), _p(c), _p(oc), _p(kb), _p(ro), _p(pb), _p(X), _p(sf), len(sf),
                                      *[_p(out[k]) for k in _REFRESH_FIELDS]))
     return out
+
+
+def debug_local_ba(problem, cam9=None):
+    """A LocalBundleAdjustment problem (the dict tests/ba_ref.py documents: off, kf, uv, ur, inv_sigma2, kf_bad, point_bad, poses
+    [n_kf, 4, 4], roles, Xw, cam, bf) from host arrays through the kernels of sd_track_local_ba (diagnostics).  Returns dict(T
+    [n_kf, 4, 4], Xw, point_status, obs_erase, info16)."""
+    L = lib()
+    q = problem
+    off = np.ascontiguousarray(q["off"], np.int32)
+    n, total = len(off) - 1, int(off[-1])
+    kf, uv = np.ascontiguousarray(q["kf"], np.int32), np.ascontiguousarray(q["uv"], np.float32).reshape(total, 2)
+    ur, inv = np.ascontiguousarray(q["ur"], np.float32), np.ascontiguousarray(q["inv_sigma2"], np.float32)
+    kb = None if q.get("kf_bad") is None else np.ascontiguousarray(q["kf_bad"], np.uint8)
+    pb = None if q.get("point_bad") is None else np.ascontiguousarray(q["point_bad"], np.uint8)
+    roles = np.ascontiguousarray(q["roles"], np.uint8)
+    T = np.ascontiguousarray(np.stack([_cm(t) for t in np.asarray(q["poses"], np.float64)]))
+    X = np.ascontiguousarray(q["Xw"], np.float64).reshape(n, 3)
+    if cam9 is None:
+        cam9 = list(q["cam"]) + [q["bf"], 0.0, 1.0, 0.0, 1.0]
+    cam = np.ascontiguousarray(cam9, np.float32)
+    assert len(kf) == len(ur) == len(inv) == total and len(T) == len(roles) and len(cam) == 9
+    To, Xo = np.zeros_like(T), np.zeros_like(X)
+    ps, er, info = np.zeros(n, np.uint8), np.zeros(total, np.uint8), np.zeros(16, np.int32)
+    _check(L.sd_debug_local_ba(n, _p(off), _p(kf), _p(uv), _p(ur), _p(inv), _p(kb), _p(pb), len(roles), _p(T), _p(roles), _p(X), _p(cam),
+                               _p(To), _p(Xo), _p(ps), _p(er), _p(info)))
+    return dict(T=np.stack([_from_cm(t) for t in To]), Xw=Xo, point_status=ps, obs_erase=er, info16=info)

@@ -223,6 +223,7 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &h->rf.max_dist, M));
   A(dalloc(h, &h->rf.min_dist, M));
   A(refresh_create(h));
+  A(ba_create(h));
   A(dalloc(h, &tb.s3_Xw1, B * K * 3));
   A(dalloc(h, &tb.s3_Xw2, B * K * 3));
   A(dalloc(h, &tb.s3_X, B * K * 6));
@@ -325,6 +326,7 @@ void sd_track_destroy(sd_track* h) {
   if (h->pnp_stream) (void)hipStreamDestroy(h->pnp_stream);
   for (void* p : h->allocs) (void)hipFree(p);
   refresh_destroy(h);
+  ba_destroy(h);
   if (h->ev_fence) (void)hipEventDestroy(h->ev_fence);
   h->pose_ring.destroy();
   h->small_ring.destroy();
@@ -929,13 +931,15 @@ int sd_debug_epnp(int n, const double* Xw, const double* uv, double fx, double f
 // diagnostics: raw copy of an internal per-frame buffer (0: pnp correspondences f32[kp_cap*6], 1: pnp keypoint indices u16[kp_cap],
 // 2: what the last sd_track_fuse projected the slot with, f64[15] = Rcw row-major | tcw | Ow; the local-map row of the slot as
 // sd_track_set_local or a write-through of sd_track_refresh_points left it -- 3: desc u8[M*32], 4: normal f64[M*3], 5: min_dist
-// f32[M], 6: max_dist f32[M], 7: mf_max_dist f32[M])
+// f32[M], 6: max_dist f32[M], 7: mf_max_dist f32[M]; the slot's poses as sd_track_set_poses or a write-back of sd_track_local_ba left
+// them -- 8: Tref f64[16], 9: Tcur f64[16], column-major)
 int sd_track_debug_read(sd_track* h, int which, int frame, void* out, size_t bytes) {
   SD_REQUIRE(h && out && frame >= 0 && frame < h->max_batch, SD_ERR_INVALID_ARG, "bad arguments");
   SD_REQUIRE(which != 2 || bytes <= 15 * sizeof(double), SD_ERR_CAPACITY, "the Fuse pose of a slot is 15 doubles");
   const size_t M = (size_t)h->max_points, row = (size_t)frame * M;
   const size_t lm_bytes[5] = {M * 32, M * 24, M * 4, M * 4, M * 4};
-  SD_REQUIRE(which < 3 || (which <= 7 && bytes <= lm_bytes[which - 3]), SD_ERR_CAPACITY, "unknown buffer or more bytes than a local-map row holds");
+  SD_REQUIRE(which < 3 || (which <= 7 && bytes <= lm_bytes[which - 3]) || ((which == 8 || which == 9) && bytes <= 16 * sizeof(double)),
+             SD_ERR_CAPACITY, "unknown buffer or more bytes than a local-map row / a pose holds");
   SD_HIP_CHECK(hipSetDevice(h->device));
   SD_HIP_CHECK(hipStreamSynchronize(h->pnp_stream));
   SD_HIP_CHECK(hipStreamSynchronize(h->cur->stream));
@@ -946,6 +950,8 @@ int sd_track_debug_read(sd_track* h, int which, int frame, void* out, size_t byt
                     : which == 5 ? (const void*)(h->tb.lm_min + row)
                     : which == 6 ? (const void*)(h->tb.lm_max + row)
                     : which == 7 ? (const void*)(h->tb.lm_mfmax + row)
+                    : which == 8 ? (const void*)(h->tb.Tref + (size_t)frame * 16)
+                    : which == 9 ? (const void*)(h->tb.Tcur + (size_t)frame * 16)
                                  : (const void*)(h->tb.pnp_kpidx + (size_t)frame * h->kp_cap);
   SD_HIP_CHECK(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
   return SD_OK;

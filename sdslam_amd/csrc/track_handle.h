@@ -90,6 +90,10 @@ struct sd_track {
   std::vector<uint8_t> scw_set;    // [max_batch] sd_track_set_fuse_scw has covered the slot
   sd::FuseBuffers fu{};
   sd::RefreshBuffers rf{};         // sd_track_set_observations / _refresh_points (track_refresh.hip; refresh_create / refresh_destroy)
+  sd::BaBuffers ba{};              // sd_track_local_ba's scratch (track_ba.hip; ba_create / ba_destroy / ba_grow)
+  std::vector<uint8_t> ba_roles;   // [max_batch + 1] the roles of sd_track_set_ba_keyframes, the current keyframe's last
+  int ba_n_ref = 0;                // its n_ref_frames
+  bool ba_roles_set = false;
   sd::TrackBuffers tb{};
   sd::TrackCam cam{};
   bool have_cam = false;
@@ -136,6 +140,10 @@ inline bool RunStamp::covers(const sd_track* h, int n_frames) const {
 // track_refresh.hip: the observation block and its pinned mirror, which sd_track_set_observations may replace (not in `allocs`)
 int refresh_create(sd_track* h);
 void refresh_destroy(sd_track* h);
+// track_ba.hip: the bundle adjustment's scratch (not in `allocs`: ba_grow replaces it when the observation block grows)
+int ba_create(sd_track* h);
+void ba_destroy(sd_track* h);
+int ba_grow(sd_track* h, size_t n_obs);
 
 // What a stage that runs now computes its result on: h->res.x.set(n, BIND_X, inputs_now(h)) after it, h->res.x.live(n, inputs_now(h)) later
 static inline sd::ResultInputs inputs_now(const sd_track* h) { return {h->cur->extract_serial, h->ref->extract_serial, h->tb.cur_bcast}; }

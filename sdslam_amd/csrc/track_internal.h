@@ -304,6 +304,56 @@ struct RefreshBuffers {
 // k_refresh_centres, then k_refresh_points on the points of row `point_row`; write_local: the results also go into that row
 int launch_refresh(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const RefreshBuffers& rf, const float* d_sf, int n_batch,
                    int point_row, int write_local, hipStream_t s);
+// Optimizer::LocalBundleAdjustment (track_ba.hip): the scratch of one problem, ONE device allocation carved by ba_carve for
+// cap_points points, cap_obs observations and n_kf cameras.  sd_track_create allocates it for max_points points of 16
+// observations each and max_batch + 1 cameras (the ref frames, then the current keyframe); sd_track_set_observations replaces
+// it by a larger one where it grows its own block.  Nothing is allocated in sd_track_local_ba.
+struct BaState;
+struct BaBuffers {
+  uint8_t* base;         // the allocation (the handle's; a debug entry carves its own)
+  size_t bytes, cap_points, cap_obs;
+  int n_kf;
+  int ran_points, ran_obs;   // what sd_track_get_local_ba downloads: the lists of the last run; ran_points -1: none
+  BaState* st;           // the device state record: status, the Levenberg bookkeeping, info16
+  // per edge (= observation, CSR order)
+  double* e_meas;        // [E][3] u, v, ur (0 for a monocular edge)
+  double* e_info;        // [E]    mvInvLevelSigma2[octave]
+  double* err;           // [E][3] _error of the last computeActiveErrors that covered the edge
+  double* chi2r;         // [E]    its term of activeRobustChi2
+  double* Jl;            // [E][3][3] _jacobianOplusXi
+  double* Jp;            // [E][3][6] _jacobianOplusXj
+  double* wr;            // [E][3] omega_r
+  double* w;             // [E]    rho[1] * information
+  int32_t* e_cam;        // [E]
+  int32_t* e_pt;         // [E]
+  uint8_t* e_flag;       // [E] BA_LIVE | BA_STEREO | BA_LEVEL1 | the refusal bits
+  uint8_t* erase;        // [E] obs_erase
+  // per point
+  double* Hll;           // [P][9]
+  double* bl;            // [P][3]
+  double* X;             // [2][P][3] the two estimate buffers
+  double* X_out;         // [P][3]
+  uint8_t* p_active;     // [P] has a level-0 edge in this round
+  uint8_t* p_status;     // [P] SD_BA_POINT_*
+  double* v_scale;       // [n_kf + P] every vertex's terms of computeScale
+  // per camera
+  double* pose;          // [2][n_kf][8] SE3Quat q (x y z w), t, 0
+  double* T_out;         // [n_kf][16]
+  int32_t* slot;         // [n_kf] number among the free cameras, -1: fixed
+  uint8_t* role;         // [n_kf]
+  uint8_t* c_has;        // [n_kf] some edge observes it
+  uint8_t* c_act;        // [n_kf] free, with a level-0 edge in this round
+  // per free camera
+  double* Hpp;           // [K][36]
+  double* bp;            // [K][6]
+  int32_t* slot_cam;     // [K]
+  int32_t* coff;         // [K + 1] its edges in clist
+  int32_t* clist;        // [E]
+  // the reduced system
+  double* S;             // packed lower triangle of the (6K)^2 matrix
+  double* bs;            // [6K]
+  double* xp;            // [6K]
+};
 int launch_stereo_from_depth(const sd_orb* cur, const TrackBuffers& tb, const TrackCam& cam, const float* d_depth, int w, int h,
                              int stride_elems, size_t frame_stride_elems, int n_frames, hipStream_t s);
 // the same on a depth map of uint16_t (u16 != 0, always converted) or float elements; convert: d = (float)raw * scale

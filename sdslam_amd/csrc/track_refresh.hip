@@ -422,6 +422,7 @@ int sd_track_set_observations(sd_track* h, int n_points, const int32_t* obs_off,
     rf.obs_bytes = want;
     rf.staged = false;
   }
+  SD_TRY(ba_grow(h, (size_t)total));   // the bundle adjustment's scratch holds as many observations as this block
   if (rf.staged) SD_HIP_CHECK(hipEventSynchronize(rf.ev_staged));   // the last upload has left the pinned block
   uint8_t* st = rf.stage;
   std::memcpy(st + pk.off, obs_off, ((size_t)n_points + 1) * 4);

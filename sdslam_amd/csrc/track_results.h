@@ -117,6 +117,13 @@ constexpr EndsRow kEndsAppend[] = {
     {"sd_track_triangulate", R_APPEND},                   // the point list sd_track_get_new_points reads after an append is overwritten
 };
 
+// The local bundle adjustment (track_ba.hip), a table of its own for the same reason.  Its own result is a record of the run
+// (like an append's) and is not in this table; write_back = 0 ends nothing.
+constexpr EndsRow kEndsBa[] = {
+    // write_back = 1 rewrites Tref / Tcur and Xw of a local row: whatever sd_track_set_poses and a write-through refresh end
+    {"sd_track_local_ba(write_back)", R_SIM3 | R_TRI | R_FUSE | R_REFRESH | R_APPEND},
+};
+
 constexpr bool same_name(const char* a, const char* b) {
   while (*a && *a == *b) ++a, ++b;
   return *a == *b;
@@ -129,6 +136,8 @@ constexpr int ends_of(const char* entry) {
     if (same_name(row.entry, entry)) return (int)row.mask;
   for (const EndsRow& row : kEndsAppend)
     if (same_name(row.entry, entry)) return (int)row.mask;
+  for (const EndsRow& row : kEndsBa)
+    if (same_name(row.entry, entry)) return (int)row.mask;
   return -1;
 }
 
@@ -137,5 +146,7 @@ static_assert(ends_of("sd_track_refresh_points(write_local)") == (ends_of("sd_tr
 static_assert(ends_of("sd_track_append_new_points") == ends_of("sd_track_set_local"), "an append ends what sd_track_set_local ends");
 static_assert(ends_of("sd_track_append_new_points(mark_flags)") == (ends_of("sd_track_set_local") | ends_of("sd_track_set_point_flags")),
               "... and with mark_flags what sd_track_set_point_flags ends");
+static_assert(ends_of("sd_track_local_ba(write_back)") == (ends_of("sd_track_set_poses") | ends_of("sd_track_refresh_points(write_local)")),
+              "a write-back ends what sd_track_set_poses and a write-through refresh end");
 
 }  // namespace sd
