@@ -183,9 +183,21 @@ def _from_cm(v):
     return np.asarray(v, np.float64).reshape(4, 4).T.copy()
 
 
-def align(cur_levels, ref_levels, inv_sf, sf, Xw, T_ref, T_cur_init, K, mode=0):
+ALIGN_COUNTERFACTUALS = ("none", "reset_visible", "keep_h", "border2", "clear_stop", "gate_last", "stale_chi2")
+ALIGN_DECISIONS = ("none", "accept", "rollback_chi2", "rollback_stop", "small", "converged", "iterations")   # orc_align_trace's codes
+ALIGN_TRACE_LEVELS = (4, 3, 2)                   # the level of trace slot 0, 1, 2
+
+
+def align(cur_levels, ref_levels, inv_sf, sf, Xw, T_ref, T_cur_init, K, mode=0, trace=False, counterfactual=0, h_order=0):
     """ImageAlign::ComputePose on explicit pyramids (lists of 2-D uint8 arrays, index = level).
-    Returns dict(ok, T (4x4), error, iters (per level), chi2)."""
+    Returns dict(ok, T (4x4), error, iters (per level), chi2).  With trace=True (orc_align_trace, the same code path) also `trace`: a list
+    with one dict per level that ran, in the order 4, 3, 2: level, exit (a name of ALIGN_DECISIONS), iters, gate (the error_ that mode 2 /
+    3 compared after the level, or None), chi2 (chi2_ after the level) and `its`, one dict per iteration: n_meas, chi2_sum (the float
+    sum), new_chi2, chi2_before, error (error_ after the decision), x[6], pose (the trial pose), decision, and the per-point flags has_jac, visible, measured
+    over the points taken.  counterfactual (trace only): 0 is the reference, ALIGN_COUNTERFACTUALS names the deliberately wrong variants
+    that test cases are shown to notice; h_order=1 (trace only) forms H and Jres in the device's order, to certify cases."""
+    counterfactual = ALIGN_COUNTERFACTUALS.index(counterfactual) if isinstance(counterfactual, str) else int(counterfactual)
+    assert trace or (counterfactual == 0 and h_order == 0)
     L = lib()
     n = len(cur_levels)
     cur = [np.ascontiguousarray(a, np.uint8) for a in cur_levels]
@@ -208,9 +220,30 @@ def align(cur_levels, ref_levels, inv_sf, sf, Xw, T_ref, T_cur_init, K, mode=0):
     L.orc_align.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
                             C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    ok = L.orc_align(n, cp, rp, _p(w), _p(h), _p(sc), _p(sr), _p(inv_sf), _p(sf), _p(Xw), len(Xw), _p(Tr), _p(Tc),
-                     float(K[0]), float(K[1]), float(K[2]), float(K[3]), mode, C.byref(err), _p(iters), C.byref(chi2))
-    return dict(ok=bool(ok), T=_from_cm(Tc), error=err.value, iters=iters, chi2=chi2.value)
+    args = (n, cp, rp, _p(w), _p(h), _p(sc), _p(sr), _p(inv_sf), _p(sf), _p(Xw), len(Xw), _p(Tr), _p(Tc),
+            float(K[0]), float(K[1]), float(K[2]), float(K[3]), mode, C.byref(err), _p(iters), C.byref(chi2))
+    if not trace:
+        ok = L.orc_align(*args)
+        return dict(ok=bool(ok), T=_from_cm(Tc), error=err.value, iters=iters, chi2=chi2.value)
+    npts = len(Xw)
+    lv_i, lv_d = np.zeros((3, 4), np.int32), np.zeros((3, 2))
+    it_i, it_d, flags = np.zeros((3, 30, 2), np.int32), np.zeros((3, 30, 28)), np.zeros((3, 30, max(npts, 1)), np.uint8)
+    L.orc_align_trace.argtypes = L.orc_align.argtypes + [C.c_void_p] * 5 + [C.c_int, C.c_int]
+    ok = L.orc_align_trace(*args, _p(lv_i), _p(lv_d), _p(it_i), _p(it_d), _p(flags), counterfactual, int(h_order))
+    taken = min(npts, 100 if mode in (2, 3) else 300)
+    levels = []
+    for s in range(3):
+        if not lv_i[s, 0]:
+            continue
+        its = []
+        for i in range(lv_i[s, 2]):
+            f = flags[s, i, :taken]
+            its.append(dict(n_meas=int(it_i[s, i, 0]), decision=ALIGN_DECISIONS[it_i[s, i, 1]], chi2_sum=it_d[s, i, 0], new_chi2=it_d[s, i, 1],
+                            chi2_before=it_d[s, i, 2], error=it_d[s, i, 3], x=it_d[s, i, 4:10].copy(), pose=it_d[s, i, 12:28].reshape(4, 4).copy(), has_jac=(f & 1) != 0,
+                            visible=(f & 2) != 0, measured=(f & 4) != 0))
+        levels.append(dict(level=ALIGN_TRACE_LEVELS[s], exit=ALIGN_DECISIONS[lv_i[s, 1]], iters=int(lv_i[s, 2]),
+                           gate=float(lv_d[s, 0]) if lv_i[s, 3] else None, chi2=float(lv_d[s, 1]), its=its))
+    return dict(ok=bool(ok), T=_from_cm(Tc), error=err.value, iters=iters, chi2=chi2.value, trace=levels)
 
 
 def se3_exp(update6):

@@ -19,10 +19,15 @@
 // reference leaves cv::Mat memory uninitialised; rows are always written before being read
 // for a visible point).  Parity status: UNPINNED (no reference tests); pinned by the
 // known-answer tests in tests/test_oracle_align.py.  Built with -ffp-contract=off.
+// orc_align_trace runs the same struct with a report per level and iteration, one of six deliberately wrong variants
+// (AlignCounterfactual) or the device's order of forming H; with none of them set it is orc_align operation for operation
+// (tests/align_cases.py, tests/test_align_cases_cpu.py).
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
+
+#include "oracle_api.h"
 
 namespace orc {
 
@@ -131,6 +136,28 @@ static void ldlt_solve6(const double Hin[6][6], const double b[6], double x[6]) 
   for (int i = 0; i < n; i++) x[i] = d[i];
 }
 
+// Ways of getting ImageAlign wrong that a test case should notice (orc_align_trace only); each breaks ONE quirk
+enum AlignCounterfactual {
+  ACF_NONE = 0,
+  ACF_RESET_VISIBLE = 1,   // visible_pts_ cleared at every level
+  ACF_KEEP_H = 2,          // H_ keeps the J J^T of points that have a Jacobian but no measurement at the trial pose
+  ACF_BORDER2 = 3,         // the current-frame clip of ComputeResiduals with a border of 2 instead of 3
+  ACF_CLEAR_STOP = 4,      // stop_ cleared at every level
+  ACF_GATE_LAST = 5,       // the mode-2 gate error_ > 0.01 checked after the last level only
+  ACF_STALE_CHI2 = 6,      // a point without a measurement keeps its previous squared residuals in the chi2 sum
+};
+enum AlignDecision { AD_NONE = 0, AD_ACCEPT = 1, AD_ROLLBACK_CHI2 = 2, AD_ROLLBACK_STOP = 3, AD_SMALL = 4, AD_CONVERGED = 5, AD_ITERATIONS = 6 };
+
+// What orc_align_trace reports on top of orc_align.  Level slot s = max_level_ - level (0: level 4, 1: level 3, 2: level 2).
+struct AlignTrace {
+  int* lv_i;        // [3][4]: level ran, exit taken (AlignDecision), iterations, gate compared (modes 2 / 3)
+  double* lv_d;     // [3][2]: the error_ the gate compared; chi2_ after the level
+  int* it_i;        // [3][30][2]: n_meas, decision (AlignDecision; AD_NONE: iteration not run)
+  double* it_d;     // [3][30][28]: float chi2 sum, new_chi2, chi2_ before the comparison, error_ after the decision, x[6], -, -, the trial pose (row-major)
+  uint8_t* flags;   // [3][30][stride]: per point bit 0 has_jac, bit 1 visible, bit 2 measured
+  int stride;
+};
+
 struct ImgView { const uint8_t* data; int cols, rows, step; const uint8_t* ptr(int y) const { return data + (size_t)y * step; } };
 
 struct ImageAlign {
@@ -147,6 +174,28 @@ struct ImageAlign {
   double Jres_[6];
   std::vector<double> jacobian_cache_;   // 6 x (size*16), column-major
   int iters_per_level[16];
+  // ---- orc_align_trace only (tr_ == NULL, cf_ == 0, h_order_ == 0: exactly ImageAlign) ----
+  const AlignTrace* tr_ = nullptr;
+  int cf_ = ACF_NONE;
+  int h_order_ = 0;                      // 1: H_ and Jres_ formed per point from the three gradient sums, as k_align forms them
+  M4 trial_pose_;                        // se3 * last_pose of the last ComputeResiduals
+  float chi2_sum_ = 0.f;                 // the float chi2 sum of the last ComputeResiduals
+  std::vector<bool> has_jac_, measured_; // jacobian_cache_ columns of the point are non-zero at this level / measured at the trial pose
+  std::vector<float> prev_sq_;           // ACF_STALE_CHI2: the 16 squared residuals of a point's last measurement
+  std::vector<float> grad_;              // h_order_ 1: dx, dy of every patch pixel
+  std::vector<double> pt_jac_;           // h_order_ 1: per point J0[6], J1[6], S dx^2, S dx dy, S dy^2
+  double Hlvl_[6][6];                    // h_order_ 1: H of the level's points with a Jacobian
+
+  void PointH(size_t counter, double f2, double sign, double H[6][6]) const {
+    const double* q = &pt_jac_[counter * 15];
+    const double ha = q[12] * f2, hb = q[13] * f2, hc = q[14] * f2;
+    for (int a = 0; a < 6; a++)
+      for (int b = a; b < 6; b++) {
+        const double v = ha * (q[a] * q[b]) + hb * (q[a] * q[6 + b] + q[6 + a] * q[b]) + hc * (q[6 + a] * q[6 + b]);
+        H[a][b] += sign * v;
+        if (b != a) H[b][a] += sign * v;
+      }
+  }
 
   bool Project(const double R[3][3], const double T[3], const V3& p, double res[2]) const {
     double x3Dc[3];
@@ -247,9 +296,15 @@ struct ImageAlign {
       if (u_first_i - border < 0 || v_first_i - border < 0 || u_first_i + border >= src.cols || v_first_i + border >= src.rows)
         continue;
       visible_pts_[counter] = true;
+      has_jac_[counter] = true;
       double xyz[3];
       for (int i = 0; i < 3; i++) xyz[i] = (R[i][0] * p.v[0] + R[i][1] * p.v[1] + R[i][2] * p.v[2]) + T[i];
       Jacobian3DToPlane(xyz, frame_jac);
+      if (h_order_) {
+        double* q = &pt_jac_[counter * 15];
+        for (int k = 0; k < 6; k++) { q[k] = frame_jac[0][k]; q[6 + k] = frame_jac[1][k]; }
+        q[12] = q[13] = q[14] = 0;
+      }
       const float subpix_u_ref = u_ref - u_first_i;
       const float subpix_v_ref = v_ref - v_first_i;
       const float w_tl = (1.0 - subpix_u_ref) * (1.0 - subpix_v_ref);
@@ -272,6 +327,12 @@ struct ImageAlign {
           double* J = &jacobian_cache_[(counter * patch_area + pixel_counter) * 6];
           const double f = cam_fx_ * scale;
           for (int k = 0; k < 6; k++) J[k] = (dx * frame_jac[0][k] + dy * frame_jac[1][k]) * f;
+          if (h_order_) {
+            grad_[(counter * patch_area + pixel_counter) * 2] = dx;
+            grad_[(counter * patch_area + pixel_counter) * 2 + 1] = dy;
+            double* q = &pt_jac_[counter * 15];
+            q[12] += (double)dx * dx; q[13] += (double)dx * dy; q[14] += (double)dy * dy;
+          }
         }
       }
     }
@@ -281,23 +342,50 @@ struct ImageAlign {
     const int half_patch = patch_size_ / 2, patch_area = patch_size_ * patch_size_, border = half_patch + 1;
     if (patches) PrecomputePatches(last_img, last_pose, scale);
     M4 pose = m4_mul(se3, last_pose);
+    trial_pose_ = pose;
     double R[3][3], T[3];
     for (int i = 0; i < 3; i++) {
       for (int j = 0; j < 3; j++) R[i][j] = pose.m[i][j];
       T[i] = pose.m[i][3];
     }
     float chi2 = 0.0;
+    const int border_cur = cf_ == ACF_BORDER2 ? half_patch : border;
+    const double fscale = cam_fx_ * scale;
+    if (h_order_) {
+      if (patches) {
+        memset(Hlvl_, 0, sizeof(Hlvl_));
+        for (size_t counter = 0; counter < points_.size(); counter++)
+          if (has_jac_[counter]) PointH(counter, fscale * fscale, 1.0, Hlvl_);
+      }
+      memcpy(H_, Hlvl_, sizeof(H_));
+    }
     for (size_t counter = 0; counter < points_.size(); counter++) {
-      if (!visible_pts_[counter]) continue;
-      double p2d[2];
-      if (!Project(R, T, points_[counter], p2d)) continue;
+      measured_[counter] = false;
+      double p2d[2] = {0, 0};
+      bool in_view = visible_pts_[counter] && Project(R, T, points_[counter], p2d);
       const float u_cur = p2d[0] * scale;
       const float v_cur = p2d[1] * scale;
       const int u_last_i = floorf(u_cur);
       const int v_last_i = floorf(v_cur);
-      if (u_last_i < 0 || v_last_i < 0 || u_last_i - border < 0 || v_last_i - border < 0 || u_last_i + border >= src.cols ||
-          v_last_i + border >= src.rows)
+      if (in_view && (u_last_i < 0 || v_last_i < 0 || u_last_i - border_cur < 0 || v_last_i - border_cur < 0 ||
+                      u_last_i + border_cur >= src.cols || v_last_i + border_cur >= src.rows))
+        in_view = false;
+      if (!in_view) {   // the reference: continue.  What the counterfactuals and the device's order of H do with such a point:
+        if (has_jac_[counter]) {
+          if (cf_ == ACF_KEEP_H)
+            for (int k = 0; k < patch_area; k++) {
+              const double* J = &jacobian_cache_[(counter * patch_area + k) * 6];
+              for (int a = 0; a < 6; a++)
+                for (int b = 0; b < 6; b++) H_[a][b] += J[a] * J[b];
+            }
+          if (h_order_) PointH(counter, fscale * fscale, -1.0, H_);
+        }
+        if (cf_ == ACF_STALE_CHI2)
+          for (int k = 0; k < patch_area; k++) chi2 += prev_sq_[counter * patch_area + k];
         continue;
+      }
+      measured_[counter] = true;
+      double s1 = 0, s2 = 0;   // h_order_ 1: S dx res, S dy res
       const float subpix_u_cur = u_cur - u_last_i;
       const float subpix_v_cur = v_cur - v_last_i;
       const float w_tl = (1.0 - subpix_u_cur) * (1.0 - subpix_v_cur);
@@ -315,6 +403,14 @@ struct ImageAlign {
           float weight = 1.0;
           chi2 += res * res * weight;
           n_meas_++;
+          if (cf_ == ACF_STALE_CHI2) prev_sq_[counter * patch_area + pixel_counter] = res * res * weight;
+          if (h_order_) {
+            if (has_jac_[counter]) {
+              s1 += (double)grad_[(counter * patch_area + pixel_counter) * 2] * (double)res;
+              s2 += (double)grad_[(counter * patch_area + pixel_counter) * 2 + 1] * (double)res;
+            }
+            continue;
+          }
           const double* J = &jacobian_cache_[(counter * patch_area + pixel_counter) * 6];
           for (int a = 0; a < 6; a++) {
             for (int b = 0; b < 6; b++) H_[a][b] += J[a] * J[b] * weight;
@@ -322,7 +418,12 @@ struct ImageAlign {
           }
         }
       }
+      if (h_order_ && has_jac_[counter]) {
+        const double* q = &pt_jac_[counter * 15];
+        for (int a = 0; a < 6; a++) Jres_[a] += -(q[a] * s1 + q[6 + a] * s2) * fscale;
+      }
     }
+    chi2_sum_ = chi2;
     return chi2 / n_meas_;
   }
 
@@ -331,6 +432,10 @@ struct ImageAlign {
     M4 se3_bk = se3;
     bool small = false;
     int its = 0;
+    std::fill(has_jac_.begin(), has_jac_.end(), false);   // jacobian_cache_ was set to zero before the call
+    if (cf_ == ACF_RESET_VISIBLE) std::fill(visible_pts_.begin(), visible_pts_.end(), false);
+    if (cf_ == ACF_CLEAR_STOP) stop_ = false;
+    int exit_taken = AD_ITERATIONS;
     for (int i = 0; i < max_its_; i++) {
       its = i + 1;
       memset(H_, 0, sizeof(H_));
@@ -340,8 +445,11 @@ struct ImageAlign {
       if (n_meas_ == 0) stop_ = true;
       ldlt_solve6(H_, Jres_, x);
       if (std::isnan(x[0])) stop_ = true;
+      const double chi2_before = chi2_;
       if ((i > 0 && new_chi2 > chi2_) || stop_) {
         se3 = se3_bk;
+        exit_taken = stop_ ? AD_ROLLBACK_STOP : AD_ROLLBACK_CHI2;
+        Record(level, i, exit_taken, new_chi2, chi2_before, x);
         break;
       }
       if (i > 0 && new_chi2 > chi2_ * 0.99) small = true;
@@ -354,15 +462,44 @@ struct ImageAlign {
       for (int k = 0; k < 6; k++)
         if (std::fabs(x[k]) > mx) mx = std::fabs(x[k]);
       error_ = mx;
-      if (error_ <= 1e-10 || small) break;
+      const bool done = error_ <= 1e-10 || small;
+      if (done) exit_taken = error_ <= 1e-10 ? AD_CONVERGED : AD_SMALL;
+      Record(level, i, done ? exit_taken : AD_ACCEPT, new_chi2, chi2_before, x);
+      if (done) break;
     }
     if (level >= 0 && level < 16) iters_per_level[level] = its;
+    if (tr_ && max_level_ - level >= 0 && max_level_ - level < 3) {
+      const int s = max_level_ - level;
+      tr_->lv_i[s * 4 + 0] = 1;
+      tr_->lv_i[s * 4 + 1] = exit_taken;
+      tr_->lv_i[s * 4 + 2] = its;
+      tr_->lv_d[s * 2 + 1] = chi2_;
+    }
+  }
+
+  void Record(int level, int i, int decision, double new_chi2, double chi2_before, const double x[6]) const {
+    const int s = max_level_ - level;
+    if (!tr_ || s < 0 || s >= 3 || i >= 30) return;
+    tr_->it_i[(s * 30 + i) * 2 + 0] = (int)n_meas_;
+    tr_->it_i[(s * 30 + i) * 2 + 1] = decision;
+    double* d = &tr_->it_d[(s * 30 + i) * 28];
+    d[0] = chi2_sum_; d[1] = new_chi2; d[2] = chi2_before; d[3] = error_;
+    for (int k = 0; k < 6; k++) d[4 + k] = x[k];
+    for (int k = 0; k < 16; k++) d[12 + k] = trial_pose_.m[k / 4][k % 4];
+    uint8_t* f = &tr_->flags[(size_t)(s * 30 + i) * tr_->stride];
+    for (size_t p = 0; p < points_.size() && (int)p < tr_->stride; p++)
+      f[p] = (has_jac_[p] ? 1 : 0) | (visible_pts_[p] ? 2 : 0) | (measured_[p] ? 4 : 0);
   }
 };
 
 }  // namespace orc
 
 using namespace orc;
+
+static int align_impl(int nlevels, const uint8_t* const* cur_lv, const uint8_t* const* ref_lv, const int* lv_w, const int* lv_h,
+                      const int* lv_step_cur, const int* lv_step_ref, const float* inv_sf, const float* sf, const double* Xw, int npts,
+                      const double* Tref_cm, double* Tcur_cm_inout, double fx, double fy, double cx, double cy, int mode, double* error_out,
+                      int* iters_out, double* chi2_out, const AlignTrace* tr, int counterfactual, int h_order);
 
 extern "C" {
 
@@ -376,7 +513,38 @@ int orc_align(int nlevels, const uint8_t* const* cur_lv, const uint8_t* const* r
               const int* lv_step_cur, const int* lv_step_ref, const float* inv_sf, const float* sf, const double* Xw, int npts,
               const double* Tref_cm, double* Tcur_cm_inout, double fx, double fy, double cx, double cy, int mode, double* error_out,
               int* iters_out /* nlevels, may be NULL */, double* chi2_out /* may be NULL */) {
+  return align_impl(nlevels, cur_lv, ref_lv, lv_w, lv_h, lv_step_cur, lv_step_ref, inv_sf, sf, Xw, npts, Tref_cm, Tcur_cm_inout, fx, fy, cx, cy,
+                    mode, error_out, iters_out, chi2_out, nullptr, ACF_NONE, 0);
+}
+
+// The same call -- the same ImageAlign struct, the same code path -- with a trace per level and iteration (struct AlignTrace: lv_i
+// [3][4], lv_d [3][2], it_i [3][30][2], it_d [3][30][28], flags [3][30][npts]; zeroed here).  counterfactual: 0 is the reference
+// (and what orc_align does); 1 .. 6 (enum AlignCounterfactual) each break ONE quirk, so that tests/test_align_cases_cpu.py can show
+// which cases notice.  h_order 1 forms H_ and Jres_ per point from the three gradient sums (the level's H over the points with a
+// Jacobian, minus the terms of those without a measurement), the order of k_align: used to certify cases, never as the expected value.
+int orc_align_trace(int nlevels, const uint8_t* const* cur_lv, const uint8_t* const* ref_lv, const int* lv_w, const int* lv_h,
+                    const int* lv_step_cur, const int* lv_step_ref, const float* inv_sf, const float* sf, const double* Xw, int npts,
+                    const double* Tref_cm, double* Tcur_cm_inout, double fx, double fy, double cx, double cy, int mode, double* error_out,
+                    int* iters_out, double* chi2_out, int* lv_i, double* lv_d, int* it_i, double* it_d, uint8_t* flags, int counterfactual,
+                    int h_order) {
+  const AlignTrace t = {lv_i, lv_d, it_i, it_d, flags, npts};
+  memset(lv_i, 0, sizeof(int) * 12);
+  memset(lv_d, 0, sizeof(double) * 6);
+  memset(it_i, 0, sizeof(int) * 180);
+  memset(it_d, 0, sizeof(double) * 2520);
+  memset(flags, 0, (size_t)90 * (npts > 0 ? npts : 0));
+  return align_impl(nlevels, cur_lv, ref_lv, lv_w, lv_h, lv_step_cur, lv_step_ref, inv_sf, sf, Xw, npts, Tref_cm, Tcur_cm_inout, fx, fy, cx, cy,
+                    mode, error_out, iters_out, chi2_out, &t, counterfactual, h_order);
+}
+
+}  // extern "C"
+
+static int align_impl(int nlevels, const uint8_t* const* cur_lv, const uint8_t* const* ref_lv, const int* lv_w, const int* lv_h,
+                      const int* lv_step_cur, const int* lv_step_ref, const float* inv_sf, const float* sf, const double* Xw, int npts,
+                      const double* Tref_cm, double* Tcur_cm_inout, double fx, double fy, double cx, double cy, int mode, double* error_out,
+                      int* iters_out, double* chi2_out, const AlignTrace* tr, int counterfactual, int h_order) {
   ImageAlign A;
+  A.tr_ = tr; A.cf_ = counterfactual; A.h_order_ = h_order;
   memset(A.iters_per_level, 0, sizeof(A.iters_per_level));
   A.cam_fx_ = fx; A.cam_fy_ = fy; A.cam_cx_ = cx; A.cam_cy_ = cy;
   if (error_out) *error_out = A.error_;
@@ -389,6 +557,20 @@ int orc_align(int nlevels, const uint8_t* const* cur_lv, const uint8_t* const* r
   A.patch_cache_.assign((size_t)size * 16, 0.f);
   A.visible_pts_.assign(size, false);
   A.jacobian_cache_.assign((size_t)size * 16 * 6, 0.0);
+  A.has_jac_.assign(size, false);
+  A.measured_.assign(size, false);
+  if (counterfactual == ACF_STALE_CHI2) A.prev_sq_.assign((size_t)size * 16, 0.f);
+  if (h_order) {
+    A.grad_.assign((size_t)size * 16 * 2, 0.f);
+    A.pt_jac_.assign((size_t)size * 15, 0.0);
+  }
+  auto gate = [&](int level, double limit) {   // the comparison of modes 2 and 3 after a level, traced
+    if (tr) {
+      tr->lv_i[(A.max_level_ - level) * 4 + 3] = 1;
+      tr->lv_d[(A.max_level_ - level) * 2] = A.error_;
+    }
+    return A.error_ > limit;
+  };
   M4 last_pose = m4_from_colmajor(Tref_cm);
   M4 cur_pose = m4_from_colmajor(Tcur_cm_inout);
   M4 current_se3 = (mode == 3) ? m4_identity() : m4_mul(cur_pose, pose_inverse(last_pose));
@@ -399,7 +581,7 @@ int orc_align(int nlevels, const uint8_t* const* cur_lv, const uint8_t* const* r
     std::fill(A.jacobian_cache_.begin(), A.jacobian_cache_.end(), 0.0);
     float scale = 1.0 / sf[level];
     A.Optimize(view(cur_lv, lv_step_cur, level), view(ref_lv, lv_step_ref, level), last_pose, current_se3, scale, level);
-    if (A.error_ > 0.03) {
+    if (gate(level, 0.03)) {
       A.error_ = 1e10;
       ret = 0;
     }
@@ -408,7 +590,7 @@ int orc_align(int nlevels, const uint8_t* const* cur_lv, const uint8_t* const* r
       std::fill(A.jacobian_cache_.begin(), A.jacobian_cache_.end(), 0.0);
       float scale = inv_sf[level];
       A.Optimize(view(cur_lv, lv_step_cur, level), view(ref_lv, lv_step_ref, level), last_pose, current_se3, scale, level);
-      if (mode == 2 && A.error_ > 0.01) {
+      if (mode == 2 && (counterfactual != ACF_GATE_LAST || level == A.min_level_) && gate(level, 0.01)) {
         A.error_ = 1e10;
         ret = 0;
         break;
@@ -425,6 +607,8 @@ int orc_align(int nlevels, const uint8_t* const* cur_lv, const uint8_t* const* r
   if (chi2_out) *chi2_out = A.chi2_;
   return ret;
 }
+
+extern "C" {
 
 // stage-level helpers for known-answer tests
 void orc_se3_exp(const double* update6, double* T_cm) { m4_to_colmajor(ImageAlign::Exp(update6), T_cm); }
