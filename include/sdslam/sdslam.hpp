@@ -868,6 +868,141 @@ class Optimizer {
       }
     return true;
   }
+  // void Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust)          src/Optimizer.cc:53-219
+  // on the device (sd_track_global_ba).  Every keyframe is a frame of the ref extractor: frameOf(KeyFrameT*) returns it, or a
+  // negative number when the keyframe is not resident (its observations then refuse the call, as in LocalBundleAdjustment); the
+  // current-keyframe slot is not used (it is given role 2 and no observation).  Entry i of local row `point_row` is vpMP[i]; a
+  // NULL or bad point is sent as a bad one.  Roles: a keyframe of vpKFs that is not bad is 1, with mnId == 0 it is 2; a bad one has
+  // none and its observations carry obs_kf_bad; so do the observations of a keyframe with mnId > maxKFid (:109).  An observation
+  // of any other keyframe outside vpKFs is the edge to a missing vertex the reference would dereference: SD_BA_NO_VERTEX.
+  // *pbStopFlag is read once, before anything is uploaded; inside the run it is not modelled.  With nLoopKF == 0 the run writes
+  // back, and then, in the reference's order (:185-217): SetPose on every keyframe of vpKFs that is not bad, and for every point
+  // that was included SetWorldPos followed by the refresh's values that are UpdateNormalAndDepth (a point whose reference keyframe
+  // does not observe it, or with an observation of a keyframe that is not resident, gets the position only).  Otherwise nothing is written back and mTcwGBA / mnBAGlobalForKF of the
+  // keyframes and mPosGBA / mnBAGlobalForKF of the included points are set from the getter (16 and 3 doubles behind .data()).
+  // Returns false, with no object touched, when the flag is set or the device refuses the problem.
+  // KeyFrameT needs mnId, N, mvuRight, isBad(), GetPose(), SetPose(const double*), mTcwGBA, mnBAGlobalForKF; MapPointT what
+  // ORBmatcher::Fuse's point upload needs, GetObservations(), GetReferenceKeyFrame(), SetWorldPos(const double*), the three setters
+  // of the refresh, mPosGBA, mnBAGlobalForKF.
+  template <class KeyFrameT, class MapPointT, class FrameOf>
+  static bool BundleAdjustment(TrackBatch& batch, const std::vector<KeyFrameT*>& vpKFs, const std::vector<MapPointT*>& vpMP, int nIterations,
+                               bool* pbStopFlag, const unsigned long nLoopKF, const bool bRobust, FrameOf frameOf, int point_row = 0) {
+    if (pbStopFlag && *pbStopFlag) return false;
+    if (vpMP.size() > (size_t)batch.max_points()) throw Error(SD_ERR_CAPACITY, "BundleAdjustment: more points than the batch's max_points");
+    GlobalBaLists<KeyFrameT> L;
+    BuildGlobalBaLists(vpKFs, vpMP, frameOf, L);
+    sd_track* h = batch.handle();
+    ORBmatcher matcher(0.6f, false);
+    matcher.UploadFusePoints(batch, point_row, vpMP, true, [](MapPointT*) { return false; });
+    for (size_t k = 0; k < L.resident.size(); k++) {
+      const auto T = L.resident[k]->GetPose();
+      check(sd_track_set_poses(h, L.resident_frame[k], 1, T.data(), T.data()));
+      if (L.resident[k]->N > 0) check(sd_track_set_uright_ref(h, L.resident_frame[k], 1, L.resident[k]->mvuRight.data(), L.resident[k]->N));
+    }
+    const int n = (int)vpMP.size(), n_ref = (int)L.kf_role.size();
+    check(sd_track_set_ba_keyframes(h, n_ref, L.kf_role.data(), 2));
+    check(sd_track_set_observations(h, n, L.obs.off.data(), L.obs.frame.data(), L.obs.kp.data(), L.ba_kf_bad.data(), L.obs.ref_obs.data(),
+                                    L.obs.point_bad.data()));
+    check(sd_track_global_ba(h, point_row, nIterations, bRobust ? 1 : 0, nLoopKF == 0 ? 1 : 0));
+    std::vector<double> T_ref((size_t)n_ref * 16 + 16, 0.0), Xw((size_t)n * 3 + 3, 0.0);
+    std::vector<uint8_t> point_status((size_t)n + 1, 0);
+    double T_cur[16];
+    int32_t info[16];
+    check(sd_track_get_global_ba(h, T_ref.data(), T_cur, Xw.data(), point_status.data(), info, n));
+    if (info[0] != SD_BA_OK) return false;
+    if (nLoopKF != 0) {
+      for (size_t k = 0; k < L.resident.size(); k++) {
+        std::memcpy(L.resident[k]->mTcwGBA.data(), &T_ref[(size_t)L.resident_frame[k] * 16], 128);
+        L.resident[k]->mnBAGlobalForKF = nLoopKF;
+      }
+      for (int i = 0; i < n; i++)
+        if (point_status[(size_t)i] == SD_BA_POINT_OPTIMISED) {   // !vbNotIncludedMP[i]
+          std::memcpy(vpMP[(size_t)i]->mPosGBA.data(), &Xw[(size_t)i * 3], 24);
+          vpMP[(size_t)i]->mnBAGlobalForKF = nLoopKF;
+        }
+      return true;
+    }
+    ORBmatcher::RefreshedRows rr((size_t)n);
+    if (n > 0) {   // UpdateNormalAndDepth reads every observation: the lists with isBad() alone, on the poses and positions written back
+      if (L.ba_kf_bad != L.obs.kf_bad)
+        check(sd_track_set_observations(h, n, L.obs.off.data(), L.obs.frame.data(), L.obs.kp.data(), L.obs.kf_bad.data(), L.obs.ref_obs.data(),
+                                        L.obs.point_bad.data()));
+      check(sd_track_refresh_points(h, point_row, 1));
+      check(sd_track_get_refreshed(h, rr.status.data(), nullptr, nullptr, nullptr, rr.normal.data(), rr.max_dist.data(), rr.min_dist.data(), n));
+    }
+    for (size_t k = 0; k < L.resident.size(); k++) L.resident[k]->SetPose(&T_ref[(size_t)L.resident_frame[k] * 16]);
+    for (int i = 0; i < n; i++) {
+      if (point_status[(size_t)i] != SD_BA_POINT_OPTIMISED) continue;
+      vpMP[(size_t)i]->SetWorldPos(&Xw[(size_t)i * 3]);
+      if ((rr.status[(size_t)i] & SD_REFRESH_NORMAL) && !L.obs.left[(size_t)i]) {
+        vpMP[(size_t)i]->SetNormalVector(&rr.normal[(size_t)i * 3]);
+        vpMP[(size_t)i]->SetMaxDistance(rr.max_dist[(size_t)i]);
+        vpMP[(size_t)i]->SetMinDistance(rr.min_dist[(size_t)i]);
+      }
+    }
+    return true;
+  }
+  // void Optimizer::GlobalBundleAdjustemnt(Map* pMap, int nIterations = 5, bool* pbStopFlag = NULL, nLoopKF = 0, bRobust = true)   :46-50
+  // (frameOf follows the reference's parameters, so their defaults cannot be kept: every argument is given)
+  template <class MapT, class FrameOf>
+  static bool GlobalBundleAdjustemnt(TrackBatch& batch, MapT* pMap, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF,
+                                     const bool bRobust, FrameOf frameOf, int point_row = 0) {
+    return BundleAdjustment(batch, pMap->GetAllKeyFrames(), pMap->GetAllMapPoints(), nIterations, pbStopFlag, nLoopKF, bRobust, frameOf, point_row);
+  }
+  template <class KeyFrameT>
+  struct GlobalBaLists {
+    std::vector<KeyFrameT*> resident;            // the keyframes of vpKFs that are not bad and are frames of the ref extractor, in vpKFs order ...
+    std::vector<int> resident_frame;             // ... and their frames
+    std::vector<uint8_t> kf_role;                // sd_track_set_ba_keyframes
+    ORBmatcher::ObservationLists obs;            // kf_bad: isBad() (what the refresh is given); left[i]: the reference keyframe is not an observation
+    std::vector<uint8_t> ba_kf_bad;              // ... || mnId > maxKFid (what the bundle adjustment is given)
+  };
+  // Host code only: the roles (:74-85) and the CSR lists (:102-110)
+  template <class KeyFrameT, class MapPointT, class FrameOf>
+  static void BuildGlobalBaLists(const std::vector<KeyFrameT*>& vpKFs, const std::vector<MapPointT*>& vpMP, FrameOf frameOf, GlobalBaLists<KeyFrameT>& L) {
+    unsigned long maxKFid = 0;
+    L.resident.clear(); L.resident_frame.clear(); L.kf_role.clear();
+    for (KeyFrameT* kf : vpKFs) {
+      if (kf->isBad()) continue;
+      if (kf->mnId > maxKFid) maxKFid = kf->mnId;
+      const int f = (int)frameOf(kf);
+      if (f < 0) continue;
+      L.resident.push_back(kf);
+      L.resident_frame.push_back(f);
+      if (L.kf_role.size() <= (size_t)f) L.kf_role.resize((size_t)f + 1, 0);
+      L.kf_role[(size_t)f] = kf->mnId == 0 ? 2 : 1;
+    }
+    ORBmatcher::ObservationLists& O = L.obs;
+    const size_t n = vpMP.size();
+    O.off.assign(1, 0);
+    O.frame.clear(); O.kp.clear(); O.kf_bad.clear(); L.ba_kf_bad.clear();
+    O.ref_obs.assign(n, 0); O.point_bad.assign(n, 0); O.left.assign(n, 0);
+    for (size_t i = 0; i < n; i++) {
+      MapPointT* pMP = vpMP[i];
+      if (!pMP || pMP->isBad()) {
+        O.point_bad[i] = 1;
+        O.off.push_back((int32_t)O.frame.size());
+        continue;
+      }
+      const KeyFrameT* pRefKF = pMP->GetReferenceKeyFrame();
+      int32_t pos = 0, ref_pos = -1;
+      for (const auto& ob : pMP->GetObservations()) {
+        KeyFrameT* pKFi = ob.first;
+        const int f = (int)frameOf(pKFi);
+        O.frame.push_back(f < 0 ? -2 : f);
+        O.kp.push_back((int32_t)ob.second);
+        O.kf_bad.push_back(pKFi->isBad() ? 1 : 0);
+        L.ba_kf_bad.push_back(pKFi->isBad() || pKFi->mnId > maxKFid ? 1 : 0);
+        if (pKFi == pRefKF) ref_pos = pos;
+        pos++;
+      }
+      if (pos > 0 && ref_pos < 0) O.left[i] = 1;
+      O.ref_obs[i] = ref_pos < 0 ? 0 : ref_pos;
+      O.off.push_back((int32_t)O.frame.size());
+    }
+    if (O.frame.empty()) O.frame.push_back(0), O.kp.push_back(0), O.kf_bad.push_back(0), L.ba_kf_bad.push_back(0);
+    if (O.ref_obs.empty()) O.ref_obs.push_back(0), O.point_bad.push_back(0);
+  }
   // lLocalKeyFrames, lLocalMapPoints and (through `resident`) lFixedCameras, and what the device is given for them
   template <class KeyFrameT, class MapPointT>
   struct LocalBaLists {

@@ -648,6 +648,42 @@ int sd_debug_local_ba(int n_points, const int32_t* obs_off, const int32_t* obs_k
                       const uint8_t* kf_role, const double* Xw, const float* cam9, double* T_out_cm16, double* Xw_out,
                       uint8_t* point_status, uint8_t* obs_erase, int32_t* info16);
 
+/* Optimizer::BundleAdjustment / GlobalBundleAdjustemnt (src/Optimizer.cc:46-219) on the same lists: points, observations and
+ *   keyframes are those of sd_track_set_observations / sd_track_set_ba_keyframes, point i is entry i of row point_row, obs_frame
+ *   >= 0 is a ref frame with Tref, -1 the current keyframe with Tcur of slot 0.  The roles are read for this call as 1 = a free
+ *   vertex, 2 = a fixed vertex (mnId == 0, :81), 0 = not a keyframe of vpKFs.  A live observation (point not bad, obs_kf_bad clear)
+ *   whose camera has role 0 would be an edge to a vertex that does not exist: the call refuses with SD_BA_NO_VERTEX.  The other
+ *   refusals are local BA's, in its order, SD_BA_NO_VERTEX last; SD_BA_TOO_MANY_KF: more than min(SD_GBA_MAX_FREE_KF,
+ *   max_batch + 1) cameras with role 1.  A point that is bad or has no edge is vbNotIncludedMP (:170-175): SD_BA_POINT_SKIPPED,
+ *   its position kept; a free keyframe without an edge keeps its pose.
+ * Edges as in local BA; with robust = 1 Huber with (float)sqrt(5.99) (sic, :87) for mono and (float)sqrt(7.815) for stereo edges,
+ *   with robust = 0 no kernel.  The run: initializeOptimization() and ONE optimize(n_iterations), 1 <= n_iterations <=
+ *   SD_GBA_MAX_ITERATIONS, by the Levenberg driver local BA restates (lambda from computeLambdaInit, at most ten trials an
+ *   iteration, the exits on rho == 0, ten rejected trials and _nBad >= 3, a zero pivot fails the trial with x = 0); no
+ *   classification.  pbStopFlag is not modelled.  The reduced system of up to SD_BA_MAX_FREE_KF free cameras is factorised in LDS
+ *   as in local BA, a larger one by a blocked LDL^T in global memory (panels of 48 columns, no pivoting, index order).
+ * sd_track_global_ba is queued on the tracking stream: no host wait, no allocation.  write_back = 1 (the nLoopKF == 0 branch), only
+ *   on SD_BA_OK: poses of the observed free cameras to Tref / Tcur, the optimised points to Xw of the row; it ends the cached
+ *   results local BA's write-back ends.  write_back = 0 (nLoopKF != 0) writes nothing: mTcwGBA / mPosGBA are read through
+ *   sd_track_get_global_ba (synchronises; NULL outputs are skipped), which answers a global run only (as sd_track_get_local_ba a
+ *   local one) and not after sd_track_set_poses.  info16 = {status, n_free, n_fixed, n_points, n_edges_mono, n_edges_stereo,
+ *   iterations, trials, exit, 0...}, exits numbered as in local BA.
+ * sd_debug_global_ba: sd_debug_local_ba's inputs, n_iterations and robust; no obs_erase.
+ * sd_debug_ldlt: only the blocked factorisation and both substitutions on a host matrix, synchronous, with buffers of its own:
+ *   A_packed_lower is the lower triangle in row order (entry (r, c), c <= r, at r (r + 1) / 2 + c), 1 <= n <= 6 *
+ *   SD_GBA_MAX_FREE_KF.  *ok = 0 and x = 0 on a zero pivot. */
+#define SD_GBA_MAX_FREE_KF 256
+#define SD_GBA_MAX_ITERATIONS 20
+#define SD_BA_NO_VERTEX 4
+int sd_track_global_ba(sd_track* h, int point_row, int n_iterations, int robust, int write_back);
+int sd_track_get_global_ba(sd_track* h, double* T_ref_cm16, double* T_cur_cm16, double* Xw, uint8_t* point_status, int32_t* info16,
+                           int cap_points);
+int sd_debug_global_ba(int n_points, const int32_t* obs_off, const int32_t* obs_kf, const float* obs_uv, const float* obs_ur,
+                       const float* obs_inv_sigma2, const uint8_t* obs_kf_bad, const uint8_t* point_bad, int n_kf, const double* T_cm16,
+                       const uint8_t* kf_role, const double* Xw, const float* cam9, int n_iterations, int robust, double* T_out_cm16,
+                       double* Xw_out, uint8_t* point_status, int32_t* info16);
+int sd_debug_ldlt(int n, const double* A_packed_lower, const double* b, double* x, int32_t* ok);
+
 int sd_track_align(sd_track* h, int n_frames, int mode);
 int sd_track_match(sd_track* h, int n_frames, float th, int mono, int check_ori);
 /* sd_track_pnp = PnPsolver(CurrentFrame, CurrentFrame.mvpMapPoints) + SetRansacParameters(...) + iterate(n_iterations)

@@ -134,6 +134,10 @@ _SIGNATURES = {
     "sd_track_local_ba": (_I, [_P, _I, _I]),
     "sd_track_get_local_ba": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I]),
     "sd_debug_local_ba": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sd_track_global_ba": (_I, [_P, _I, _I, _I, _I]),
+    "sd_track_get_global_ba": (_I, [_P, _P, _P, _P, _P, _P, _I]),
+    "sd_debug_global_ba": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "sd_debug_ldlt": (_I, [_I, _P, _P, _P, _P]),
     "sd_track_align": (_I, [_P, _I, _I]),
     "sd_track_match": (_I, [_P, _I, _F, _I, _I]),
     "sd_track_pnp": (_I, [_P, _I, _D, _I, _I, _I, _F, _F, _I]),
@@ -852,6 +856,21 @@ class Tracker:
         _check(self.L.sd_track_local_ba(self.h, int(point_row), int(write_back)))
         self._n_ba = (self._n_refresh, self._n_refresh_obs)
 
+    def global_ba(self, point_row=0, n_iterations=10, robust=False, write_back=False):
+        """Optimizer::BundleAdjustment (src/Optimizer.cc:46-219): one optimize(n_iterations) on the points of set_observations at
+        row `point_row`, every keyframe with role 1 free.  write_back: the nLoopKF == 0 branch."""
+        _check(self.L.sd_track_global_ba(self.h, int(point_row), int(n_iterations), int(robust), int(write_back)))
+        self._n_gba = self._n_refresh
+
+    def get_global_ba(self):
+        """dict(T_ref [n_ref, 4, 4], T_cur [4, 4], Xw, point_status, info16) of the last global_ba()."""
+        n = getattr(self, "_n_gba", 0)
+        Tr, Tc = np.zeros((self._n_ba_ref, 16)), np.zeros(16)
+        out = dict(Xw=np.zeros((n, 3)), point_status=np.zeros(n, np.uint8), info16=np.zeros(16, np.int32))
+        _check(self.L.sd_track_get_global_ba(self.h, _p(Tr), _p(Tc), _p(out["Xw"]), _p(out["point_status"]), _p(out["info16"]), n))
+        out.update(T_ref=np.stack([_from_cm(t) for t in Tr]) if len(Tr) else np.zeros((0, 4, 4)), T_cur=_from_cm(Tc))
+        return out
+
     def read_poses(self, n):
         """Tref and Tcur of slots 0 .. n - 1 as they are on the device: ([n, 4, 4], [n, 4, 4])."""
         out = np.zeros((2, n, 16))
@@ -1225,3 +1244,38 @@ def debug_local_ba(problem, cam9=None):
     _check(L.sd_debug_local_ba(n, _p(off), _p(kf), _p(uv), _p(ur), _p(inv), _p(kb), _p(pb), len(roles), _p(T), _p(roles), _p(X), _p(cam),
                                _p(To), _p(Xo), _p(ps), _p(er), _p(info)))
     return dict(T=np.stack([_from_cm(t) for t in To]), Xw=Xo, point_status=ps, obs_erase=er, info16=info)
+
+
+def debug_global_ba(problem, n_iterations, robust, cam9=None):
+    """A BundleAdjustment problem (the dict of debug_local_ba; roles 1 free, 2 fixed, 0 no vertex) through the kernels of
+    sd_track_global_ba (diagnostics).  Returns dict(T [n_kf, 4, 4], Xw, point_status, info16)."""
+    L = lib()
+    q = problem
+    off = np.ascontiguousarray(q["off"], np.int32)
+    n, total = len(off) - 1, int(off[-1])
+    kf, uv = np.ascontiguousarray(q["kf"], np.int32), np.ascontiguousarray(q["uv"], np.float32).reshape(total, 2)
+    ur, inv = np.ascontiguousarray(q["ur"], np.float32), np.ascontiguousarray(q["inv_sigma2"], np.float32)
+    kb = None if q.get("kf_bad") is None else np.ascontiguousarray(q["kf_bad"], np.uint8)
+    pb = None if q.get("point_bad") is None else np.ascontiguousarray(q["point_bad"], np.uint8)
+    roles = np.ascontiguousarray(q["roles"], np.uint8)
+    T = np.ascontiguousarray(np.stack([_cm(t) for t in np.asarray(q["poses"], np.float64)]))
+    X = np.ascontiguousarray(q["Xw"], np.float64).reshape(n, 3)
+    if cam9 is None:
+        cam9 = list(q["cam"]) + [q["bf"], 0.0, 1.0, 0.0, 1.0]
+    cam = np.ascontiguousarray(cam9, np.float32)
+    assert len(kf) == len(ur) == len(inv) == total and len(T) == len(roles) and len(cam) == 9
+    To, Xo = np.zeros_like(T), np.zeros_like(X)
+    ps, info = np.zeros(n, np.uint8), np.zeros(16, np.int32)
+    _check(L.sd_debug_global_ba(n, _p(off), _p(kf), _p(uv), _p(ur), _p(inv), _p(kb), _p(pb), len(roles), _p(T), _p(roles), _p(X), _p(cam),
+                                int(n_iterations), int(robust), _p(To), _p(Xo), _p(ps), _p(info)))
+    return dict(T=np.stack([_from_cm(t) for t in To]), Xw=Xo, point_status=ps, info16=info)
+
+
+def debug_ldlt(A, b):
+    """The blocked LDL^T of sd_track_global_ba alone on the symmetric matrix A [n, n] (its lower triangle is read): (ok, x)."""
+    A, b = np.asarray(A, np.float64), np.ascontiguousarray(b, np.float64)
+    n = len(b)
+    packed = np.ascontiguousarray(A[np.tril_indices(n)])          # row order: (0, 0), (1, 0), (1, 1), ...
+    x, ok = np.zeros(n), np.zeros(1, np.int32)
+    _check(lib().sd_debug_ldlt(n, _p(packed), _p(b), _p(x), _p(ok)))
+    return bool(ok[0]), x

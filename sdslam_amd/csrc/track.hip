@@ -376,6 +376,9 @@ int sd_track_set_poses(sd_track* h, int frame0, int n_frames, const double* Tref
   TRACK_RANGE(h, frame0, n_frames);
   SD_REQUIRE(Tref_cm && Tcur_cm, SD_ERR_INVALID_ARG, "NULL argument");
   END_RESULTS(h, "sd_track_set_poses");
+  // a global bundle adjustment's result is kept aside for poses that are being replaced (mTcwGBA is applied relative to them);
+  // a local one's is a record of its run and stays (track_results.h, kEndsBa)
+  if (h->ba.ran_global) h->ba.ran_points = -1;
   hipStream_t s = h->cur->stream;
   SD_TRY(upload(h->tb.Tref, Tref_cm, frame0, n_frames, 16, s));
   SD_TRY(upload(h->tb.Tprior, Tcur_cm, frame0, n_frames, 16, s));

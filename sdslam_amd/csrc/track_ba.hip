@@ -5,6 +5,8 @@
 //   BaseBinaryEdge::constructQuadraticForm, robustInformation = rho[1] * information, RobustKernelHuber
 //   EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ, SE3Quat (track_se3.h), LinearSolverEigen (fails on a zero pivot only)
 // tests/ba_ref.py is the same restatement in numpy.
+// Optimizer::BundleAdjustment (:46-219, sd_track_global_ba, tests/gba_ref.py) runs on the same kernels: BaProblem::mode and the
+// fields beside it say what differs, and above SD_BA_MAX_FREE_KF free cameras the k_gba_* kernels factorise the reduced system.
 //
 // The problem: points = the list of sd_track_set_observations (CSR), one edge per observation that is neither of a bad point
 // nor of a bad keyframe, in CSR order.  Cameras 0 .. n_kf - 1 carry a role: 1 local (a free vertex, at most SD_BA_MAX_FREE_KF),
@@ -37,6 +39,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <cmath>
 #include <cstddef>
 #include <cstring>
 #include <type_traits>
@@ -48,10 +51,11 @@
 
 namespace sd {
 
-enum { BA_LIVE = 1, BA_STEREO = 2, BA_LEVEL1 = 4, BA_NOT_RESIDENT = 8, BA_BAD_INDEX = 16 };
+enum { BA_LIVE = 1, BA_STEREO = 2, BA_LEVEL1 = 4, BA_NOT_RESIDENT = 8, BA_BAD_INDEX = 16, BA_NO_VERTEX = 32 /* k_ba_setup's own */ };
 enum { BA_EXIT_NOT_RUN = 0, BA_EXIT_NBAD = 1, BA_EXIT_QMAX = 2, BA_EXIT_RHO_ZERO = 3, BA_EXIT_ITERATIONS = 4 };   // poseopt_oracle.cc
 constexpr int BA_K = SD_BA_MAX_FREE_KF, BA_N = 6 * BA_K, BA_PACKED = BA_N * (BA_N + 1) / 2;
 constexpr int BA_EDGE_DOUBLES = 3 + 1 + 3 + 1 + 9 + 18 + 3 + 1;
+constexpr int GBA_NB = 48;   // the panel of the blocked factorisation: 8 cameras; a block with its padding is 18 KB of LDS
 
 struct BaState {
   int32_t status, round, round_live, iter, max_iter, trial_live, qmax, nbad, robust, cur, solve_ok, n_slots;
@@ -64,7 +68,9 @@ static __device__ __forceinline__ bool ba_trial_wanted(const BaState* st, int it
   return ba_iter_wanted(st, it) && st->trial_live && st->qmax == q;
 }
 
-void ba_carve(BaBuffers& b, uint8_t* base, size_t P, size_t E, size_t n_kf) {
+void ba_carve(BaBuffers& b, uint8_t* base, size_t P, size_t E, size_t n_kf, size_t kcap) {
+  kcap = std::max<size_t>(kcap, BA_K);   // k_ba_solve writes BA_N entries of xp whatever the problem's size
+  const size_t n = 6 * kcap, cw = (kcap + 31) / 32;
   size_t o = 0;
   auto take = [&](auto** p, size_t count) {
     using T = std::remove_pointer_t<std::remove_pointer_t<decltype(p)>>;
@@ -75,18 +81,20 @@ void ba_carve(BaBuffers& b, uint8_t* base, size_t P, size_t E, size_t n_kf) {
   take(&b.e_meas, E * 3); take(&b.e_info, E); take(&b.err, E * 3); take(&b.chi2r, E); take(&b.Jl, E * 9); take(&b.Jp, E * 18);
   take(&b.wr, E * 3); take(&b.w, E);
   take(&b.Hll, P * 9); take(&b.bl, P * 3); take(&b.X, 2 * P * 3); take(&b.v_scale, n_kf + P);
-  take(&b.Hpp, (size_t)BA_K * 36); take(&b.bp, (size_t)BA_K * 6); take(&b.pose, 2 * n_kf * 8);
-  take(&b.S, (size_t)BA_PACKED); take(&b.bs, (size_t)BA_N); take(&b.xp, (size_t)BA_N);
+  take(&b.Hpp, kcap * 36); take(&b.bp, kcap * 6); take(&b.pose, 2 * n_kf * 8);
+  // S: the packed lower triangle and one more row, the right-hand side as the blocked factorisation carries it (k_gba_diag)
+  take(&b.S, (n + 1) * (n + 2) / 2); take(&b.bs, n); take(&b.xp, n);
+  take(&b.W, kcap > BA_K ? (n + 1) * GBA_NB : 0); take(&b.covis, kcap * cw);
   take(&b.T_out, n_kf * 16); take(&b.X_out, P * 3);
-  take(&b.e_cam, E); take(&b.e_pt, E); take(&b.clist, E); take(&b.coff, (size_t)BA_K + 1); take(&b.slot, n_kf); take(&b.slot_cam, (size_t)BA_K);
+  take(&b.e_cam, E); take(&b.e_pt, E); take(&b.clist, E); take(&b.coff, kcap + 1); take(&b.slot, n_kf); take(&b.slot_cam, kcap);
   take(&b.e_flag, E); take(&b.p_active, P); take(&b.p_status, P); take(&b.c_has, n_kf); take(&b.c_act, n_kf); take(&b.erase, E);
   take(&b.role, n_kf);
   b.bytes = o;
-  b.cap_points = P; b.cap_obs = E; b.n_kf = (int)n_kf;
+  b.cap_points = P; b.cap_obs = E; b.n_kf = (int)n_kf; b.kcap = (int)kcap;
 }
-size_t ba_bytes(size_t P, size_t E, size_t n_kf) {
+size_t ba_bytes(size_t P, size_t E, size_t n_kf, size_t kcap) {
   BaBuffers b{};
-  ba_carve(b, nullptr, P, E, n_kf);
+  ba_carve(b, nullptr, P, E, n_kf, kcap);
   return b.bytes;
 }
 
@@ -121,7 +129,18 @@ struct BaProblem {
   double* wb_Tref;           // NULL: no write-back
   double* wb_Tcur;
   double fx, fy, cx, cy, bf;
+  // what tells the two callers apart.  mode 0: LocalBundleAdjustment (two rounds of 5 and 10 iterations, the level-1 / erase
+  // classification, role 0 = a fixed camera if observed); mode 1: BundleAdjustment (one optimize(n_iterations), robust or not,
+  // role 0 = no vertex: an edge to it refuses the call)
+  int mode, n_iterations, robust;
+  int kcap;                  // the free cameras the scratch holds: SD_BA_MAX_FREE_KF for mode 0
+  double delta_mono, delta_stereo;   // the Huber deltas where the kernel is on
 };
+static void ba_set_mode(BaProblem& pr, int mode, int n_iterations, int robust, int kcap) {
+  pr.mode = mode; pr.n_iterations = n_iterations; pr.robust = robust; pr.kcap = kcap;
+  pr.delta_mono = (double)(float)std::sqrt(mode ? 5.99 : 5.991);   // thHuber2D = sqrt(5.99) (sic, Optimizer.cc:87); sqrt(5.991) at :520
+  pr.delta_stereo = (double)(float)std::sqrt(7.815);
+}
 
 static __device__ __forceinline__ const double* ba_pose_in(const BaProblem& pr, int c) {
   if (pr.d_kf) return pr.d_T + (size_t)c * 16;
@@ -204,6 +223,8 @@ __global__ __launch_bounds__(256) void k_ba_setup(BaProblem pr, BaBuffers b) {
   const int t = threadIdx.x, nt = blockDim.x;
   if (t == 0) s_flags = s_cnt[0] = s_cnt[1] = s_cnt[2] = 0;
   for (int c = t; c < pr.n_kf; c += nt) b.c_has[c] = b.c_act[c] = 0;
+  if (pr.mode)
+    for (int k = t; k < pr.kcap * ((pr.kcap + 31) / 32); k += nt) b.covis[k] = 0;
   __syncthreads();
   int fl = 0, mono = 0, st = 0;
   for (int e = t; e < pr.n_obs; e += nt) {
@@ -211,6 +232,7 @@ __global__ __launch_bounds__(256) void k_ba_setup(BaProblem pr, BaBuffers b) {
     fl |= f & (BA_NOT_RESIDENT | BA_BAD_INDEX);
     if (f & BA_LIVE) {
       b.c_has[b.e_cam[e]] = 1;
+      if (pr.mode && b.role[b.e_cam[e]] == 0) fl |= BA_NO_VERTEX;
       if (f & BA_STEREO) st++; else mono++;
     }
   }
@@ -224,16 +246,16 @@ __global__ __launch_bounds__(256) void k_ba_setup(BaProblem pr, BaBuffers b) {
       const int role = b.role[c];
       b.slot[c] = -1;
       if (role == 1) {
-        if (n_free < BA_K) { b.slot[c] = n_free; b.slot_cam[n_free] = c; }
+        if (n_free < pr.kcap) { b.slot[c] = n_free; b.slot_cam[n_free] = c; }
         n_free++;
       } else if (role == 2 || b.c_has[c]) n_fixed++;
     }
     const int status = (s_flags & BA_NOT_RESIDENT) ? SD_BA_NOT_RESIDENT : (s_flags & BA_BAD_INDEX) ? SD_BA_BAD_INDEX
-                       : n_free > BA_K ? SD_BA_TOO_MANY_KF : SD_BA_OK;
+                       : n_free > pr.kcap ? SD_BA_TOO_MANY_KF : (s_flags & BA_NO_VERTEX) ? SD_BA_NO_VERTEX : SD_BA_OK;
     s_status = status;
     BaState* S = b.st;
     S->status = status; S->round = 0; S->round_live = 0; S->iter = 0; S->max_iter = 0; S->trial_live = 0; S->qmax = 0; S->nbad = 0;
-    S->robust = 1; S->cur = 0; S->solve_ok = 0; S->n_slots = min(n_free, BA_K);
+    S->robust = 1; S->cur = 0; S->solve_ok = 0; S->n_slots = min(n_free, pr.kcap);
     S->lambda = -1.0; S->ni = 2.0; S->cur_chi = S->ini_chi = S->rho = 0.0;
     for (int i = 0; i < 16; i++) S->info[i] = 0;
     S->info[0] = status;
@@ -273,12 +295,13 @@ __global__ __launch_bounds__(256) void k_ba_setup(BaProblem pr, BaBuffers b) {
 
 // The edges of free camera `slot`, in edge order: coff[slot] .. coff[slot + 1] - 1 of clist
 __global__ __launch_bounds__(1024) void k_ba_index(BaProblem pr, BaBuffers b) {
-  __shared__ int s_n[BA_K], s_off[BA_K + 1];
+  __shared__ int s_n[SD_GBA_MAX_FREE_KF], s_off[SD_GBA_MAX_FREE_KF + 1];
   if (b.st->status != 0) return;
+  const int K = b.st->n_slots;   // a slot past it has no camera and no edge
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
   const unsigned long long lt = lanemask_lt(lane);
   for (int pass = 0; pass < 2; pass++) {
-    for (int s = wave; s < BA_K; s += n_waves) {
+    for (int s = wave; s < K; s += n_waves) {
       int n = pass ? s_off[s] : 0;
       for (int e0 = 0; e0 < pr.n_obs; e0 += 64) {
         const int e = e0 + lane;
@@ -291,8 +314,8 @@ __global__ __launch_bounds__(1024) void k_ba_index(BaProblem pr, BaBuffers b) {
     __syncthreads();
     if (!pass && threadIdx.x == 0) {
       int o = 0;
-      for (int s = 0; s < BA_K; s++) { s_off[s] = o; b.coff[s] = o; o += s_n[s]; }
-      s_off[BA_K] = o; b.coff[BA_K] = o;
+      for (int s = 0; s < K; s++) { s_off[s] = o; b.coff[s] = o; o += s_n[s]; }
+      for (int s = K; s <= pr.kcap; s++) b.coff[s] = o;
     }
     __syncthreads();
   }
@@ -322,8 +345,8 @@ __global__ __launch_bounds__(256) void k_ba_round_begin(BaProblem pr, BaBuffers 
   if (any) atomicOr(&s_any, 1);
   __syncthreads();
   if (t == 0) {
-    S->round = round; S->round_live = s_any; S->iter = 0; S->max_iter = round ? 10 : 5; S->trial_live = 0; S->qmax = 0; S->nbad = 0;
-    S->robust = round ? 0 : 1;   // e->setRobustKernel(0) on every edge after round 1
+    S->round = round; S->round_live = s_any; S->iter = 0; S->max_iter = pr.mode ? pr.n_iterations : round ? 10 : 5; S->trial_live = 0; S->qmax = 0; S->nbad = 0;
+    S->robust = pr.mode ? pr.robust : round ? 0 : 1;   // e->setRobustKernel(0) on every edge after round 1
     S->lambda = -1.0; S->ni = 2.0;
   }
 }
@@ -369,7 +392,7 @@ static __device__ __forceinline__ void ba_edge_error(const BaProblem& pr, const 
   const double chi2 = ba_error(pr, pc, b.e_meas + (size_t)e * 3, stereo, b.e_info[e], err);
   for (int i = 0; i < 3; i++) b.err[(size_t)e * 3 + i] = err[i];
   double rho0 = chi2, rho1 = 1.0;
-  if (robust) ba_huber(chi2, (double)(stereo ? (float)sqrt(7.815) : (float)sqrt(5.991)), &rho0, &rho1);
+  if (robust) ba_huber(chi2, stereo ? pr.delta_stereo : pr.delta_mono, &rho0, &rho1);
   b.chi2r[e] = rho0;
   if (rho1_out) *rho1_out = rho1;
 }
@@ -568,6 +591,10 @@ __global__ __launch_bounds__(64) void k_ba_schur(BaProblem pr, BaBuffers b, int 
   const double lambda = S->lambda;
   const int o0 = b.coff[i], n = b.coff[i + 1] - o0;
   double acc = 0.0;
+  if (pr.mode && i != j && !((b.covis[(size_t)i * ((pr.kcap + 31) / 32) + (j >> 5)] >> (j & 31)) & 1)) {   // no common point: the block is 0
+    if (lane < 36) b.S[(size_t)(6 * j + lane % 6) * (6 * j + lane % 6 + 1) / 2 + 6 * i + lane / 6] = 0.0;
+    return;
+  }
   if (i == j) {
     if (lane < 36) acc = b.Hpp[(size_t)i * 36 + lane] + (lane % 7 == 0 ? lambda : 0.0);
     else if (lane < 42) acc = b.bp[(size_t)i * 6 + lane - 36];
@@ -827,7 +854,197 @@ __global__ __launch_bounds__(256) void k_ba_finish(BaProblem pr, BaBuffers b) {
   }
 }
 
-#define BA_LAUNCH(kernel, grid, block, ...)                                      \
+// mode 1, once per call: bit j of row i (i < j) says that free cameras i and j see a common point, so block (i, j) of S can be
+// other than 0.  Integer atomics on a bitmap k_ba_setup cleared; the bitmap does not depend on their order.
+__global__ __launch_bounds__(256) void k_gba_covis(BaProblem pr, BaBuffers b) {
+  if (b.st->status != 0) return;
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= pr.n_points) return;
+  const int cw = (pr.kcap + 31) / 32;
+  for (int e = pr.off[p]; e < pr.off[p + 1]; e++) {
+    const int si = (b.e_flag[e] & BA_LIVE) ? b.slot[b.e_cam[e]] : -1;
+    if (si < 0) continue;
+    for (int e2 = pr.off[p]; e2 < pr.off[p + 1]; e2++) {
+      const int sj = (b.e_flag[e2] & BA_LIVE) ? b.slot[b.e_cam[e2]] : -1;
+      if (sj > si) atomicOr(&b.covis[(size_t)si * cw + (sj >> 5)], 1u << (sj & 31));
+    }
+  }
+}
+
+// ---- The blocked LDL^T of the reduced system in global memory, for more free cameras than k_ba_solve's LDS holds ----
+// The same factorisation as k_ba_solve, without pivoting and in index order, on the packed lower triangle k_ba_schur writes
+// (entry (r, c) at r (r + 1) / 2 + c), in panels of GBA_NB columns.  The right-hand side is row n of the triangle (k_gba_diag of
+// panel 0 puts it there), so the forward substitution and the division by D are the panel and trailing steps of one more row:
+// its "L" entries are y = D^-1 L^-1 b.  Per panel:
+//   k_gba_diag    one workgroup: the diagonal block in LDS; L and D back in place, the unscaled columns (L D) of its rows into W
+//   k_gba_panel   a lane per row below the block: the triangular solve against the block; L in place, L D into W
+//   k_gba_trail   a workgroup per 32 x 32 tile of the trailing triangle: A(i, j) -= sum_k L(i, k) W(j, k), k ascending
+// then, panels in descending order, k_gba_back: every workgroup solves the panel's x from the block's L^T (the same values in
+// each), workgroup 0 stores it, and each lane owns one earlier entry of y and subtracts the panel's terms, k descending.
+// Every entry has one owning lane and takes its terms one by one in the order the unblocked loop takes them, so L and D are
+// k_ba_solve's to the bit (y is not: it forms (z_k / d_k) * (L D)(j, k) where k_ba_solve forms L(j, k) * z_k).  A zero pivot clears solve_ok in the record; every later solver kernel of the trial returns on it.
+struct LdltArgs {
+  BaState* st;
+  double* A;    // packed lower triangle, n + 1 rows
+  double* bs;   // [n] the right-hand side; the backward substitution's working vector
+  double* W;    // [n + 1][GBA_NB] the current panel's L D
+  double* x;    // [n]
+  int n;        // >= 0: the size (sd_debug_ldlt); -1: 6 * n_slots of the record
+};
+static __device__ __forceinline__ size_t tri(int r, int c) { return (size_t)r * (r + 1) / 2 + c; }
+static __device__ __forceinline__ int ldlt_n(const LdltArgs& a) { return a.n >= 0 ? a.n : 6 * a.st->n_slots; }
+
+__global__ __launch_bounds__(256) void k_gba_diag(LdltArgs a, int it, int q, int panel) {
+  __shared__ double s_A[GBA_NB][GBA_NB + 1], s_col[GBA_NB], s_l[GBA_NB];
+  __shared__ int s_fail;
+  BaState* S = a.st;
+  if (!ba_trial_wanted(S, it, q)) return;
+  if (panel > 0 && !S->solve_ok) return;
+  const int n = ldlt_n(a), c0 = panel * GBA_NB;
+  if (c0 >= n) return;
+  const int w = min(GBA_NB, n - c0), t = threadIdx.x, tx = t & 15, ty = t >> 4;
+  if (panel == 0)
+    for (int k = t; k < n; k += 256) a.A[tri(n, k)] = a.bs[k];
+  for (int e = t; e < w * w; e += 256) {
+    const int r = e / w, c = e % w;
+    if (c <= r) s_A[r][c] = a.A[tri(c0 + r, c0 + c)];
+  }
+  if (t == 0) s_fail = 0;
+  __syncthreads();
+  for (int k = 0; k < w; k++) {
+    const double d = s_A[k][k];
+    if (d == 0.0) {   // uniform
+      if (t == 0) s_fail = 1;
+      break;
+    }
+    for (int i = k + 1 + t; i < w; i += 256) {
+      const double v = s_A[i][k];
+      s_col[i] = v;
+      s_l[i] = v / d;
+    }
+    __syncthreads();
+    for (int i = k + 1 + t; i < w; i += 256) {
+      s_A[i][k] = s_l[i];
+      a.W[(size_t)(c0 + i) * GBA_NB + k] = s_col[i];
+    }
+    for (int i = k + 1 + ty; i < w; i += 16)
+      for (int j = k + 1 + tx; j <= i; j += 16) s_A[i][j] -= s_l[i] * s_col[j];
+    __syncthreads();
+  }
+  __syncthreads();
+  const bool ok = !s_fail;
+  if (ok)
+    for (int e = t; e < w * w; e += 256) {
+      const int r = e / w, c = e % w;
+      if (c <= r) a.A[tri(c0 + r, c0 + c)] = s_A[r][c];
+    }
+  if (t == 0 && (panel == 0 || !ok)) S->solve_ok = ok;
+}
+
+__global__ __launch_bounds__(64) void k_gba_panel(LdltArgs a, int it, int q, int panel) {
+  __shared__ double s_W11[GBA_NB][GBA_NB + 1], s_d[GBA_NB], s_row[64][GBA_NB + 1];
+  const BaState* S = a.st;
+  if (!ba_trial_wanted(S, it, q) || !S->solve_ok) return;
+  const int n = ldlt_n(a), c0 = panel * GBA_NB;
+  if (c0 >= n) return;
+  const int w = min(GBA_NB, n - c0), c1 = c0 + w, t = threadIdx.x, r0 = c1 + blockIdx.x * 64;
+  if (r0 > n) return;
+  const int rows = min(64, n + 1 - r0);
+  for (int e = t; e < w * w; e += 64) {
+    const int r = e / w, c = e % w;
+    if (c < r) s_W11[r][c] = a.W[(size_t)(c0 + r) * GBA_NB + c];
+    else if (c == r) s_d[r] = a.A[tri(c0 + r, c0 + r)];
+  }
+  for (int e = t; e < rows * w; e += 64) s_row[e / w][e % w] = a.A[tri(r0 + e / w, c0 + e % w)];
+  __syncthreads();
+  if (t < rows) {
+    const int i = r0 + t;
+    for (int j = 0; j < w; j++) {
+      double v = s_row[t][j];
+      for (int k = 0; k < j; k++) v -= s_row[t][k] * s_W11[j][k];   // s_row[t][k], k < j, already holds L(i, k)
+      const double l = v / s_d[j];
+      s_row[t][j] = l;
+      a.W[(size_t)i * GBA_NB + j] = v;
+      if (i == n) a.bs[c0 + j] = l;   // y, where k_gba_back takes it
+    }
+  }
+  __syncthreads();
+  for (int e = t; e < rows * w; e += 64) a.A[tri(r0 + e / w, c0 + e % w)] = s_row[e / w][e % w];
+}
+
+__global__ __launch_bounds__(256) void k_gba_trail(LdltArgs a, int it, int q, int panel) {
+  __shared__ double s_L[32][GBA_NB + 1], s_W[32][GBA_NB + 1];
+  const BaState* S = a.st;
+  if (!ba_trial_wanted(S, it, q) || !S->solve_ok) return;
+  const int n = ldlt_n(a), c0 = panel * GBA_NB, c1 = c0 + GBA_NB;
+  if (c1 >= n) return;   // the last panel has only row n below it, and row n has no entry right of column n - 1
+  // tile (I, J), J <= I, of rows c1 .. n, columns c1 .. n - 1
+  int I = (int)((sqrtf(8.f * (float)blockIdx.x + 1.f) - 1.f) * 0.5f);
+  while ((I + 1) * (I + 2) / 2 <= (int)blockIdx.x) I++;
+  while (I * (I + 1) / 2 > (int)blockIdx.x) I--;
+  const int J = blockIdx.x - I * (I + 1) / 2, i0 = c1 + 32 * I, j0 = c1 + 32 * J;
+  if (i0 > n) return;
+  const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+  for (int e = t; e < 32 * GBA_NB; e += 256) {
+    const int r = e / GBA_NB, k = e % GBA_NB;
+    s_L[r][k] = i0 + r <= n ? a.A[tri(i0 + r, c0 + k)] : 0.0;
+    s_W[r][k] = j0 + r < n ? a.W[(size_t)(j0 + r) * GBA_NB + k] : 0.0;
+  }
+  __syncthreads();
+  for (int di = 0; di < 2; di++)
+    for (int dj = 0; dj < 2; dj++) {
+      const int li = ty + 16 * di, lj = tx + 16 * dj, i = i0 + li, j = j0 + lj;
+      if (i > n || j > i || j >= n) continue;
+      double v = a.A[tri(i, j)];
+      for (int k = 0; k < GBA_NB; k++) v -= s_L[li][k] * s_W[lj][k];
+      a.A[tri(i, j)] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_gba_back(LdltArgs a, int it, int q, int panel) {
+  __shared__ double s_L[GBA_NB][GBA_NB + 1], s_x[GBA_NB];
+  const BaState* S = a.st;
+  if (!ba_trial_wanted(S, it, q) || !S->solve_ok) return;
+  const int n = ldlt_n(a), c0 = panel * GBA_NB;
+  if (c0 >= n) return;
+  const int w = min(GBA_NB, n - c0), t = threadIdx.x;
+  for (int e = t; e < w * w; e += 256) {
+    const int r = e / w, c = e % w;
+    if (c < r) s_L[r][c] = a.A[tri(c0 + r, c0 + c)];
+  }
+  if (t < w) s_x[t] = a.bs[c0 + t];
+  __syncthreads();
+  for (int k = w - 1; k > 0; k--) {
+    if (t < k) s_x[t] -= s_L[k][t] * s_x[k];
+    __syncthreads();
+  }
+  if (blockIdx.x == 0 && t < w) a.x[c0 + t] = s_x[t];
+  const int j = blockIdx.x * 256 + t;
+  if (j >= c0) return;
+  double v = a.bs[j];
+  for (int k = w - 1; k >= 0; k--) v -= a.A[tri(c0 + k, j)] * s_x[k];
+  a.bs[j] = v;
+}
+
+// The factorisation and both substitutions of an n x n system, n known to the host: 4 launches a panel
+static int launch_ldlt(const LdltArgs& a, int n, int it, int q, hipStream_t s) {
+  const int np = (n + GBA_NB - 1) / GBA_NB;
+  for (int p = 0; p < np; p++) {
+    const int c1 = std::min(n, (p + 1) * GBA_NB), below = n + 1 - c1;
+    hipLaunchKernelGGL(k_gba_diag, dim3(1), dim3(256), 0, s, a, it, q, p);
+    hipLaunchKernelGGL(k_gba_panel, dim3((below + 63) / 64), dim3(64), 0, s, a, it, q, p);
+    if (c1 < n) {
+      const int T = (below + 31) / 32;
+      hipLaunchKernelGGL(k_gba_trail, dim3(T * (T + 1) / 2), dim3(256), 0, s, a, it, q, p);
+    }
+    SD_HIP_CHECK(hipGetLastError());
+  }
+  for (int p = np - 1; p >= 0; p--) hipLaunchKernelGGL(k_gba_back, dim3(std::max(1, (p * GBA_NB + 255) / 256)), dim3(256), 0, s, a, it, q, p);
+  SD_HIP_CHECK(hipGetLastError());
+  return SD_OK;
+}
+
+#define BA_LAUNCH(kernel, grid, block, ...)                                    \
   do {                                                                           \
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, pr, b, ##__VA_ARGS__); \
     SD_HIP_CHECK(hipGetLastError());                                             \
@@ -835,28 +1052,31 @@ __global__ __launch_bounds__(256) void k_ba_finish(BaProblem pr, BaBuffers b) {
 
 // The whole schedule.  n_free: the cameras with role 1 as the host counts them (more than SD_BA_MAX_FREE_KF: the device refuses)
 int launch_ba(const BaProblem& pr, const BaBuffers& b, int n_free, hipStream_t s) {
-  const int P = pr.n_points, E = pr.n_obs, K = std::min(n_free, BA_K);
+  const int P = pr.n_points, E = pr.n_obs, K = std::min(n_free, pr.kcap);
   const int gp = std::max(1, (P + 255) / 256), ge = std::max(1, (E + 255) / 256), gv = std::max(1, (P + pr.n_kf + 255) / 256);
+  const LdltArgs la{b.st, b.S, b.bs, b.W, b.xp, -1};
   BA_LAUNCH(k_ba_gather, gp, 256);
   BA_LAUNCH(k_ba_setup, 1, 256);
-  if (n_free <= BA_K && E > 0) {
+  if (n_free <= pr.kcap && E > 0) {
     BA_LAUNCH(k_ba_index, 1, 1024);
-    for (int round = 0; round < 2; round++) {
+    if (pr.mode) BA_LAUNCH(k_gba_covis, gp, 256);
+    for (int round = 0; round < (pr.mode ? 1 : 2); round++) {
       BA_LAUNCH(k_ba_round_begin, 1, 256, round);
-      for (int it = 0; it < (round ? 10 : 5); it++) {
+      for (int it = 0; it < (pr.mode ? pr.n_iterations : round ? 10 : 5); it++) {
         BA_LAUNCH(k_ba_linearise, ge, 256, it);
         BA_LAUNCH(k_ba_sum_points, std::max(1, (P + 3) / 4), 256, it);
         if (K > 0) BA_LAUNCH(k_ba_sum_cameras, K, 64, it);
         BA_LAUNCH(k_ba_iter_begin, 1, 1024, it);
         for (int q = 0; q < 10; q++) {
           if (K > 0) BA_LAUNCH(k_ba_schur, K * (K + 1) / 2, 64, it, q);
-          BA_LAUNCH(k_ba_solve, 1, 256, it, q);
+          if (K <= BA_K) BA_LAUNCH(k_ba_solve, 1, 256, it, q);   // the reduced system fits one workgroup's LDS
+          else SD_TRY(launch_ldlt(la, 6 * K, it, q, s));
           BA_LAUNCH(k_ba_update, gv, 256, it, q);
           BA_LAUNCH(k_ba_errors, ge, 256, it, q);
           BA_LAUNCH(k_ba_decide, 1, 1024, it, q);
         }
       }
-      BA_LAUNCH(k_ba_classify, ge, 256, round);
+      if (!pr.mode) BA_LAUNCH(k_ba_classify, ge, 256, round);
     }
   }
   BA_LAUNCH(k_ba_finish, gv, 256);
@@ -867,10 +1087,13 @@ int launch_ba(const BaProblem& pr, const BaBuffers& b, int n_free, hipStream_t s
 
 using namespace sd;
 
+// The handle's scratch holds min(SD_GBA_MAX_FREE_KF, n_kf) free cameras (and never fewer than SD_BA_MAX_FREE_KF)
+static size_t ba_handle_kcap(size_t n_kf) { return std::max<size_t>(BA_K, std::min<size_t>(SD_GBA_MAX_FREE_KF, n_kf)); }
+
 static int ba_alloc(BaBuffers& b, size_t P, size_t E, size_t n_kf) {
   uint8_t* base = nullptr;
-  SD_HIP_CHECK(hipMalloc((void**)&base, ba_bytes(P, E, n_kf)));
-  ba_carve(b, base, P, E, n_kf);
+  SD_HIP_CHECK(hipMalloc((void**)&base, ba_bytes(P, E, n_kf, ba_handle_kcap(n_kf))));
+  ba_carve(b, base, P, E, n_kf, ba_handle_kcap(n_kf));
   b.base = base;
   return SD_OK;
 }
@@ -908,6 +1131,7 @@ int count_free(const uint8_t* roles, size_t n) {
 }
 
 const char* const kNoBa = "sd_track_local_ba has not run (or sd_track_set_observations has replaced its scratch since)";
+const char* const kNoGba = "sd_track_global_ba has not run (or sd_track_set_observations has replaced its scratch since)";
 
 }  // namespace
 
@@ -930,8 +1154,14 @@ int sd_track_set_ba_keyframes(sd_track* h, int n_ref_frames, const uint8_t* kf_r
   return SD_OK;
 }
 
-int sd_track_local_ba(sd_track* h, int point_row, int write_back) {
+}  // extern "C"
+
+// sd_track_local_ba (mode 0) and sd_track_global_ba (mode 1): the checks, the problem on the resident buffers, the queued schedule
+static int queue_ba(sd_track* h, int point_row, int write_back, int mode, int n_iterations, int robust) {
   SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
+  SD_REQUIRE(!mode || (n_iterations >= 1 && n_iterations <= SD_GBA_MAX_ITERATIONS), SD_ERR_INVALID_ARG,
+             "n_iterations outside [1, SD_GBA_MAX_ITERATIONS]");
+  SD_REQUIRE(robust == 0 || robust == 1, SD_ERR_INVALID_ARG, "robust must be 0 or 1");
   SD_REQUIRE(h->have_cam, SD_ERR_INVALID_ARG, "sd_track_set_camera has not been called");
   SD_REQUIRE(h->rf.n_points >= 0, SD_ERR_INVALID_ARG, "sd_track_set_observations has not been called");
   SD_REQUIRE(h->ba_roles_set, SD_ERR_INVALID_ARG, "sd_track_set_ba_keyframes has not been called");
@@ -947,7 +1177,8 @@ int sd_track_local_ba(sd_track* h, int point_row, int write_back) {
   SD_REQUIRE((size_t)h->rf.n_obs <= h->ba.cap_obs && (size_t)h->rf.n_points <= h->ba.cap_points, SD_ERR_CAPACITY,
              "the observation lists exceed the bundle adjustment's scratch");
   SD_HIP_CHECK(hipSetDevice(h->device));
-  if (write_back) END_RESULTS(h, "sd_track_local_ba(write_back)");
+  if (write_back && mode) END_RESULTS(h, "sd_track_global_ba(write_back)");
+  else if (write_back) END_RESULTS(h, "sd_track_local_ba(write_back)");
   h->ba.ran_points = -1;
   const RefreshBuffers& rf = h->rf;
   const TrackBuffers& tb = h->tb;
@@ -977,17 +1208,20 @@ int sd_track_local_ba(sd_track* h, int point_row, int write_back) {
   pr.Xw = tb.lm_Xw + (size_t)point_row * tb.max_points * 3;
   if (write_back) { pr.wb_Tref = tb.Tref; pr.wb_Tcur = tb.Tcur; }
   pr.fx = h->cam.fx; pr.fy = h->cam.fy; pr.cx = h->cam.cx; pr.cy = h->cam.cy; pr.bf = h->cam.bf;
+  ba_set_mode(pr, mode, n_iterations, robust, mode ? h->ba.kcap : BA_K);
   const int n_free = count_free(h->ba_roles.data(), h->ba_roles.size());
   SD_TRY(run_stage(h, true, false, STAGE_NONE, [&](hipStream_t s) { return launch_ba(pr, h->ba, n_free, s); }));
   h->ba.ran_points = rf.n_points;
   h->ba.ran_obs = rf.n_obs;
+  h->ba.ran_global = mode;
   return SD_OK;
 }
 
-int sd_track_get_local_ba(sd_track* h, double* T_ref_cm16, double* T_cur_cm16, double* Xw, uint8_t* point_status, uint8_t* obs_erase,
-                          int32_t* info16, int cap_points, int cap_obs) {
+// What both getters download; obs_erase NULL: not wanted
+static int get_ba(sd_track* h, int mode, double* T_ref_cm16, double* T_cur_cm16, double* Xw, uint8_t* point_status, uint8_t* obs_erase,
+                  int32_t* info16, int cap_points, int cap_obs) {
   TRACK_RANGE(h, 0, 1);
-  SD_REQUIRE(h->ba.ran_points >= 0, SD_ERR_INVALID_ARG, kNoBa);
+  SD_REQUIRE(h->ba.ran_points >= 0 && h->ba.ran_global == mode, SD_ERR_INVALID_ARG, mode ? kNoGba : kNoBa);
   const size_t P = (size_t)h->ba.ran_points, E = (size_t)h->ba.ran_obs;
   SD_REQUIRE(!(Xw || point_status) || (cap_points >= 0 && (size_t)cap_points >= P), SD_ERR_CAPACITY, "cap_points smaller than the number of points");
   SD_REQUIRE(!obs_erase || (cap_obs >= 0 && (size_t)cap_obs >= E), SD_ERR_CAPACITY, "cap_obs smaller than the number of observations");
@@ -1002,30 +1236,56 @@ int sd_track_get_local_ba(sd_track* h, double* T_ref_cm16, double* T_cur_cm16, d
   return wait_for(s);
 }
 
-int sd_debug_local_ba(int n_points, const int32_t* obs_off, const int32_t* obs_kf, const float* obs_uv, const float* obs_ur,
-                      const float* obs_inv_sigma2, const uint8_t* obs_kf_bad, const uint8_t* point_bad, int n_kf, const double* T_cm16,
-                      const uint8_t* kf_role, const double* Xw, const float* cam9, double* T_out_cm16, double* Xw_out,
-                      uint8_t* point_status, uint8_t* obs_erase, int32_t* info16) {
+extern "C" {
+
+int sd_track_local_ba(sd_track* h, int point_row, int write_back) { return queue_ba(h, point_row, write_back, 0, 0, 1); }
+
+int sd_track_global_ba(sd_track* h, int point_row, int n_iterations, int robust, int write_back) {
+  return queue_ba(h, point_row, write_back, 1, n_iterations, robust);
+}
+
+int sd_track_get_global_ba(sd_track* h, double* T_ref_cm16, double* T_cur_cm16, double* Xw, uint8_t* point_status, int32_t* info16,
+                           int cap_points) {
+  return get_ba(h, 1, T_ref_cm16, T_cur_cm16, Xw, point_status, nullptr, info16, cap_points, 0);
+}
+
+int sd_track_get_local_ba(sd_track* h, double* T_ref_cm16, double* T_cur_cm16, double* Xw, uint8_t* point_status, uint8_t* obs_erase,
+                          int32_t* info16, int cap_points, int cap_obs) {
+  return get_ba(h, 0, T_ref_cm16, T_cur_cm16, Xw, point_status, obs_erase, info16, cap_points, cap_obs);
+}
+
+}  // extern "C"
+
+// sd_debug_local_ba (mode 0) and sd_debug_global_ba (mode 1, obs_erase NULL)
+static int debug_ba(const char* name, int mode, int n_iterations, int robust, int n_points, const int32_t* obs_off, const int32_t* obs_kf,
+                    const float* obs_uv, const float* obs_ur, const float* obs_inv_sigma2, const uint8_t* obs_kf_bad,
+                    const uint8_t* point_bad, int n_kf, const double* T_cm16, const uint8_t* kf_role, const double* Xw, const float* cam9,
+                    double* T_out_cm16, double* Xw_out, uint8_t* point_status, uint8_t* obs_erase, int32_t* info16) {
+  SD_REQUIRE(!mode || (n_iterations >= 1 && n_iterations <= SD_GBA_MAX_ITERATIONS), SD_ERR_INVALID_ARG,
+             "n_iterations outside [1, SD_GBA_MAX_ITERATIONS]");
+  SD_REQUIRE(robust == 0 || robust == 1, SD_ERR_INVALID_ARG, "robust must be 0 or 1");
   SD_REQUIRE(n_points >= 0 && obs_off && obs_off[0] == 0, SD_ERR_INVALID_ARG, "NULL list, negative n_points or obs_off[0] != 0");
   for (int i = 0; i < n_points; i++) SD_REQUIRE(obs_off[i + 1] >= obs_off[i], SD_ERR_INVALID_ARG, "obs_off is not monotone");
   const int total = obs_off[n_points];
   SD_REQUIRE(n_points <= (1 << 20) && total <= (1 << 22) && n_kf >= 1 && n_kf <= (1 << 16), SD_ERR_CAPACITY,
              "at most 2^20 points, 2^22 observations and 2^16 keyframes");
   SD_REQUIRE((total == 0 || (obs_kf && obs_uv && obs_ur && obs_inv_sigma2)) && T_cm16 && kf_role && (n_points == 0 || Xw) && cam9 &&
-                 T_out_cm16 && (n_points == 0 || (Xw_out && point_status)) && (total == 0 || obs_erase) && info16,
+                 T_out_cm16 && (n_points == 0 || (Xw_out && point_status)) && (total == 0 || mode || obs_erase) && info16,
              SD_ERR_INVALID_ARG, "NULL array");
   for (int c = 0; c < n_kf; c++) SD_REQUIRE(kf_role[c] <= 2, SD_ERR_INVALID_ARG, "kf_role must be 0, 1 or 2");
   const size_t P = (size_t)n_points, E = (size_t)total, Kn = (size_t)n_kf;
+  const int n_free = count_free(kf_role, Kn);
+  const size_t kcap = mode ? (size_t)std::min(std::max(n_free, BA_K), SD_GBA_MAX_FREE_KF) : (size_t)BA_K;
   Blob blob;
   const size_t o_off = blob.reserve(P + 1, obs_off, P + 1), o_kf = blob.reserve(E + 1, obs_kf, E), o_uv = blob.reserve(2 * E + 2, obs_uv, 2 * E);
   const size_t o_ur = blob.reserve(E + 1, obs_ur, E), o_inv = blob.reserve(E + 1, obs_inv_sigma2, E);
   const size_t o_kb = blob.reserve(E + 1, obs_kf_bad, obs_kf_bad ? E : 0), o_pb = blob.reserve(P + 1, point_bad, point_bad ? P : 0);
   const size_t o_T = blob.reserve(Kn * 16, T_cm16, Kn * 16), o_X = blob.reserve(P * 3 + 3, Xw, P * 3);
-  const size_t o_scratch = blob.reserve(ba_bytes(P, E, Kn), (const uint8_t*)nullptr, 0);
+  const size_t o_scratch = blob.reserve(ba_bytes(P, E, Kn, kcap), (const uint8_t*)nullptr, 0);
   BaBuffers b{};
-  SD_TRY(blob.run("sd_debug_local_ba", [&] {
-    ba_carve(b, blob.dev<uint8_t>(o_scratch), P, E, Kn);
-    if (hipError_t e = hipMemcpy(b.role, kf_role, Kn, hipMemcpyHostToDevice); e != hipSuccess) return hip_error("sd_debug_local_ba", e);
+  SD_TRY(blob.run(name, [&] {
+    ba_carve(b, blob.dev<uint8_t>(o_scratch), P, E, Kn, kcap);
+    if (hipError_t e = hipMemcpy(b.role, kf_role, Kn, hipMemcpyHostToDevice); e != hipSuccess) return hip_error(name, e);
     BaProblem pr{};
     pr.off = blob.dev<int32_t>(o_off);
     pr.point_bad = point_bad ? blob.dev<uint8_t>(o_pb) : nullptr;
@@ -1036,7 +1296,8 @@ int sd_debug_local_ba(int n_points, const int32_t* obs_off, const int32_t* obs_k
     pr.Xw = blob.dev<double>(o_X);
     const TrackCam cam = make_cam(cam9[0], cam9[1], cam9[2], cam9[3], cam9[4], cam9[5], cam9[6], cam9[7], cam9[8]);
     pr.fx = cam.fx; pr.fy = cam.fy; pr.cx = cam.cx; pr.cy = cam.cy; pr.bf = cam.bf;
-    SD_TRY(launch_ba(pr, b, count_free(kf_role, Kn), 0));
+    ba_set_mode(pr, mode, n_iterations, robust, (int)kcap);
+    SD_TRY(launch_ba(pr, b, n_free, 0));
     SD_HIP_CHECK(hipDeviceSynchronize());
     return SD_OK;
   }));
@@ -1045,8 +1306,49 @@ int sd_debug_local_ba(int n_points, const int32_t* obs_off, const int32_t* obs_k
   blob.take(T_out_cm16, host(b.T_out), Kn * 16 * 8);
   blob.take(Xw_out, host(b.X_out), P * 24);
   blob.take(point_status, host(b.p_status), P);
-  blob.take(obs_erase, host(b.erase), E);
+  if (obs_erase) blob.take(obs_erase, host(b.erase), E);
   blob.take(info16, host(b.st) + offsetof(BaState, info), 64);
+  return SD_OK;
+}
+
+extern "C" {
+
+int sd_debug_local_ba(int n_points, const int32_t* obs_off, const int32_t* obs_kf, const float* obs_uv, const float* obs_ur,
+                      const float* obs_inv_sigma2, const uint8_t* obs_kf_bad, const uint8_t* point_bad, int n_kf, const double* T_cm16,
+                      const uint8_t* kf_role, const double* Xw, const float* cam9, double* T_out_cm16, double* Xw_out,
+                      uint8_t* point_status, uint8_t* obs_erase, int32_t* info16) {
+  return debug_ba("sd_debug_local_ba", 0, 0, 1, n_points, obs_off, obs_kf, obs_uv, obs_ur, obs_inv_sigma2, obs_kf_bad, point_bad, n_kf, T_cm16,
+                  kf_role, Xw, cam9, T_out_cm16, Xw_out, point_status, obs_erase, info16);
+}
+
+int sd_debug_global_ba(int n_points, const int32_t* obs_off, const int32_t* obs_kf, const float* obs_uv, const float* obs_ur,
+                       const float* obs_inv_sigma2, const uint8_t* obs_kf_bad, const uint8_t* point_bad, int n_kf, const double* T_cm16,
+                       const uint8_t* kf_role, const double* Xw, const float* cam9, int n_iterations, int robust, double* T_out_cm16,
+                       double* Xw_out, uint8_t* point_status, int32_t* info16) {
+  return debug_ba("sd_debug_global_ba", 1, n_iterations, robust, n_points, obs_off, obs_kf, obs_uv, obs_ur, obs_inv_sigma2, obs_kf_bad,
+                  point_bad, n_kf, T_cm16, kf_role, Xw, cam9, T_out_cm16, Xw_out, point_status, nullptr, info16);
+}
+
+int sd_debug_ldlt(int n, const double* A_packed_lower, const double* b, double* x, int32_t* ok) {
+  SD_REQUIRE(n >= 1 && n <= 6 * SD_GBA_MAX_FREE_KF, SD_ERR_INVALID_ARG, "n outside [1, 6 * SD_GBA_MAX_FREE_KF]");
+  SD_REQUIRE(A_packed_lower && b && x && ok, SD_ERR_INVALID_ARG, "NULL array");
+  const size_t N = (size_t)n;
+  BaState st{};   // a record that wants (iteration 0, trial 0)
+  st.round_live = 1;
+  st.trial_live = 1;
+  Blob blob;
+  const size_t o_st = blob.reserve(1, &st, 1), o_A = blob.reserve((N + 1) * (N + 2) / 2, A_packed_lower, N * (N + 1) / 2);
+  const size_t o_b = blob.reserve(N, b, N), o_W = blob.reserve((N + 1) * GBA_NB, (const double*)nullptr, 0);
+  const size_t o_x = blob.reserve(N, (const double*)nullptr, 0);
+  SD_TRY(blob.run("sd_debug_ldlt", [&] {
+    const LdltArgs la{blob.dev<BaState>(o_st), blob.dev<double>(o_A), blob.dev<double>(o_b), blob.dev<double>(o_W), blob.dev<double>(o_x), n};
+    SD_TRY(launch_ldlt(la, n, 0, 0, 0));
+    SD_HIP_CHECK(hipDeviceSynchronize());
+    return SD_OK;
+  }));
+  blob.take(&st, o_st, sizeof st);
+  *ok = st.solve_ok;
+  blob.take(x, o_x, N * 8);   // never written after a zero pivot: the zeros it was uploaded with
   return SD_OK;
 }
 

@@ -314,6 +314,10 @@ struct BaBuffers {
   size_t bytes, cap_points, cap_obs;
   int n_kf;
   int ran_points, ran_obs;   // what sd_track_get_local_ba downloads: the lists of the last run; ran_points -1: none
+  int ran_global;        // that run was sd_track_global_ba's: each getter answers its own kind only
+  int kcap;              // the free cameras it holds: >= SD_BA_MAX_FREE_KF; the handle's min(SD_GBA_MAX_FREE_KF, n_kf) if that is more
+  double* W;             // [6 kcap + 1][48] the blocked factorisation's current panel, L D (kcap > SD_BA_MAX_FREE_KF)
+  uint32_t* covis;       // [kcap][ceil(kcap / 32)] bit j of row i < j: free cameras i and j see a common point (global BA)
   BaState* st;           // the device state record: status, the Levenberg bookkeeping, info16
   // per edge (= observation, CSR order)
   double* e_meas;        // [E][3] u, v, ur (0 for a monocular edge)
@@ -350,7 +354,7 @@ struct BaBuffers {
   int32_t* coff;         // [K + 1] its edges in clist
   int32_t* clist;        // [E]
   // the reduced system
-  double* S;             // packed lower triangle of the (6K)^2 matrix
+  double* S;             // packed lower triangle of the (6K)^2 matrix, and one more row for the blocked solver's right-hand side
   double* bs;            // [6K]
   double* xp;            // [6K]
 };

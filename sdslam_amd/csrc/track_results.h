@@ -122,6 +122,9 @@ constexpr EndsRow kEndsAppend[] = {
 constexpr EndsRow kEndsBa[] = {
     // write_back = 1 rewrites Tref / Tcur and Xw of a local row: whatever sd_track_set_poses and a write-through refresh end
     {"sd_track_local_ba(write_back)", R_SIM3 | R_TRI | R_FUSE | R_REFRESH | R_APPEND},
+    // ... and so does the global one's (the nLoopKF == 0 branch).  Its own result (mTcwGBA / mPosGBA with write_back = 0) is kept
+    // in the same scratch as the local one's, answers only its own getter, and is ended by sd_track_set_poses besides
+    {"sd_track_global_ba(write_back)", R_SIM3 | R_TRI | R_FUSE | R_REFRESH | R_APPEND},
 };
 
 constexpr bool same_name(const char* a, const char* b) {
@@ -148,5 +151,6 @@ static_assert(ends_of("sd_track_append_new_points(mark_flags)") == (ends_of("sd_
               "... and with mark_flags what sd_track_set_point_flags ends");
 static_assert(ends_of("sd_track_local_ba(write_back)") == (ends_of("sd_track_set_poses") | ends_of("sd_track_refresh_points(write_local)")),
               "a write-back ends what sd_track_set_poses and a write-through refresh end");
+static_assert(ends_of("sd_track_global_ba(write_back)") == ends_of("sd_track_local_ba(write_back)"), "... whichever bundle adjustment wrote");
 
 }  // namespace sd
