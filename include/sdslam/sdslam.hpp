@@ -708,8 +708,7 @@ class ORBmatcher {
     BuildObservationLists(pKF, vpMapPoints, frameOf, L);
     const int n = (int)vpMapPoints.size();
     if (n == 0) return {};
-    check(sd_track_set_observations(batch.handle(), n, L.off.data(), L.frame.data(), L.kp.data(), L.kf_bad.data(), L.ref_obs.data(),
-                                    L.point_bad.data()));
+    SetObservations(batch.handle(), n, L);
     check(sd_track_refresh_points(batch.handle(), point_row, 1));
     RefreshedRows r(n);
     check(sd_track_get_refreshed(batch.handle(), r.status.data(), nullptr, nullptr, r.desc.data(), r.normal.data(), r.max_dist.data(),
@@ -727,9 +726,14 @@ class ORBmatcher {
     std::vector<float> max_dist, min_dist;
     explicit RefreshedRows(size_t n) : status(n, 0), desc(n * 32, 0), normal(n * 3, 0.0), max_dist(n, 0.f), min_dist(n, 0.f) {}
   };
-  // Host code only: every point's observations in iteration order.  A NULL point is sent as a bad one (both functions skip it).
-  template <class KeyFrameT, class MapPointT, class FrameOf>
-  static void BuildObservationLists(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, FrameOf frameOf, ObservationLists& L) {
+  // Host code only: every point's GetObservations() in ITS iteration order into the CSR lists; the one walk behind the refresh and
+  // both bundle adjustments.  pKF (may be null) is frame -1, a keyframe frameOf() does not know -2.  ask_bad: a NULL or bad point is
+  // sent as a bad one, without its observations; otherwise every point is taken as it stands (it must not be NULL).  left[i]: the
+  // reference keyframe is not among the observations (the reference would read observations[pRefKF] of a keyframe that is not
+  // there).  edge(i, pKFi, keypoint index) is called for every entry, in order.
+  template <class KeyFrameT, class MapPointT, class FrameOf, class Edge>
+  static void WalkObservations(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, bool ask_bad, FrameOf frameOf, ObservationLists& L,
+                               Edge edge) {
     const size_t n = vpMapPoints.size();
     L.off.assign(1, 0);
     L.frame.clear(); L.kp.clear(); L.kf_bad.clear();
@@ -738,30 +742,37 @@ class ORBmatcher {
     L.left.assign(n, 0);
     for (size_t i = 0; i < n; i++) {
       MapPointT* pMP = vpMapPoints[i];
-      if (!pMP || pMP->isBad()) {
+      if (ask_bad && (!pMP || pMP->isBad())) {
         L.point_bad[i] = 1;
         L.off.push_back((int32_t)L.frame.size());
         continue;
       }
-      const auto observations = pMP->GetObservations();
+      const auto& observations = pMP->GetObservations();
       const KeyFrameT* pRefKF = pMP->GetReferenceKeyFrame();
       int32_t pos = 0, ref_pos = -1;
       for (const auto& ob : observations) {
         KeyFrameT* pKFi = ob.first;
-        L.frame.push_back(pKFi == pKF ? -1 : ((int)frameOf(pKFi) < 0 ? -2 : (int)frameOf(pKFi)));
+        const int f = pKFi == pKF ? -1 : (int)frameOf(pKFi);
+        L.frame.push_back(pKFi == pKF ? -1 : (f < 0 ? -2 : f));
         L.kp.push_back((int32_t)ob.second);
         L.kf_bad.push_back(pKFi->isBad() ? 1 : 0);
+        edge(i, pKFi, ob.second);
         if (pKFi == pRefKF) ref_pos = pos;
         pos++;
       }
-      if (pos > 0 && ref_pos < 0) {   // (the reference would read observations[pRefKF] of a keyframe that is not there)
-        L.left[i] = 1;
-        L.frame[(size_t)L.off.back()] = -2;   // the device leaves the point, and its row, alone
-      }
+      if (pos > 0 && ref_pos < 0) L.left[i] = 1;
       L.ref_obs[i] = ref_pos < 0 ? 0 : ref_pos;
       L.off.push_back((int32_t)L.frame.size());
     }
-    if (L.frame.empty()) L.frame.push_back(0), L.kp.push_back(0), L.kf_bad.push_back(0);   // (data() of an empty vector may be NULL)
+    // (data() of an empty vector may be NULL: no entry is sent as one entry of zeros; SetObservations sees to the lists per point)
+    if (L.frame.empty()) L.frame.push_back(0), L.kp.push_back(0), L.kf_bad.push_back(0);
+  }
+  // Host code only: the lists of RefreshMapPoints.  A NULL point is sent as a bad one (both functions skip it).
+  template <class KeyFrameT, class MapPointT, class FrameOf>
+  static void BuildObservationLists(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, FrameOf frameOf, ObservationLists& L) {
+    WalkObservations(pKF, vpMapPoints, true, frameOf, L, [](size_t, KeyFrameT*, size_t) {});
+    for (size_t i = 0; i < vpMapPoints.size(); i++)
+      if (L.left[i]) L.frame[(size_t)L.off[i]] = -2;   // the device leaves the point, and its row, alone
   }
   // Host code only: the setters for what the status names; returns the points that stay with the caller
   template <class MapPointT>
@@ -777,16 +788,27 @@ class ORBmatcher {
       }
       if (st & SD_REFRESH_BAD_INDEX) throw Error(SD_ERR_INVALID_ARG, "RefreshMapPoints: an observation's keypoint index is outside its keyframe");
       if (st & SD_REFRESH_DESC) pMP->SetDescriptor(&r.desc[i * 32]);
-      if (st & SD_REFRESH_NORMAL) {
-        pMP->SetNormalVector(&r.normal[i * 3]);
-        pMP->SetMaxDistance(r.max_dist[i]);
-        pMP->SetMinDistance(r.min_dist[i]);
-      }
+      if (st & SD_REFRESH_NORMAL) SetNormalAndDepth(pMP, r, i);
     }
     return left;
   }
 
  protected:
+  friend class Optimizer;   // (the bundle adjustments upload the same lists and apply the same refresh)
+  // The one sd_track_set_observations call from the lists; kf_bad: another per-entry flag list than L.kf_bad
+  static void SetObservations(sd_track* h, int n, const ObservationLists& L, const std::vector<uint8_t>* kf_bad = nullptr) {
+    static const int32_t no_ref = 0;   // n == 0: data() of an empty vector may be NULL
+    static const uint8_t not_bad = 0;
+    check(sd_track_set_observations(h, n, L.off.data(), L.frame.data(), L.kp.data(), (kf_bad ? *kf_bad : L.kf_bad).data(),
+                                    n ? L.ref_obs.data() : &no_ref, n ? L.point_bad.data() : &not_bad));
+  }
+  // What UpdateNormalAndDepth writes, from row i of the refresh's results
+  template <class MapPointT>
+  static void SetNormalAndDepth(MapPointT* pMP, const RefreshedRows& r, size_t i) {
+    pMP->SetNormalVector(&r.normal[i * 3]);
+    pMP->SetMaxDistance(r.max_dist[i]);
+    pMP->SetMinDistance(r.min_dist[i]);
+  }
   float mfNNratio;
   bool mbCheckOrientation;
 };
@@ -835,17 +857,11 @@ class Optimizer {
     const auto Tc = pKF->GetPose();
     check(sd_track_set_poses(h, 0, 1, Tc.data(), Tc.data()));
     if (pKF->N > 0) batch.SetURight(0, pKF->mvuRight.data(), pKF->N);
-    for (size_t k = 0; k < L.resident.size(); k++) {
-      KeyFrameT* kf = L.resident[k];
-      const int f = L.resident_frame[k];
-      const auto T = kf->GetPose();
-      check(sd_track_set_poses(h, f, 1, T.data(), f == 0 ? Tc.data() : T.data()));
-      if (kf->N > 0) check(sd_track_set_uright_ref(h, f, 1, kf->mvuRight.data(), kf->N));
-    }
+    for (size_t k = 0; k < L.resident.size(); k++)   // (Tcur of slot 0 is the current keyframe's pose, not the resident keyframe's)
+      UploadBaKeyFrame(h, L.resident_frame[k], L.resident[k], L.resident_frame[k] == 0 ? Tc.data() : nullptr);
     const int n = (int)L.points.size(), n_ref = (int)L.kf_role.size();
     check(sd_track_set_ba_keyframes(h, n_ref, L.kf_role.data(), L.cur_role));
-    check(sd_track_set_observations(h, n, L.obs.off.data(), L.obs.frame.data(), L.obs.kp.data(), L.obs.kf_bad.data(), L.obs.ref_obs.data(),
-                                    L.obs.point_bad.data()));
+    ORBmatcher::SetObservations(h, n, L.obs);
     check(sd_track_local_ba(h, point_row, 1));
     LocalBaResult r((size_t)n_ref, (size_t)n, L.edge_kf.size());
     check(sd_track_get_local_ba(h, r.T_ref.data(), r.T_cur, r.Xw.data(), r.point_status.data(), r.obs_erase.data(), r.info, n, (int)L.edge_kf.size()));
@@ -854,19 +870,22 @@ class Optimizer {
     if (n == 0) return true;
     if (erased) {   // the lists the refresh reads are the points' observations as they are now
       BuildBaObservations(pKF, frameOf, L);
-      check(sd_track_set_observations(h, n, L.obs.off.data(), L.obs.frame.data(), L.obs.kp.data(), L.obs.kf_bad.data(), L.obs.ref_obs.data(),
-                                      L.obs.point_bad.data()));
+      ORBmatcher::SetObservations(h, n, L.obs);
     }
     check(sd_track_refresh_points(h, point_row, 1));
     ORBmatcher::RefreshedRows rr((size_t)n);
     check(sd_track_get_refreshed(h, rr.status.data(), nullptr, nullptr, nullptr, rr.normal.data(), rr.max_dist.data(), rr.min_dist.data(), n));
-    for (int i = 0; i < n; i++)   // pMP->UpdateNormalAndDepth() (:712); a point whose reference keyframe does not observe it stays as it is
-      if ((rr.status[i] & SD_REFRESH_NORMAL) && !L.obs.left[i]) {
-        L.points[i]->SetNormalVector(&rr.normal[(size_t)i * 3]);
-        L.points[i]->SetMaxDistance(rr.max_dist[i]);
-        L.points[i]->SetMinDistance(rr.min_dist[i]);
-      }
+    for (size_t i = 0; i < (size_t)n; i++)   // pMP->UpdateNormalAndDepth() (:712); a point whose reference keyframe does not observe it stays as it is
+      if ((rr.status[i] & SD_REFRESH_NORMAL) && !L.obs.left[i]) ORBmatcher::SetNormalAndDepth(L.points[i], rr, i);
     return true;
+  }
+  // A resident keyframe of either bundle adjustment into its slot: the pose (Tcur: what the slot's current-frame pose is given when
+  // it is not the keyframe's own), then its mvuRight row.  (ORBmatcher::UploadFuseKeyFrame sends the same two in the other order.)
+  template <class KeyFrameT>
+  static void UploadBaKeyFrame(sd_track* h, int slot, KeyFrameT* kf, const double* Tcur = nullptr) {
+    const auto T = kf->GetPose();
+    check(sd_track_set_poses(h, slot, 1, T.data(), Tcur ? Tcur : T.data()));
+    if (kf->N > 0) check(sd_track_set_uright_ref(h, slot, 1, kf->mvuRight.data(), kf->N));
   }
   // void Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust)          src/Optimizer.cc:53-219
   // on the device (sd_track_global_ba).  Every keyframe is a frame of the ref extractor: frameOf(KeyFrameT*) returns it, or a
@@ -894,15 +913,10 @@ class Optimizer {
     sd_track* h = batch.handle();
     ORBmatcher matcher(0.6f, false);
     matcher.UploadFusePoints(batch, point_row, vpMP, true, [](MapPointT*) { return false; });
-    for (size_t k = 0; k < L.resident.size(); k++) {
-      const auto T = L.resident[k]->GetPose();
-      check(sd_track_set_poses(h, L.resident_frame[k], 1, T.data(), T.data()));
-      if (L.resident[k]->N > 0) check(sd_track_set_uright_ref(h, L.resident_frame[k], 1, L.resident[k]->mvuRight.data(), L.resident[k]->N));
-    }
+    for (size_t k = 0; k < L.resident.size(); k++) UploadBaKeyFrame(h, L.resident_frame[k], L.resident[k]);
     const int n = (int)vpMP.size(), n_ref = (int)L.kf_role.size();
     check(sd_track_set_ba_keyframes(h, n_ref, L.kf_role.data(), 2));
-    check(sd_track_set_observations(h, n, L.obs.off.data(), L.obs.frame.data(), L.obs.kp.data(), L.ba_kf_bad.data(), L.obs.ref_obs.data(),
-                                    L.obs.point_bad.data()));
+    ORBmatcher::SetObservations(h, n, L.obs, &L.ba_kf_bad);
     check(sd_track_global_ba(h, point_row, nIterations, bRobust ? 1 : 0, nLoopKF == 0 ? 1 : 0));
     std::vector<double> T_ref((size_t)n_ref * 16 + 16, 0.0), Xw((size_t)n * 3 + 3, 0.0);
     std::vector<uint8_t> point_status((size_t)n + 1, 0);
@@ -924,21 +938,15 @@ class Optimizer {
     }
     ORBmatcher::RefreshedRows rr((size_t)n);
     if (n > 0) {   // UpdateNormalAndDepth reads every observation: the lists with isBad() alone, on the poses and positions written back
-      if (L.ba_kf_bad != L.obs.kf_bad)
-        check(sd_track_set_observations(h, n, L.obs.off.data(), L.obs.frame.data(), L.obs.kp.data(), L.obs.kf_bad.data(), L.obs.ref_obs.data(),
-                                        L.obs.point_bad.data()));
+      if (L.ba_kf_bad != L.obs.kf_bad) ORBmatcher::SetObservations(h, n, L.obs);
       check(sd_track_refresh_points(h, point_row, 1));
       check(sd_track_get_refreshed(h, rr.status.data(), nullptr, nullptr, nullptr, rr.normal.data(), rr.max_dist.data(), rr.min_dist.data(), n));
     }
     for (size_t k = 0; k < L.resident.size(); k++) L.resident[k]->SetPose(&T_ref[(size_t)L.resident_frame[k] * 16]);
-    for (int i = 0; i < n; i++) {
-      if (point_status[(size_t)i] != SD_BA_POINT_OPTIMISED) continue;
-      vpMP[(size_t)i]->SetWorldPos(&Xw[(size_t)i * 3]);
-      if ((rr.status[(size_t)i] & SD_REFRESH_NORMAL) && !L.obs.left[(size_t)i]) {
-        vpMP[(size_t)i]->SetNormalVector(&rr.normal[(size_t)i * 3]);
-        vpMP[(size_t)i]->SetMaxDistance(rr.max_dist[(size_t)i]);
-        vpMP[(size_t)i]->SetMinDistance(rr.min_dist[(size_t)i]);
-      }
+    for (size_t i = 0; i < (size_t)n; i++) {
+      if (point_status[i] != SD_BA_POINT_OPTIMISED) continue;
+      vpMP[i]->SetWorldPos(&Xw[i * 3]);
+      if ((rr.status[i] & SD_REFRESH_NORMAL) && !L.obs.left[i]) ORBmatcher::SetNormalAndDepth(vpMP[i], rr, i);
     }
     return true;
   }
@@ -972,36 +980,11 @@ class Optimizer {
       if (L.kf_role.size() <= (size_t)f) L.kf_role.resize((size_t)f + 1, 0);
       L.kf_role[(size_t)f] = kf->mnId == 0 ? 2 : 1;
     }
-    ORBmatcher::ObservationLists& O = L.obs;
-    const size_t n = vpMP.size();
-    O.off.assign(1, 0);
-    O.frame.clear(); O.kp.clear(); O.kf_bad.clear(); L.ba_kf_bad.clear();
-    O.ref_obs.assign(n, 0); O.point_bad.assign(n, 0); O.left.assign(n, 0);
-    for (size_t i = 0; i < n; i++) {
-      MapPointT* pMP = vpMP[i];
-      if (!pMP || pMP->isBad()) {
-        O.point_bad[i] = 1;
-        O.off.push_back((int32_t)O.frame.size());
-        continue;
-      }
-      const KeyFrameT* pRefKF = pMP->GetReferenceKeyFrame();
-      int32_t pos = 0, ref_pos = -1;
-      for (const auto& ob : pMP->GetObservations()) {
-        KeyFrameT* pKFi = ob.first;
-        const int f = (int)frameOf(pKFi);
-        O.frame.push_back(f < 0 ? -2 : f);
-        O.kp.push_back((int32_t)ob.second);
-        O.kf_bad.push_back(pKFi->isBad() ? 1 : 0);
-        L.ba_kf_bad.push_back(pKFi->isBad() || pKFi->mnId > maxKFid ? 1 : 0);
-        if (pKFi == pRefKF) ref_pos = pos;
-        pos++;
-      }
-      if (pos > 0 && ref_pos < 0) O.left[i] = 1;
-      O.ref_obs[i] = ref_pos < 0 ? 0 : ref_pos;
-      O.off.push_back((int32_t)O.frame.size());
-    }
-    if (O.frame.empty()) O.frame.push_back(0), O.kp.push_back(0), O.kf_bad.push_back(0), L.ba_kf_bad.push_back(0);
-    if (O.ref_obs.empty()) O.ref_obs.push_back(0), O.point_bad.push_back(0);
+    L.ba_kf_bad.clear();
+    ORBmatcher::WalkObservations((KeyFrameT*)nullptr, vpMP, true, frameOf, L.obs, [&](size_t, KeyFrameT* pKFi, size_t) {
+      L.ba_kf_bad.push_back(pKFi->isBad() || pKFi->mnId > maxKFid ? 1 : 0);
+    });
+    if (L.ba_kf_bad.empty()) L.ba_kf_bad.push_back(0);   // as the walk pads kf_bad
   }
   // lLocalKeyFrames, lLocalMapPoints and (through `resident`) lFixedCameras, and what the device is given for them
   template <class KeyFrameT, class MapPointT>
@@ -1067,34 +1050,13 @@ class Optimizer {
   // Host code only: the observations of L.points as they are now, in iteration order
   template <class KeyFrameT, class MapPointT, class FrameOf>
   static void BuildBaObservations(KeyFrameT* pKF, FrameOf frameOf, LocalBaLists<KeyFrameT, MapPointT>& L) {
-    ORBmatcher::ObservationLists& O = L.obs;
-    const size_t n = L.points.size();
-    O.off.assign(1, 0);
-    O.frame.clear(); O.kp.clear(); O.kf_bad.clear();
-    O.ref_obs.assign(n, 0); O.point_bad.assign(n, 0); O.left.assign(n, 0);
     L.edge_kf.clear(); L.edge_pt.clear(); L.edge_stereo.clear();
-    for (size_t i = 0; i < n; i++) {
-      MapPointT* pMP = L.points[i];
-      const KeyFrameT* pRefKF = pMP->GetReferenceKeyFrame();
-      int32_t pos = 0, ref_pos = -1;
-      for (const auto& ob : pMP->GetObservations()) {
-        KeyFrameT* pKFi = ob.first;
-        const int f = pKFi == pKF ? -1 : (int)frameOf(pKFi);
-        O.frame.push_back(pKFi == pKF ? -1 : (f < 0 ? -2 : f));
-        O.kp.push_back((int32_t)ob.second);
-        O.kf_bad.push_back(pKFi->isBad() ? 1 : 0);
-        L.edge_kf.push_back(pKFi);
-        L.edge_pt.push_back((int32_t)i);
-        L.edge_stereo.push_back(ob.second < pKFi->mvuRight.size() && !(pKFi->mvuRight[ob.second] < 0) ? 1 : 0);
-        if (pKFi == pRefKF) ref_pos = pos;
-        pos++;
-      }
-      if (pos > 0 && ref_pos < 0) O.left[i] = 1;
-      O.ref_obs[i] = ref_pos < 0 ? 0 : ref_pos;
-      O.off.push_back((int32_t)O.frame.size());
-    }
-    if (O.frame.empty()) O.frame.push_back(0), O.kp.push_back(0), O.kf_bad.push_back(0);   // (data() of an empty vector may be NULL)
-    if (O.ref_obs.empty()) O.ref_obs.push_back(0), O.point_bad.push_back(0);
+    // (lLocalMapPoints is sent as collected: isBad() is not asked again, nor after the erasures)
+    ORBmatcher::WalkObservations(pKF, L.points, false, frameOf, L.obs, [&](size_t i, KeyFrameT* pKFi, size_t kp) {
+      L.edge_kf.push_back(pKFi);
+      L.edge_pt.push_back((int32_t)i);
+      L.edge_stereo.push_back(kp < pKFi->mvuRight.size() && !(pKFi->mvuRight[kp] < 0) ? 1 : 0);
+    });
   }
   // Host code only: :685-713 without the refresh.  Returns whether anything was erased.
   template <class KeyFrameT, class MapPointT>

@@ -862,14 +862,24 @@ class Tracker:
         _check(self.L.sd_track_global_ba(self.h, int(point_row), int(n_iterations), int(robust), int(write_back)))
         self._n_gba = self._n_refresh
 
-    def get_global_ba(self):
-        """dict(T_ref [n_ref, 4, 4], T_cur [4, 4], Xw, point_status, info16) of the last global_ba()."""
-        n = getattr(self, "_n_gba", 0)
+    def _get_ba(self, getter, n, n_obs=None):
+        """What both bundle adjustments' getters return; n_obs: the getter has obs_erase [n_obs] as well."""
         Tr, Tc = np.zeros((self._n_ba_ref, 16)), np.zeros(16)
-        out = dict(Xw=np.zeros((n, 3)), point_status=np.zeros(n, np.uint8), info16=np.zeros(16, np.int32))
-        _check(self.L.sd_track_get_global_ba(self.h, _p(Tr), _p(Tc), _p(out["Xw"]), _p(out["point_status"]), _p(out["info16"]), n))
+        out = dict(Xw=np.zeros((n, 3)), point_status=np.zeros(n, np.uint8))
+        if n_obs is not None:
+            out["obs_erase"] = np.zeros(n_obs, np.uint8)
+        out["info16"] = np.zeros(16, np.int32)
+        _check(getter(self.h, _p(Tr), _p(Tc), *[_p(a) for a in out.values()], n, *([] if n_obs is None else [n_obs])))
         out.update(T_ref=np.stack([_from_cm(t) for t in Tr]) if len(Tr) else np.zeros((0, 4, 4)), T_cur=_from_cm(Tc))
         return out
+
+    def get_global_ba(self):
+        """dict(T_ref [n_ref, 4, 4], T_cur [4, 4], Xw, point_status, info16) of the last global_ba()."""
+        return self._get_ba(self.L.sd_track_get_global_ba, getattr(self, "_n_gba", 0))
+
+    def get_local_ba(self):
+        """dict(T_ref [n_ref, 4, 4], T_cur [4, 4], Xw, point_status, obs_erase, info16) of the last local_ba()."""
+        return self._get_ba(self.L.sd_track_get_local_ba, *self._n_ba)
 
     def read_poses(self, n):
         """Tref and Tcur of slots 0 .. n - 1 as they are on the device: ([n, 4, 4], [n, 4, 4])."""
@@ -878,16 +888,6 @@ class Tracker:
             for f in range(n):
                 _check(self.L.sd_track_debug_read(self.h, 8 + side, f, _p(out[side, f]), 128))
         return np.stack([_from_cm(t) for t in out[0]]), np.stack([_from_cm(t) for t in out[1]])
-
-    def get_local_ba(self):
-        """dict(T_ref [n_ref, 4, 4], T_cur [4, 4], Xw, point_status, obs_erase, info16) of the last local_ba()."""
-        n, e = self._n_ba
-        Tr, Tc = np.zeros((self._n_ba_ref, 16)), np.zeros(16)
-        out = dict(Xw=np.zeros((n, 3)), point_status=np.zeros(n, np.uint8), obs_erase=np.zeros(e, np.uint8), info16=np.zeros(16, np.int32))
-        _check(self.L.sd_track_get_local_ba(self.h, _p(Tr), _p(Tc), _p(out["Xw"]), _p(out["point_status"]), _p(out["obs_erase"]),
-                                            _p(out["info16"]), n, e))
-        out.update(T_ref=np.stack([_from_cm(t) for t in Tr]) if len(Tr) else np.zeros((0, 4, 4)), T_cur=_from_cm(Tc))
-        return out
 
     # --- Sim3Solver on the SearchByPoints pairing (src/Sim3Solver.cc; caller LoopClosing::ComputeSim3) ---
     def set_sim3_points(self, frame0, Xw_cur, Xw_ref):
@@ -1220,12 +1220,9 @@ def debug_refresh_points(obs_off, obs_desc, obs_centre, obs_octave, ref_obs, Xw,
     return out
 
 
-def debug_local_ba(problem, cam9=None):
-    """A LocalBundleAdjustment problem (the dict tests/ba_ref.py documents: off, kf, uv, ur, inv_sigma2, kf_bad, point_bad, poses
-    [n_kf, 4, 4], roles, Xw, cam, bf) from host arrays through the kernels of sd_track_local_ba (diagnostics).  Returns dict(T
-    [n_kf, 4, 4], Xw, point_status, obs_erase, info16)."""
-    L = lib()
-    q = problem
+def _ba_marshal(q, cam9, erase):
+    """A bundle-adjustment problem dict as (the arguments both debug entries begin with: n .. cam9, their output buffers in the
+    entries' order: T, Xw, point_status, obs_erase if `erase`, info16)"""
     off = np.ascontiguousarray(q["off"], np.int32)
     n, total = len(off) - 1, int(off[-1])
     kf, uv = np.ascontiguousarray(q["kf"], np.int32), np.ascontiguousarray(q["uv"], np.float32).reshape(total, 2)
@@ -1239,36 +1236,33 @@ def debug_local_ba(problem, cam9=None):
         cam9 = list(q["cam"]) + [q["bf"], 0.0, 1.0, 0.0, 1.0]
     cam = np.ascontiguousarray(cam9, np.float32)
     assert len(kf) == len(ur) == len(inv) == total and len(T) == len(roles) and len(cam) == 9
-    To, Xo = np.zeros_like(T), np.zeros_like(X)
-    ps, er, info = np.zeros(n, np.uint8), np.zeros(total, np.uint8), np.zeros(16, np.int32)
-    _check(L.sd_debug_local_ba(n, _p(off), _p(kf), _p(uv), _p(ur), _p(inv), _p(kb), _p(pb), len(roles), _p(T), _p(roles), _p(X), _p(cam),
-                               _p(To), _p(Xo), _p(ps), _p(er), _p(info)))
-    return dict(T=np.stack([_from_cm(t) for t in To]), Xw=Xo, point_status=ps, obs_erase=er, info16=info)
+    out = dict(T=np.zeros_like(T), Xw=np.zeros_like(X), point_status=np.zeros(n, np.uint8))
+    if erase:
+        out["obs_erase"] = np.zeros(total, np.uint8)
+    out["info16"] = np.zeros(16, np.int32)
+    return [n, off, kf, uv, ur, inv, kb, pb, len(roles), T, roles, X, cam], out
+
+
+def _ba_call(entry, args, out):
+    """The debug entry on the arguments (arrays as pointers) and the buffers, and the buffers as the result dict"""
+    _check(entry(*[a if isinstance(a, int) else _p(a) for a in args + list(out.values())]))
+    out["T"] = np.stack([_from_cm(t) for t in out["T"]])
+    return out
+
+
+def debug_local_ba(problem, cam9=None):
+    """A LocalBundleAdjustment problem (the dict tests/ba_ref.py documents: off, kf, uv, ur, inv_sigma2, kf_bad, point_bad, poses
+    [n_kf, 4, 4], roles, Xw, cam, bf) from host arrays through the kernels of sd_track_local_ba (diagnostics).  Returns dict(T
+    [n_kf, 4, 4], Xw, point_status, obs_erase, info16)."""
+    args, out = _ba_marshal(problem, cam9, True)
+    return _ba_call(lib().sd_debug_local_ba, args, out)
 
 
 def debug_global_ba(problem, n_iterations, robust, cam9=None):
     """A BundleAdjustment problem (the dict of debug_local_ba; roles 1 free, 2 fixed, 0 no vertex) through the kernels of
     sd_track_global_ba (diagnostics).  Returns dict(T [n_kf, 4, 4], Xw, point_status, info16)."""
-    L = lib()
-    q = problem
-    off = np.ascontiguousarray(q["off"], np.int32)
-    n, total = len(off) - 1, int(off[-1])
-    kf, uv = np.ascontiguousarray(q["kf"], np.int32), np.ascontiguousarray(q["uv"], np.float32).reshape(total, 2)
-    ur, inv = np.ascontiguousarray(q["ur"], np.float32), np.ascontiguousarray(q["inv_sigma2"], np.float32)
-    kb = None if q.get("kf_bad") is None else np.ascontiguousarray(q["kf_bad"], np.uint8)
-    pb = None if q.get("point_bad") is None else np.ascontiguousarray(q["point_bad"], np.uint8)
-    roles = np.ascontiguousarray(q["roles"], np.uint8)
-    T = np.ascontiguousarray(np.stack([_cm(t) for t in np.asarray(q["poses"], np.float64)]))
-    X = np.ascontiguousarray(q["Xw"], np.float64).reshape(n, 3)
-    if cam9 is None:
-        cam9 = list(q["cam"]) + [q["bf"], 0.0, 1.0, 0.0, 1.0]
-    cam = np.ascontiguousarray(cam9, np.float32)
-    assert len(kf) == len(ur) == len(inv) == total and len(T) == len(roles) and len(cam) == 9
-    To, Xo = np.zeros_like(T), np.zeros_like(X)
-    ps, info = np.zeros(n, np.uint8), np.zeros(16, np.int32)
-    _check(L.sd_debug_global_ba(n, _p(off), _p(kf), _p(uv), _p(ur), _p(inv), _p(kb), _p(pb), len(roles), _p(T), _p(roles), _p(X), _p(cam),
-                                int(n_iterations), int(robust), _p(To), _p(Xo), _p(ps), _p(info)))
-    return dict(T=np.stack([_from_cm(t) for t in To]), Xw=Xo, point_status=ps, info16=info)
+    args, out = _ba_marshal(problem, cam9, False)
+    return _ba_call(lib().sd_debug_global_ba, args + [int(n_iterations), int(robust)], out)
 
 
 def debug_ldlt(A, b):

@@ -14,6 +14,10 @@ Quirks kept: lambda re-initialised at iteration 0 of each optimize(); Terminate 
 the two classification loops is the error of the LAST computeActiveErrors (after a rejected last trial that of the rejected step;
 for a level-1 edge in round 2, round 1's last value) while isDepthPositive() is taken at the estimate.
 A zero pivot in the reduced system's LDL^T (the only way Eigen's SimplicialLDLT reports failure) fails the trial with x = 0.
+
+levenberg() is the one Levenberg driver: run() calls it twice (5 robust iterations, classify(), 10 plain ones on level 0, classify()),
+tests/gba_ref.py (Optimizer::BundleAdjustment) once on every edge.  Its solvers of the reduced system, ldlt_solve and
+blocked_ldlt_solve (the order the device takes for more than MAX_FREE_KF free cameras), are at the end of the file.
 """
 import numpy as np
 
@@ -195,195 +199,209 @@ def _setup(p):
     return s
 
 
+def _load(p, s):
+    """The graph of an accepted problem on s: the edges' data, full length and indexed by observation (cam, pt of _setup, stereo, meas,
+    info, and err = the error of the last computeActiveErrors), the free cameras' slots and the estimate (Q, Tt, X)."""
+    s.K = tuple(float(np.float32(v)) for v in p["cam"]) + (float(np.float32(p["bf"])),)
+    s.cam = np.where(s.live, s.kf, 0)
+    uv, ur = np.asarray(p["uv"], np.float32), np.asarray(p["ur"], np.float32)
+    s.stereo = ~(ur < 0)
+    s.meas = np.stack([uv[:, 0], uv[:, 1], np.where(s.stereo, ur, 0)], 1).astype(np.float64)
+    s.info = np.asarray(p["inv_sigma2"], np.float32).astype(np.float64)
+    s.err = np.zeros((s.E, 3))
+    s.free = s.roles == 1
+    free_ids = np.flatnonzero(s.free)
+    s.slot = -np.ones(s.n_kf, np.int64)
+    s.slot[free_ids] = np.arange(len(free_ids))
+    s.Kf = len(free_ids)
+    T_in = np.asarray(p["poses"], np.float64)
+    s.Q, s.Tt = np.zeros((s.n_kf, 4)), np.zeros((s.n_kf, 3))
+    for c in range(s.n_kf):
+        s.Q[c], s.Tt[c] = se3_from_T(T_in[c])
+    s.X = np.asarray(p["Xw"], np.float64).copy()
+
+
+def _chi2_of(s, idx):
+    return (s.err[idx] * (s.info[idx, None] * s.err[idx])).sum(1)
+
+
+def levenberg(s, act, iterations, robust, delta, solver, trace):
+    """One optimize(iterations) of OptimizationAlgorithmLevenberg on the edges `act` (indices into the observations) of the graph that
+    _load put on s; delta [E] is each edge's Huber width, read if robust.  solver: "schur" (ldlt_solve on the reduced system), "blocked"
+    (blocked_ldlt_solve on it) or "dense" (np.linalg.solve on the whole system).  Appends one dict(chi2, lambda0, trials=[dict(lam,
+    rho, accept, temp_chi, scale)]) per iteration to trace, leaves s.Q, s.Tt, s.X and s.err[act] updated and returns (iterations done,
+    trials, exit taken)."""
+    P, Kf, slot, K = s.P, s.Kf, s.slot, s.K
+    a_pt = np.zeros(P, bool)
+    a_pt[s.pt[act]] = True
+    a_kf = np.zeros(s.n_kf, bool)
+    a_kf[s.cam[act]] = True
+    a_kf &= s.free
+    if not (a_pt.any() or a_kf.any()):
+        return 0, 0, EXIT_NOT_RUN
+    e_cam, e_pt, e_st = s.cam[act], s.pt[act], s.stereo[act]
+    e_slot = slot[e_cam]
+    fe = np.flatnonzero(a_kf[e_cam])                    # the edges of a free camera
+    a_slots = slot[np.flatnonzero(a_kf)]
+    info, meas, delta = s.info[act], s.meas[act], delta[act]
+
+    def active_errors():
+        s.err[act] = edge_errors(map_points(s.Q, s.Tt, s.X, e_cam, e_pt), e_st, meas, K)
+        c2 = _chi2_of(s, act)
+        return float((huber(c2, delta)[0] if robust else c2).sum())
+
+    lam, ni, n_bad, done, trials, exit_taken = -1.0, 2.0, 0, 0, 0, EXIT_NOT_RUN
+    for it in range(iterations):
+        cur_chi = active_errors()
+        ini_chi = cur_chi
+        pc = map_points(s.Q, s.Tt, s.X, e_cam, e_pt)
+        Rall = np.stack([q_to_R(s.Q[c]) for c in range(s.n_kf)])
+        Jl, Jp = edge_jacobians(pc, Rall[e_cam], e_st, K)
+        c2 = _chi2_of(s, act)
+        rho1 = huber(c2, delta)[1] if robust else np.ones(len(act))
+        w = rho1 * info
+        wr = -(info * rho1)[:, None] * s.err[act]                         # omega_r = -omega * error * rho[1]
+        Hll, bl = np.zeros((P, 3, 3)), np.zeros((P, 3))
+        np.add.at(Hll, e_pt, np.einsum("nda,n,ndb->nab", Jl, w, Jl))
+        np.add.at(bl, e_pt, np.einsum("nda,nd->na", Jl, wr))
+        Hpp, bp = np.zeros((Kf, 6, 6)), np.zeros((Kf, 6))
+        np.add.at(Hpp, e_slot[fe], np.einsum("nda,n,ndb->nab", Jp[fe], w[fe], Jp[fe]))
+        np.add.at(bp, e_slot[fe], np.einsum("nda,nd->na", Jp[fe], wr[fe]))
+        Hpl = np.einsum("nda,n,ndb->nab", Jp, w, Jl)                      # [n, 6, 3], used where fe
+        if it == 0:
+            diag = [np.abs(np.diagonal(Hll[a_pt], axis1=1, axis2=2)).ravel(), np.abs(np.diagonal(Hpp[a_slots], axis1=1, axis2=2)).ravel()]
+            lam, ni, n_bad = 1e-5 * float(np.concatenate(diag + [np.zeros(1)]).max()), 2.0, 0
+        it_rec = dict(chi2=cur_chi, lambda0=lam, trials=[])
+        trace.append(it_rec)
+        rho, qmax = 0.0, 0
+        while True:
+            backup = (s.Q.copy(), s.Tt.copy(), s.X.copy())
+            xp, xl, ok = np.zeros((Kf, 6)), np.zeros((P, 3)), True
+            if solver in REDUCED_SOLVERS:
+                Dinv = np.zeros((P, 3, 3))
+                Dinv[a_pt] = np.linalg.inv(Hll[a_pt] + lam * np.eye(3))
+                db = np.einsum("pab,pb->pa", Dinv, bl)
+                S = np.zeros((Kf, 6, Kf, 6))
+                for k in a_slots:
+                    S[k, :, k, :] = Hpp[k] + lam * np.eye(6)
+                bs = bp.copy()
+                np.subtract.at(bs, e_slot[fe], np.einsum("nab,nb->na", Hpl[fe], db[e_pt[fe]]))
+                order = np.argsort(e_pt[fe], kind="stable")
+                fes = fe[order]
+                for grp in np.split(fes, np.flatnonzero(np.diff(e_pt[fes])) + 1):
+                    if len(grp) == 0:
+                        continue
+                    D = Dinv[e_pt[grp[0]]]
+                    for a in grp:
+                        BD = Hpl[a] @ D
+                        for b in grp:
+                            S[e_slot[a], :, e_slot[b], :] -= BD @ Hpl[b].T
+                idx = (a_slots[:, None] * 6 + np.arange(6)).ravel()
+                if len(idx):
+                    ok, sol = REDUCED_SOLVERS[solver](S.reshape(Kf * 6, Kf * 6)[np.ix_(idx, idx)], bs.reshape(-1)[idx])
+                    if ok:
+                        xp.reshape(-1)[idx] = sol
+                if ok:
+                    cl = bl.copy()
+                    np.subtract.at(cl, e_pt[fe], np.einsum("nab,na->nb", Hpl[fe], xp[e_slot[fe]]))
+                    xl[a_pt] = np.einsum("pab,pb->pa", Dinv, cl)[a_pt]
+                else:
+                    xp[:] = 0
+            else:                                    # the same system, solved densely at once
+                assert solver == "dense"
+                pi = np.flatnonzero(a_pt)
+                n = 6 * len(a_slots) + 3 * len(pi)
+                col_k = -np.ones(Kf, np.int64)
+                col_k[a_slots] = np.arange(len(a_slots)) * 6
+                col_p = -np.ones(P, np.int64)
+                col_p[pi] = 6 * len(a_slots) + np.arange(len(pi)) * 3
+                H, b = np.zeros((n, n)), np.zeros(n)
+                for k in a_slots:
+                    H[col_k[k]:col_k[k] + 6, col_k[k]:col_k[k] + 6] = Hpp[k]
+                    b[col_k[k]:col_k[k] + 6] = bp[k]
+                for q in pi:
+                    H[col_p[q]:col_p[q] + 3, col_p[q]:col_p[q] + 3] = Hll[q]
+                    b[col_p[q]:col_p[q] + 3] = bl[q]
+                for a in fe:
+                    r, c = col_k[e_slot[a]], col_p[e_pt[a]]
+                    H[r:r + 6, c:c + 3] += Hpl[a]
+                    H[c:c + 3, r:r + 6] += Hpl[a].T
+                H[np.arange(n), np.arange(n)] += lam
+                sol = np.linalg.solve(H, b)
+                for k in a_slots:
+                    xp[k] = sol[col_k[k]:col_k[k] + 6]
+                for q in pi:
+                    xl[q] = sol[col_p[q]:col_p[q] + 3]
+            for c in np.flatnonzero(a_kf):
+                s.Q[c], s.Tt[c] = se3_mul(*se3_exp(xp[slot[c]]), s.Q[c], s.Tt[c])
+            s.X[a_pt] = s.X[a_pt] + xl[a_pt]
+            temp_chi = active_errors()
+            if not ok:
+                temp_chi = np.finfo(np.float64).max
+            rho = cur_chi - temp_chi
+            scale = 0.0
+            for k in a_slots:
+                scale += float((xp[k] * (lam * xp[k] + bp[k])).sum())
+            scale += float((xl[a_pt] * (lam * xl[a_pt] + bl[a_pt])).sum())
+            rho /= scale + 1e-3
+            accept = bool(rho > 0 and np.isfinite(temp_chi))
+            it_rec["trials"].append(dict(lam=lam, rho=rho, accept=accept, temp_chi=temp_chi, scale=scale))
+            if accept:
+                alpha = min(1. - (2 * rho - 1) ** 3, 2. / 3.)
+                lam *= max(1. / 3., alpha)
+                ni = 2.0
+                cur_chi = temp_chi
+            else:
+                lam *= ni
+                ni *= 2
+                s.Q, s.Tt, s.X = backup
+            qmax += 1
+            trials += 1
+            if not (rho < 0 and qmax < 10):
+                break
+        done += 1
+        exit_taken = EXIT_ITERATIONS
+        if qmax == 10 or rho == 0:
+            exit_taken = EXIT_QMAX if qmax == 10 else EXIT_RHO_ZERO
+            break
+        n_bad = n_bad + 1 if (ini_chi - cur_chi) * 1e3 < ini_chi else 0
+        if n_bad >= 3:
+            exit_taken = EXIT_NBAD
+            break
+    return done, trials, exit_taken
+
+
 def run(p, solver="schur"):
-    """The whole call.  Returns dict(status, T [n_kf, 4, 4], Xw, point_status, obs_erase, info16, trace); trace[r] is a list of
-    iterations, each dict(chi2, lambda0, trials=[dict(lam, rho, accept, temp_chi)])."""
+    """The whole call.  Returns dict(status, T [n_kf, 4, 4], Xw, point_status, obs_erase, info16, trace); trace[r] is the trace of
+    levenberg() in round r."""
     s = _setup(p)
-    T_in, X_in = np.asarray(p["poses"], np.float64), np.asarray(p["Xw"], np.float64)
-    out = dict(status=s.status, T=T_in.copy(), Xw=X_in.copy(), point_status=s.point_status, obs_erase=np.zeros(s.E, np.uint8),
-               info16=np.zeros(16, np.int32), trace=[[], []])
-    out["info16"][0] = s.status
+    out = dict(status=s.status, T=np.array(p["poses"], np.float64), Xw=np.array(p["Xw"], np.float64), point_status=s.point_status,
+               obs_erase=np.zeros(s.E, np.uint8), info16=np.zeros(16, np.int32), trace=[[], []])
+    info16 = out["info16"]
+    info16[0] = s.status
     if s.status != SD_BA_OK:
         return out
-    K = tuple(float(np.float32(v)) for v in p["cam"]) + (float(np.float32(p["bf"])),)
-    E, P, n_kf, pt, cam = s.E, s.P, s.n_kf, s.pt, np.where(s.live, s.kf, 0)
-    edge = s.live.copy()
-    uv, ur = np.asarray(p["uv"], np.float32), np.asarray(p["ur"], np.float32)
-    stereo = ~(ur < 0)
-    meas = np.stack([uv[:, 0], uv[:, 1], np.where(stereo, ur, 0)], 1).astype(np.float64)
-    info = np.asarray(p["inv_sigma2"], np.float32).astype(np.float64)
+    _load(p, s)
+    E, edge, stereo, cam, pt = s.E, s.live.copy(), s.stereo, s.cam, s.pt
     delta = np.where(stereo, DELTA_STEREO, DELTA_MONO)
-    has_edge_pt = np.zeros(P, bool)
+    has_edge_pt = np.zeros(s.P, bool)
     has_edge_pt[pt[edge]] = True
     s.point_status[has_edge_pt] = POINT_OPTIMISED
-    has_edge_kf = np.zeros(n_kf, bool)
+    has_edge_kf = np.zeros(s.n_kf, bool)
     has_edge_kf[cam[edge]] = True
-    free = s.roles == 1
-    free_ids = np.flatnonzero(free)
-    slot = -np.ones(n_kf, np.int64)
-    slot[free_ids] = np.arange(len(free_ids))
-    Kf = len(free_ids)
     n_fixed = int(((s.roles == 2) | ((s.roles == 0) & has_edge_kf)).sum())
-    Q, Tt = np.zeros((n_kf, 4)), np.zeros((n_kf, 3))
-    for c in range(n_kf):
-        Q[c], Tt[c] = se3_from_T(T_in[c])
-    X = X_in.copy()
-    err = np.zeros((E, 3))
     level = np.zeros(E, np.int8)
-    info16 = out["info16"]
-    info16[1:6] = [Kf, n_fixed, int(has_edge_pt.sum()), int((edge & ~stereo).sum()), int((edge & stereo).sum())]
-
-    def chi2_of(idx):
-        return (err[idx] * (info[idx, None] * err[idx])).sum(1)
+    info16[1:6] = [s.Kf, n_fixed, int(has_edge_pt.sum()), int((edge & ~stereo).sum()), int((edge & stereo).sum())]
 
     def optimize(iterations, robust, trace):
-        nonlocal Q, Tt, X
-        act = np.flatnonzero(edge & (level == 0))
-        a_pt = np.zeros(P, bool)
-        a_pt[pt[act]] = True
-        a_kf = np.zeros(n_kf, bool)
-        a_kf[cam[act]] = True
-        a_kf &= free
-        if not (a_pt.any() or a_kf.any()):
-            return 0, 0, EXIT_NOT_RUN
-        e_cam, e_pt, e_st = cam[act], pt[act], stereo[act]
-        e_slot = slot[e_cam]
-        e_free = a_kf[e_cam]
-
-        def active_errors():
-            err[act] = edge_errors(map_points(Q, Tt, X, e_cam, e_pt), e_st, meas[act], K)
-            c2 = chi2_of(act)
-            return float((huber(c2, delta[act])[0] if robust else c2).sum())
-
-        lam, ni, n_bad, done, trials, exit_taken = -1.0, 2.0, 0, 0, 0, EXIT_NOT_RUN
-        for it in range(iterations):
-            cur_chi = active_errors()
-            ini_chi = cur_chi
-            pc = map_points(Q, Tt, X, e_cam, e_pt)
-            Rall = np.stack([q_to_R(Q[c]) for c in range(n_kf)])
-            Jl, Jp = edge_jacobians(pc, Rall[e_cam], e_st, K)
-            c2 = chi2_of(act)
-            rho1 = huber(c2, delta[act])[1] if robust else np.ones(len(act))
-            w = rho1 * info[act]
-            wr = -(info[act] * rho1)[:, None] * err[act]                      # omega_r = -omega * error * rho[1]
-            Hll, bl = np.zeros((P, 3, 3)), np.zeros((P, 3))
-            np.add.at(Hll, e_pt, np.einsum("nda,n,ndb->nab", Jl, w, Jl))
-            np.add.at(bl, e_pt, np.einsum("nda,nd->na", Jl, wr))
-            Hpp, bp = np.zeros((Kf, 6, 6)), np.zeros((Kf, 6))
-            fe = np.flatnonzero(e_free)
-            np.add.at(Hpp, e_slot[fe], np.einsum("nda,n,ndb->nab", Jp[fe], w[fe], Jp[fe]))
-            np.add.at(bp, e_slot[fe], np.einsum("nda,nd->na", Jp[fe], wr[fe]))
-            Hpl = np.einsum("nda,n,ndb->nab", Jp, w, Jl)                      # [n, 6, 3], used where e_free
-            a_slots = slot[np.flatnonzero(a_kf)]
-            if it == 0:
-                diag = [np.abs(np.diagonal(Hll[a_pt], axis1=1, axis2=2)).ravel(), np.abs(np.diagonal(Hpp[a_slots], axis1=1, axis2=2)).ravel()]
-                lam, ni, n_bad = 1e-5 * float(np.concatenate(diag + [np.zeros(1)]).max()), 2.0, 0
-            it_rec = dict(chi2=cur_chi, lambda0=lam, trials=[])
-            trace.append(it_rec)
-            rho, qmax = 0.0, 0
-            while True:
-                backup = (Q.copy(), Tt.copy(), X.copy())
-                xp, xl, ok = np.zeros((Kf, 6)), np.zeros((P, 3)), True
-                if solver == "schur":
-                    Dinv = np.zeros((P, 3, 3))
-                    Dinv[a_pt] = np.linalg.inv(Hll[a_pt] + lam * np.eye(3))
-                    db = np.einsum("pab,pb->pa", Dinv, bl)
-                    S = np.zeros((Kf, 6, Kf, 6))
-                    for k in a_slots:
-                        S[k, :, k, :] = Hpp[k] + lam * np.eye(6)
-                    bs = bp.copy()
-                    np.subtract.at(bs, e_slot[fe], np.einsum("nab,nb->na", Hpl[fe], db[e_pt[fe]]))
-                    order = np.argsort(e_pt[fe], kind="stable")
-                    fes = fe[order]
-                    bounds = np.flatnonzero(np.diff(e_pt[fes])) + 1
-                    for grp in np.split(fes, bounds):
-                        if len(grp) == 0:
-                            continue
-                        D = Dinv[e_pt[grp[0]]]
-                        for a in grp:
-                            BD = Hpl[a] @ D
-                            for b in grp:
-                                S[e_slot[a], :, e_slot[b], :] -= BD @ Hpl[b].T
-                    idx = (a_slots[:, None] * 6 + np.arange(6)).ravel()
-                    Sm = S.reshape(Kf * 6, Kf * 6)[np.ix_(idx, idx)]
-                    if len(idx):
-                        ok, sol = ldlt_solve(Sm, bs.reshape(-1)[idx])
-                        if ok:
-                            xp.reshape(-1)[idx] = sol
-                    if ok:
-                        cl = bl.copy()
-                        np.subtract.at(cl, e_pt[fe], np.einsum("nab,na->nb", Hpl[fe], xp[e_slot[fe]]))
-                        xl[a_pt] = np.einsum("pab,pb->pa", Dinv, cl)[a_pt]
-                    else:
-                        xp[:] = 0
-                else:                                # the same system, solved densely at once
-                    pi = np.flatnonzero(a_pt)
-                    n = 6 * len(a_slots) + 3 * len(pi)
-                    col_k = -np.ones(Kf, np.int64)
-                    col_k[a_slots] = np.arange(len(a_slots)) * 6
-                    col_p = -np.ones(P, np.int64)
-                    col_p[pi] = 6 * len(a_slots) + np.arange(len(pi)) * 3
-                    H, b = np.zeros((n, n)), np.zeros(n)
-                    for k in a_slots:
-                        H[col_k[k]:col_k[k] + 6, col_k[k]:col_k[k] + 6] = Hpp[k]
-                        b[col_k[k]:col_k[k] + 6] = bp[k]
-                    for q in pi:
-                        H[col_p[q]:col_p[q] + 3, col_p[q]:col_p[q] + 3] = Hll[q]
-                        b[col_p[q]:col_p[q] + 3] = bl[q]
-                    for a in fe:
-                        r, c = col_k[e_slot[a]], col_p[e_pt[a]]
-                        H[r:r + 6, c:c + 3] += Hpl[a]
-                        H[c:c + 3, r:r + 6] += Hpl[a].T
-                    H[np.arange(n), np.arange(n)] += lam
-                    sol = np.linalg.solve(H, b)
-                    for k in a_slots:
-                        xp[k] = sol[col_k[k]:col_k[k] + 6]
-                    for q in pi:
-                        xl[q] = sol[col_p[q]:col_p[q] + 3]
-                for c in np.flatnonzero(a_kf):
-                    Q[c], Tt[c] = se3_mul(*se3_exp(xp[slot[c]]), Q[c], Tt[c])
-                X[a_pt] = X[a_pt] + xl[a_pt]
-                temp_chi = active_errors()
-                if not ok:
-                    temp_chi = np.finfo(np.float64).max
-                rho = cur_chi - temp_chi
-                scale = 0.0
-                for k in a_slots:
-                    scale += float((xp[k] * (lam * xp[k] + bp[k])).sum())
-                scale += float((xl[a_pt] * (lam * xl[a_pt] + bl[a_pt])).sum())
-                rho /= scale + 1e-3
-                accept = bool(rho > 0 and np.isfinite(temp_chi))
-                it_rec["trials"].append(dict(lam=lam, rho=rho, accept=accept, temp_chi=temp_chi, scale=scale))
-                if accept:
-                    alpha = min(1. - (2 * rho - 1) ** 3, 2. / 3.)
-                    lam *= max(1. / 3., alpha)
-                    ni = 2.0
-                    cur_chi = temp_chi
-                else:
-                    lam *= ni
-                    ni *= 2
-                    Q, Tt, X = backup
-                qmax += 1
-                trials += 1
-                if not (rho < 0 and qmax < 10):
-                    break
-            done += 1
-            exit_taken = EXIT_ITERATIONS
-            if qmax == 10 or rho == 0:
-                exit_taken = EXIT_QMAX if qmax == 10 else EXIT_RHO_ZERO
-                break
-            n_bad = n_bad + 1 if (ini_chi - cur_chi) * 1e3 < ini_chi else 0
-            if n_bad >= 3:
-                exit_taken = EXIT_NBAD
-                break
-        return done, trials, exit_taken
+        return levenberg(s, np.flatnonzero(edge & (level == 0)), iterations, robust, delta, solver, trace)
 
     def classify():
         """(the edges the test puts aside, the chi2 and the depth it read) -- chi2 from `err` as it stands, depth at the estimate"""
         idx = np.flatnonzero(edge)
         chi2, z = np.zeros(E), np.ones(E)
-        chi2[idx] = chi2_of(idx)
-        z[idx] = map_points(Q, Tt, X, cam[idx], pt[idx])[:, 2]
+        chi2[idx] = _chi2_of(s, idx)
+        z[idx] = map_points(s.Q, s.Tt, s.X, cam[idx], pt[idx])[:, 2]
         return edge & ((chi2 > np.where(stereo, CHI2_STEREO, CHI2_MONO)) | ~(z > 0.0)), chi2, z
 
     info16[6:9] = optimize(5, True, out["trace"][0])
@@ -396,9 +414,9 @@ def run(p, solver="schur"):
     out["level1"] = (level == 1).astype(np.uint8)
     out["stereo"], out["edge"] = stereo, edge
     info16[13] = int(erase.sum())
-    for c in np.flatnonzero(free & has_edge_kf):
-        out["T"][c] = se3_to_T(Q[c], Tt[c])
-    out["Xw"][has_edge_pt] = X[has_edge_pt]
+    for c in np.flatnonzero(s.free & has_edge_kf):
+        out["T"][c] = se3_to_T(s.Q[c], s.Tt[c])
+    out["Xw"][has_edge_pt] = s.X[has_edge_pt]
     return out
 
 
@@ -415,3 +433,45 @@ def ldlt_solve(A, b):
         A[k + 1:, k + 1:] -= np.outer(L[k + 1:, k], A[k + 1:, k])
     y = np.linalg.solve(L, b) if n else b
     return True, np.linalg.solve(L.T, y / d)
+
+
+PANEL = 48
+
+
+def blocked_ldlt_solve(A, b, panel=PANEL):
+    """LDL^T without pivoting in index order, in panels: (ok, x); (False, None) on a zero pivot.  The factorisation the device runs
+    for more than MAX_FREE_KF free cameras (sdslam_amd/csrc/track_ba.hip, k_gba_*): the same sums as ldlt_solve taken panel by panel,
+    and the right-hand side carried as one more row of the triangle."""
+    n = len(b)
+    M = np.zeros((n + 1, n))
+    M[:n] = np.tril(A)
+    M[n] = b                                           # the right-hand side rides along as row n
+    d = np.zeros(n)
+    for c0 in range(0, n, panel):
+        c1 = min(n, c0 + panel)
+        w = c1 - c0
+        W = np.zeros((n + 1, w))                       # L D of the panel's columns
+        for k in range(w):                             # the diagonal block
+            d[c0 + k] = M[c0 + k, c0 + k]
+            if d[c0 + k] == 0:
+                return False, None
+            col = M[c0 + k + 1:c1, c0 + k].copy()
+            W[c0 + k + 1:c1, k] = col
+            l = col / d[c0 + k]
+            M[c0 + k + 1:c1, c0 + k] = l
+            M[c0 + k + 1:c1, c0 + k + 1:c1] -= np.tril(np.outer(l, col))
+        for j in range(w):                             # the rows below it
+            v = M[c1:, c0 + j].copy()
+            for k in range(j):
+                v -= M[c1:, c0 + k] * W[c0 + j, k]
+            W[c1:, j] = v
+            M[c1:, c0 + j] = v / d[c0 + j]
+        for k in range(w):                             # the trailing triangle (row n has no entry right of column n - 1)
+            M[c1:, c1:] -= np.outer(M[c1:, c0 + k], W[c1:n, k])
+    x = M[n].copy()                                    # y = D^-1 L^-1 b
+    for k in range(n - 1, 0, -1):
+        x[:k] -= M[k, :k] * x[k]
+    return True, x
+
+
+REDUCED_SOLVERS = dict(schur=ldlt_solve, blocked=blocked_ldlt_solve)     # levenberg()'s solvers of the reduced (Schur) system

@@ -4,93 +4,12 @@
 // nLoopKF branches and compares what the objects were given, byte for byte, with sd_debug_global_ba on lists built by straight
 // loops; the order of the SetPose / SetWorldPos / refresh calls with the reference's (:185-217); the normals and distances with a
 // restatement of MapPoint::UpdateNormalAndDepth; and checks that a set stop flag and a refusal return false and touch nothing.
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <utility>
-#include <vector>
+#if !defined(HOST_PART_ONLY) && !defined(RUN_ON_GPU)   // (the test's build defines nothing; -DHOST_PART_ONLY builds host_part()
+#define RUN_ON_GPU                                     // alone and links nothing)
+#endif
+#include "mock_map.h"
 
-#include "sdslam/sdslam.hpp"
-
-#define CHECK(cond, ...)                 \
-  do {                                   \
-    if (!(cond)) {                       \
-      std::printf("FAILED %s: ", #cond); \
-      std::printf(__VA_ARGS__);          \
-      std::printf("\n");                 \
-      std::exit(1);                      \
-    }                                    \
-  } while (0)
-
-struct Mat4 {
-  double v[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // column-major
-  const double* data() const { return v; }
-  double* data() { return v; }
-};
-struct Vec3 {
-  double v[3] = {0, 0, 0};
-  double operator()(int k) const { return v[k]; }
-  double* data() { return v; }
-};
-struct MapPoint;
-enum { EV_POSE = 0, EV_POS = 1, EV_NORMAL = 2 };
-static std::vector<std::pair<int, int>> g_calls;   // (what, keyframe mnId or point id), in call order
-
-struct KeyFrame {
-  unsigned long mnId = 0, mnBAGlobalForKF = 0;
-  int N = 0;
-  bool bad = false;
-  std::vector<float> mvuRight;
-  std::vector<sd_keypoint> keys;
-  Mat4 T, mTcwGBA;
-  bool isBad() const { return bad; }
-  Mat4 GetPose() const { return T; }
-  void SetPose(const double* t) { std::memcpy(T.v, t, 128); g_calls.push_back({EV_POSE, (int)mnId}); }
-  int add_keypoint(float x, float y, int octave, float ur) {
-    keys.push_back(sd_keypoint{x, y, 31.f, 0.f, 1.f, octave, -1});
-    mvuRight.push_back(ur);
-    return N++;
-  }
-};
-struct ById {
-  bool operator()(const KeyFrame* a, const KeyFrame* b) const { return a->mnId < b->mnId; }
-};
-struct MapPoint {
-  int id = 0;
-  unsigned long mnBAGlobalForKF = 0;
-  bool bad = false;
-  Vec3 X, normal, mPosGBA;
-  float max_dist = 0.f, min_dist = 0.f;
-  uint8_t desc[32] = {};
-  std::map<KeyFrame*, size_t, ById> obs;   // (the reference keys by pointer; by id here, so that the order is the test's)
-  KeyFrame* ref = nullptr;
-  bool isBad() const { return bad; }
-  Vec3 GetWorldPos() const { return X; }
-  Vec3 GetNormal() const { return normal; }
-  float GetMinDistanceInvariance() const { return 0.8f * min_dist; }
-  float GetMaxDistanceInvariance() const { return 1.2f * max_dist; }
-  float GetMaxDistance() const { return max_dist; }
-  const uint8_t* GetDescriptor() const { return desc; }
-  const std::map<KeyFrame*, size_t, ById>& GetObservations() const { return obs; }
-  KeyFrame* GetReferenceKeyFrame() const { return ref; }
-  void SetWorldPos(const double* x) { std::memcpy(X.v, x, 24); g_calls.push_back({EV_POS, id}); }
-  void SetNormalVector(const double* n) { std::memcpy(normal.v, n, 24); g_calls.push_back({EV_NORMAL, id}); }
-  void SetMaxDistance(float v) { max_dist = v; }
-  void SetMinDistance(float v) { min_dist = v; }
-};
-struct Map {
-  std::vector<KeyFrame*> kfs;
-  std::vector<MapPoint*> mps;
-  std::vector<KeyFrame*> GetAllKeyFrames() const { return kfs; }
-  std::vector<MapPoint*> GetAllMapPoints() const { return mps; }
-};
-
-static void observe(KeyFrame& kf, MapPoint& p, float x, float y, int octave, float ur) {
-  p.obs[&kf] = (size_t)kf.add_keypoint(x, y, octave, ur);
-}
+using namespace mock;
 
 static void host_part() {
   // keyframes by mnId: 0 (fixed by its id), 1, 2 (bad), 3 (not resident), 9 (not in vpKFs, id above maxKFid = 3).  Frames: 0 -> 2, 1 -> 0, 2 -> 1, 9 -> 3.
@@ -122,14 +41,7 @@ static void host_part() {
   CHECK(L.obs.ref_obs == (std::vector<int32_t>{1, 0, 0, 0, 0}) && L.obs.left == (std::vector<uint8_t>{0, 0, 0, 1, 0}), "ref_obs / left");
 }
 
-static void check(int rc, const char* what) { CHECK(rc == SD_OK, "%s: %s", what, sd_last_error()); }
-static uint32_t g_seed = 2463534242u;
-static double uni() {   // (-1, 1)
-  g_seed ^= g_seed << 13; g_seed ^= g_seed >> 17; g_seed ^= g_seed << 5;
-  return (double)(g_seed >> 8) / 8388608.0 - 1.0;
-}
-
-static const float FX = 458.654f, FY = 457.296f, CX = 367.215f, CY = 248.375f, BF = 47.9f;
+#ifdef RUN_ON_GPU
 static const int B = 6, NKF = 8, NP = 60;   // keyframes 0 .. 5 are frames 0 .. 5 of the ref extractor; 6 is bad, 7 is newer than vpKFs
 
 struct Scene {
@@ -144,15 +56,8 @@ static void make_scene(Scene& s) {
   s.pts.assign(NP + 2, MapPoint());
   const unsigned long ids[NKF] = {0, 11, 12, 13, 4, 5, 7, 99};
   for (int c = 0; c < NKF; c++) {
-    KeyFrame& k = s.kfs[(size_t)c];
-    k.mnId = ids[c];
-    const double ang = 0.03 * (c - 3), centre[3] = {0.3 * c - 0.9, 0.02 * c, -0.01 * c};
-    const double cs = std::cos(ang), sn = std::sin(ang);
-    const double R[3][3] = {{cs, 0, sn}, {0, 1, 0}, {-sn, 0, cs}};
-    for (int r = 0; r < 3; r++) {
-      for (int cc = 0; cc < 3; cc++) k.T.v[cc * 4 + r] = R[r][cc];
-      k.T.v[12 + r] = -(R[r][0] * centre[0] + R[r][1] * centre[1] + R[r][2] * centre[2]);
-    }
+    s.kfs[(size_t)c].mnId = ids[c];
+    pose_on_the_line(s.kfs[(size_t)c], c);
   }
   s.kfs[6].bad = true;
   for (int i = 0; i < NP; i++) {
@@ -182,23 +87,6 @@ static void make_scene(Scene& s) {
   s.map.kfs = {&s.kfs[2], &s.kfs[0], &s.kfs[6], &s.kfs[1], &s.kfs[3], &s.kfs[4], &s.kfs[5]};
   for (int i = 0; i < NP + 2; i++) s.map.mps.push_back(&s.pts[(size_t)i]);
   s.map.mps.insert(s.map.mps.begin() + 3, nullptr);
-}
-
-static void plant(SD_SLAM::ORBextractor& ref_x, Scene& s) {
-  const int cap = 128;
-  std::vector<sd_keypoint> kps((size_t)B * cap, sd_keypoint{0, 0, 0, 0, 0, 0, -1});
-  std::vector<uint8_t> desc((size_t)B * cap * 32, 0);
-  int32_t n[B];
-  for (int f = 0; f < B; f++) {
-    CHECK(s.kfs[(size_t)f].N <= cap, "keyframe %d has %d keypoints", f, s.kfs[(size_t)f].N);
-    n[f] = s.kfs[(size_t)f].N;
-    std::copy(s.kfs[(size_t)f].keys.begin(), s.kfs[(size_t)f].keys.end(), kps.begin() + (size_t)f * cap);
-  }
-  check(sd_debug_orb_set_keypoints(ref_x.handle(), 0, B, n, kps.data(), desc.data(), cap), "plant ref");
-}
-
-static void centre_of(const double* T, double* Ow) {   // Ow = -R^T t in the library's operation order
-  for (int r = 0; r < 3; r++) Ow[r] = -((T[r * 4] * T[12] + T[r * 4 + 1] * T[13]) + T[r * 4 + 2] * T[14]);
 }
 
 struct Expected {
@@ -255,7 +143,7 @@ static void gpu_part() {
   check(sd_track_set_camera(batch.handle(), FX, FY, CX, CY, BF, 0, (float)W, 0, (float)H), "set_camera");
   Scene s;
   make_scene(s);
-  plant(ref_x, s);
+  plant(ref_x, &s.kfs[0], B, "plant ref");
   auto frameOf = [&](KeyFrame* k) { return (int)(k - &s.kfs[0]) < B ? (int)(k - &s.kfs[0]) : -1; };
   const std::vector<MapPoint*>& mps = s.map.mps;
   double T0[16];
@@ -293,7 +181,7 @@ static void gpu_part() {
   // ---- nLoopKF == 0: SetPose on every keyframe, then per point SetWorldPos and the refresh
   const Expected init = expected(s, 10, 1);
   CHECK(SD_SLAM::Optimizer::GlobalBundleAdjustemnt(batch, &s.map, 10, &stop, 0, true, frameOf, 1), "the nLoopKF == 0 branch: %s", sd_last_error());
-  std::vector<std::pair<int, int>> want;
+  std::vector<Call> want;
   for (KeyFrame* k : s.map.kfs)
     if (!k->bad) want.push_back({EV_POSE, (int)k->mnId});
   for (size_t i = 0; i < mps.size(); i++)
@@ -311,20 +199,9 @@ static void gpu_part() {
   for (int i = 0; i < NP; i++) {   // UpdateNormalAndDepth over every observation, at the optimised poses and positions
     const MapPoint& p = s.pts[(size_t)i];
     if (i == 5 || i % 7 == 0) continue;   // (point 5 has no reference observation; the others' lists name keyframes that are not resident)
-    double normal[3] = {0, 0, 0}, Ow[3], d[3];
-    int n = 0;
-    for (const auto& ob : p.obs) {
-      centre_of(ob.first->T.v, Ow);
-      for (int k = 0; k < 3; k++) d[k] = p.X.v[k] - Ow[k];
-      const double len = std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-      for (int k = 0; k < 3; k++) normal[k] = normal[k] + d[k] / len;
-      n++;
-    }
-    for (int k = 0; k < 3; k++) normal[k] = normal[k] / n;
-    centre_of(p.ref->T.v, Ow);
-    for (int k = 0; k < 3; k++) d[k] = p.X.v[k] - Ow[k];
-    const float dist = (float)std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-    const float max_dist = dist * (float)(1 << p.ref->keys[p.obs.at(p.ref)].octave), min_dist = max_dist / 4.f;
+    const NormalAndDepth nd = update_normal_and_depth(p);
+    const double* normal = nd.normal;
+    const float max_dist = nd.max_dist, min_dist = nd.min_dist;
     CHECK(std::memcmp(p.normal.v, normal, 24) == 0, "normal of point %d: %.17g %.17g", p.id, p.normal.v[0], normal[0]);
     CHECK(p.max_dist == max_dist && p.min_dist == min_dist, "distances of point %d: %.9g %.9g", p.id, p.max_dist, max_dist);
   }
@@ -343,9 +220,13 @@ static void gpu_part() {
   CHECK(g_calls.size() == before && s.kfs[1].mnBAGlobalForKF == 17, "... touches nothing either");
 }
 
+#endif
+
 int main() {
   host_part();
+#ifdef RUN_ON_GPU
   gpu_part();
+#endif
   std::printf("facade_global_ba OK\n");
   return 0;
 }

@@ -5,103 +5,10 @@
 // With RUN_ON_GPU (tests/test_local_ba_facade.py, linked against the library): the whole method on planted keyframes, once with
 // wrong observations (erasures) and once without, against sd_debug_local_ba on lists the test builds with straight loops, and the
 // refresh against a straight restatement of MapPoint::UpdateNormalAndDepth over the observations as they are afterwards.
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <utility>
-#include <vector>
+#include "mock_map.h"
 
-#include "sdslam/sdslam.hpp"
-
-#define CHECK(cond, ...)                 \
-  do {                                   \
-    if (!(cond)) {                       \
-      std::printf("FAILED %s: ", #cond); \
-      std::printf(__VA_ARGS__);          \
-      std::printf("\n");                 \
-      std::exit(1);                      \
-    }                                    \
-  } while (0)
-
-struct Mat4 {
-  double v[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // column-major
-  const double* data() const { return v; }
-};
-struct Vec3 {
-  double v[3] = {0, 0, 0};
-  double operator()(int k) const { return v[k]; }
-};
-struct MapPoint;
-struct KeyFrame;
-static std::vector<std::pair<int, int>> g_erased;   // (keyframe id, point id), in call order
-
-struct KeyFrame {
-  unsigned long mnId = 0, mnBALocalForKF = ~0ul, mnBAFixedForKF = ~0ul;
-  int N = 0;
-  bool bad = false;
-  std::vector<float> mvuRight;
-  std::vector<sd_keypoint> keys;
-  std::vector<KeyFrame*> covisible;
-  std::vector<MapPoint*> mps;   // by keypoint index
-  Mat4 T;
-  int set_pose = 0, erased_matches = 0;
-  bool isBad() const { return bad; }
-  std::vector<KeyFrame*> GetVectorCovisibleKeyFrames() const { return covisible; }
-  std::vector<MapPoint*> GetMapPointMatches() const { return mps; }
-  Mat4 GetPose() const { return T; }
-  void SetPose(const double* t) { std::memcpy(T.v, t, 128); set_pose++; }
-  void EraseMapPointMatch(MapPoint* p) {
-    for (MapPoint*& m : mps)
-      if (m == p) m = nullptr, erased_matches++;
-  }
-  int add_keypoint(float x, float y, int octave, float ur) {
-    keys.push_back(sd_keypoint{x, y, 31.f, 0.f, 1.f, octave, -1});
-    mvuRight.push_back(ur);
-    mps.push_back(nullptr);
-    return N++;
-  }
-};
-struct ById {
-  bool operator()(const KeyFrame* a, const KeyFrame* b) const { return a->mnId < b->mnId; }
-};
-struct MapPoint {
-  int id = 0;
-  unsigned long mnBALocalForKF = ~0ul;
-  bool bad = false;
-  Vec3 X, normal;
-  float max_dist = 0.f, min_dist = 0.f;
-  uint8_t desc[32] = {};
-  std::map<KeyFrame*, size_t, ById> obs;   // (the reference keys by pointer; by id here, so that the order is the test's)
-  KeyFrame* ref = nullptr;
-  int set_pos = 0, set_normal = 0;
-  bool isBad() const { return bad; }
-  Vec3 GetWorldPos() const { return X; }
-  Vec3 GetNormal() const { return normal; }
-  float GetMinDistanceInvariance() const { return 0.8f * min_dist; }
-  float GetMaxDistanceInvariance() const { return 1.2f * max_dist; }
-  float GetMaxDistance() const { return max_dist; }
-  const uint8_t* GetDescriptor() const { return desc; }
-  const std::map<KeyFrame*, size_t, ById>& GetObservations() const { return obs; }
-  KeyFrame* GetReferenceKeyFrame() const { return ref; }
-  void EraseObservation(KeyFrame* kf) {
-    g_erased.push_back({(int)kf->mnId, id});
-    obs.erase(kf);
-  }
-  void SetWorldPos(const double* x) { std::memcpy(X.v, x, 24); set_pos++; }
-  void SetNormalVector(const double* n) { std::memcpy(normal.v, n, 24); set_normal++; }
-  void SetMaxDistance(float v) { max_dist = v; }
-  void SetMinDistance(float v) { min_dist = v; }
-};
+using namespace mock;
 using Lists = SD_SLAM::Optimizer::LocalBaLists<KeyFrame, MapPoint>;
-
-static void observe(KeyFrame& kf, MapPoint& p, float x, float y, int octave, float ur) {
-  const int k = kf.add_keypoint(x, y, octave, ur);
-  kf.mps[(size_t)k] = &p;
-  p.obs[&kf] = (size_t)k;
-}
 
 static void host_part() {
   // keyframes by mnId: 0 (local, fixed by its id), 1 (local), 2 (covisible but bad), 3 and 4 (see local points: fixed cameras),
@@ -150,15 +57,15 @@ static void host_part() {
   for (int f = 0; f < 3; f++) r.T_ref[(size_t)f * 16 + 12] = 100.0 + f;
   r.T_cur[12] = 55.0;
   for (int i = 0; i < 4; i++) r.Xw[(size_t)i * 3] = 10.0 + i;
-  g_erased.clear();
+  g_calls.clear();
   CHECK(SD_SLAM::Optimizer::ApplyLocalBa(cur, L, r), "something was erased");
   const std::vector<std::pair<int, int>> order = {{1, 0}, {3, 4}, {3, 1}, {5, 0}};
-  CHECK(g_erased == order, "erase order: all mono edges, then all stereo edges");
+  CHECK(erased() == order, "erase order: all mono edges, then all stereo edges");
   CHECK(cur->mps[2] == nullptr && kfs[1].mps[0] == nullptr && kfs[3].mps[0] == nullptr && kfs[3].mps[1] == nullptr && cur->mps[0] == &pts[1], "matches");
   CHECK(pts[0].obs.empty() && pts[1].obs.size() == 2 && pts[4].obs.size() == 2, "observations");
-  CHECK(cur->T.v[12] == 55.0 && kfs[1].T.v[12] == 100.0 && kfs[0].T.v[12] == 102.0 && cur->set_pose + kfs[1].set_pose + kfs[0].set_pose == 3, "SetPose");
-  CHECK(kfs[3].set_pose == 0 && kfs[4].set_pose == 0, "fixed cameras keep their pose objects");
-  CHECK(pts[1].X.v[0] == 10.0 && pts[0].X.v[0] == 11.0 && pts[3].X.v[0] == 12.0 && pts[4].X.v[0] == 13.0 && pts[2].set_pos == 0, "SetWorldPos");
+  CHECK(cur->T.v[12] == 55.0 && kfs[1].T.v[12] == 100.0 && kfs[0].T.v[12] == 102.0 && cur->set_pose() + kfs[1].set_pose() + kfs[0].set_pose() == 3, "SetPose");
+  CHECK(kfs[3].set_pose() == 0 && kfs[4].set_pose() == 0, "fixed cameras keep their pose objects");
+  CHECK(pts[1].X.v[0] == 10.0 && pts[0].X.v[0] == 11.0 && pts[3].X.v[0] == 12.0 && pts[4].X.v[0] == 13.0 && pts[2].set_pos() == 0, "SetWorldPos");
   SD_SLAM::Optimizer::BuildBaObservations(cur, frameOf, L);   // what the refresh is given after the erasures
   CHECK(L.obs.off == (std::vector<int32_t>{0, 2, 2, 4, 6}) && L.obs.frame == (std::vector<int32_t>{-2, -1, 0, -2, 2, 5}), "lists after the erasures");
   SD_SLAM::Optimizer::LocalBaResult none(3, 4, 6);
@@ -166,14 +73,6 @@ static void host_part() {
 }
 
 #ifdef RUN_ON_GPU
-static void check(int rc, const char* what) { CHECK(rc == SD_OK, "%s: %s", what, sd_last_error()); }
-static uint32_t g_seed = 2463534242u;
-static double uni() {   // (-1, 1)
-  g_seed ^= g_seed << 13; g_seed ^= g_seed >> 17; g_seed ^= g_seed << 5;
-  return (double)(g_seed >> 8) / 8388608.0 - 1.0;
-}
-
-static const float FX = 458.654f, FY = 457.296f, CX = 367.215f, CY = 248.375f, BF = 47.9f;
 static const int B = 6, NKF = 7;   // keyframes 0 .. 5 are frames 0 .. 5 of the ref extractor, keyframe 6 is the current one
 
 struct Scene {
@@ -186,18 +85,9 @@ static void make_scene(Scene& s, bool wrong) {
   s.kfs.assign(NKF, KeyFrame());
   s.pts.assign(60, MapPoint());
   const unsigned long ids[NKF] = {0, 11, 12, 13, 4, 5, 20};   // mnId 0: local and fixed; 4, 5: fixed cameras; 20: the current keyframe
-  double centre[NKF][3], ang[NKF];
   for (int c = 0; c < NKF; c++) {
-    KeyFrame& k = s.kfs[(size_t)c];
-    k.mnId = ids[c];
-    ang[c] = 0.03 * (c - 3);
-    centre[c][0] = 0.3 * c - 0.9; centre[c][1] = 0.02 * c; centre[c][2] = -0.01 * c;
-    const double cs = std::cos(ang[c]), sn = std::sin(ang[c]);
-    const double R[3][3] = {{cs, 0, sn}, {0, 1, 0}, {-sn, 0, cs}};
-    for (int r = 0; r < 3; r++) {
-      for (int cc = 0; cc < 3; cc++) k.T.v[cc * 4 + r] = R[r][cc];
-      k.T.v[12 + r] = -(R[r][0] * centre[c][0] + R[r][1] * centre[c][1] + R[r][2] * centre[c][2]);
-    }
+    s.kfs[(size_t)c].mnId = ids[c];
+    pose_on_the_line(s.kfs[(size_t)c], c);
   }
   for (int i = 0; i < 60; i++) {
     MapPoint& p = s.pts[(size_t)i];
@@ -226,32 +116,11 @@ static void make_scene(Scene& s, bool wrong) {
   s.kfs[6].covisible = {&s.kfs[2], &s.kfs[1], &s.kfs[3], &s.kfs[0]};
 }
 
-static void plant(SD_SLAM::ORBextractor& cur_x, SD_SLAM::ORBextractor& ref_x, Scene& s) {
-  const int cap = 128;
-  std::vector<sd_keypoint> kps((size_t)B * cap, sd_keypoint{0, 0, 0, 0, 0, 0, -1});
-  std::vector<uint8_t> desc((size_t)B * cap * 32, 0);
-  int32_t n[B];
-  for (int f = 0; f < B; f++) {
-    CHECK(s.kfs[(size_t)f].N <= cap, "keyframe %d has %d keypoints", f, s.kfs[(size_t)f].N);
-    n[f] = s.kfs[(size_t)f].N;
-    std::copy(s.kfs[(size_t)f].keys.begin(), s.kfs[(size_t)f].keys.end(), kps.begin() + (size_t)f * cap);
-  }
-  check(sd_debug_orb_set_keypoints(ref_x.handle(), 0, B, n, kps.data(), desc.data(), cap), "plant ref");
-  n[0] = s.kfs[6].N;
-  CHECK(n[0] <= cap, "the current keyframe has %d keypoints", n[0]);
-  std::copy(s.kfs[6].keys.begin(), s.kfs[6].keys.end(), kps.begin());
-  check(sd_debug_orb_set_keypoints(cur_x.handle(), 0, 1, n, kps.data(), desc.data(), cap), "plant cur");
-}
-
-// Ow = -R^T t in the library's operation order (camera_centre)
-static void centre_of(const double* T, double* Ow) {
-  for (int r = 0; r < 3; r++) Ow[r] = -((T[r * 4] * T[12] + T[r * 4 + 1] * T[13]) + T[r * 4 + 2] * T[14]);
-}
-
 static void run_case(SD_SLAM::ORBextractor& cur_x, SD_SLAM::ORBextractor& ref_x, SD_SLAM::TrackBatch& batch, bool wrong) {
   Scene s;
   make_scene(s, wrong);
-  plant(cur_x, ref_x, s);
+  plant(ref_x, &s.kfs[0], B, "plant ref");
+  plant(cur_x, &s.kfs[6], 1, "plant cur");
   KeyFrame* cur = &s.kfs[6];
   auto frameOf = [&](KeyFrame* k) { return (int)(k - &s.kfs[0]) < B ? (int)(k - &s.kfs[0]) : -1; };
   // the lists with straight loops: local keyframes in covisibility order, their matches by keypoint index, first seen first
@@ -299,43 +168,32 @@ static void run_case(SD_SLAM::ORBextractor& cur_x, SD_SLAM::ORBextractor& ref_x,
     for (KeyFrame& k : s.kfs) k.mnBALocalForKF = k.mnBAFixedForKF = ~0ul;
     for (MapPoint& q : s.pts) q.mnBALocalForKF = ~0ul;
   };
-  g_erased.clear();
+  g_calls.clear();
   bool stop = true;
-  CHECK(!SD_SLAM::Optimizer::LocalBundleAdjustment(batch, cur, &stop, frameOf, 1) && cur->set_pose == 0 && pl[0]->set_pos == 0, "pbStopFlag");
+  CHECK(!SD_SLAM::Optimizer::LocalBundleAdjustment(batch, cur, &stop, frameOf, 1) && cur->set_pose() == 0 && pl[0]->set_pos() == 0, "pbStopFlag");
   stop = false;
   unmark();
   CHECK(SD_SLAM::Optimizer::LocalBundleAdjustment(batch, cur, &stop, frameOf, 1), "the call: %s", sd_last_error());
-  CHECK(g_erased == want_erased, "%zu erased, %zu expected, in the reference's order", g_erased.size(), want_erased.size());
+  CHECK(erased() == want_erased, "%zu erased, %zu expected, in the reference's order", erased().size(), want_erased.size());
   for (int c = 0; c < NKF; c++) {
     const bool is_local = c <= 3 || c == 6;
-    CHECK(s.kfs[(size_t)c].set_pose == (is_local ? 1 : 0), "SetPose calls of keyframe %d", c);
+    CHECK(s.kfs[(size_t)c].set_pose() == (is_local ? 1 : 0), "SetPose calls of keyframe %d", c);
     CHECK(std::memcmp(s.kfs[(size_t)c].T.v, &To[(size_t)c * 16], 128) == 0, "pose of keyframe %d", c);
   }
   CHECK(std::memcmp(s.kfs[1].T.v, &T[16], 128) != 0 && std::memcmp(s.kfs[0].T.v, &T[0], 128) == 0, "local poses move, the fixed one does not");
   for (size_t i = 0; i < pl.size(); i++)
-    CHECK(pl[i]->set_pos == 1 && std::memcmp(pl[i]->X.v, &Xo[i * 3], 24) == 0, "position of local point %zu", i);
+    CHECK(pl[i]->set_pos() == 1 && std::memcmp(pl[i]->X.v, &Xo[i * 3], 24) == 0, "position of local point %zu", i);
   // UpdateNormalAndDepth over the observations as they are now, at the optimised poses and positions
   for (size_t i = 0; i < pl.size(); i++) {
     const MapPoint& p = *pl[i];
     if (p.obs.empty() || !p.obs.count(p.ref)) {
-      CHECK(p.set_normal == 0, "point %d has no reference observation and was refreshed", p.id);
+      CHECK(p.set_normal() == 0, "point %d has no reference observation and was refreshed", p.id);
       continue;
     }
-    double normal[3] = {0, 0, 0}, Ow[3], d[3];
-    int n = 0;
-    for (const auto& ob : p.obs) {
-      centre_of(ob.first->T.v, Ow);
-      for (int k = 0; k < 3; k++) d[k] = p.X.v[k] - Ow[k];
-      const double len = std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-      for (int k = 0; k < 3; k++) normal[k] = normal[k] + d[k] / len;
-      n++;
-    }
-    for (int k = 0; k < 3; k++) normal[k] = normal[k] / n;
-    centre_of(p.ref->T.v, Ow);
-    for (int k = 0; k < 3; k++) d[k] = p.X.v[k] - Ow[k];
-    const float dist = (float)std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-    const float max_dist = dist * (float)(1 << p.ref->keys[p.obs.at(p.ref)].octave), min_dist = max_dist / 4.f;
-    CHECK(p.set_normal == 1 && std::memcmp(p.normal.v, normal, 24) == 0, "normal of point %d: %.17g %.17g", p.id, p.normal.v[0], normal[0]);
+    const NormalAndDepth want = update_normal_and_depth(p);
+    const double* normal = want.normal;
+    const float max_dist = want.max_dist, min_dist = want.min_dist;
+    CHECK(p.set_normal() == 1 && std::memcmp(p.normal.v, normal, 24) == 0, "normal of point %d: %.17g %.17g", p.id, p.normal.v[0], normal[0]);
     CHECK(p.max_dist == max_dist && p.min_dist == min_dist, "distances of point %d: %.9g %.9g", p.id, p.max_dist, max_dist);
   }
   // the device holds what the objects hold
@@ -346,10 +204,10 @@ static void run_case(SD_SLAM::ORBextractor& cur_x, SD_SLAM::ORBextractor& ref_x,
   CHECK(std::memcmp(Td, cur->T.v, 128) == 0, "Tcur of slot 0");
   if (!wrong) {   // a refusal: keyframe 5 is not resident any more -> false, nothing touched
     auto fewer = [&](KeyFrame* k) { return (int)(k - &s.kfs[0]) < B - 1 ? (int)(k - &s.kfs[0]) : -1; };
-    const size_t before = g_erased.size();
+    const size_t before = erased().size();
     unmark();
     CHECK(!SD_SLAM::Optimizer::LocalBundleAdjustment(batch, cur, nullptr, fewer, 1), "a keyframe that is not resident");
-    CHECK(g_erased.size() == before && cur->set_pose == 1 && pl[0]->set_pos == 1 && pl[0]->set_normal <= 1, "a refusal touches nothing");
+    CHECK(erased().size() == before && cur->set_pose() == 1 && pl[0]->set_pos() == 1 && pl[0]->set_normal() <= 1, "a refusal touches nothing");
   }
 }
 

@@ -4,25 +4,7 @@
 // (ApplyRefreshed) -- against lists and results typed in below.
 // With RUN_ON_GPU (tests/test_refresh_facade.py, linked against the library): the whole method on two small extractions, against
 // a straight C++ restatement of src/MapPoint.cc:225-343 over the same observation order (compiled with -ffp-contract=off).
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <vector>
-
-#include "sdslam/sdslam.hpp"
-
-#define CHECK(cond, ...)                 \
-  do {                                   \
-    if (!(cond)) {                       \
-      std::printf("FAILED %s: ", #cond); \
-      std::printf(__VA_ARGS__);          \
-      std::printf("\n");                 \
-      std::exit(1);                      \
-    }                                    \
-  } while (0)
+#include "mock_map.h"   // CHECK and the UpdateNormalAndDepth restatement; the classes are this file's (they record the descriptor too)
 
 struct KeyFrame {
   int id = 0;
@@ -116,7 +98,6 @@ static int popcount256(const uint8_t* a, const uint8_t* b) {
   for (int i = 0; i < 32; i++) d += __builtin_popcount((unsigned)(a[i] ^ b[i]));
   return d;
 }
-static double dot3(const double* x, const double* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
 static void check(int rc, const char* what) { CHECK(rc == SD_OK, "%s: %s", what, sd_last_error()); }
 
 // src/MapPoint.cc:225-343 on the toy classes, over GetObservations() in iteration order
@@ -139,21 +120,10 @@ static void reference_refresh(MapPoint& p, const float* sf, int nlevels, MapPoin
     }
     std::memcpy(out.desc, v[best], 32);
   }
-  double normal[3] = {0, 0, 0};
-  int n = 0;
-  for (const auto& ob : p.obs) {
-    double d[3];
-    for (int k = 0; k < 3; k++) d[k] = p.X[k] - ob.first->Ow[k];
-    const double len = std::sqrt(dot3(d, d));
-    for (int k = 0; k < 3; k++) normal[k] = normal[k] + d[k] / len;
-    n++;
-  }
-  double pc[3];
-  for (int k = 0; k < 3; k++) pc[k] = p.X[k] - p.ref->Ow[k];
-  const float dist = (float)std::sqrt(dot3(pc, pc));
-  out.max_dist = dist * sf[p.ref->keys[p.obs.at(p.ref)].octave];
-  out.min_dist = out.max_dist / sf[nlevels - 1];
-  for (int k = 0; k < 3; k++) out.normal[k] = normal[k] / n;
+  const NormalAndDepth nd = update_normal_and_depth(p, p.X, sf, nlevels, [](const KeyFrame* k, double* Ow) { std::memcpy(Ow, k->Ow, 24); });
+  std::memcpy(out.normal, nd.normal, 24);
+  out.max_dist = nd.max_dist;
+  out.min_dist = nd.min_dist;
 }
 
 static void gpu_part() {

@@ -124,6 +124,16 @@ def test_robust_switch_changes_the_run():
     assert np.abs(a["T"] - b["T"]).max() > G.GPU_BOUND
 
 
+def test_first_local_round_is_a_global_run_of_five_robust_iterations():
+    """On roles 1 and 2 alone the two callers of ba_ref.levenberg hand it the same graph: local BA's first round (5 iterations, robust,
+    every edge on level 0) is BundleAdjustment(5, bRobust) with local BA's sqrt(5.991), step for step and bit for bit."""
+    p = G.scene(11, [1, 1, 1, 1, 2, 2], 40, 4, stereo_share=0.3, pix_noise=0.4, pose_noise=0.003, point_noise=0.02)
+    g, l = gba_ref.run(p, 5, 1, delta_mono=ba_ref.DELTA_MONO), ba_ref.run(p)
+    assert g["status"] == 0 and l["status"] == 0 and len(g["trace"]) == 5 and (~(p["ur"] < 0)).any()
+    assert g["trace"] == l["trace"][0]
+    assert g["info16"][6:9].tolist() == l["info16"][6:9].tolist()
+
+
 def test_huber_delta_pins_the_sic_constant():
     """thHuber2D = sqrt(5.99) (Optimizer.cc:87), not local BA's sqrt(5.991): the case tells them apart above the GPU bound"""
     a = run("huber_delta")[0]
