@@ -843,8 +843,12 @@ class Optimizer {
   // GetMapPointMatches(), GetPose() (16 doubles column-major behind .data()), SetPose(const double*), EraseMapPointMatch(pMP).
   // MapPointT needs what ORBmatcher::Fuse's point upload needs, and mnBALocalForKF, GetObservations(), GetReferenceKeyFrame(),
   // EraseObservation(pKF), SetWorldPos(const double*) and the three setters of the refresh.
+  // erase_on_device: when something was erased, sd_track_erase_observations(SD_ERASE_LOCAL_BA) kills the same entries on the
+  // resident lists before the refresh, instead of the second walk and upload; the objects' EraseObservation must then cascade as
+  // the reference's does (nObs <= 2: SetBadFlag, mpRefKF to the first observation), which is what the device does to the lists.
   template <class KeyFrameT, class FrameOf>
-  static bool LocalBundleAdjustment(TrackBatch& batch, KeyFrameT* pKF, bool* pbStopFlag, FrameOf frameOf, int point_row = 0) {
+  static bool LocalBundleAdjustment(TrackBatch& batch, KeyFrameT* pKF, bool* pbStopFlag, FrameOf frameOf, int point_row = 0,
+                                    bool erase_on_device = false) {
     using MapPointT = typename std::remove_pointer<typename std::decay<decltype(pKF->GetMapPointMatches())>::type::value_type>::type;
     LocalBaLists<KeyFrameT, MapPointT> L;
     BuildLocalBaLists(pKF, frameOf, L);
@@ -868,7 +872,9 @@ class Optimizer {
     if (r.info[0] != SD_BA_OK) return false;
     const bool erased = ApplyLocalBa(pKF, L, r);
     if (n == 0) return true;
-    if (erased) {   // the lists the refresh reads are the points' observations as they are now
+    if (erased && erase_on_device) {
+      check(sd_track_erase_observations(h, SD_ERASE_LOCAL_BA));
+    } else if (erased) {   // the lists the refresh reads are the points' observations as they are now
       BuildBaObservations(pKF, frameOf, L);
       ORBmatcher::SetObservations(h, n, L.obs);
     }
@@ -1076,6 +1082,65 @@ class Optimizer {
     }
     for (size_t i = 0; i < L.points.size(); i++) L.points[i]->SetWorldPos(&r.Xw[i * 3]);
     return erased;
+  }
+};
+
+// void LocalMapping::KeyFrameCulling()          src/LocalMapping.cc:580-634, the last step of LocalMapping::Run
+// on the device (sd_track_cull_keyframes), on the observation lists that are resident: the caller's last
+// sd_track_set_observations (Optimizer::LocalBundleAdjustment leaves the local points' lists there), as
+// sd_track_erase_observations may have compacted them.
+class LocalMapping {
+ public:
+  // What the device is asked: the candidates in GetVectorCovisibleKeyFrames() order and their flags
+  struct CullCandidates {
+    std::vector<int32_t> frame;
+    std::vector<uint8_t> flags;
+    bool resident = true;   // false: a covisible keyframe is not a frame of the ref extractor
+  };
+  // Host code only.  frameOf(KeyFrameT*): the frame of the ref extractor that holds a keyframe, negative: not resident;
+  // notErase(KeyFrameT*): mbNotErase
+  template <class KeyFrameT, class FrameOf, class NotErase>
+  static CullCandidates BuildCullCandidates(const std::vector<KeyFrameT*>& vpLocalKeyFrames, FrameOf frameOf, NotErase notErase) {
+    CullCandidates c;
+    for (KeyFrameT* pKF : vpLocalKeyFrames) {
+      const int f = (int)frameOf(pKF);
+      if (f < 0) c.resident = false;
+      c.frame.push_back(f);
+      c.flags.push_back((uint8_t)((pKF->mnId == 0 ? 1 : 0) | (notErase(pKF) ? 2 : 0)));
+    }
+    return c;
+  }
+  // Host code only: pKF->SetBadFlag() on the keyframes the test passed for, in candidate order -- the caller's own objects do their
+  // own cascade (EraseObservation, MapPoint::SetBadFlag, the spanning tree), and a keyframe with mbNotErase sets mbToBeErased.
+  // Returns the number of calls.
+  template <class KeyFrameT>
+  static int ApplyCullVerdicts(const std::vector<KeyFrameT*>& vpLocalKeyFrames, const std::vector<uint8_t>& verdict) {
+    int n = 0;
+    for (size_t c = 0; c < vpLocalKeyFrames.size(); c++)
+      if (verdict[c] == SD_CULL_CULLED || verdict[c] == SD_CULL_TO_BE_ERASED) vpLocalKeyFrames[c]->SetBadFlag(), n++;
+    return n;
+  }
+  // Returns false, with no object touched, when a covisible keyframe is not resident or the device refuses (an observation of a
+  // live point in a keyframe that is not resident, a keypoint index outside its frame).  KeyFrameT needs mnId,
+  // GetVectorCovisibleKeyFrames() and SetBadFlag().
+  template <class KeyFrameT, class FrameOf, class NotErase>
+  static bool KeyFrameCulling(TrackBatch& batch, KeyFrameT* pCurrentKF, bool bMonocular, float thDepth, FrameOf frameOf, NotErase notErase) {
+    const std::vector<KeyFrameT*> vpLocalKeyFrames = pCurrentKF->GetVectorCovisibleKeyFrames();
+    const CullCandidates c = BuildCullCandidates(vpLocalKeyFrames, frameOf, notErase);
+    if (!c.resident) return false;
+    const int n = (int)c.frame.size();
+    check(sd_track_cull_keyframes(batch.handle(), n, c.frame.data(), c.flags.data(), bMonocular ? 1 : 0, thDepth));
+    std::vector<uint8_t> verdict((size_t)n + 1, 0);
+    int32_t info[8];
+    check(sd_track_get_culled(batch.handle(), verdict.data(), nullptr, nullptr, nullptr, nullptr, nullptr, info, n, 0, 0));
+    if (info[0] != SD_CULL_OK) return false;
+    ApplyCullVerdicts(vpLocalKeyFrames, verdict);
+    return true;
+  }
+  // ... with mbNotErase read off the keyframe
+  template <class KeyFrameT, class FrameOf>
+  static bool KeyFrameCulling(TrackBatch& batch, KeyFrameT* pCurrentKF, bool bMonocular, float thDepth, FrameOf frameOf) {
+    return KeyFrameCulling(batch, pCurrentKF, bMonocular, thDepth, frameOf, [](KeyFrameT* pKF) { return pKF->mbNotErase; });
   }
 };
 

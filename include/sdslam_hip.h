@@ -592,8 +592,9 @@ int sd_debug_refresh_points(int n_points, const int32_t* obs_off, const uint8_t*
                             const double* Xw, const float* scale_factors, int nlevels, uint8_t* status, int32_t* best_obs,
                             int32_t* best_median, uint8_t* desc, double* normal, float* max_dist, float* min_dist);
 
-/* Optimizer::LocalBundleAdjustment (src/Optimizer.cc:417-714) on the lists of sd_track_set_observations: the last step of the
- *   LocalMapping chain, behind sd_track_append_new_points / _fuse / _refresh_points, without taking the map to the host.
+/* Optimizer::LocalBundleAdjustment (src/Optimizer.cc:417-714) on the lists of sd_track_set_observations: the step of the
+ *   LocalMapping chain behind sd_track_append_new_points / _fuse / _refresh_points and before sd_track_cull_keyframes, without
+ *   taking the map to the host.
  * The problem.  Points: point i of the list = entry i of row point_row of the sd_track_set_local buffers; the caller builds
  *   lLocalMapPoints in the reference's order (:432-445).  A point with point_bad set is not in the problem; an observation with
  *   obs_kf_bad set gives no edge (:541).  Keyframes: obs_frame >= 0 is a frame of the ref extractor with pose Tref, -1 the current
@@ -617,7 +618,8 @@ int sd_debug_refresh_points(int n_points, const int32_t* obs_off, const uint8_t*
  *   write_back = 1, and only on SD_BA_OK: the optimised poses of the local keyframes with role 1 that some point observes go to
  *   Tref / Tcur, the positions of the SD_BA_POINT_OPTIMISED points to Xw of the row; everything else keeps its bytes.  It ends
  *   the cached results that sd_track_set_poses and a write-through refresh end; write_back = 0 ends none.  A
- *   sd_track_refresh_points queued behind it is the UpdateNormalAndDepth of :712, provided no observation was erased.
+ *   sd_track_refresh_points queued behind it is the UpdateNormalAndDepth of :712, provided no observation was erased (otherwise
+ *   behind sd_track_erase_observations(h, SD_ERASE_LOCAL_BA)).
  *   SD_ERR_INVALID_ARG: no sd_track_set_observations / sd_track_set_ba_keyframes / sd_track_set_camera before it.
  * sd_track_get_local_ba (synchronises; NULL outputs are skipped): T_ref_cm16 [n_ref_frames][16] and T_cur_cm16 [16] column-major,
  *   Xw [cap_points][3], point_status [cap_points] = SD_BA_POINT_OPTIMISED, _SKIPPED (bad, or no edge) or _BAD_INDEX (a keypoint
@@ -683,6 +685,71 @@ int sd_debug_global_ba(int n_points, const int32_t* obs_off, const int32_t* obs_
                        const uint8_t* kf_role, const double* Xw, const float* cam9, int n_iterations, int robust, double* T_out_cm16,
                        double* Xw_out, uint8_t* point_status, int32_t* info16);
 int sd_debug_ldlt(int n, const double* A_packed_lower, const double* b, double* x, int32_t* ok);
+
+/* LocalMapping::KeyFrameCulling (src/LocalMapping.cc:580-634), the last step of LocalMapping::Run, and the erasure of
+ *   observations (MapPoint::EraseObservation, src/MapPoint.cc:110-134, with MapPoint::SetBadFlag, :146-161) on the lists of
+ *   sd_track_set_observations.  A keyframe appears at most once in a point's list.  A point with point_bad set has neither
+ *   observations nor matches in the reference: its entries are not read, counted or killed by either call.
+ * sd_track_cull_keyframes is queued on the tracking stream: no host wait, no allocation (its scratch is allocated by
+ *   sd_track_create and grows where sd_track_set_observations grows its block).  cand_frame[c] >= 0 is candidate c of
+ *   mpCurrentKeyFrame->GetVectorCovisibleKeyFrames(), in that order, as a frame of the ref extractor; cand_flags[c] bit 0: mnId
+ *   == 0 (the `continue` of :589), bit 1: mbNotErase (SetBadFlag only sets mbToBeErased).  SD_ERR_INVALID_ARG: a candidate outside
+ *   [0, max_batch) or named twice, n_cand < 0, no observations set.  For each candidate in order, on the lists as the earlier
+ *   candidates left them (:591-632): its points are those with a live entry in that frame that are not bad and have not gone bad
+ *   in this run; with monocular == 0 a point whose mvDepth (the ref side's row of sd_track_set_tri_depth; -1 on a new handle) is
+ *   > th_depth or < 0 is skipped; nMPs counts the others; one is redundant if Observations() > 3 -- the sum over its live entries
+ *   of 2 where mvuRight >= 0 and 1 otherwise, obs_kf_bad entries included -- and at least 3 OTHER live entries have octave_i <=
+ *   octave + 1 (the resident keypoints' octaves).  The keyframe is culled iff (double)nRedundant > 0.9 * (double)nMPs.  Verdicts:
+ *   SD_CULL_SKIPPED_ID0, _KEPT, _CULLED, _TO_BE_ERASED (the test passed but bit 1 is set: nothing is erased).  Only _CULLED
+ *   cascades: every live entry in that frame dies, its point's nObs falls by the entry's weight, a ref_obs that died moves to the
+ *   first surviving entry in list order (-1: none), and at nObs <= 2 the point goes bad and all its entries die.
+ *   The resident lists themselves are not changed.
+ * sd_track_get_culled (synchronises; NULL outputs are skipped): verdict [n_cand], counts2 [n_cand][2] = {nRedundant, nMPs},
+ *   obs_dead [n entries] = 0 live, 1 culled with its keyframe, 2 cleared because its point went bad, point_bad [n_points] = 1 iff
+ *   the point went bad in this run, ref_obs (a position in the list as uploaded), n_obs = nObs, info8 = {status, n_culled,
+ *   n_to_be_erased, n_entries_dead, n_points_bad, 0, 0, 0}.  status is SD_CULL_OK or a refusal, made before anything but info8 is
+ *   written: SD_CULL_NOT_RESIDENT (a point that is not bad has an entry with frame -2), SD_CULL_BAD_INDEX (a frame or keypoint
+ *   index that names nothing; nothing is read through it).
+ * sd_track_erase_observations is queued on the tracking stream as well.  source SD_ERASE_LOCAL_BA: the obs_erase of the last
+ *   sd_track_local_ba (EraseMapPointMatch + EraseObservation per flagged entry); SD_ERASE_CULL: the non-zero obs_dead of the last
+ *   cull.  Either must have run on the lists as they stand (SD_ERR_INVALID_ARG otherwise); a run that refused erases nothing.
+ *   nObs falls by the weight of every erased entry; a point with an erased entry and nObs <= 2 goes bad and loses every entry.
+ *   The survivors are compacted stably into the list block's twin and the two are swapped: obs_off, obs_frame, obs_kp,
+ *   obs_kf_bad and ref_obs hold the survivors in the caller's order (a ref_obs that died becomes the first survivor), point_bad
+ *   gains the points that went bad, such a point has an empty list and ref_obs 0.  The call ends every cached result that
+ *   sd_track_set_observations ends; a following sd_track_refresh_points, _local_ba, _global_ba or _cull_keyframes sees the lists
+ *   as if the caller had rebuilt and uploaded them.  The getters of runs on the old lists (sd_track_get_local_ba, _get_culled)
+ *   keep answering / refuse as after a sd_track_set_observations.
+ * sd_track_get_erased (synchronises; NULL outputs are skipped): obs_off_new [n_points + 1], obs_map [n old entries] = the new
+ *   position or -1, point_bad (the resident flags), ref_obs, n_obs (0 for a point that went bad), info8 = {0, n_entries_erased,
+ *   n_points_bad, n_entries_left, 0, 0, 0, 0}.
+ * sd_debug_cull_keyframes / sd_debug_erase_observations: the same kernels from host arrays, synchronous, with buffers of their
+ *   own.  Per observation its keyframe obs_kf (an index into n_kf keyframes; -1: the current keyframe, -2: not resident,
+ *   anything else outside [0, n_kf): a bad index), octave, stereo flag (mvuRight >= 0) and mvDepth; the CSR offsets, ref_obs and
+ *   point_bad (or NULL); candidates as indices into the n_kf keyframes.  Outputs as the getters'. */
+#define SD_ERASE_LOCAL_BA 0
+#define SD_ERASE_CULL 1
+#define SD_CULL_OK 0
+#define SD_CULL_NOT_RESIDENT 1
+#define SD_CULL_BAD_INDEX 2
+#define SD_CULL_SKIPPED_ID0 0
+#define SD_CULL_KEPT 1
+#define SD_CULL_CULLED 2
+#define SD_CULL_TO_BE_ERASED 3
+int sd_track_cull_keyframes(sd_track* h, int n_cand, const int32_t* cand_frame, const uint8_t* cand_flags, int monocular, float th_depth);
+int sd_track_get_culled(sd_track* h, uint8_t* verdict, int32_t* counts2, uint8_t* obs_dead, uint8_t* point_bad, int32_t* ref_obs,
+                        int32_t* n_obs, int32_t* info8, int cap_cand, int cap_points, int cap_obs);
+int sd_track_erase_observations(sd_track* h, int source);
+int sd_track_get_erased(sd_track* h, int32_t* obs_off_new, int32_t* obs_map, uint8_t* point_bad, int32_t* ref_obs, int32_t* n_obs,
+                        int32_t* info8, int cap_points, int cap_obs);
+int sd_debug_cull_keyframes(int n_points, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* obs_octave,
+                            const uint8_t* obs_stereo, const float* obs_depth, const int32_t* ref_obs, const uint8_t* point_bad,
+                            int n_kf, int n_cand, const int32_t* cand_kf, const uint8_t* cand_flags, int monocular, float th_depth,
+                            uint8_t* verdict, int32_t* counts2, uint8_t* obs_dead, uint8_t* point_bad_out, int32_t* ref_obs_out,
+                            int32_t* n_obs, int32_t* info8);
+int sd_debug_erase_observations(int n_points, const int32_t* obs_off, const uint8_t* obs_stereo, const uint8_t* obs_erase,
+                                const int32_t* ref_obs, const uint8_t* point_bad, int32_t* obs_off_new, int32_t* obs_map,
+                                uint8_t* point_bad_out, int32_t* ref_obs_out, int32_t* n_obs, int32_t* info8);
 
 int sd_track_align(sd_track* h, int n_frames, int mode);
 int sd_track_match(sd_track* h, int n_frames, float th, int mono, int check_ori);

@@ -138,6 +138,12 @@ _SIGNATURES = {
     "sd_track_get_global_ba": (_I, [_P, _P, _P, _P, _P, _P, _I]),
     "sd_debug_global_ba": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "sd_debug_ldlt": (_I, [_I, _P, _P, _P, _P]),
+    "sd_track_cull_keyframes": (_I, [_P, _I, _P, _P, _I, _F]),
+    "sd_track_get_culled": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
+    "sd_track_erase_observations": (_I, [_P, _I]),
+    "sd_track_get_erased": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I]),
+    "sd_debug_cull_keyframes": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P, _P]),
+    "sd_debug_erase_observations": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sd_track_align": (_I, [_P, _I, _I]),
     "sd_track_match": (_I, [_P, _I, _F, _I, _I]),
     "sd_track_pnp": (_I, [_P, _I, _D, _I, _I, _I, _F, _F, _I]),
@@ -881,6 +887,33 @@ class Tracker:
         """dict(T_ref [n_ref, 4, 4], T_cur [4, 4], Xw, point_status, obs_erase, info16) of the last local_ba()."""
         return self._get_ba(self.L.sd_track_get_local_ba, *self._n_ba)
 
+    # --- LocalMapping::KeyFrameCulling (src/LocalMapping.cc:580-634) and the erasure of observations, on the same lists ---
+    def cull_keyframes(self, cand_frame, cand_flags, monocular, th_depth):
+        """The candidates (ref frames, in GetVectorCovisibleKeyFrames() order; flags bit 0 mnId == 0, bit 1 mbNotErase) against
+        the lists of set_observations; the lists themselves stay."""
+        cf, fl = np.ascontiguousarray(cand_frame, np.int32), np.ascontiguousarray(cand_flags, np.uint8)
+        assert len(cf) == len(fl)
+        _check(self.L.sd_track_cull_keyframes(self.h, len(cf), _p(cf), _p(fl), int(monocular), float(th_depth)))
+        self._n_cull = (len(cf), self._n_refresh, self._n_refresh_obs)
+
+    def get_culled(self):
+        """dict(verdict, counts2, obs_dead, point_bad, ref_obs, n_obs, info8) of the last cull_keyframes()."""
+        out = _cull_outputs(*self._n_cull)
+        _check(self.L.sd_track_get_culled(self.h, *[_p(a) for a in out.values()], *self._n_cull))
+        return out
+
+    def erase_observations(self, source):
+        """Kill the obs_erase of the last local_ba() (ERASE_LOCAL_BA) or the dead entries of the last cull (ERASE_CULL) with the
+        reference's cascade and compact the resident lists.  The entry count the handle was packed for stays an upper bound."""
+        _check(self.L.sd_track_erase_observations(self.h, int(source)))
+        self._n_erased = (self._n_refresh, self._n_refresh_obs)
+
+    def get_erased(self):
+        """dict(obs_off, obs_map, point_bad, ref_obs, n_obs, info8) of the last erase_observations()."""
+        out = _erase_outputs(*self._n_erased)
+        _check(self.L.sd_track_get_erased(self.h, *[_p(a) for a in out.values()], *self._n_erased))
+        return out
+
     def read_poses(self, n):
         """Tref and Tcur of slots 0 .. n - 1 as they are on the device: ([n, 4, 4], [n, 4, 4])."""
         out = np.zeros((2, n, 16))
@@ -1217,6 +1250,54 @@ def debug_refresh_points(obs_off, obs_desc, obs_centre, obs_octave, ref_obs, Xw,
     out = _refresh_outputs(n, fill)
     _check(L.sd_debug_refresh_points(n, _p(off), _p(d), _p(c), _p(oc), _p(kb), _p(ro), _p(pb), _p(X), _p(sf), len(sf),
                                      *[_p(out[k]) for k in _REFRESH_FIELDS]))
+    return out
+
+
+ERASE_LOCAL_BA, ERASE_CULL = 0, 1
+CULL_OK, CULL_NOT_RESIDENT, CULL_BAD_INDEX = 0, 1, 2
+CULL_SKIPPED_ID0, CULL_KEPT, CULL_CULLED, CULL_TO_BE_ERASED = 0, 1, 2, 3
+
+
+def _cull_outputs(n_cand, n, total):
+    """The output arrays of both culling entries, in their order"""
+    return dict(verdict=np.zeros(n_cand, np.uint8), counts2=np.zeros((n_cand, 2), np.int32), obs_dead=np.zeros(total, np.uint8),
+                point_bad=np.zeros(n, np.uint8), ref_obs=np.zeros(n, np.int32), n_obs=np.zeros(n, np.int32),
+                info8=np.zeros(8, np.int32))
+
+
+def _erase_outputs(n, total):
+    """The output arrays of both erasing entries, in their order"""
+    return dict(obs_off=np.zeros(n + 1, np.int32), obs_map=np.zeros(total, np.int32), point_bad=np.zeros(n, np.uint8),
+                ref_obs=np.zeros(n, np.int32), n_obs=np.zeros(n, np.int32), info8=np.zeros(8, np.int32))
+
+
+def debug_cull_keyframes(q, cand_kf, cand_flags, monocular, th_depth):
+    """A culling problem (the dict tests/cull_ref.py documents: off, kf, octave, stereo, depth, ref_obs, point_bad or None, n_kf)
+    from host arrays through k_cull (diagnostics).  Returns dict(verdict, counts2, obs_dead, point_bad, ref_obs, n_obs, info8)."""
+    off = np.ascontiguousarray(q["off"], np.int32)
+    n, total = len(off) - 1, int(off[-1])
+    kf, oc = np.ascontiguousarray(q["kf"], np.int32), np.ascontiguousarray(q["octave"], np.int32)
+    st, dp = np.ascontiguousarray(q["stereo"], np.uint8), np.ascontiguousarray(q["depth"], np.float32)
+    ro = np.ascontiguousarray(q["ref_obs"], np.int32)
+    pb = None if q.get("point_bad") is None else np.ascontiguousarray(q["point_bad"], np.uint8)
+    cf, fl = np.ascontiguousarray(cand_kf, np.int32), np.ascontiguousarray(cand_flags, np.uint8)
+    assert len(kf) == len(oc) == len(st) == len(dp) == total and len(ro) == n and len(cf) == len(fl) and (pb is None or len(pb) == n)
+    out = _cull_outputs(len(cf), n, total)
+    _check(lib().sd_debug_cull_keyframes(n, _p(off), _p(kf), _p(oc), _p(st), _p(dp), _p(ro), _p(pb), int(q["n_kf"]), len(cf), _p(cf),
+                                         _p(fl), int(monocular), float(th_depth), *[_p(a) for a in out.values()]))
+    return out
+
+
+def debug_erase_observations(off, stereo, erase, ref_obs, point_bad=None):
+    """Observation lists and erase flags from host arrays through k_erase (diagnostics).  Returns dict(obs_off, obs_map,
+    point_bad, ref_obs, n_obs, info8)."""
+    off = np.ascontiguousarray(off, np.int32)
+    n, total = len(off) - 1, int(off[-1])
+    st, er, ro = np.ascontiguousarray(stereo, np.uint8), np.ascontiguousarray(erase, np.uint8), np.ascontiguousarray(ref_obs, np.int32)
+    pb = None if point_bad is None else np.ascontiguousarray(point_bad, np.uint8)
+    assert len(st) == len(er) == total and len(ro) == n and (pb is None or len(pb) == n)
+    out = _erase_outputs(n, total)
+    _check(lib().sd_debug_erase_observations(n, _p(off), _p(st), _p(er), _p(ro), _p(pb), *[_p(a) for a in out.values()]))
     return out
 
 

@@ -224,6 +224,7 @@ int sd_track_create(sd_orb* cur, sd_orb* ref, int max_points, int max_batch, int
   A(dalloc(h, &h->rf.min_dist, M));
   A(refresh_create(h));
   A(ba_create(h));
+  A(cull_create(h));
   A(dalloc(h, &tb.s3_Xw1, B * K * 3));
   A(dalloc(h, &tb.s3_Xw2, B * K * 3));
   A(dalloc(h, &tb.s3_X, B * K * 6));
@@ -327,6 +328,7 @@ void sd_track_destroy(sd_track* h) {
   for (void* p : h->allocs) (void)hipFree(p);
   refresh_destroy(h);
   ba_destroy(h);
+  cull_destroy(h);
   if (h->ev_fence) (void)hipEventDestroy(h->ev_fence);
   h->pose_ring.destroy();
   h->small_ring.destroy();

@@ -149,6 +149,9 @@ static __device__ __forceinline__ const double* ba_pose_in(const BaProblem& pr, 
 
 __global__ void k_ba_gather(BaProblem pr, BaBuffers b) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  // After sd_track_erase_observations the lists end at off[n_points], before the n_obs entries the block was packed for (only
+  // the device knows where): the entries behind the end are nobody's edges.  Every kernel that walks e < n_obs asks e_flag first.
+  for (int e = pr.off[pr.n_points] + p; e < pr.n_obs; e += gridDim.x * blockDim.x) b.e_flag[e] = b.erase[e] = 0;
   if (p >= pr.n_points) return;
   const bool pbad = pr.point_bad && pr.point_bad[p];
   for (int e = pr.off[p]; e < pr.off[p + 1]; e++) {
@@ -1214,6 +1217,7 @@ static int queue_ba(sd_track* h, int point_row, int write_back, int mode, int n_
   h->ba.ran_points = rf.n_points;
   h->ba.ran_obs = rf.n_obs;
   h->ba.ran_global = mode;
+  h->ba_serial = rf.serial;
   return SD_OK;
 }
 

@@ -94,6 +94,8 @@ struct sd_track {
   std::vector<uint8_t> ba_roles;   // [max_batch + 1] the roles of sd_track_set_ba_keyframes, the current keyframe's last
   int ba_n_ref = 0;                // its n_ref_frames
   bool ba_roles_set = false;
+  unsigned long long ba_serial = 0;   // rf.serial of the lists the last bundle adjustment ran on
+  sd::CullBuffers cu{};            // sd_track_cull_keyframes / _erase_observations (track_cull.hip; cull_create / cull_destroy / cull_grow)
   sd::TrackBuffers tb{};
   sd::TrackCam cam{};
   bool have_cam = false;
@@ -144,6 +146,10 @@ void refresh_destroy(sd_track* h);
 int ba_create(sd_track* h);
 void ba_destroy(sd_track* h);
 int ba_grow(sd_track* h, size_t n_obs);
+// track_cull.hip: the culling's scratch (not in `allocs`: cull_grow replaces it when the observation block grows)
+int cull_create(sd_track* h);
+void cull_destroy(sd_track* h);
+int cull_grow(sd_track* h, size_t n_obs);
 
 // What a stage that runs now computes its result on: h->res.x.set(n, BIND_X, inputs_now(h)) after it, h->res.x.live(n, inputs_now(h)) later
 static inline sd::ResultInputs inputs_now(const sd_track* h) { return {h->cur->extract_serial, h->ref->extract_serial, h->tb.cur_bcast}; }

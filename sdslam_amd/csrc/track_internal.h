@@ -282,13 +282,16 @@ struct RefreshBuffers {
   // observations each; sd_track_set_observations replaces both by larger ones (after a wait for the tracking stream) when a call
   // needs more, and never shrinks them.  Nothing is allocated in sd_track_refresh_points.
   uint8_t* obs;          // device
+  uint8_t* twin;         // device, as large as obs: sd_track_erase_observations compacts the lists into it and swaps the two
   uint8_t* stage;        // pinned host
-  size_t obs_bytes;      // capacity of either
+  size_t obs_bytes;      // capacity of each
   hipEvent_t ev_staged;  // the copy out of `stage` has run
   bool staged;
   size_t o_off, o_ref, o_frame, o_kp, o_pbad, o_kbad;   // byte offsets of the arrays of the last upload; o_pbad / o_kbad 0: NULL
+  size_t at_pbad, at_kbad;   // where the block keeps room for the two flag arrays, given or not
   int n_points;          // -1: no observations have been set
-  int n_obs;
+  int n_obs;             // entries the block was packed for; after an erase an upper bound, the lists end at obs_off[n_points]
+  unsigned long long serial;   // counts the uploads and erasures: what ran on the lists is stamped with it
   int max_ref_frame;     // largest obs_frame of the last upload (-1: none)
   bool has_cur;          // an observation names the current keyframe (-1)
   double* centre;        // [B + 1][3] camera centres of the ref frames (Tref), then of the current keyframe (Tcur of slot 0)
@@ -304,6 +307,38 @@ struct RefreshBuffers {
 // k_refresh_centres, then k_refresh_points on the points of row `point_row`; write_local: the results also go into that row
 int launch_refresh(const sd_orb* cur, const sd_orb* ref, const TrackBuffers& tb, const RefreshBuffers& rf, const float* d_sf, int n_batch,
                    int point_row, int write_local, hipStream_t s);
+// LocalMapping::KeyFrameCulling and the erasure of observations (track_cull.hip): ONE device allocation carved by cull_carve for
+// cap_points points, cap_obs observations and n_cand candidates.  sd_track_create allocates it beside the bundle adjustment's
+// scratch and sd_track_set_observations grows it with its own block.  Nothing is allocated in either call.
+struct CullBuffers {
+  uint8_t* base;
+  size_t bytes, cap_points, cap_obs;
+  // what k_cull_gather makes of the resident lists, per observation: its camera (ref frame, max_batch = the current keyframe),
+  // octave, mvDepth (ref side) and weight in nObs (2: mvuRight >= 0); per point the refusal bits of its entries
+  int32_t* e_kf;
+  int32_t* e_oct;
+  float* e_depth;
+  uint8_t* e_w;
+  uint8_t* p_flag;
+  int32_t* cand;         // [2 n_cand] the candidates' frames, then their flags
+  // the last cull
+  uint8_t* verdict;      // [n_cand]
+  int32_t* counts2;      // [n_cand][2]
+  uint8_t* dead;         // [E]
+  uint8_t* pbad;         // [P] went bad in the run
+  int32_t* ref_new;      // [P]
+  int32_t* nobs;         // [P]
+  int32_t* info;         // [8]
+  // the last erasure
+  int32_t* er_map;       // [E] old entry -> new position, -1: erased
+  int32_t* er_nobs;      // [P]
+  int32_t* er_cnt;       // [P] survivors
+  int32_t* er_info;      // [8]
+  int ran_cand, ran_points, ran_obs;   // the last cull: ran_cand -1: none
+  unsigned long long ran_serial;       // ... and the lists it ran on
+  int er_points, er_obs;               // the last erasure: er_points -1: none
+  unsigned long long er_serial;        // ... and the lists it left
+};
 // Optimizer::LocalBundleAdjustment (track_ba.hip): the scratch of one problem, ONE device allocation carved by ba_carve for
 // cap_points points, cap_obs observations and n_kf cameras.  sd_track_create allocates it for max_points points of 16
 // observations each and max_batch + 1 cameras (the ref frames, then the current keyframe); sd_track_set_observations replaces

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(64 * REFRESH_WAVES) void k_refresh_points(RefreshAr
     n = a.off[p + 1] - o0;
     if ((a.point_bad && a.point_bad[p]) || n <= 0) status = SD_REFRESH_SKIPPED;
     else if (n > REFRESH_CAP) status = SD_REFRESH_TOO_MANY;
-    else if (o0 < 0 || o0 + n > a.n_obs || a.ref_obs[p] < 0 || a.ref_obs[p] >= n) status = SD_REFRESH_BAD_INDEX;
+    else if (o0 < 0 || o0 + n > min(a.n_obs, a.off[a.n_points]) || a.ref_obs[p] < 0 || a.ref_obs[p] >= n) status = SD_REFRESH_BAD_INDEX;
   }
   if (have_point && status == 0) {
     int why = 0;
@@ -351,6 +351,7 @@ int refresh_create(sd_track* h) {
   rf.n_points = -1;
   rf.obs_bytes = ObsPack((size_t)h->max_points, (size_t)h->max_points * 16).bytes;
   SD_HIP_CHECK(hipMalloc((void**)&rf.obs, rf.obs_bytes));
+  SD_HIP_CHECK(hipMalloc((void**)&rf.twin, rf.obs_bytes));
   SD_HIP_CHECK(hipHostMalloc((void**)&rf.stage, rf.obs_bytes, hipHostMallocDefault));
   SD_HIP_CHECK(hipEventCreateWithFlags(&rf.ev_staged, hipEventDisableTiming));
   return SD_OK;
@@ -358,9 +359,10 @@ int refresh_create(sd_track* h) {
 void refresh_destroy(sd_track* h) {
   RefreshBuffers& rf = h->rf;
   if (rf.obs) (void)hipFree(rf.obs);
+  if (rf.twin) (void)hipFree(rf.twin);
   if (rf.stage) (void)hipHostFree(rf.stage);
   if (rf.ev_staged) (void)hipEventDestroy(rf.ev_staged);
-  rf.obs = rf.stage = nullptr;
+  rf.obs = rf.twin = rf.stage = nullptr;
   rf.ev_staged = nullptr;
 }
 
@@ -408,21 +410,27 @@ int sd_track_set_observations(sd_track* h, int n_points, const int32_t* obs_off,
   const ObsPack pk((size_t)n_points, (size_t)total);
   if (pk.bytes > rf.obs_bytes) {   // the one grow-only allocation (track_internal.h): queued kernels may still read the old block
     SD_HIP_CHECK(hipStreamSynchronize(h->pnp_stream));
-    uint8_t *d = nullptr, *st = nullptr;
+    uint8_t *d = nullptr, *tw = nullptr, *st = nullptr;
     const size_t want = std::max(pk.bytes, rf.obs_bytes * 2);
     SD_HIP_CHECK(hipMalloc((void**)&d, want));
-    if (hipError_t e = hipHostMalloc((void**)&st, want, hipHostMallocDefault); e != hipSuccess) {
+    hipError_t e = hipMalloc((void**)&tw, want);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&st, want, hipHostMallocDefault);
+    if (e != hipSuccess) {
       (void)hipFree(d);
+      if (tw) (void)hipFree(tw);
       return hip_error("sd_track_set_observations", e);
     }
     (void)hipFree(rf.obs);
+    (void)hipFree(rf.twin);
     (void)hipHostFree(rf.stage);
     rf.obs = d;
+    rf.twin = tw;
     rf.stage = st;
     rf.obs_bytes = want;
     rf.staged = false;
   }
   SD_TRY(ba_grow(h, (size_t)total));   // the bundle adjustment's scratch holds as many observations as this block
+  SD_TRY(cull_grow(h, (size_t)total));   // ... and so does the culling's
   if (rf.staged) SD_HIP_CHECK(hipEventSynchronize(rf.ev_staged));   // the last upload has left the pinned block
   uint8_t* st = rf.stage;
   std::memcpy(st + pk.off, obs_off, ((size_t)n_points + 1) * 4);
@@ -439,6 +447,8 @@ int sd_track_set_observations(sd_track* h, int n_points, const int32_t* obs_off,
   rf.o_off = pk.off; rf.o_ref = pk.ref; rf.o_frame = pk.frame; rf.o_kp = pk.kp;
   rf.o_pbad = point_bad ? pk.pbad : 0;
   rf.o_kbad = obs_kf_bad ? pk.kbad : 0;
+  rf.at_pbad = pk.pbad; rf.at_kbad = pk.kbad;
+  rf.serial++;
   rf.n_points = n_points;
   rf.n_obs = total;
   rf.max_ref_frame = max_ref;

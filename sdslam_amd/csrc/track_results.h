@@ -127,6 +127,12 @@ constexpr EndsRow kEndsBa[] = {
     {"sd_track_global_ba(write_back)", R_SIM3 | R_TRI | R_FUSE | R_REFRESH | R_APPEND},
 };
 
+// The erasure of observations (track_cull.hip), a table of its own for the same reason.  sd_track_cull_keyframes changes nothing
+// and ends nothing; its own result and the erase's are records stamped with the lists' serial (RefreshBuffers::serial).
+constexpr EndsRow kEndsCull[] = {
+    {"sd_track_erase_observations", R_REFRESH},           // the lists the result was computed on are compacted: what an upload ends
+};
+
 constexpr bool same_name(const char* a, const char* b) {
   while (*a && *a == *b) ++a, ++b;
   return *a == *b;
@@ -141,6 +147,8 @@ constexpr int ends_of(const char* entry) {
     if (same_name(row.entry, entry)) return (int)row.mask;
   for (const EndsRow& row : kEndsBa)
     if (same_name(row.entry, entry)) return (int)row.mask;
+  for (const EndsRow& row : kEndsCull)
+    if (same_name(row.entry, entry)) return (int)row.mask;
   return -1;
 }
 
@@ -151,6 +159,7 @@ static_assert(ends_of("sd_track_append_new_points(mark_flags)") == (ends_of("sd_
               "... and with mark_flags what sd_track_set_point_flags ends");
 static_assert(ends_of("sd_track_local_ba(write_back)") == (ends_of("sd_track_set_poses") | ends_of("sd_track_refresh_points(write_local)")),
               "a write-back ends what sd_track_set_poses and a write-through refresh end");
+static_assert(ends_of("sd_track_erase_observations") == ends_of("sd_track_set_observations"), "an erasure ends what an upload of the lists ends");
 static_assert(ends_of("sd_track_global_ba(write_back)") == ends_of("sd_track_local_ba(write_back)"), "... whichever bundle adjustment wrote");
 
 }  // namespace sd
