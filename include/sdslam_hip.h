@@ -50,6 +50,9 @@ const char* sd_version(void);
  *                                    call's selection (beside its descriptor kernel) instead of behind the whole previous call; 0: as before
  *   extract.pyr_early          0     1: ... and, on an extractor with two output sets (one a tracker is attached to), the resize chain as
  *                                    well, on the auxiliary stream in front of the blur (measured: loses 8 % with the PnP step)
+ *   extract.pyr_rows           1     plan: levels resized by k_pyr_rows (runs of consecutive rows that share source rows): 0 none,
+ *                                    1 the levels whose runs fill four fifths of the row blocks (scale 1.2), 2 every level tall
+ *                                    enough for single-reflection borders -- tests force short runs through the kernel
  * Results never depend on an option (each setting is covered by a parity test); only speed does. */
 int sd_set_option(const char* name, int value);
 int sd_get_option(const char* name, int* value);
@@ -90,6 +93,13 @@ int sd_orb_features_per_level(const sd_orb* h, int32_t* quota);
 int sd_orb_plan_info(int nfeatures, float scale_factor, int nlevels, int th_fast, int w, int hgt,
                      int32_t* level_info /* nlevels x 8 */, int32_t* cell_zones /* cap x 6, may be NULL */,
                      int cell_cap, int32_t* n_cells, uint64_t* bytes_per_frame);
+
+/* Host-only: how pyramid level `level` of that geometry is resized under the current "extract.pyr_rows".  *n_blocks = 0: by
+ * k_pyr_split (rows a quarter of the level apart).  Otherwise by k_pyr_rows, and per row block {first interior row y0, rows n
+ * (1..5), first source row, 1 if a row of the block is stored a second time as a REFLECT_101 border row}: rows y0 .. y0 + n - 1
+ * resize source rows sy0 + r and sy0 + r + 1. */
+int sd_orb_plan_row_blocks(int nfeatures, float scale_factor, int nlevels, int th_fast, int w, int hgt, int level,
+                           int32_t* blocks /* cap x 4, may be NULL */, int block_cap, int32_t* n_blocks);
 
 /* operator()(image, mask(ignored), keypoints, descriptors, pyramid): one 8-bit grey frame in
  * host memory -> keypoints (cap entries), descriptors (cap x 32 bytes), *n_out.  The image

@@ -50,6 +50,7 @@ _SIGNATURES = {
     "sd_orb_scale_tables": (_I, [_P, _P, _P, _P, _P]),
     "sd_orb_features_per_level": (_I, [_P, _P]),
     "sd_orb_plan_info": (_I, [_I, _F, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "sd_orb_plan_row_blocks": (_I, [_I, _F, _I, _I, _I, _I, _I, _P, _I, _P]),
     "sd_orb_extract": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P]),
     "sd_orb_extract_batch": (_I, [_P, _P, _I, _I, _I, _I, _Z, _P, _P, _I, _P]),
     "sd_orb_extract_batch_device": (_I, [_P, _P, _I, _I, _I, _I, _Z]),
@@ -279,6 +280,15 @@ def plan_info(nfeatures, scale_factor, nlevels, th_fast, w, h):
     _check(lib().sd_orb_plan_info(nfeatures, scale_factor, nlevels, th_fast, w, h, _p(lv), _p(zones), len(zones),
                                   C.byref(n), C.byref(nbytes)))
     return dict(levels=lv, cells=zones[:n.value].copy(), bytes_per_frame=nbytes.value)
+
+
+def plan_row_blocks(nfeatures, scale_factor, nlevels, th_fast, w, h, level):
+    """Row blocks [n, 4] = {y0, rows, first source row, carries border rows} k_pyr_rows walks on that level (host-only);
+    empty where k_pyr_split resizes the level."""
+    out = np.zeros((4096, 4), np.int32)
+    n = C.c_int32()
+    _check(lib().sd_orb_plan_row_blocks(nfeatures, scale_factor, nlevels, th_fast, w, h, level, _p(out), len(out), C.byref(n)))
+    return out[:n.value].copy()
 
 
 def pinned_array(shape, dtype=np.uint8):

@@ -7,7 +7,9 @@
 //
 //   k_pyr_split      ComputePyramid: resize + copyMakeBorder   src/ORBextractor.cc:680-700 (one launch per level: aligned 4-pixel
 //                    groups of every padded row, table-driven bilinear at REFLECT_101 column indices; border rows as second stores)
-//   k_pyr_level      same, single generic pass     (exact-2x INTER_AREA levels, byte-unaligned inputs, tiny levels)
+//   k_pyr_rows       same, for levels whose rows come in runs on consecutive source rows (scale 1.2): five consecutive rows per
+//                    thread, each source row loaded and horizontally resized once
+//   k_pyr_level      same, single generic pass    (exact-2x INTER_AREA levels, byte-unaligned inputs, tiny levels)
 //   k_fast_cells     cv::FAST per grid cell        src/ORBextractor.cc:501-552 (FAST-9/16, score, cell-local 3x3 NMS)
 //   k_select_*       quota loop + retainBest       src/ORBextractor.cc:554-605 (wave-parallel libstdc++ introselect replay)
 //   k_blur           GaussianBlur 7x7 s=2          src/ORBextractor.cc:659-660 (8-bit fixed point, separable)
@@ -273,6 +275,10 @@ __global__ __launch_bounds__(256) void k_pyr_level(const LevelGeom L, const Leve
 // here like any other row instead of being copied by a third kernel after the first two (k_pyr_rows, gone): ONE launch per level
 // (k_pyr_split), 8 pyramid launches per step instead of 24.  r3: where the level is tall enough for single reflections the border
 // rows are second stores of their source rows (`mirror`).
+// r10: rows a quarter of the level apart share no source rows, so every output row loads and horizontally resizes both of its
+// own.  The levels whose rows come in runs on consecutive source rows (every resized level of the 8 x 1.2 pyramid) have gone to
+// k_pyr_rows below, which gives a thread five CONSECUTIVE rows on six source rows; PYR_RPT and this body remain for level 0 (the
+// copy), for levels under 48 rows, and for scale factors whose runs are short (1.5: two rows).
 __device__ __forceinline__ void pyr_resize_body(const LevelGeom& L, const LevelGeom& S, size_t pyr_frame_bytes, int level,
                                                 const int32_t* __restrict__ coef, const uint8_t* __restrict__ src0, int src_stride,
                                                 size_t src_frame_stride, uint8_t* __restrict__ pyr, int G, unsigned magicG, int Hh,
@@ -414,6 +420,80 @@ __global__ __launch_bounds__(256) void k_pyr_split(const LevelGeom L, const Leve
   xcd_frame_block(uframe, bx);
   pyr_resize_body(L, S, pyr_frame_bytes, level, coef, src0, src_stride, src_frame_stride, pyr, G, magicG, Hh, (int)uframe,
                   bx * 256 + threadIdx.x, mirror);
+}
+
+// k_pyr_rows: the resize of a level >= 1 whose rows come in runs that share source rows (orb_plan.cpp row_blocks; scale 1.2).
+// k_pyr_split gives a thread four rows a quarter of the level apart, so every output row loads and horizontally resizes both of
+// its source rows.  Here a thread owns one 4-pixel group of a row BLOCK: up to SD_PYR_BLOCK_ROWS consecutive interior rows whose
+// first source rows are consecutive too, so row r combines horizontal results r and r + 1 of the block's
+// SD_PYR_BLOCK_ROWS + 1 source rows -- which two never depends on the block, so nothing is selected per lane and (block, group)
+// pairs are dealt flat over the lanes like k_pyr_split's (row, group) pairs.  Per output row 1.2 source rows (3.6 dword loads,
+// 1.2 horizontal passes) instead of 2 (6 loads, 2 passes); the integer operations per output pixel are k_pyr_split's.
+// A block shorter than SD_PYR_BLOCK_ROWS computes its missing rows and does not store them; source rows are clamped to the
+// source level's last interior row (as the per-row table of k_pyr_split clamps them), never branched around.
+__global__ __launch_bounds__(256) void k_pyr_rows(const LevelGeom L, const LevelGeom S, size_t pyr_frame_bytes,
+                                                  const int32_t* __restrict__ coef, uint8_t* __restrict__ pyr, int G, unsigned magicG) {
+  constexpr int R = SD_PYR_BLOCK_ROWS;
+  unsigned uframe, bx;
+  xcd_frame_block(uframe, bx);
+  const unsigned e = bx * 256 + threadIdx.x;
+  const unsigned bi = __umulhi(e, magicG);        // e / G
+  if (bi >= (unsigned)L.nblk) return;
+  const int gi = (int)(e - bi * (unsigned)G);
+  const int4* gt = (const int4*)(coef + L.cg) + 3 * gi;
+  const int4* bt = (const int4*)(coef + L.cb) + 2 * bi;
+  const int4 t0 = gt[0], t1 = gt[1], t2 = gt[2];
+  const int4 k0 = bt[0], k1 = bt[1];   // {y0, n | border << 8, sy0, bb[0]}, {bb[1 ... 4]}
+  typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+  const uint32_t selP[4] = {(uint32_t)t0.y, (uint32_t)t0.z, (uint32_t)t0.w, (uint32_t)t1.x};
+  const uint32_t ab[4] = {(uint32_t)t1.y, (uint32_t)t1.z, (uint32_t)t1.w, (uint32_t)t2.x};
+  const uint32_t bb[R] = {(uint32_t)k0.w, (uint32_t)k1.x, (uint32_t)k1.y, (uint32_t)k1.z, (uint32_t)k1.w};
+  const int y0 = k0.x, n = k0.y & 0xff, sy0 = k0.z;
+  const uint8_t* sb = pyr + (size_t)uframe * pyr_frame_bytes + S.off;   // 64-byte aligned (level offsets and row pitches are)
+  uint8_t* dstb = pyr + (size_t)uframe * pyr_frame_bytes + L.off;
+  // byte offset of the group's first source column in interior row 0 of the source level; the row pitch is a multiple of 64, so
+  // the misalignment of the 12-byte window is the same in every source row
+  const uint32_t c0 = (uint32_t)(SD_EDGE * S.pstride + SD_EDGE + t0.x);
+  const unsigned sh = c0 & 3u;
+  uint32_t u[R + 1][3];
+#pragma unroll
+  for (int j = 0; j <= R; j++) {   // all loads first
+    const uint32_t* q = (const uint32_t*)(sb + ((c0 & ~3u) + (uint32_t)__mul24(min(sy0 + j, S.h - 1), S.pstride)));
+#pragma unroll
+    for (int k = 0; k < 3; k++) u[j][k] = q[k];
+  }
+  uint32_t hz[R + 1][4];   // horizontal pass, once per source row (with the & ~15 of the vertical multiply)
+#pragma unroll
+  for (int j = 0; j <= R; j++) {
+    const uint32_t lo = __builtin_amdgcn_alignbyte(u[j][1], u[j][0], sh), hi = __builtin_amdgcn_alignbyte(u[j][2], u[j][1], sh);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      hz[j][k] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(hi, lo, selP[k])), __builtin_bit_cast(us2, ab[k]), 0u, false) & ~15u;
+  }
+  const uint32_t dst_x = 4u * (uint32_t)gi;
+  const int nvalid = L.w + 2 * SD_EDGE - (int)dst_x;   // columns beyond the padded width (last group of a row) stay zero
+  const uint32_t keep = nvalid >= 4 ? 0xffffffffu : (1u << (8 * nvalid)) - 1u;
+  uint32_t packed[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const uint32_t b0 = (bb[r] & 0xffffu) << 12, b1 = bb[r] >> 16 << 12;
+    uint32_t pk = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)   // (b * (h >> 4)) >> 16 == mulhi(b << 12, h & ~15); no saturation needed (k_pyr_split)
+      pk |= ((__umulhi(b0, hz[r][k]) + __umulhi(b1, hz[r + 1][k]) + 2u) >> 2) << (8 * k);
+    packed[r] = pk & keep;
+  }
+#pragma unroll
+  for (int r = 0; r < R; r++)
+    if (r < n) *(uint32_t*)(dstb + (dst_x + (uint32_t)__mul24(y0 + r + SD_EDGE, L.pstride))) = packed[r];
+  if (k0.y >> 8) {   // the block holds rows that are border rows as well (k_pyr_split's `mirror` second stores)
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const int Yi = y0 + r;
+      const int prow2 = Yi >= 1 && Yi <= SD_EDGE ? SD_EDGE - Yi : (Yi >= L.h - 20 && Yi <= L.h - 2 ? 2 * L.h + 17 - Yi : -1);
+      if (r < n && prow2 >= 0) *(uint32_t*)(dstb + (dst_x + (uint32_t)__mul24(prow2, L.pstride))) = packed[r];
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1441,6 +1521,12 @@ struct Pipeline {
     }
     auto magic = [](unsigned d) { return (unsigned)(0xFFFFFFFFull / d) + 1u; };   // e / d == umulhi(e, magic) for e < 2^31 / d
     const int G = (L.w + 2 * SD_EDGE + 3) / 4;   // 4-pixel groups of a padded row
+    if (l > 0 && L.nblk > 0) {   // rows in runs that share source rows (orb_plan.cpp row_blocks): one thread per (row block, group)
+      const unsigned n_rows = (unsigned)(((size_t)L.nblk * G + 255) / 256);
+      hipLaunchKernelGGL(k_pyr_rows, dim3(n_rows, n), dim3(256), 0, ps, L, S, (size_t)P.pyr_frame_bytes, h->d_coef, h->d_pyr, G,
+                         magic((unsigned)G));
+      return SD_OK;
+    }
     const bool mirror = L.h >= 48;   // border rows as second stores of their source rows (single reflections)
     const int Hh = ((mirror ? L.h : L.prows) + PYR_RPT - 1) / PYR_RPT;   // (padded) rows per row-slot of a thread
     const unsigned n_resize = (unsigned)(((size_t)Hh * G + 255) / 256);

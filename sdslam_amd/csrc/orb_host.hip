@@ -331,6 +331,33 @@ int sd_orb_plan_info(int nfeatures, float scale_factor, int nlevels, int th_fast
   return SD_OK;
 }
 
+// Host-only: the row-block table k_pyr_rows would walk on `level` of that geometry (under the current "extract.pyr_rows")
+int sd_orb_plan_row_blocks(int nfeatures, float scale_factor, int nlevels, int th_fast, int w, int hgt, int level, int32_t* blocks,
+                           int block_cap, int32_t* n_blocks) {
+  SD_REQUIRE(n_blocks, SD_ERR_INVALID_ARG, "NULL argument");
+  SD_REQUIRE(nfeatures > 0 && nlevels >= 1 && nlevels <= SD_MAX_LEVELS && scale_factor > 1.0f && level >= 0 && level < nlevels,
+             SD_ERR_INVALID_ARG, "bad extractor parameters");
+  HostPlan hp;
+  plan_tables(nfeatures, scale_factor, nlevels, hp);
+  const char* why = "";
+  if (!plan_geometry(nfeatures, nlevels, th_fast, w, hgt, hp, &why)) {
+    set_error(std::string("unsupported geometry: ") + why);
+    return SD_ERR_INVALID_ARG;
+  }
+  const LevelGeom& L = hp.plan.lv[level];
+  *n_blocks = L.nblk;
+  if (blocks) {
+    SD_REQUIRE(block_cap >= L.nblk, SD_ERR_CAPACITY, "block_cap too small");
+    for (int b = 0; b < L.nblk; b++) {
+      PyrRowBlock k;
+      memcpy(&k, hp.coef.data() + L.cb + (size_t)b * (sizeof(PyrRowBlock) / 4), sizeof(k));
+      int32_t* o = blocks + 4 * b;
+      o[0] = k.y0; o[1] = k.n_border & 0xff; o[2] = k.sy0; o[3] = k.n_border >> 8;
+    }
+  }
+  return SD_OK;
+}
+
 int sd_orb_scale_tables(const sd_orb* h, float* sf, float* inv_sf, float* sigma2, float* inv_sigma2) {
   SD_REQUIRE(h, SD_ERR_INVALID_ARG, "handle is NULL");
   for (int i = 0; i < h->nlevels; i++) {

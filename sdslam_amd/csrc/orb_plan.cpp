@@ -109,6 +109,37 @@ static bool group_table(LevelGeom& L, int src_w, const std::vector<int32_t>* xo,
   return ok;
 }
 
+// k_pyr_rows' row-block table: the interior rows of a level cut into runs of at most SD_PYR_BLOCK_ROWS rows whose first source
+// rows step by exactly one (at scale 1.2 four steps out of five do: runs of five rows on six source rows, now and then four).
+// The level takes that path (L.nblk > 0) where its border rows are single reflections (h >= 48, as for k_pyr_split's second
+// stores) and, option "extract.pyr_rows" = 1, the runs fill at least four fifths of the blocks' row slots: a thread computes
+// every slot, so short runs (scale 1.5: two rows, scale 2: one) cost more vertical passes than the shared source rows save.
+// 2 takes every level with single reflections (tests: every run length through the kernel), 0 none.
+static void row_blocks(LevelGeom& L, const std::vector<int32_t>& yo, const std::vector<int32_t>& yb, int mode,
+                       std::vector<int32_t>& coef) {
+  if (mode == 0 || L.h < 48) return;
+  std::vector<PyrRowBlock> blocks;
+  for (int y0 = 0; y0 < L.h;) {
+    int n = 1;
+    while (n < SD_PYR_BLOCK_ROWS && y0 + n < L.h && yo[y0 + n] == yo[y0 + n - 1] + 1) n++;
+    PyrRowBlock b;
+    memset(&b, 0, sizeof(b));
+    b.y0 = y0;
+    b.sy0 = yo[y0];
+    const bool border = (y0 <= SD_EDGE && y0 + n - 1 >= 1) || (y0 <= L.h - 2 && y0 + n - 1 >= L.h - 20);
+    b.n_border = n | (border ? 1 << 8 : 0);
+    for (int r = 0; r < SD_PYR_BLOCK_ROWS; r++) b.bb[r] = (uint32_t)yb[std::min(y0 + r, L.h - 1)];
+    blocks.push_back(b);
+    y0 += n;
+  }
+  if (mode == 1 && (size_t)L.h * 5 < blocks.size() * SD_PYR_BLOCK_ROWS * 4) return;
+  while (coef.size() % 4) coef.push_back(0);
+  L.cb = (int)coef.size();
+  L.nblk = (int)blocks.size();
+  const int32_t* p = (const int32_t*)blocks.data();
+  coef.insert(coef.end(), p, p + blocks.size() * (sizeof(PyrRowBlock) / 4));
+}
+
 bool plan_geometry(int nfeatures, int nlevels, int thFAST, int w, int h, HostPlan& hp, const char** why) {
   (void)nfeatures;
   if (nlevels < 1 || nlevels > SD_MAX_LEVELS) { *why = "nlevels out of range"; return false; }
@@ -165,7 +196,7 @@ bool plan_geometry(int nfeatures, int nlevels, int thFAST, int w, int h, HostPla
     // resize tables (level l from level l-1)
     L.area2x2 = 0;
     L.fast_resize = 0;
-    L.cx = L.cy = L.cg = L.cr = 0;
+    L.cx = L.cy = L.cg = L.cr = L.cb = L.nblk = 0;
     L.scale_x = L.scale_y = 1.0;
     if (l > 0) {
       const LevelGeom& S = P.lv[l - 1];
@@ -207,6 +238,7 @@ bool plan_geometry(int nfeatures, int nlevels, int thFAST, int w, int h, HostPla
             hp.coef.push_back(yb[y]);
             hp.coef.push_back(0);
           }
+          row_blocks(L, yo, yb, opt(OPT_PYR_ROWS), hp.coef);
         }
         L.fast_resize = ok ? 1 : 0;
       }

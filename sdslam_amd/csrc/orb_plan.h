@@ -29,6 +29,8 @@ struct LevelGeom {
   int cx, cy;            // offsets of the x / y resize tables inside the coefficient array: {ofs[dn], a0|a1<<16 [dn]}
   int cr;                // offset of the per-row table of k_pyr_split (4 dwords per interior row: byte offsets of the two source rows, b0|b1<<16, 0)
   int cg;                // offset of the per-group table of k_pyr_split (12 dwords per 4-pixel group of a padded row, 16-byte aligned)
+  int cb, nblk;          // offset and length of the row-block table of k_pyr_rows (PyrRowBlock, 8 dwords per block, 16-byte aligned);
+                         // nblk == 0: the level is resized by k_pyr_split
   int fast_resize;       // level qualifies for k_pyr_resize (bilinear, 4 outputs read <= 8 source bytes)
   double scale_x, scale_y;   // cv::resize: 1. / ((double)dst / src) from level l-1 to l
   float scale;           // mvScaleFactor[level]
@@ -45,6 +47,19 @@ struct CellGeom {
   int strip_rows;        // zone rows per LDS strip
   int evaluated;         // 0: the reference `continue`s over this cell (never calls FAST)
 };
+
+// k_pyr_rows work item: up to SD_PYR_BLOCK_ROWS consecutive interior rows y0 ... y0 + n - 1 of a level whose first source rows
+// are consecutive as well (row y0 + r resizes source rows sy0 + r and sy0 + r + 1): the block needs n + 1 horizontally resized
+// source rows instead of 2 n, and which two of them a row combines does not depend on the block.  `border`: some row of the
+// block is stored a second time as a top / bottom REFLECT_101 border row (rows 1 ... 19 and h - 20 ... h - 2).
+#define SD_PYR_BLOCK_ROWS 5
+struct PyrRowBlock {
+  int32_t y0;                        // first interior row
+  int32_t n_border;                  // n | border << 8
+  int32_t sy0;                       // first source row (interior coordinates of the source level)
+  uint32_t bb[SD_PYR_BLOCK_ROWS];    // vertical coefficient pair b0 | b1 << 16 of each row
+};
+static_assert(sizeof(PyrRowBlock) == 32, "k_pyr_rows reads a block as two 16-byte loads");
 
 // k_blur work item: 16 consecutive (64-column strip, 32-row band) pairs of a level, pair p = band * nstrips + strip
 struct BlurTile { int level, p0, nstrips; unsigned magic; };   // magic: p / nstrips == umulhi(p, magic)

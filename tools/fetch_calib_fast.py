@@ -86,7 +86,7 @@ out["all FAST launches of a step"] = {"unique_bytes": tot_u, "FETCH_SIZE_bytes_r
 pdisp = []
 for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
     for r in csv.DictReader(open(f)):
-        if "k_pyr_split" in r["Kernel_Name"] and r["Counter_Name"] == "FETCH_SIZE":
+        if ("k_pyr_split" in r["Kernel_Name"] or "k_pyr_rows" in r["Kernel_Name"]) and r["Counter_Name"] == "FETCH_SIZE":
             pdisp.append((int(r["Dispatch_Id"]), float(r["Counter_Value"]) * 1024.0))
 pdisp.sort()
 NL = CFG[2]
