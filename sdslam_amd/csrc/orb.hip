@@ -32,6 +32,7 @@
 
 #include "introselect.h"
 #include "introselect_wave.h"
+#include "orb_fast_lds.h"
 #include "orb_internal.h"
 #include "sd_sincosf.h"
 
@@ -265,10 +266,7 @@ __global__ __launch_bounds__(256) void k_pyr_level(const LevelGeom L, const Leve
 // (r1-r3 had a second role for the border columns and the interior pixels outside the aligned interior groups, on the generic
 // per-byte path pyr_px4: a fifth of every launch's workgroups.)  Level 0 is the frame copied into the padded layout by the same kernel.
 // ------------------------------------------------------------------------------------------
-#ifndef PYR_RPT
-#define PYR_RPT 4
-#endif
-// rows per thread: rows Y, Y + ceil(h / 4), ... share the group's column data and give independent load chains (r1: 3 rows 130.8 k,
+// PYR_RPT (orb_plan.h: the plan sizes the launch with it) rows per thread: rows Y, Y + ceil(h / 4), ... share the group's column data and give independent load chains (r1: 3 rows 130.8 k,
 // 2 rows 130.4 k frames/s, 4 rows no better than 2; r3, with the per-group / per-row tables as the fixed cost of a thread: 4 rows and
 // the descriptor patch on 8-byte loads 226.2 k vs 222.3 k with 3 rows; 4 / 5 / 6 rows 229.4 / 226.9 / 225.4 k, alternating runs)
 // **r2**: the rows are PADDED rows (0 .. h + 37): a top / bottom border row is the resize of its REFLECT_101 interior row, computed
@@ -600,9 +598,7 @@ __device__ unsigned long long g_fast_prof_wg[(size_t)FPROF_FRAMES * FPROF_CELLS 
 //      re-compacted in place (still raster order) and their scores go to the LDS score map;
 //   C. after a block barrier, NMS on the queued corners against the LDS score map, then ordered
 //      emission (wave bands are contiguous in raster order, so per-wave counts give offsets).
-#ifndef FAST_STAGE_DEPTH
-#define FAST_STAGE_DEPTH 12   // tile dwords in flight per thread while staging (256 threads x 12 x 4 B = 12 KB per round trip)
-#endif
+// (FAST_STAGE_DEPTH, the tile dwords in flight per thread while staging, is orb_fast_lds.h's: the staging loops' index range depends on it)
 typedef uint32_t fast_u4 __attribute__((ext_vector_type(4)));   // one 16-byte staging unit (global_load_dwordx4 / ds_write_b128)
 
 // 8 waves per SIMD: the kernel needed 65 VGPRs, one over the 64-register step; held to 64 it gains a resident wave per SIMD
@@ -640,25 +636,18 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
   const int pstride = src.pstride[C.level];
   uint32_t* out = cand + (size_t)frame * cand_per_frame + C.cand_off;
   const int zw = C.zw, zh = C.zh, S = C.strip_rows;
-  // r5: the tile's left edge is aligned down to 16 bytes and its pitch is a multiple of 16, so a row is a whole number of
-  // 16-byte units both in the source and in LDS; the score map has the SAME pitch, so that a pixel's byte offset from the
-  // tile's first zone pixel (the queue entry) addresses its ring (tile0 + entry) and its score (sc0 + entry) alike.
-  const int xs = C.zx0 - 3 + edge;   // x of tile column 0 in the source rows (before alignment)
-  const int xa = xs & ~15, sh = xs - xa;
-  const int TPU = (sh + zw + 6 + 15) >> 4;   // tile pitch in 16-byte units
-  const int TP = TPU * 16;
-  const int NSR = min(S + 2, zh);           // zone rows a strip scores at most: its own and one above / below (a whole-cell strip has neither)
-  const int RPW = (NSR + 3) >> 2;           // score rows per wave (upper bound)
-  const int QCAP = RPW * zw;                // queue entries per wave (worst case: every pixel)
-  uint8_t* tile = smem;
-  uint8_t* sc = smem + (size_t)TP * (NSR + 6);   // score map: rows -1 ... nsr, columns -1 ... TP - 2 of the zone
-  uint16_t* queue = (uint16_t*)(sc + (size_t)TP * (NSR + 2)) + (size_t)wave * QCAP;
+  // the tile, the score map and the wave queues, and the four flat-index divisions with their checked ranges: orb_fast_lds.h
+  const LdsFastTile T(C.zx0, zw, zh, S, edge);
+  const int xa = T.xa, TPU = T.TPU, TP = T.TP;
+  uint8_t* tile = smem + T.tile;
+  uint8_t* sc = smem + T.sc;
+  uint16_t* queue = (uint16_t*)(smem + T.queue_of(wave));
   // the wave's queue as a scalar byte offset into the dynamic LDS (phase A stores through SGPR base + lane offset)
-  const uint32_t qbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)((size_t)TP * (2 * NSR + 8) + (size_t)wave * QCAP * 2));
-  const unsigned magic = 0xFFFFFFFFu / (unsigned)zw + 1u;   // q / zw == umulhi(q, magic) for q < 2^16, zw < 2^12
-  const unsigned magic_tp = 0xFFFFFFFFu / (unsigned)TP + 1u;   // queue entry / TP (entries < 2^16: the tile is < 64 KB)
-  const uint8_t* tile0 = tile + 3 * TP + 3 + sh;   // zone pixel (0, 0) of the strip
-  uint8_t* sc0 = sc + TP + 1;                      // its score
+  const uint32_t qbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)T.queue_of(wave));
+  const unsigned magic = fastdiv_magic((unsigned)zw);    // flat pixel index / zw
+  const unsigned magic_tp = fastdiv_magic((unsigned)TP);   // queue entry / TP
+  const uint8_t* tile0 = smem + T.tile0;   // zone pixel (0, 0) of the strip
+  uint8_t* sc0 = smem + T.sc0;             // its score
   const unsigned long long lt = lanemask_lt((int)__lane_id());
   int total = 0;
   FPROF_DECL;
@@ -670,8 +659,7 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
     const int npr = nsr + 6;
     // ---- stage pixels and clear the score map.  The tile's 16-byte units are numbered row-major and dealt to the 256 threads
     // FAST_STAGE_DEPTH / 4 at a time, all loads before the first LDS store: a tile of up to 12 KB is ONE global round trip (the
-    // strip's life is mostly this wait: with 8 rows per wave and batch it was three).  Row and column are computed once per
-    // unit; unit i lands at LDS byte 16 * i (the tile is linear in its units).
+    // strip's life is mostly this wait: with 8 rows per wave and batch it was three).  Row and column are computed once per unit.
     // Why the last unit of a row never leaves the source row's allocation: a tile row ends at up(xe, 16), xe = zx0 + zw + 3 +
     // edge the first column the ring does not need, and zx0 + zw <= w - SD_EDGE for every cell the plan evaluates.  Pyramid
     // (edge = SD_EDGE): xe <= w + 3 <= w + 2 * SD_EDGE <= pstride, and pstride is a multiple of 64, hence up(xe, 16) <= pstride.
@@ -683,9 +671,7 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
       asm volatile("" : "+v"(t0));   // opaque per strip: otherwise the row / column of every slot is hoisted out of the strip loop and spilled
       if (wide16) {   // wave-uniform (kernel argument)
         const int nu = __mul24(TPU, npr);
-        // (2 i + 1) * floor(2^31 / d) >> 32 == i / d for i * d <= 2^30 -- and, unlike the usual magic number, for d == 1 (zones
-        // narrower than 11 pixels have one-unit rows)
-        const unsigned magic_tpu = 0x80000000u / (unsigned)TPU;
+        const unsigned magic_tpu = fastdiv_magic_odd((unsigned)TPU);   // the odd recipe: TPU may be 1
         for (int i0 = t0; i0 < nu; i0 += 256 * (FAST_STAGE_DEPTH / 4)) {
           fast_u4 v[FAST_STAGE_DEPTH / 4];
 #pragma unroll
@@ -701,9 +687,9 @@ __global__ __launch_bounds__(256, 8) void k_fast_cells(const CellGeom* __restric
           }
         }
       } else {   // caller frames that are only 4-byte aligned: the same tile, one dword at a time
-        const int TPW = TPU * 4;
+        const int TPW = T.TPW;
         const int ndw = __mul24(TPW, npr);
-        const unsigned magic_tpw = 0xFFFFFFFFu / (unsigned)TPW + 1u;   // tile dword index / TPW (indices < 2^16: the tile is < 64 KB)
+        const unsigned magic_tpw = fastdiv_magic((unsigned)TPW);   // tile dword index / TPW
         for (int i0 = t0; i0 < ndw; i0 += 256 * FAST_STAGE_DEPTH) {
           uint32_t v[FAST_STAGE_DEPTH];
 #pragma unroll
@@ -1519,19 +1505,14 @@ struct Pipeline {
       hipLaunchKernelGGL(k_pyr_level, grid, block, 0, ps, L, S, (size_t)P.pyr_frame_bytes, l, d_imgs, stride, frame_stride, h->d_pyr);
       return SD_OK;
     }
-    auto magic = [](unsigned d) { return (unsigned)(0xFFFFFFFFull / d) + 1u; };   // e / d == umulhi(e, magic) for e < 2^31 / d
-    const int G = (L.w + 2 * SD_EDGE + 3) / 4;   // 4-pixel groups of a padded row
+    const PyrGroups& D = hp.pyr[l];   // groups per padded row, their checked magic number, k_pyr_split's row slots (orb_plan.cpp)
     if (l > 0 && L.nblk > 0) {   // rows in runs that share source rows (orb_plan.cpp row_blocks): one thread per (row block, group)
-      const unsigned n_rows = (unsigned)(((size_t)L.nblk * G + 255) / 256);
-      hipLaunchKernelGGL(k_pyr_rows, dim3(n_rows, n), dim3(256), 0, ps, L, S, (size_t)P.pyr_frame_bytes, h->d_coef, h->d_pyr, G,
-                         magic((unsigned)G));
+      hipLaunchKernelGGL(k_pyr_rows, dim3(pyr_blocks(L.nblk, D.G), n), dim3(256), 0, ps, L, S, (size_t)P.pyr_frame_bytes, h->d_coef, h->d_pyr,
+                         D.G, D.magic);
       return SD_OK;
     }
-    const bool mirror = L.h >= 48;   // border rows as second stores of their source rows (single reflections)
-    const int Hh = ((mirror ? L.h : L.prows) + PYR_RPT - 1) / PYR_RPT;   // (padded) rows per row-slot of a thread
-    const unsigned n_resize = (unsigned)(((size_t)Hh * G + 255) / 256);
-    hipLaunchKernelGGL(k_pyr_split, dim3(n_resize, n), dim3(256), 0, ps, L, S, (size_t)P.pyr_frame_bytes, l, h->d_coef, d_imgs, stride,
-                       frame_stride, h->d_pyr, G, magic((unsigned)G), Hh, mirror ? 1 : 0);
+    hipLaunchKernelGGL(k_pyr_split, dim3(pyr_blocks(D.Hh, D.G), n), dim3(256), 0, ps, L, S, (size_t)P.pyr_frame_bytes, l, h->d_coef, d_imgs,
+                       stride, frame_stride, h->d_pyr, D.G, D.magic, D.Hh, D.mirror);
     return SD_OK;
   }
 

@@ -1,10 +1,12 @@
 // See orb_plan.h.  Pure host code (no HIP).
 #include "orb_plan.h"
+#include "orb_fast_lds.h"
 #include "sd_common.h"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -14,6 +16,15 @@ static inline int cv_round(float v) { return (int)lrintf(v); }
 static inline int cv_round(double v) { return (int)lrint(v); }
 static inline int cv_floor(double v) { int i = (int)v; return i - (i > v); }
 static inline size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline int padded_groups(int w) { return (w + 2 * SD_EDGE + 3) / 4; }   // aligned 4-pixel groups of a padded row
+
+// A refusal that names its cell or level, in a buffer of the calling thread (orb_plan.h states the lifetime)
+static bool refuse(const char** why, const char* what, int level, int index, const char* quantity) {
+  static thread_local char text[192];
+  snprintf(text, sizeof(text), "%s %d of level %d: %s", what, index, level, quantity);
+  *why = text;
+  return false;
+}
 
 // reference src/ORBextractor.cc:406-434 (note: the member scaleFactor is a double holding the
 // float ctor argument, src/ORBextractor.h:38,78 -- the products below promote accordingly)
@@ -78,7 +89,7 @@ static bool group_table(LevelGeom& L, int src_w, const std::vector<int32_t>* xo,
     return p;
   };
   bool ok = true;
-  const int G = (L.w + 2 * SD_EDGE + 3) / 4;
+  const int G = padded_groups(L.w);
   for (int gi = 0; gi < G; gi++) {
     int Xr[4], sx[4] = {0, 0, 0, 0};
     uint32_t ab[4] = {0, 0, 0, 0}, selP[4] = {0, 0, 0, 0};
@@ -140,6 +151,27 @@ static void row_blocks(LevelGeom& L, const std::vector<int32_t>& yo, const std::
   coef.insert(coef.end(), p, p + blocks.size() * (sizeof(PyrRowBlock) / 4));
 }
 
+// The cell as k_fast_cells will lay it out, for each edge it can be launched with (level 0 from the caller's frames, edge 0, or,
+// like every other level, from the padded pyramid): inside the bytes its launch requests, and every flat-index division exact
+// over all the kernel can present (orb_fast_lds.h).  With frames of at most SD_MAX_DIM pixels a side none of this can fail; it
+// is here so that a change of the layout or of a limit is refused by the plan and not found on the device.
+static bool check_fast_cell(const CellGeom& c, int index, size_t request, const char** why) {
+  for (int edge : {0, SD_EDGE}) {
+    if (edge == 0 && c.level != 0) continue;
+    const LdsFastTile T(c.zx0, c.zw, c.zh, c.strip_rows, edge);
+    const FastDiv zw = T.div_zw(), tp = T.div_tp(), tpu = T.div_tpu(), tpw = T.div_tpw();
+    const char* bad = T.bytes > request                         ? "the LDS layout exceeds the bytes its launch requests"
+                      : !T.entries_fit16()                      ? "queue entries exceed 16 bits"
+                      : !fastdiv_exact(zw.d, zw.max_e)          ? "pixel index / zone width is not exact"
+                      : !fastdiv_exact(tp.d, tp.max_e)          ? "queue entry / tile pitch is not exact"
+                      : !fastdiv_odd_exact(tpu.d, tpu.max_e)    ? "staging unit / units per tile row is not exact"
+                      : !fastdiv_exact(tpw.d, tpw.max_e)        ? "staging dword / dwords per tile row is not exact"
+                                                                : nullptr;
+    if (bad) return refuse(why, "FAST zone of grid cell", c.level, index, bad);
+  }
+  return true;
+}
+
 bool plan_geometry(int nfeatures, int nlevels, int thFAST, int w, int h, HostPlan& hp, const char** why) {
   (void)nfeatures;
   if (nlevels < 1 || nlevels > SD_MAX_LEVELS) { *why = "nlevels out of range"; return false; }
@@ -172,6 +204,7 @@ bool plan_geometry(int nfeatures, int nlevels, int thFAST, int w, int h, HostPla
     hp.fast_merge_from = std::max(1, opt(OPT_FAST_MERGE_FROM));
   }
   for (int l = 0; l < SD_MAX_LEVELS; l++) hp.fast_lds_level[l] = 0;
+  memset(hp.pyr, 0, sizeof(hp.pyr));
   double sum_px = 0, px0 = 0, px_last = 0;
 
   for (int l = 0; l < nlevels; l++) {
@@ -288,9 +321,10 @@ bool plan_geometry(int nfeatures, int nlevels, int thFAST, int w, int h, HostPla
           c.zy0 = iniY + 3;
           c.zw = ok ? hX - 6 : 0;
           c.zh = ok ? hY - 6 : 0;
-          // k_fast_cells walks a zone as one flat pixel range and recovers the row with a 32-bit multiply-high magic number, which
-          // does not exist for a divisor of 1 (frames a few dozen pixels wide with hundreds of features per level): refused, not guessed
-          if (c.zw == 1) { *why = "a grid cell's FAST zone is one pixel wide (frame too small for this many features per level)"; return false; }
+          // k_fast_cells walks a zone as one flat pixel range and recovers the row by multiply-high (orb_fast_lds.h, div_zw): a divisor
+          // of 1 fails that division's predicate whatever the dividend, there is no 32-bit magic number for it (frames a few dozen
+          // pixels wide with hundreds of features per level): refused, not guessed
+          if (c.zw > 0 && !fastdiv_exact((uint32_t)c.zw, 0)) { *why = "a grid cell's FAST zone is one pixel wide (frame too small for this many features per level)"; return false; }
           c.cap = ok ? (uint32_t)(((c.zw + 1) / 2) * ((c.zh + 1) / 2)) : 0;
           c.cand_off = cand;
           cand += c.cap;
@@ -310,27 +344,22 @@ bool plan_geometry(int nfeatures, int nlevels, int thFAST, int w, int h, HostPla
             // 34-KB level would take every small cell of that launch from 6 to 4 workgroups per CU -- 720p: 81.3 k -> 77.7 k)
             bool whole_pass = l < hp.fast_merge_from;   // first candidate: the whole cell under the larger budget
             if (!whole_pass) S = std::min(c.zh, std::max(1, 12288 / c.zw));
-            // r5: the tile's left edge is aligned down to 16 bytes (staged with 16-byte loads and LDS stores) and the score map has
-            // the tile's pitch (a queue entry is the pixel's byte offset in the tile, its score sits a constant further on).  The
-            // STRIP decision is still taken on the r2 sizes the budgets were measured with (4-byte alignment, tight score
-            // pitch): a cell that was one strip stays one strip, and the request is what the wider rows then need (up to 12 + 24
-            // bytes per row more; the kernel's queue entries are 16 bits, hence the tile-offset bound).
+            // The STRIP decision is taken on the r2 sizes the budgets were measured with, the REQUEST is the kernel's layout at the
+            // worst pad (orb_fast_lds.h: 16-byte aligned tile rows, the score map at the tile's pitch, 16-bit queue entries).
+            size_t request = 0;   // the bytes this cell's launch must provide: the layout at the worst pad, plus the slack
             for (;;) {
-              size_t tp = up((size_t)c.zw + 6 + 3, 4), sp = up((size_t)c.zw + 2, 4);
-              size_t rpw = (size_t)(S + 2 + 3) / 4;
-              const size_t tp16 = up((size_t)c.zw + 6 + 15, 16);   // any pad 0...15: the same cell is staged from the frames (edge 0) or the pyramid
-              size_t need = tp * (S + 2 + 6) + sp * (S + 2 + 2) + 2 * 4 * rpw * c.zw + 64;
-              const size_t budget = whole_pass ? std::max(whole_kb, lds_kb) : lds_kb;
-              bool fits = need <= budget * 1024 && rpw * c.zw <= 4096 && (size_t)(std::min(S + 2, c.zh) + 1) * tp16 <= 65536;
-              const size_t nsr = (size_t)std::min(S + 2, c.zh);   // rows a strip scores: a whole-cell strip has no rows above / below
-              need = tp16 * (nsr + 6) + tp16 * (nsr + 2) + 2 * 4 * ((nsr + 3) / 4) * c.zw + 64;
-              fits = fits && need <= std::max(budget * 1024, (size_t)65536);   // (a launch may ask for 64 KB without opting in)
+              const size_t budget = 1024 * (whole_pass ? std::max(whole_kb, lds_kb) : lds_kb);
+              const LdsFastTile worst = LdsFastTile::worst_pad(c.zw, c.zh, S);
+              const size_t need = worst.bytes + kFastLdsSlack;
+              const bool fits = fast_r2_bytes(c.zw, S) <= budget && fast_queue_chunks_fit(c.zw, S) && worst.entries_fit16() &&
+                                need <= fast_request_limit(budget);
               if (whole_pass && !fits) {
                 whole_pass = false;
                 S = std::min(c.zh, std::max(1, 12288 / c.zw));
                 continue;
               }
               if (fits || S == 1) {
+                request = need;
                 lds_max = std::max(lds_max, need);
                 hp.fast_lds_level[l] = std::max(hp.fast_lds_level[l], need);
                 break;
@@ -338,6 +367,7 @@ bool plan_geometry(int nfeatures, int nlevels, int thFAST, int w, int h, HostPla
               S = std::max(1, S - std::max(1, S / 8));
             }
             c.strip_rows = S;
+            if (!check_fast_cell(c, (int)hp.cells.size() - L.cell0, request, why)) return false;
           }
           hp.cells.push_back(c);
         }
@@ -348,8 +378,22 @@ bool plan_geometry(int nfeatures, int nlevels, int thFAST, int w, int h, HostPla
 
     {   // k_blur: a 16-lane group per (64-column strip, 32-row band), sixteen groups per workgroup, dealt flat over the level
       const int nstrips = (L.w + 63) / 64, npairs = nstrips * ((L.h + 31) / 32);
-      for (int p0 = 0; p0 < npairs; p0 += 16)
-        hp.blur_tiles.push_back(BlurTile{l, p0, nstrips, (unsigned)(0xFFFFFFFFull / (unsigned)nstrips) + 1u});
+      for (int p0 = 0; p0 < npairs; p0 += 16) {
+        if (nstrips >= 2 && !fastdiv_exact((uint32_t)nstrips, (uint64_t)p0 + 15)) return refuse(why, "blur tile", l, p0 / 16, "pair / strips is not exact");
+        hp.blur_tiles.push_back(BlurTile{l, p0, nstrips, fastdiv_magic((uint32_t)nstrips)});   // (0 for a single strip: the kernel does not divide)
+      }
+    }
+    {   // what the level's resize launch divides by (orb_plan.h PyrGroups), exact for every thread of either kernel's launch.
+        // Filled and checked for every level, whichever kernel resizes it: which one does is decided at launch (the alignment
+        // of the caller's frames sends level 0 to k_pyr_level, which does not divide), and no level of a frame within SD_MAX_DIM
+        // can fail (G <= 1034, fewer than 2^21 threads)
+      PyrGroups& D = hp.pyr[l];
+      D.G = padded_groups(L.w);
+      D.magic = fastdiv_magic((uint32_t)D.G);
+      D.mirror = L.h >= 48 ? 1 : 0;   // border rows as second stores of their source rows (single reflections)
+      D.Hh = ((D.mirror ? L.h : L.prows) + PYR_RPT - 1) / PYR_RPT;   // (padded) rows per row-slot of a thread
+      const uint64_t threads = 256ull * std::max(pyr_blocks(D.Hh, D.G), pyr_blocks(L.nblk, D.G));
+      if (!fastdiv_exact((uint32_t)D.G, threads - 1)) return refuse(why, "resize launch", l, 0, "thread index / groups per padded row is not exact");
     }
   }
   P.ncells = (int)hp.cells.size();

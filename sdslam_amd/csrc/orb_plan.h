@@ -5,6 +5,7 @@
 //   grid / cell zones                      src/ORBextractor.cc:469-532
 // The structs below are uploaded verbatim and read by the kernels in orb.hip.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <vector>
 
@@ -62,7 +63,19 @@ struct PyrRowBlock {
 static_assert(sizeof(PyrRowBlock) == 32, "k_pyr_rows reads a block as two 16-byte loads");
 
 // k_blur work item: 16 consecutive (64-column strip, 32-row band) pairs of a level, pair p = band * nstrips + strip
-struct BlurTile { int level, p0, nstrips; unsigned magic; };   // magic: p / nstrips == umulhi(p, magic)
+// magic: p / nstrips == umulhi(p, magic), checked by the plan for p <= p0 + 15 (sd_fastdiv.h); 0 for a single strip, which has no
+// magic number and which the kernel does not divide by
+struct BlurTile { int level, p0, nstrips; unsigned magic; };
+
+// k_pyr_split / k_pyr_rows deal (row slot or row block, 4-pixel group of a PADDED row) pairs flat over their threads, pair
+// e = row * G + group, and recover the row as umulhi(e, magic): exact for every thread of either launch, the ones past the last
+// pair included (their early-out relies on the quotient), checked by the plan.  Hh, mirror: k_pyr_split's row slots -- a thread
+// resizes PYR_RPT rows Hh apart, of the interior where the border rows are single reflections (mirror), else of the padded level.
+#ifndef PYR_RPT
+#define PYR_RPT 4
+#endif
+struct PyrGroups { int G; unsigned magic; int Hh, mirror; };
+inline unsigned pyr_blocks(int rows, int G) { return (unsigned)(((size_t)rows * G + 255) / 256); }   // 256-thread workgroups of a launch
 
 struct OrbPlan {
   int nlevels, ncells, nsel;   // nsel = sum of quotas (<= nfeatures)
@@ -84,6 +97,7 @@ struct HostPlan {
   int fast_merge_from;         // levels >= this share one k_fast_cells launch (orb.hip); they keep the strip budget
   size_t fast_lds_level[SD_MAX_LEVELS];   // ... per level: the small levels' cells need far less than the budget, and a launch
                                           // that asks for less LDS keeps more workgroups per CU
+  PyrGroups pyr[SD_MAX_LEVELS];   // per level: what the resize launches divide by
   int max_cells_per_level;
   int max_cell_pixels;         // largest FAST detection zone (pixels): sizes the selection kernels' LDS cell buffers
   double stage_bytes[8];       // algorithmic bytes per frame per stage
@@ -91,7 +105,8 @@ struct HostPlan {
 
 // Tables that depend only on the ctor arguments.
 void plan_tables(int nfeatures, float scaleFactor, int nlevels, HostPlan& hp);
-// Geometry for a w x h frame. Returns false (with message) if unsupported.
+// Geometry for a w x h frame. Returns false (with message) if unsupported.  *why is a string literal or, where it names a cell or
+// a level, a buffer of the calling thread that the thread's next refused plan_geometry call overwrites: copy it before that.
 bool plan_geometry(int nfeatures, int nlevels, int thFAST, int w, int h, HostPlan& hp, const char** why);
 
 }  // namespace sd

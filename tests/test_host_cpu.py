@@ -177,6 +177,33 @@ def test_orb_host_helpers_under_sanitizers(tmp_path):
     assert out.returncode == 0 and "orb_host_check OK" in out.stdout, out.stdout + out.stderr
 
 
+def test_fast_lds_layout_and_divisions_under_sanitizers(tmp_path):
+    """k_fast_cells' LDS layout (orb_fast_lds.h) and every multiply-high division of the extraction path (sd_fastdiv.h): both
+    recipes against plain division up to their predicates' bounds, every cell, blur tile and resize launch of the geometries
+    the suite extracts at, the VGA plan replayed index by index, the one-pixel-zone refusal, and the plans unchanged from the
+    ones recorded before the headers existed.  Stand-alone program linked with the plan's sources, AddressSanitizer and UBSan."""
+    from sdslam_amd import build
+    exe = str(tmp_path / "orb_fast_lds_check")
+    inc = os.path.join(os.path.dirname(os.path.dirname(build.HIPCC)), "include")
+    csrc = os.path.join(ROOT, "sdslam_amd", "csrc")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-pthread", "-D__HIP_PLATFORM_AMD__=1", "-I", inc, "-I", csrc, os.path.join(ROOT, "tests", "native", "orb_fast_lds_check.cpp"),
+                           os.path.join(csrc, "orb_plan.cpp"), os.path.join(csrc, "sd_options.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "orb_fast_lds_check OK" in out.stdout, out.stdout + out.stderr
+
+
+def test_one_pixel_zone_is_refused_through_the_c_abi(sd):
+    """A frame whose grid has more columns than pixels between its borders (44 x 44, 500 features on two levels: 6 columns of
+    pixels, a grid of 7) has FAST zones one pixel wide: SD_ERR_INVALID_ARG and the plan's message, not a guess on the device."""
+    with pytest.raises(sd.SdError) as ei:
+        sd.plan_info(500, 1.2, 2, 20, 44, 44)
+    assert ei.value.code == 1                                                     # SD_ERR_INVALID_ARG
+    assert ("unsupported geometry: a grid cell's FAST zone is one pixel wide (frame too small for this many features per level)"
+            in str(ei.value))
+    assert sd.plan_info(100, 1.2, 2, 20, 44, 44)["cells"][:, 3].max() > 1         # the same frame with fewer features is planned
+
+
 def test_match_lds_layouts_under_sanitizers(tmp_path):
     """Every dynamic-LDS layout of the matchers (track_match_lds.h), for every capacity a launcher can pass: arrays aligned, disjoint,
     inside the total, and the total equal to the launchers' former byte formulas.  Stand-alone program, AddressSanitizer and UBSan."""
